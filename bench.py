@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric: decompressed GB/s + fraction of the HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg4|cfg5] [--full] [--dump-outputs DIR]
+
+A plain run sets up the config, warms up, checks bit-exactness, times exactly K steps and prints one JSON
+line (`value`, `ms_per_step` = milliseconds of one timed step, `roofline` of those steps).  Everything else
+-- cpu_baseline, the per-kind and order records, cfg5_strong, cfg3_png -- is measured only with --full.
+
+--dump-outputs DIR: after the timed steps, what the last step computed goes to DIR/<name>.npy (float32 /
+  float64, at most 64 MB): every unit's result flags and sizes, and the output bytes of a fixed, seeded
+  sample of the units (whole streams; rows of a few images for cfg4).  Rank r > 0 writes DIR/rank<r>/.
 
 --config cfg2 (default; BASELINE config 2 = configs[1], SURVEY.md 8d "cfg2"): per GPU 4096
   fixed-Huffman streams + 4096 stored-block streams, every stream inflating to one 64 KiB
@@ -21,15 +29,15 @@ include/debig_hip.h) over this rank's whole shard, inputs already resident in HB
 
   value         decompressed GB/s, whole job = sum over ranks of D bytes / max-over-ranks time
   roofline      the whole batch: algorithmic bytes C + D per step / average step duration measured
-                with events on the launch stream.  cfg2 also carries roofline_huffman and
+                with events on the launch stream.  With --full, cfg2 also carries roofline_huffman and
                 roofline_stored: each stream kind launched alone, timed the same way.
-  cpu_baseline  the compiled reference (oracle/_ref; or the oracle port if that prebuilt library
+  cpu_baseline  (--full) the compiled reference (oracle/_ref; or the oracle port if that prebuilt library
                 is absent) on the host cores: one thread per kind, blended, and all cores.
 
-Default run (`--config cfg2`, no --no-cfg5): the line also carries `cfg5_strong`, BASELINE config 5
+`--full` run (`--config cfg2`, no --no-cfg5): the line also carries `cfg5_strong`, BASELINE config 5
 measured by the same command on the same ranks -- 65536 gzip members of 1 MiB, member i -> GPU
 i mod N, strong scaling (value, ms_per_step, roofline on C + D, max-over-ranks time) -- so the
-SCALE runs (`--gpus 1/2/4/8`, no other flag) report both the weak-scaling headline and config 5.
+SCALE runs (`--gpus 1/2/4/8 --full`) report both the weak-scaling headline and config 5.
 `value` of the line itself stays the cfg2 headline at every N.  At N = 1 the line also carries `cfg3_png`,
 BASELINE config 3 (1024 PNGs cycled from the reference's sample files, decode_png -> RGBA, resident in HBM): what
 DevicePngBatch.launch() picks, the pair of launches and the fused kernel, digests against the reference's.
@@ -60,6 +68,8 @@ STREAM_BYTES = 65536
 CFG5_MEMBERS = 65536
 CFG5_MEMBER_BYTES = 1 << 20
 CFG5_DISTINCT = 512  # distinct member seeds in the whole job; member i has seed i mod 512
+DUMP_SEED = 0xD0D0  # --dump-outputs: the sample of units and rows, the same in every run
+DUMP_VALUES = 8 << 20  # --dump-outputs: output bytes in the sample, written as float32 (32 MB)
 
 
 def parse_args():
@@ -83,7 +93,14 @@ def parse_args():
     ap.add_argument("--no-kinds", action="store_true", help="cfg2: skip roofline_huffman / roofline_stored / ms_with_plan / roofline_interleaved "
                     "(profiling runs: the kernel statistics then hold whole-batch launches only)")
     ap.add_argument("--cfg5-steps", type=int, default=3, help="timed steps of the cfg5_strong record")
+    ap.add_argument("--full", action="store_true", help="also measure the secondary records (cpu_baseline, roofline_huffman / "
+                    "roofline_stored / ms_with_plan / roofline_interleaved, cfg5_strong, cfg3_png); the --no-* switches "
+                    "leave out single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed, seeded sample of what the last "
+                    "timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_kinds = args.no_cfg5 = args.no_cfg3 = True
     if args.steps is None:
         args.steps = 100 if args.config == "cfg2" else 5
     if args.warmup is None:
@@ -410,6 +427,40 @@ def timed_steps(torch, np, dist, coll_dev, batch, verify, steps, warmup, c_bytes
     return float(t.item()), step_ms, float(tot[0].item()), float(tot[1].item()), res
 
 
+def stream_outputs(np, batch, unit_bytes):
+    """cfg2 / cfg5: what a caller of the batched inflate receives -- every stream's good flag and final size -- and the
+    first unit_bytes output bytes of a seeded sample of the streams"""
+    res = batch.results()
+    n = len(res)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, max(1, min(n, DUMP_VALUES // unit_bytes)), replace=False))
+    offs = batch.streams_host["out_off"].astype(np.int64)[idx]
+    rows = np.stack([batch.d_out[o:o + unit_bytes].cpu().numpy() for o in offs])
+    return {"good": res["good"].astype(np.float64), "final_size": res["final_size"].astype(np.float64),
+            "sample_streams": idx.astype(np.float64), "sample_bytes": rows.astype(np.float32)}
+
+
+def image_outputs(np, pbatch):
+    """cfg4: what a caller of decode_png's batched path receives -- every image's inflate and de-filter good flags --
+    and seeded rows of the RGBA of up to 4 seeded images"""
+    res, ires = pbatch.results()
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(pbatch.n, min(pbatch.n, 4), replace=False))
+    where, rows = [], []
+    for i in pick:
+        w, h = pbatch.items[i]["w"], pbatch.items[i]["h"]
+        ys = np.sort(rng.choice(h, max(1, min(h, DUMP_VALUES // len(pick) // (4 * w))), replace=False))
+        rows.append(pbatch.rgba(int(i)).reshape(h, 4 * w)[ys])
+        where += [(i, y) for y in ys]
+    return {"inflate_good": res["good"].astype(np.float64), "defilter_good": ires["good"].astype(np.float64),
+            "sample_rows": np.array(where, dtype=np.float64), "sample_rgba": np.concatenate(rows).astype(np.float32)}
+
+
+def dump_outputs(np, dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def roof(c, d, ms, what, launches):
     ach = (c + d) / (ms * 1e-3) / 1e9
     return {"kernel": what, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -572,6 +623,9 @@ def main():
     # ---- timed region: exactly K steps between barrier+sync on both sides
     dt_max, step_ms, job_d, job_c, res = timed_steps(torch, np, dist, coll_dev, batch, verify, args.steps, args.warmup,
                                                      c_bytes, d_bytes)
+    if args.dump_outputs:
+        dump_outputs(np, args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     image_outputs(np, pbatch) if cfg4 else stream_outputs(np, batch, unit_bytes))
 
     line = None
     if rank == 0:

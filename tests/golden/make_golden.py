@@ -62,10 +62,29 @@ def corrupt_corpus():
     print("corpus_corrupt.json:", len(keep), "cases; reference deaths:", w.crashes)
 
 
+def vs_reference():
+    """7. the reference's answers (digests) to exactly the inputs of tests/test_oracle_vs_reference.py, recorded by
+    running that module's tests against the live reference (build A in process, build B in a child process)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_vs_reference as t
+    from ref_worker import RefWorker
+
+    w = RefWorker()
+    ref = t.StoredReference({}, live=(binding.Reference("A"), w))
+    orc = binding.Oracle()
+    for name in sorted(n for n in dir(t) if n.startswith("test_")):
+        getattr(t, name)(orc, ref)
+    w.close()
+    json.dump(ref.answers, open(t.ANSWERS, "w"), sort_keys=True, separators=(",", ":"))
+    print(os.path.basename(t.ANSWERS) + ":", len(ref.answers), "answers; reference deaths:", w.crashes)
+
+
 def main():
     binding.build(ref=True)
     if "--only-corrupt" in sys.argv:
         return corrupt_corpus()
+    if "--only-vs-reference" in sys.argv:
+        return vs_reference()
     A = binding.Reference("A")  # silent, asserts on (canonical)
     B = binding.Reference("B")  # silent, asserts off (inputs on which A aborts)
 
@@ -155,6 +174,7 @@ def main():
                      "good": int(good), "rgba_sha256": sha(out.tobytes())})
     json.dump(pngs, open(os.path.join(HERE, "png_synth.json"), "w"))
     corrupt_corpus()
+    vs_reference()
     print("golden fixtures written:", sorted(os.listdir(HERE)))
 
 

@@ -1,26 +1,68 @@
-"""CPU, build container only: the oracle against the COMPILED, UNMODIFIED reference
-(oracle/_ref, built in place from /root/reference by oracle/Makefile).  Skipped where the
-reference library is absent and cannot be built."""
+"""CPU: the oracle against the COMPILED, UNMODIFIED reference (oracle/_ref, built by oracle/Makefile), on
+fuzzed, flush-heavy, damaged and sample inputs.  The reference's answers to exactly these inputs are stored as
+digests in tests/golden/vs_reference.json: tests/golden/make_golden.py --only-vs-reference records them by
+running this module against the live reference, so the module needs nothing outside the repository."""
 import glob
+import hashlib
+import json
 import os
 import random
 import zlib
 
-import numpy as np
 import pytest
 
-from oracle import binding
-
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ANSWERS = os.path.join(GOLD, "vs_reference.json")
+
+
+def _digest(b):
+    return hashlib.sha256(bytes(b)).hexdigest()[:32]
+
+
+class StoredReference:
+    """The reference's answers as digests: inflate -> (good, final, sha), decode_png / decode_gz -> (good, sha),
+    inflate_b (build B, asserts off, in a child process) -> (good, final, sha) or None where it died.
+    live = (binding.Reference("A"), ref_worker.RefWorker()): record the answers instead of looking them up."""
+
+    def __init__(self, answers, live=None):
+        self.answers, self.live = answers, live
+
+    def _answer(self, op, size, data, compute):
+        k = hashlib.sha256(f"{op} {size} ".encode() + bytes(data)).hexdigest()[:32]
+        if self.live is not None:
+            self.answers[k] = compute()
+        assert k in self.answers, f"{op}: input not in {ANSWERS} (tests/golden/make_golden.py --only-vs-reference)"
+        a = self.answers[k]
+        return None if a is None else tuple(a)
+
+    def inflate(self, raw, cap):
+        def live():
+            g, f, o = self.live[0].inflate(raw, cap)
+            return [g, f, _digest(o)]
+        return self._answer("inflate", cap, raw, live)
+
+    def inflate_b(self, raw, cap):
+        def live():
+            r = self.live[1].inflate("B", raw, cap)
+            return None if r is None else [r[0], r[1], r[2][:32]]
+        return self._answer("inflate_b", cap, raw, live)
+
+    def decode_png(self, data, rgba_size=None):
+        def live():
+            g, o = self.live[0].decode_png(data, tid=2, rgba_size=rgba_size)
+            return [g, _digest(o)]
+        return self._answer("decode_png", rgba_size, data, live)
+
+    def decode_gz(self, data, expect_size):
+        def live():
+            g, o = self.live[0].decode_gz(data, expect_size)
+            return [g, _digest(o)]
+        return self._answer("decode_gz", expect_size, data, live)
 
 
 @pytest.fixture(scope="module")
 def ref():
-    if not binding.ref_available("A") and os.path.isdir("/root/reference/src"):
-        binding.build(ref=True)
-    if not binding.ref_available("A"):
-        pytest.skip("reference library not built (no /root/reference here)")
-    return binding.Reference("A")
+    return StoredReference(json.load(open(ANSWERS)))
 
 
 def test_raw_inflate_fuzz(oracle, ref):
@@ -43,8 +85,7 @@ def test_raw_inflate_fuzz(oracle, ref):
         raw = c.compress(data) + c.flush()
         cap = max(len(data) + 1, len(raw))
         a = oracle.inflate(raw, cap)
-        b = ref.inflate(raw, cap)
-        assert a == b, it
+        assert (a[0], a[1], _digest(a[2])) == ref.inflate(raw, cap), it
         truncated += a[2] != data
     assert truncated > 10  # the tail rule Q2 really fires and both sides agree on it
 
@@ -66,7 +107,8 @@ def test_flush_heavy_streams(oracle, ref):
             raw += c.flush(rng.choice([zlib.Z_SYNC_FLUSH, zlib.Z_FULL_FLUSH, zlib.Z_BLOCK]))
         raw += c.flush()
         cap = max(len(data) + 1, len(raw))
-        assert oracle.inflate(raw, cap) == ref.inflate(raw, cap), it
+        g, f, o = oracle.inflate(raw, cap)
+        assert (g, f, _digest(o)) == ref.inflate(raw, cap), it
 
 
 def test_gates(oracle, ref):
@@ -82,12 +124,10 @@ def test_resources(oracle, ref):
     for f in sorted(glob.glob(os.path.join(GOLD, "resources", "*.png"))):
         d = open(f, "rb").read()
         g1, o1 = oracle.decode_png(d)
-        g2, o2 = ref.decode_png(d, tid=2)
-        assert g1 == g2 and np.array_equal(o1, o2), os.path.basename(f)
+        assert (g1, _digest(o1)) == ref.decode_png(d), os.path.basename(f)
     d = open(os.path.join(GOLD, "resources", "gzipsample.gz"), "rb").read()
     g1, o1, n = oracle.decode_gz(d, 600000)
-    g2, o2 = ref.decode_gz(d, n)
-    assert g1 == g2 == 1 and o1 == o2
+    assert (g1, _digest(o1)) == ref.decode_gz(d, n) and g1 == 1
 
 
 def _safe_offsets(png):
@@ -121,15 +161,15 @@ def test_png_rejects_agree(oracle, ref):
         for _ in range(rng.randint(1, 2)):
             d[rng.choice(offs)] ^= 1 << rng.randrange(8)
         g1, o1 = oracle.decode_png(bytes(d), rgba_size=400)
-        g2, o2 = ref.decode_png(bytes(d), tid=2, rgba_size=400)
+        g2, o2 = ref.decode_png(bytes(d), rgba_size=400)
         assert g1 == g2, it
         rejected += g1 == 0
         if g1:
-            assert np.array_equal(o1, o2), it
+            assert _digest(o1) == o2, it
     assert rejected > 50
 
 
-from ref_worker import RefWorker, corrupt_cases  # noqa: E402
+from ref_worker import corrupt_cases  # noqa: E402
 
 
 def test_corrupted_raw_streams_fail_like_the_reference(oracle, ref):
@@ -139,23 +179,18 @@ def test_corrupted_raw_streams_fail_like_the_reference(oracle, ref):
     pinned on the same mutators the GPU suite leans on.  Reference build B (asserts off: build A
     aborts where B reports), in a child process; cases on which the oracle notes undefined
     behaviour of the reference (ub_flags) or the reference dies are excluded."""
-    import hashlib
-
-    w = RefWorker()
-    compared = failed = partial = 0
-    try:
-        for it, (raw, cap) in enumerate(corrupt_cases(4242, 1500)):
-            g, f, o, st = oracle.inflate(raw, cap, want_stats=True)
-            if st.ub_flags:
-                continue
-            r = w.inflate("B", raw, cap)
-            if r is None:
-                continue
-            assert (g, f, hashlib.sha256(o).hexdigest()) == r, it
-            compared += 1
-            failed += g == 0
-            partial += g == 0 and bool(f)
-    finally:
-        w.close()
-    assert compared > 800 and failed > 150 and partial > 100, (compared, failed, partial, w.crashes)
-    assert w.crashes < 20, w.crashes
+    compared = failed = partial = crashes = 0
+    for it, (raw, cap) in enumerate(corrupt_cases(4242, 1500)):
+        g, f, o, st = oracle.inflate(raw, cap, want_stats=True)
+        if st.ub_flags:
+            continue
+        r = ref.inflate_b(raw, cap)
+        if r is None:
+            crashes += 1
+            continue
+        assert (g, f, _digest(o)) == r, it
+        compared += 1
+        failed += g == 0
+        partial += g == 0 and bool(f)
+    assert compared > 800 and failed > 150 and partial > 100, (compared, failed, partial, crashes)
+    assert crashes < 20, crashes

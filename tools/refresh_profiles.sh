@@ -30,7 +30,7 @@ bash tools/pmc_split.sh fixed > $O/pmc_split_fixed.txt 2>&1 || true
 python3 tools/prof_split.py fixed 4096 65536 0x10 > $O/phases_split_fixed.txt 2>&1 || true
 python3 tools/prof_split.py dynamic 4096 65536 0x10 > $O/phases_split_dynamic.txt 2>&1 || true
 echo "[refresh] bench line"
-python3 bench.py > $O/bench_line.json 2> $O/bench_stderr.log
+python3 bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log
 tail -1 $O/bench_line.json | cut -c1-400
 echo "[refresh] the long-segment scan (DEBIG_WAVES_STRAND): counters, phases"
 bash tools/pmc_width.sh fixed 0x12 debig_strand_kernel > $O/pmc_strand_fixed.txt 2>&1 || true
