@@ -208,3 +208,58 @@ def gunzip_batch(datas, out_caps):
     rc = L.debig_gunzip_batch(in_ptrs, in_sizes, out_ptrs, caps, sizes, status, members, n)
     N.check(rc, "debig_gunzip_batch")
     return [(status[i], outs[i][: sizes[i]].tobytes(), members[i]) for i in range(n)]
+
+
+PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
+              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output"}
+PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
+
+
+class PngInfo(C.Structure):  # include/decode_png.h: debig_png_info
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("bit_depth", C.c_uint8), ("color_type", C.c_uint8),
+                ("interlace", C.c_uint8), ("has_trns", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+def _info_dict(inf):
+    return {k: int(getattr(inf, k)) for k in ("width", "height", "bit_depth", "color_type", "interlace", "has_trns")}
+
+
+def _png_spec_lib():
+    L = N.lib()
+    L.debig_png_info_get.restype = C.c_uint32
+    L.debig_png_info_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PngInfo)]
+    L.debig_png_decode_batch.restype = C.c_int
+    L.debig_png_decode_batch.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32]
+    return L
+
+
+def png_info(data):
+    """signature, IHDR and the chunks up to the first IDAT (host only, include/decode_png.h: debig_png_info_get)
+    -> (status, info dict), status as in PNG_STATUS"""
+    d = _u8(data)
+    inf = PngInfo()
+    st = _png_spec_lib().debig_png_info_get(d.ctypes.data, len(d), C.byref(inf))
+    return st, _info_dict(inf)
+
+
+def png_decode_batch(datas, force_general=False):
+    """every PNG the specification allows -> RGBA8 (include/decode_png.h: debig_png_decode_batch).
+    -> [(status, rgba ndarray (h, w, 4) or None, info dict)], status as in PNG_STATUS"""
+    L = _png_spec_lib()
+    n = len(datas)
+    ins = [_u8(d) for d in datas]
+    shapes = []
+    for a in ins:
+        st, inf = png_info(a)
+        shapes.append((inf["height"], inf["width"]) if st == 0 else (0, 0))
+    outs = [np.empty((h, w, 4), dtype=np.uint8) if h * w else np.empty(4, dtype=np.uint8) for h, w in shapes]
+    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
+    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
+    out_ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    caps = (C.c_uint64 * n)(*[4 * h * w for h, w in shapes])
+    status = (C.c_uint32 * n)()
+    infos = (PngInfo * n)()
+    rc = L.debig_png_decode_batch(in_ptrs, in_sizes, out_ptrs, caps, status, infos, n,
+                                  PNG_FORCE_GENERAL if force_general else 0)
+    N.check(rc, "debig_png_decode_batch")
+    return [(int(status[i]), outs[i] if status[i] == 0 else None, _info_dict(infos[i])) for i in range(n)]

@@ -13,6 +13,7 @@
 #include "inflate_chunk_kernel.inc"
 #include "png_kernel.inc"
 #include "png_fused_kernel.inc"
+#include "png_spec_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -729,6 +730,17 @@ int debig_hip_png_defilter_batch(const void *d_streams_arena, void *d_rgba_arena
     hipLaunchKernelGGL(debig_png_p3_kernel, dim3(n), dim3(PNG_P3_THREADS), 0, s,
                        (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images,
                        d_results, n);
+    return (int)hipGetLastError();
+}
+
+// the general de-filter (png_spec_kernel.inc): one workgroup of PNG_SPEC_NWD wavefronts per (image, pass) task
+int debig_hip_png_spec_defilter_batch(void *d_arena, void *d_rgba_arena, const debig_png_spec_task *d_tasks,
+                                      debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
+{
+    if (n == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    hipLaunchKernelGGL(debig_png_spec_defilter_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
+                       (uint8_t *)d_arena, (uint8_t *)d_rgba_arena, d_tasks, d_results, n);
     return (int)hipGetLastError();
 }
 

@@ -1,0 +1,502 @@
+/*
+ * debig_png_info_get / debig_png_decode_batch (include/decode_png.h): every PNG the specification allows, to RGBA8.
+ * Not a reference function.
+ *
+ * Host side (plain C): the chunk walk and the rules decided by headers alone.  On the GPU: chunk CRC-32 and the
+ * Adler-32 trailer (debig_hip_checksum_batch), the IDAT concatenation (debig_hip_gather), inflate (the batch inflate,
+ * plain RFC 1951) and the de-filter -- the tuned kernels for non-interlaced 8-bit RGB / RGBA, the general kernel
+ * (debig_hip_png_spec_defilter_batch: every colour type, depth, Adam7 pass, tRNS) for everything else.
+ */
+#include <stdlib.h>
+#include <string.h>
+#include "decode_png.h"
+#include "debig_ctx.h"
+
+typedef struct spec_piece { uint64_t off, len; } spec_piece;
+typedef struct spec_chunk { uint64_t off, len; uint32_t crc; } spec_chunk;
+
+typedef struct spec_file {
+    uint32_t status;
+    debig_png_info info;
+    uint32_t n_chunks, cap_chunks, n_idat, cap_idat;
+    spec_chunk *chunks; /* type + data spans and the CRCs stored in the file */
+    spec_piece *idat;   /* IDAT payloads, in file order */
+    uint64_t z_total;   /* bytes of the concatenated IDAT payloads (zlib header + DEFLATE + trailer) */
+    uint32_t pal[256];  /* RGBA, tRNS alpha folded in */
+    uint32_t n_pal;
+    uint16_t key[3];
+    uint32_t has_key, general;
+    uint64_t scan;      /* scanline stream bytes */
+    /* device layout */
+    uint64_t file_off, in_off, out_off, pal_off, scratch_off, rgba_off;
+} spec_file;
+
+static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+static const uint32_t adam7[7][4] = {{0, 0, 8, 8}, {4, 0, 8, 8}, {0, 4, 4, 8}, {2, 0, 4, 4}, {0, 2, 2, 4}, {1, 0, 2, 2}, {0, 1, 1, 2}};
+
+static uint32_t sbe32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+static uint32_t channels_of(uint32_t ct) { return ct == 0 ? 1u : ct == 2 ? 3u : ct == 3 ? 1u : ct == 4 ? 2u : 4u; }
+static int depth_ok(uint32_t ct, uint32_t d)
+{
+    switch (ct) {
+    case 0: return d == 1 || d == 2 || d == 4 || d == 8 || d == 16;
+    case 3: return d == 1 || d == 2 || d == 4 || d == 8;
+    case 2: case 4: case 6: return d == 8 || d == 16;
+    default: return 0;
+    }
+}
+
+/* pass p of a w x h image (interlace 0: p = 0 is the whole image) */
+static void pass_dims(uint32_t w, uint32_t h, uint32_t il, uint32_t p, uint32_t g[4], uint32_t *wp, uint32_t *hp)
+{
+    static const uint32_t whole[4] = {0, 0, 1, 1};
+    const uint32_t *q = il ? adam7[p] : whole;
+    memcpy(g, q, 4 * sizeof(uint32_t));
+    *wp = w > q[0] ? (w - q[0] + q[2] - 1) / q[2] : 0;
+    *hp = h > q[1] ? (h - q[1] + q[3] - 1) / q[3] : 0;
+}
+static uint64_t row_bytes(uint64_t wp, uint32_t ct, uint32_t depth) { return (wp * channels_of(ct) * depth + 7u) / 8u; }
+
+static int grow(void **p, uint32_t *cap, uint32_t n, size_t elem)
+{
+    if (n < *cap) return 1;
+    uint32_t c = *cap ? 2 * *cap : 16;
+    void *q = realloc(*p, (size_t)c * elem);
+    if (!q) return 0;
+    *p = q;
+    *cap = c;
+    return 1;
+}
+
+/* byte k of the IDAT concatenation (k < z_total) */
+static uint8_t z_byte(const spec_file *F, const uint8_t *in, uint64_t k)
+{
+    for (uint32_t i = 0; i < F->n_idat; i++) {
+        if (k < F->idat[i].len) return in[F->idat[i].off + k];
+        k -= F->idat[i].len;
+    }
+    return 0;
+}
+
+/* The chunk walk.  info_only: stop at the first IDAT (debig_png_info_get).  Returns a DEBIG_PNG_* status. */
+static uint32_t spec_walk(const uint8_t *in, uint64_t size, spec_file *F, int info_only)
+{
+    if (!in || size < 8 || memcmp(in, png_sig, 8)) return DEBIG_PNG_E_SIGNATURE;
+    uint64_t pos = 8;
+    int seen_ihdr = 0, seen_plte = 0, seen_idat = 0, idat_done = 0, have_pal = 0;
+    int64_t trns_at = -1;
+    uint32_t trns_len = 0;
+    int trns_after_plte = 0;
+    for (;;) {
+        if (pos + 8 > size) return DEBIG_PNG_E_CHUNK;
+        const uint32_t len = sbe32(in + pos);
+        const uint8_t *type = in + pos + 4;
+        if (len > 0x7fffffffu || pos + 12 + (uint64_t)len > size) return DEBIG_PNG_E_CHUNK;
+        const uint8_t *body = in + pos + 8;
+        if (!seen_ihdr && memcmp(type, "IHDR", 4)) return DEBIG_PNG_E_CHUNK;
+        int is_iend = 0;
+        if (!memcmp(type, "IHDR", 4)) {
+            if (seen_ihdr) return DEBIG_PNG_E_CHUNK;
+            if (len != 13) return DEBIG_PNG_E_IHDR;
+            const uint32_t w = sbe32(body), h = sbe32(body + 4);
+            const uint32_t d = body[8], ct = body[9];
+            if (w < 1 || w > 0x7fffffffu || h < 1 || h > 0x7fffffffu || !depth_ok(ct, d) || body[10] || body[11] || body[12] > 1)
+                return DEBIG_PNG_E_IHDR;
+            F->info.width = w;
+            F->info.height = h;
+            F->info.bit_depth = (uint8_t)d;
+            F->info.color_type = (uint8_t)ct;
+            F->info.interlace = body[12];
+            seen_ihdr = 1;
+        } else if (!memcmp(type, "IDAT", 4)) {
+            if (idat_done) return DEBIG_PNG_E_CHUNK;
+            if (info_only) break;
+            seen_idat = 1;
+            if (len) {
+                if (!grow((void **)&F->idat, &F->cap_idat, F->n_idat, sizeof(spec_piece))) return DEBIG_PNG_E_CHUNK;
+                F->idat[F->n_idat].off = pos + 8;
+                F->idat[F->n_idat].len = len;
+                F->n_idat++;
+                F->z_total += len;
+            }
+        } else {
+            if (seen_idat) idat_done = 1;
+            const uint32_t ct = F->info.color_type;
+            if (!memcmp(type, "IEND", 4)) {
+                is_iend = 1;
+            } else if (!memcmp(type, "PLTE", 4)) {
+                if (seen_plte || seen_idat || ct == 0 || ct == 4) return DEBIG_PNG_E_CHUNK;
+                seen_plte = 1;
+                if (ct == 3) {
+                    if (len % 3u || len < 3 || len > 768) return DEBIG_PNG_E_PALETTE;
+                    F->n_pal = len / 3u;
+                    for (uint32_t k = 0; k < F->n_pal; k++)
+                        F->pal[k] = (uint32_t)body[3 * k] | ((uint32_t)body[3 * k + 1] << 8) | ((uint32_t)body[3 * k + 2] << 16) | 0xff000000u;
+                    have_pal = 1;
+                }
+            } else if (!memcmp(type, "tRNS", 4)) {
+                if (!seen_idat) {
+                    trns_at = (int64_t)(pos + 8);
+                    trns_len = len;
+                    trns_after_plte = have_pal;
+                }
+            } else if (!(type[0] & 0x20u)) {
+                return DEBIG_PNG_E_CHUNK; /* unknown critical chunk */
+            }
+        }
+        if (!info_only) {
+            if (!grow((void **)&F->chunks, &F->cap_chunks, F->n_chunks, sizeof(spec_chunk))) return DEBIG_PNG_E_CHUNK;
+            F->chunks[F->n_chunks].off = pos + 4;
+            F->chunks[F->n_chunks].len = (uint64_t)len + 4u;
+            F->chunks[F->n_chunks].crc = sbe32(body + len);
+            F->n_chunks++;
+        }
+        pos += 12 + (uint64_t)len;
+        if (is_iend) break;
+    }
+    const uint32_t ct = F->info.color_type;
+    if (ct == 3 && !have_pal) return DEBIG_PNG_E_CHUNK;
+    if (trns_at >= 0) {
+        const uint8_t *b = in + trns_at;
+        if (ct == 3 && trns_after_plte && trns_len <= F->n_pal) {
+            for (uint32_t k = 0; k < trns_len; k++) F->pal[k] = (F->pal[k] & 0x00ffffffu) | ((uint32_t)b[k] << 24);
+            F->info.has_trns = 1;
+        } else if (ct == 0 && trns_len == 2) {
+            F->key[0] = (uint16_t)((b[0] << 8) | b[1]);
+            F->has_key = F->info.has_trns = 1;
+        } else if (ct == 2 && trns_len == 6) {
+            for (int k = 0; k < 3; k++) F->key[k] = (uint16_t)((b[2 * k] << 8) | b[2 * k + 1]);
+            F->has_key = F->info.has_trns = 1;
+        }
+    }
+    if (info_only) return DEBIG_PNG_OK;
+    if (!seen_idat) return DEBIG_PNG_E_CHUNK;
+    return DEBIG_PNG_OK;
+}
+
+static void spec_free(spec_file *F)
+{
+    free(F->chunks);
+    free(F->idat);
+    F->chunks = NULL;
+    F->idat = NULL;
+}
+
+DEBIG_API uint32_t debig_png_info_get(const uint8_t *p, uint64_t size, debig_png_info *info)
+{
+    spec_file F;
+    memset(&F, 0, sizeof F);
+    const uint32_t st = spec_walk(p, size, &F, 1);
+    if (info) *info = F.info;
+    spec_free(&F);
+    return st;
+}
+
+/* the host rules after the walk: zlib header, output size; and the sizes the device needs */
+static uint32_t spec_host_rules(spec_file *F, const uint8_t *in, uint8_t *out, uint64_t out_cap)
+{
+    if (F->z_total < 2) return DEBIG_PNG_E_ZLIB;
+    const uint32_t cmf = z_byte(F, in, 0), flg = z_byte(F, in, 1);
+    if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u || (flg & 0x20u)) return DEBIG_PNG_E_ZLIB;
+    const uint64_t w = F->info.width, h = F->info.height; /* < 2^31 each: 4wh fits */
+    if (!out || out_cap < 4u * w * h) return DEBIG_PNG_E_OUTPUT;
+    const uint32_t ct = F->info.color_type, d = F->info.bit_depth, il = F->info.interlace;
+    F->scan = 0;
+    for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
+        uint32_t g[4], wp, hp;
+        pass_dims((uint32_t)w, (uint32_t)h, il, p, g, &wp, &hp);
+        if (wp && hp) F->scan += (uint64_t)hp * (1u + row_bytes(wp, ct, d));
+    }
+    return DEBIG_PNG_OK;
+}
+
+DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                                     const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                     uint32_t flags)
+{
+    if (n == 0) return 0;
+    spec_file *F = (spec_file *)calloc(n, sizeof(spec_file));
+    uint32_t *live = (uint32_t *)calloc(n, sizeof(uint32_t)); /* files still good, in order */
+    debig_span *spans = NULL;
+    uint32_t *sums = NULL;
+    debig_copy *copies = NULL;
+    debig_stream *desc = NULL;
+    debig_result *res = NULL;
+    debig_png_image *img = NULL;
+    debig_png_result *ires = NULL;
+    debig_png_spec_task *tasks = NULL;
+    debig_png_spec_result *tres = NULL;
+    uint32_t *task_file = NULL, *img_file = NULL;
+    uint8_t **dn_dst = NULL;
+    uint64_t *dn_size = NULL, *dn_off = NULL, *up_size = NULL, *up_off = NULL;
+    int rc = 2;
+    if (!F || !live) goto done;
+    rc = 0;
+    /* ---- host rules */
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        spec_file *f = &F[i];
+        f->status = spec_walk(inputs[i], input_sizes[i], f, 0);
+        if (f->status == DEBIG_PNG_OK) f->status = spec_host_rules(f, inputs[i], outs[i], out_caps[i]);
+        if (f->status == DEBIG_PNG_OK) live[m++] = i;
+    }
+    if (m == 0) goto report; /* nothing for the device */
+    debig_ctx *c = debig_ctx_get(0);
+    if (!c) { rc = 1; goto done; }
+    /* ---- device layout: whole files (c->files); IDAT concatenations (c->in); per file in c->out the scanline stream
+     *      (+ 16 readable bytes), the palette and the scratch rings of its general-kernel tasks; RGBA (c->rgba) */
+    uint64_t files_total = 0, in_total = 0, out_total = 64, rgba_total = 0;
+    uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0;
+    for (uint32_t k = 0; k < m; k++) {
+        spec_file *f = &F[live[k]];
+        const uint32_t ct = f->info.color_type, d = f->info.bit_depth, il = f->info.interlace;
+        f->general = (flags & DEBIG_PNG_FORCE_GENERAL) || il || d != 8 || !(ct == 6 || (ct == 2 && !f->has_key));
+        f->file_off = files_total;
+        files_total += debig_align16(input_sizes[live[k]]) + 16;
+        f->in_off = in_total;
+        in_total += debig_align16(f->z_total) + 32;
+        f->out_off = out_total;
+        out_total += debig_align16(f->scan) + 32;
+        f->pal_off = out_total;
+        if (ct == 3) out_total += 1024;
+        f->scratch_off = out_total;
+        f->rgba_off = rgba_total;
+        rgba_total += debig_align16(4ull * f->info.width * f->info.height) + 16;
+        n_chunks += f->n_chunks;
+        n_pieces += f->n_idat;
+        if (f->general) {
+            for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
+                uint32_t g[4], wp, hp;
+                pass_dims(f->info.width, f->info.height, il, p, g, &wp, &hp);
+                if (!wp || !hp) continue;
+                out_total += DEBIG_PNG_SPEC_SCRATCH_BYTES(row_bytes(wp, ct, d));
+                n_tasks++;
+            }
+        } else {
+            n_img++;
+        }
+    }
+    spans = (debig_span *)calloc((size_t)n_chunks + m, sizeof(debig_span));
+    sums = (uint32_t *)calloc((size_t)n_chunks + m, sizeof(uint32_t));
+    copies = (debig_copy *)calloc((size_t)n_pieces + 1, sizeof(debig_copy));
+    desc = (debig_stream *)calloc(m, sizeof(debig_stream));
+    res = (debig_result *)calloc(m, sizeof(debig_result));
+    img = (debig_png_image *)calloc((size_t)n_img + 1, sizeof(debig_png_image));
+    ires = (debig_png_result *)calloc((size_t)n_img + 1, sizeof(debig_png_result));
+    img_file = (uint32_t *)calloc((size_t)n_img + 1, sizeof(uint32_t));
+    tasks = (debig_png_spec_task *)calloc((size_t)n_tasks + 1, sizeof(debig_png_spec_task));
+    tres = (debig_png_spec_result *)calloc((size_t)n_tasks + 1, sizeof(debig_png_spec_result));
+    task_file = (uint32_t *)calloc((size_t)n_tasks + 1, sizeof(uint32_t));
+    up_size = (uint64_t *)calloc(n, sizeof(uint64_t));
+    up_off = (uint64_t *)calloc(n, sizeof(uint64_t));
+    dn_dst = (uint8_t **)calloc(n, sizeof(uint8_t *));
+    dn_size = (uint64_t *)calloc(n, sizeof(uint64_t));
+    dn_off = (uint64_t *)calloc(n, sizeof(uint64_t));
+    if (!spans || !sums || !copies || !desc || !res || !img || !ires || !img_file || !tasks || !tres || !task_file ||
+        !up_size || !up_off || !dn_dst || !dn_size || !dn_off) {
+        rc = 2;
+        goto done;
+    }
+    if ((rc = debig_devbuf_reserve(&c->files, files_total + 64)) || (rc = debig_devbuf_reserve(&c->in, in_total + 64)) ||
+        (rc = debig_devbuf_reserve(&c->out, out_total + 64)) || (rc = debig_devbuf_reserve(&c->rgba, rgba_total + 64)) ||
+        (rc = debig_devbuf_reserve(&c->spans, ((uint64_t)n_chunks + m) * sizeof(debig_span))) ||
+        (rc = debig_devbuf_reserve(&c->crcs, ((uint64_t)n_chunks + m) * sizeof(uint32_t))) ||
+        (rc = debig_devbuf_reserve(&c->copies, ((uint64_t)n_pieces + 1) * sizeof(debig_copy))))
+        goto done;
+    /* ---- whole files up; chunk CRCs and the IDAT concatenation on the device */
+    for (uint32_t k = 0; k < m; k++) {
+        up_size[live[k]] = input_sizes[live[k]];
+        up_off[live[k]] = F[live[k]].file_off;
+    }
+    if ((rc = debig_upload_packed(c, c->files.ptr, inputs, up_size, up_off, n, files_total))) goto done;
+    {
+        uint32_t ci = 0, pi = 0;
+        for (uint32_t k = 0; k < m; k++) {
+            spec_file *f = &F[live[k]];
+            for (uint32_t j = 0; j < f->n_chunks; j++, ci++) {
+                spans[ci].off = f->file_off + f->chunks[j].off;
+                spans[ci].len = f->chunks[j].len;
+            }
+            uint64_t dst = f->in_off;
+            for (uint32_t j = 0; j < f->n_idat; j++, pi++) {
+                copies[pi].src_off = f->file_off + f->idat[j].off;
+                copies[pi].dst_off = dst;
+                copies[pi].len = f->idat[j].len;
+                dst += f->idat[j].len;
+            }
+        }
+        if ((rc = debig_hip_memcpy_h2d(c->spans.ptr, spans, (uint64_t)n_chunks * sizeof(debig_span), NULL)) ||
+            (rc = debig_hip_checksum_batch(c->files.ptr, (const debig_span *)c->spans.ptr, (uint32_t *)c->crcs.ptr, n_chunks, 0, NULL)) ||
+            (rc = debig_hip_memcpy_d2h(sums, c->crcs.ptr, (uint64_t)n_chunks * sizeof(uint32_t), NULL)) ||
+            (n_pieces && (rc = debig_hip_memcpy_h2d(c->copies.ptr, copies, (uint64_t)n_pieces * sizeof(debig_copy), NULL))) ||
+            (n_pieces && (rc = debig_hip_gather(c->files.ptr, c->in.ptr, (const debig_copy *)c->copies.ptr, n_pieces, NULL))) ||
+            (rc = debig_hip_stream_sync(NULL)))
+            goto done;
+        ci = 0;
+        for (uint32_t k = 0; k < m; k++) {
+            spec_file *f = &F[live[k]];
+            for (uint32_t j = 0; j < f->n_chunks; j++, ci++)
+                if (f->status == DEBIG_PNG_OK && sums[ci] != f->chunks[j].crc) f->status = DEBIG_PNG_E_CRC;
+        }
+    }
+    /* ---- inflate: plain RFC 1951 into exactly the scanline stream; the trailer and what follows stay in the span */
+    uint32_t ns = 0;
+    for (uint32_t k = 0; k < m; k++) {
+        spec_file *f = &F[live[k]];
+        if (f->status != DEBIG_PNG_OK) continue;
+        live[ns] = live[k];
+        desc[ns].in_off = f->in_off + 2u;
+        desc[ns].in_len = f->z_total - 2u;
+        desc[ns].out_off = f->out_off;
+        desc[ns].out_cap = f->scan;
+        desc[ns].flags = DEBIG_STREAM_NO_REF_GATES | DEBIG_STREAM_IMAGE_ROWS;
+        ns++;
+    }
+    m = ns;
+    if (m == 0) goto report;
+    if ((rc = debig_launch_inflate_planned(c, c->in.ptr, desc, res, m))) goto done;
+    ns = 0;
+    for (uint32_t k = 0; k < m; k++) {
+        spec_file *f = &F[live[k]];
+        if (!res[k].good) {
+            f->status = res[k].status == DEBIG_E_OUTPUT_FULL ? DEBIG_PNG_E_DATA_LONG : DEBIG_PNG_E_INFLATE;
+            continue;
+        }
+        if (res[k].final_size < f->scan) { f->status = DEBIG_PNG_E_DATA_SHORT; continue; }
+        const uint64_t t = 2u + (res[k].in_end_bits + 7u) / 8u; /* the Adler-32 trailer, in the concatenation */
+        if (t + 4u > f->z_total) { f->status = DEBIG_PNG_E_ADLER; continue; }
+        sums[ns] = ((uint32_t)z_byte(f, inputs[live[k]], t) << 24) | ((uint32_t)z_byte(f, inputs[live[k]], t + 1) << 16) |
+                   ((uint32_t)z_byte(f, inputs[live[k]], t + 2) << 8) | z_byte(f, inputs[live[k]], t + 3);
+        spans[ns].off = f->out_off;
+        spans[ns].len = f->scan;
+        live[ns++] = live[k];
+    }
+    m = ns;
+    if (m == 0) goto report;
+    {
+        uint32_t *adl = sums + m; /* (sums holds n_chunks + m words, n_chunks >= 3 per file) */
+        if ((rc = debig_hip_memcpy_h2d(c->spans.ptr, spans, (uint64_t)m * sizeof(debig_span), NULL)) ||
+            (rc = debig_hip_checksum_batch(c->out.ptr, (const debig_span *)c->spans.ptr, (uint32_t *)c->crcs.ptr, m, 1, NULL)) ||
+            (rc = debig_hip_memcpy_d2h(adl, c->crcs.ptr, (uint64_t)m * sizeof(uint32_t), NULL)) ||
+            (rc = debig_hip_stream_sync(NULL)))
+            goto done;
+        ns = 0;
+        for (uint32_t k = 0; k < m; k++) {
+            if (adl[k] != sums[k]) { F[live[k]].status = DEBIG_PNG_E_ADLER; continue; }
+            live[ns++] = live[k];
+        }
+        m = ns;
+    }
+    if (m == 0) goto report;
+    /* ---- de-filter: tuned kernels for non-interlaced 8-bit RGB / RGBA, the general kernel for the rest */
+    n_img = n_tasks = 0;
+    for (uint32_t k = 0; k < m; k++) {
+        const uint32_t i = live[k];
+        spec_file *f = &F[i];
+        const uint32_t ct = f->info.color_type, d = f->info.bit_depth, il = f->info.interlace;
+        if (!f->general) {
+            debig_png_image *im = &img[n_img];
+            im->stream_off = f->out_off;
+            im->rgba_off = f->rgba_off;
+            im->width = f->info.width;
+            im->height = f->info.height;
+            im->color_type = ct;
+            img_file[n_img++] = i;
+            continue;
+        }
+        if (ct == 3 && (rc = debig_hip_memcpy_h2d((uint8_t *)c->out.ptr + f->pal_off, f->pal, 1024, NULL))) goto done;
+        uint64_t pos = f->out_off, scratch = f->scratch_off;
+        for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
+            uint32_t g[4], wp, hp;
+            pass_dims(f->info.width, f->info.height, il, p, g, &wp, &hp);
+            if (!wp || !hp) continue;
+            const uint64_t rb = row_bytes(wp, ct, d);
+            debig_png_spec_task *t = &tasks[n_tasks];
+            t->stream_off = pos;
+            t->rgba_off = f->rgba_off;
+            t->pal_off = f->pal_off;
+            t->scratch_off = scratch;
+            t->width = wp;
+            t->height = hp;
+            t->img_width = f->info.width;
+            t->x0 = g[0]; t->y0 = g[1]; t->dx = g[2]; t->dy = g[3];
+            t->depth = (uint8_t)d;
+            t->color_type = (uint8_t)ct;
+            t->channels = (uint8_t)channels_of(ct);
+            t->bpp_f = (uint8_t)(t->channels * d / 8u ? t->channels * d / 8u : 1u);
+            memcpy(t->key, f->key, sizeof t->key);
+            t->has_key = (uint16_t)f->has_key;
+            t->n_pal = (uint16_t)f->n_pal;
+            task_file[n_tasks++] = i;
+            pos += (uint64_t)hp * (1u + rb);
+            scratch += DEBIG_PNG_SPEC_SCRATCH_BYTES(rb);
+        }
+    }
+    if (n_img) {
+        if ((rc = debig_devbuf_reserve(&c->img, (uint64_t)n_img * sizeof(debig_png_image))) ||
+            (rc = debig_devbuf_reserve(&c->imgres, (uint64_t)n_img * sizeof(debig_png_result))) ||
+            (rc = debig_hip_memcpy_h2d(c->img.ptr, img, (uint64_t)n_img * sizeof(debig_png_image), NULL)) ||
+            (rc = debig_hip_png_defilter_batch(c->out.ptr, c->rgba.ptr, (const debig_png_image *)c->img.ptr,
+                                               (debig_png_result *)c->imgres.ptr, n_img, NULL)) ||
+            (rc = debig_hip_memcpy_d2h(ires, c->imgres.ptr, (uint64_t)n_img * sizeof(debig_png_result), NULL)))
+            goto done;
+    }
+    if (n_tasks) {
+        if ((rc = debig_devbuf_reserve(&c->spec_tasks, (uint64_t)n_tasks * sizeof(debig_png_spec_task))) ||
+            (rc = debig_devbuf_reserve(&c->spec_res, (uint64_t)n_tasks * sizeof(debig_png_spec_result))) ||
+            (rc = debig_hip_memcpy_h2d(c->spec_tasks.ptr, tasks, (uint64_t)n_tasks * sizeof(debig_png_spec_task), NULL)) ||
+            (rc = debig_hip_png_spec_defilter_batch(c->out.ptr, c->rgba.ptr, (const debig_png_spec_task *)c->spec_tasks.ptr,
+                                                    (debig_png_spec_result *)c->spec_res.ptr, n_tasks, NULL)) ||
+            (rc = debig_hip_memcpy_d2h(tres, c->spec_res.ptr, (uint64_t)n_tasks * sizeof(debig_png_spec_result), NULL)))
+            goto done;
+    }
+    if ((rc = debig_hip_stream_sync(NULL))) goto done;
+    for (uint32_t k = 0; k < n_img; k++)
+        if (!ires[k].good) F[img_file[k]].status = DEBIG_PNG_E_FILTER;
+    for (uint32_t k = 0; k < n_tasks; k++) { /* a filter error anywhere in the image outranks a palette error */
+        spec_file *f = &F[task_file[k]];
+        if (tres[k].status == DEBIG_PNG_SPEC_E_FILTER) f->status = DEBIG_PNG_E_FILTER;
+        else if (tres[k].status == DEBIG_PNG_SPEC_E_PALETTE && f->status == DEBIG_PNG_OK) f->status = DEBIG_PNG_E_PALETTE;
+    }
+    /* ---- RGBA down */
+    {
+        uint64_t last_end = 0;
+        for (uint32_t k = 0; k < m; k++) {
+            const uint32_t i = live[k];
+            if (F[i].status != DEBIG_PNG_OK) continue;
+            dn_dst[i] = outs[i];
+            dn_size[i] = 4ull * F[i].info.width * F[i].info.height;
+            dn_off[i] = F[i].rgba_off;
+            if (dn_off[i] + dn_size[i] > last_end) last_end = dn_off[i] + dn_size[i];
+        }
+        if (last_end && (rc = debig_download_unpack(c, c->rgba.ptr, dn_dst, dn_size, dn_off, n, last_end))) goto done;
+    }
+report:
+    for (uint32_t i = 0; i < n; i++) {
+        status[i] = F[i].status;
+        if (infos) infos[i] = F[i].info;
+    }
+done:
+    if (F)
+        for (uint32_t i = 0; i < n; i++) spec_free(&F[i]);
+    free(F);
+    free(live);
+    free(spans);
+    free(sums);
+    free(copies);
+    free(desc);
+    free(res);
+    free(img);
+    free(ires);
+    free(img_file);
+    free(tasks);
+    free(tres);
+    free(task_file);
+    free(up_size);
+    free(up_off);
+    free(dn_dst);
+    free(dn_size);
+    free(dn_off);
+    return rc;
+}

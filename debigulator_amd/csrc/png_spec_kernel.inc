@@ -1,0 +1,323 @@
+// png_spec_kernel.inc -- the general PNG de-filter (include/decode_png.h: debig_png_decode_batch).
+//
+// Every colour type and bit depth the PNG specification allows, Adam7 passes and tRNS, to RGBA8.  One TASK is one
+// (image, pass) sub-image (debig_png_spec_task); a non-interlaced image is one task placed at (0, 0, 1, 1).
+//
+// Mapping (what png_kernel.inc measured, generalised to a filter unit of BPP = 1, 2, 3, 4, 6 or 8 bytes):
+//   - one workgroup of PNG_SPEC_NWD wavefronts per task; wavefront k takes the bands of 64 rows k, k + NWD, ...;
+//   - lane r of a band owns row band*64 + r and runs ONE GROUP of K units (K*BPP = 8, 12 or 16 bytes) behind the row
+//     above: the group's "up" bytes are what the lane above produced in the previous macro-step (DPP one-lane shift),
+//     "left" and "up-left" are the last unit of the lane's own previous group and of its previous "up";
+//   - the row bytes are staged through a padded LDS tile, PNG_SPEC_BLOCK macro-steps per bulk load phase;
+//   - the predictors run on packed 2 x 16-bit halves (pk_defilter of png_kernel.inc), one or two dwords per unit;
+//   - the first row of a band takes its "up" bytes from the de-filtered last row of the band above, which lane 63 of
+//     that band's wavefront stores (raw bytes, not pixels) into a per-task scratch ring of NWD rows; the wavefronts run
+//     as a pipeline on LDS progress words, as the NWD template of png_kernel.inc does;
+//   - sub-byte unpacking, 16 -> 8 reduction, the tRNS key, the palette lookup and the strided Adam7 store happen
+//     after the de-filter, in registers.
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_kernel.inc in front of it.
+
+#define PNG_SPEC_NWD 4u
+#define PNG_SPEC_BLOCK 8u                         /* macro-steps per load phase                                    */
+#define PNG_SPEC_QUADS (PNG_SPEC_BLOCK + 1u)      /* 16 B pieces per row and phase: 8 groups of <= 16 B + alignment */
+#define PNG_SPEC_ROW_DW (4u * PNG_SPEC_QUADS)     /* 36 dwords: an odd number of quads, b128 reads conflict-free   */
+
+struct __attribute__((aligned(16))) PngSpecLds {
+    uint32_t tile[PNG_SPEC_NWD][64 * PNG_SPEC_ROW_DW]; /* raw row bytes, one row per lane          */
+    uint32_t uptile[PNG_SPEC_NWD][PNG_SPEC_BLOCK * 4]; /* lane 0: the de-filtered row above the band */
+    uint32_t pal[256];                                 /* RGBA, tRNS alpha folded in                 */
+    uint32_t progress[PNG_SPEC_NWD];                   /* band * (ngroups + 1) + groups of its last row in the scratch ring */
+    uint32_t first_bad;                                /* first row whose filter byte is > 4         */
+    uint32_t pal_bad;                                  /* a palette index >= the number of entries   */
+};
+
+// units per group: 8..16 bytes, a multiple of 4 (the scratch row and the tile are addressed in dwords)
+template <int BPP> struct PngSpecShape {
+    static constexpr uint32_t K = BPP == 1 ? 8u : BPP <= 4 ? 4u : 2u;
+    static constexpr uint32_t GB = K * (uint32_t)BPP; /* bytes per group: 8, 8, 12, 16, 12, 16 */
+    static constexpr uint32_t GD = GB / 4u;           /* dwords per group                      */
+    static constexpr uint32_t ND = BPP > 4 ? 2u : 1u; /* dwords per unit                       */
+};
+
+// nb (<= 4) bytes at byte offset off of the dword array d (d has one dword of padding)
+DEV_INLINE uint32_t spec_get(const uint32_t *d, uint32_t off, uint32_t nb)
+{
+    const uint32_t w = off >> 2, s = off & 3u;
+    const uint32_t x = s ? (d[w] >> (8u * s)) | (d[w + 1] << (32u - 8u * s)) : d[w];
+    return nb >= 4u ? x : x & ((1u << (8u * nb)) - 1u);
+}
+DEV_INLINE void spec_put(uint32_t *d, uint32_t off, uint32_t v)
+{
+    const uint32_t w = off >> 2, s = off & 3u;
+    d[w] |= v << (8u * s);
+    if (s) d[w + 1] |= v >> (32u - 8u * s);
+}
+
+// one group, serial in x: a = my previous unit, c = the previous "up" unit (both carried from group to group)
+template <int BPP, int FT>
+DEV_INLINE void spec_defilter_group(const uint32_t *v, const uint32_t *u, uint32_t *a, uint32_t *c, uint32_t *r)
+{
+    typedef PngSpecShape<BPP> S;
+DEV_UNROLL
+    for (uint32_t i = 0; i <= S::GD; i++) r[i] = 0u;
+DEV_UNROLL
+    for (uint32_t j = 0; j < S::K; j++) {
+DEV_UNROLL
+        for (uint32_t d = 0; d < S::ND; d++) {
+            const uint32_t off = j * (uint32_t)BPP + 4u * d;
+            const uint32_t nb = (uint32_t)BPP - 4u * d < 4u ? (uint32_t)BPP - 4u * d : 4u;
+            const uint32_t vb = spec_get(v, off, nb), ub = spec_get(u, off, nb);
+            const PkPx x = pk_defilter<FT>(pk_split(vb), pk_split(a[d]), pk_split(ub), pk_split(c[d]));
+            a[d] = pk_join(x);
+            c[d] = ub;
+            spec_put(r, off, a[d]);
+        }
+    }
+}
+
+// one pixel of a unit of >= 8-bit samples (bytes in stream order, lo = bytes 0..3, hi = bytes 4..7)
+DEV_INLINE uint32_t spec_pixel(uint32_t lo, uint32_t hi, uint32_t ct, uint32_t depth, const debig_png_spec_task &t,
+                               const uint32_t *pal, uint32_t &pal_bad)
+{
+    const uint32_t b0 = lo & 0xffu, b1 = (lo >> 8) & 0xffu, b2 = (lo >> 16) & 0xffu, b3 = lo >> 24;
+    const uint32_t b4 = hi & 0xffu, b5 = (hi >> 8) & 0xffu, b6 = (hi >> 16) & 0xffu;
+    if (depth == 16u) {
+        if (ct == 0u) {
+            const uint32_t a = t.has_key && ((b0 << 8) | b1) == t.key[0] ? 0u : 255u;
+            return b0 * 0x010101u | (a << 24);
+        }
+        if (ct == 2u) {
+            const uint32_t a = t.has_key && ((b0 << 8) | b1) == t.key[0] && ((b2 << 8) | b3) == t.key[1] &&
+                                       ((b4 << 8) | b5) == t.key[2] ? 0u : 255u;
+            return b0 | (b2 << 8) | (b4 << 16) | (a << 24);
+        }
+        if (ct == 4u) return b0 * 0x010101u | (b2 << 24);
+        return b0 | (b2 << 8) | (b4 << 16) | (b6 << 24); /* 6 */
+    }
+    if (ct == 0u) {
+        const uint32_t a = t.has_key && b0 == t.key[0] ? 0u : 255u;
+        return b0 * 0x010101u | (a << 24);
+    }
+    if (ct == 2u) {
+        const uint32_t a = t.has_key && b0 == t.key[0] && b1 == t.key[1] && b2 == t.key[2] ? 0u : 255u;
+        return b0 | (b1 << 8) | (b2 << 16) | (a << 24);
+    }
+    if (ct == 3u) {
+        pal_bad |= b0 >= t.n_pal;
+        return pal[b0];
+    }
+    if (ct == 4u) return b0 * 0x010101u | (b1 << 24);
+    return lo; /* 6 */
+}
+// one pixel of a 1-, 2- or 4-bit sample (colour types 0 and 3)
+DEV_INLINE uint32_t spec_pixel_sub(uint32_t s, uint32_t ct, uint32_t depth, const debig_png_spec_task &t, const uint32_t *pal,
+                                   uint32_t &pal_bad)
+{
+    if (ct == 3u) {
+        pal_bad |= s >= t.n_pal;
+        return pal[s];
+    }
+    const uint32_t g = s * (depth == 1u ? 255u : depth == 2u ? 85u : 17u);
+    const uint32_t a = t.has_key && s == t.key[0] ? 0u : 255u;
+    return g * 0x010101u | (a << 24);
+}
+
+template <int BPP>
+DEV_INLINE void png_spec_task(PngSpecLds &L, uint8_t *__restrict__ arena, uint8_t *__restrict__ rgba_arena,
+                              const debig_png_spec_task &t, const uint32_t tid)
+{
+    typedef PngSpecShape<BPP> S;
+    constexpr uint32_t K = S::K, GB = S::GB, GD = S::GD, ND = S::ND;
+    const uint32_t lane = tid & 63u, wv = tid >> 6;
+    uint32_t *tile = &L.tile[wv][lane * PNG_SPEC_ROW_DW];
+    uint32_t *uptile = L.uptile[wv];
+    const uint32_t w = t.width, h = t.height, ct = t.color_type, depth = t.depth;
+    const uint64_t rowb = ((uint64_t)w * t.channels * depth + 7u) / 8u;
+    const uint32_t ngroups = (uint32_t)((rowb + GB - 1u) / GB);
+    const uint32_t ppb = depth < 8u ? 8u / depth : 1u; /* pixels per byte (sub-byte samples) */
+    const uint64_t base_al = t.stream_off & ~(uint64_t)3;
+    const uint8_t *sbase = arena + base_al;
+    const int64_t stream_len_al = (int64_t)(t.stream_off & 3u) + (int64_t)h * (int64_t)(rowb + 1u);
+    const uint64_t pitch = ((uint64_t)ngroups * GB + 15u) & ~(uint64_t)15u; /* scratch ring: one row per wavefront */
+    uint32_t *ring = reinterpret_cast<uint32_t *>(arena + t.scratch_off);
+    uint8_t *out = rgba_arena + t.rgba_off;
+    uint32_t pal_bad = 0;
+    for (uint32_t band = wv; (uint64_t)band * 64u < h; band += PNG_SPEC_NWD) {
+        if (__any(*(volatile uint32_t *)&L.first_bad != 0xffffffffu)) break; /* another wavefront failed the image */
+        const uint32_t row = band * 64u + lane;
+        const int active = row < h;
+        const int64_t rs = (int64_t)(t.stream_off & 3u) + (int64_t)(active ? row : 0u) * (int64_t)(rowb + 1u); /* filter byte */
+        const uint32_t ft = active ? (uint32_t)sbase[rs] : 0u;
+        const unsigned long long badm = __ballot(active && ft > 4u);
+        if (badm) {
+            if (lane == 0) atomicMin(&L.first_bad, band * 64u + (uint32_t)(__ffsll(badm) - 1));
+            break;
+        }
+        const uint32_t row_sh = (uint32_t)((rs + 1) & 3);
+        const uint32_t *upring = ring + (pitch / 4u) * ((band + PNG_SPEC_NWD - 1u) % PNG_SPEC_NWD);
+        uint32_t *myring = ring + (pitch / 4u) * (band % PNG_SPEC_NWD);
+        const uint64_t out_y = (uint64_t)t.y0 + (uint64_t)(active ? row : 0u) * t.dy;
+        uint8_t *orow = out + (out_y * t.img_width + t.x0) * 4u;
+        const uint64_t ostep = 4u * (uint64_t)t.dx;
+        uint32_t R[GD + 1], a[ND], c[ND];
+DEV_UNROLL
+        for (uint32_t i = 0; i <= GD; i++) R[i] = 0u;
+DEV_UNROLL
+        for (uint32_t d = 0; d < ND; d++) a[d] = c[d] = 0u;
+        const uint32_t nsteps = ngroups + 63u;
+        int stop = 0;
+        for (uint32_t T0 = 0; T0 < nsteps && !stop; T0 += PNG_SPEC_BLOCK) {
+            png_wave_sync<(int)PNG_SPEC_NWD>();
+            if (band > 0) {
+                // the groups [T0, T0 + BLOCK) of the row above my band must be in the ring: poll its producer
+                const uint32_t prod = (wv + PNG_SPEC_NWD - 1u) % PNG_SPEC_NWD;
+                const uint32_t need_g = T0 + PNG_SPEC_BLOCK < ngroups ? T0 + PNG_SPEC_BLOCK : ngroups;
+                const uint32_t need = (band - 1u) * (ngroups + 1u) + need_g;
+                uint32_t spins = 0, fbv = 0xffffffffu;
+                for (;;) {
+                    const uint32_t have = *(volatile uint32_t *)&L.progress[prod];
+                    fbv = *(volatile uint32_t *)&L.first_bad;
+                    const int done = have >= need || fbv != 0xffffffffu || ++spins > (1u << 24);
+                    if (__all(done)) break;
+#ifndef DEBIG_EMU
+                    __builtin_amdgcn_s_sleep(4);
+#endif
+                }
+                const int timed_out = spins > (1u << 24);
+                if (__any(fbv != 0xffffffffu) || timed_out) {
+                    if (timed_out && lane == 0) atomicMin(&L.first_bad, 0xfffffffeu); /* internal guard: fail the image */
+                    stop = 1;
+                    continue;
+                }
+            }
+            {
+                // my row's groups T0 - lane .. + BLOCK - 1 as 16 B pieces; pieces that hold none of the bytes I need are 0
+                const int64_t gbase = (int64_t)T0 - (int64_t)lane;
+                const int64_t need_lo = rs + 1 + (gbase > 0 ? gbase : 0) * (int64_t)GB;
+                const int64_t o0 = (rs + 1 + gbase * (int64_t)GB) & ~(int64_t)3;
+                PngQuad q[PNG_SPEC_QUADS];
+                uint32_t okm = 0;
+DEV_UNROLL
+                for (uint32_t c4 = 0; c4 < PNG_SPEC_QUADS; c4++) {
+                    const int64_t po = o0 + 16 * (int64_t)c4;
+                    const int ok = active && po + 16 > need_lo && po < stream_len_al;
+                    okm |= (uint32_t)ok << c4;
+                    q[c4] = png_ld_quad<false>(sbase + (ok ? po : rs));
+                }
+                PNG_ISSUE_BARRIER();
+DEV_UNROLL
+                for (uint32_t c4 = 0; c4 < PNG_SPEC_QUADS; c4++) {
+                    const int ok = (int)((okm >> c4) & 1u);
+                    uint4 v;
+                    v.x = ok ? q[c4].x : 0u; v.y = ok ? q[c4].y : 0u; v.z = ok ? q[c4].z : 0u; v.w = ok ? q[c4].w : 0u;
+                    *reinterpret_cast<uint4 *>(&tile[4u * c4]) = v;
+                }
+                if (band > 0 && lane < PNG_SPEC_BLOCK) { /* lane 0's "up" groups T0 .. T0 + BLOCK - 1 */
+                    const uint32_t gq = T0 + lane;
+DEV_UNROLL
+                    for (uint32_t i = 0; i < GD; i++) uptile[lane * GD + i] = gq < ngroups ? ld_hist_u32(upring + gq * GD + i) : 0u;
+                }
+            }
+            png_wave_sync<(int)PNG_SPEC_NWD>();
+            const uint32_t kend = nsteps - T0 < PNG_SPEC_BLOCK ? nsteps - T0 : PNG_SPEC_BLOCK;
+            for (uint32_t k = 0; k < kend; k++) {
+                const int g = (int)(T0 + k) - (int)lane;
+                const int valid = active && g >= 0 && g < (int)ngroups;
+                uint32_t U[GD + 1], V[GD + 1];
+DEV_UNROLL
+                for (uint32_t i = 0; i < GD; i++) U[i] = png_lane_above(R[i]);
+                U[GD] = 0u;
+                if (lane == 0) {
+DEV_UNROLL
+                    for (uint32_t i = 0; i < GD; i++) U[i] = band > 0 ? uptile[k * GD + i] : 0u;
+                }
+                if (valid) {
+DEV_UNROLL
+                    for (uint32_t i = 0; i < GD; i++) V[i] = png_funnel(tile[k * GD + i + 1u], tile[k * GD + i], row_sh);
+                    V[GD] = 0u;
+                    if (g == 0) {
+DEV_UNROLL
+                        for (uint32_t d = 0; d < ND; d++) a[d] = c[d] = 0u;
+                    }
+                    switch (ft) { /* per row, i.e. per lane */
+                    case 0: spec_defilter_group<BPP, 0>(V, U, a, c, R); break;
+                    case 1: spec_defilter_group<BPP, 1>(V, U, a, c, R); break;
+                    case 2: spec_defilter_group<BPP, 2>(V, U, a, c, R); break;
+                    case 3: spec_defilter_group<BPP, 3>(V, U, a, c, R); break;
+                    default: spec_defilter_group<BPP, 4>(V, U, a, c, R); break;
+                    }
+                    if (lane == 63u) { /* the row the band below starts from */
+DEV_UNROLL
+                        for (uint32_t i = 0; i < GD; i++) myring[(uint32_t)g * GD + i] = R[i];
+                    }
+                    // ---- pixels: unpack / reduce / key / palette, strided Adam7 store
+                    if (BPP == 1 && depth < 8u) {
+                        const uint32_t mask = (1u << depth) - 1u;
+DEV_UNROLL
+                        for (uint32_t j = 0; j < K; j++) {
+                            const uint32_t byte = spec_get(R, j, 1u);
+                            const uint64_t xb = ((uint64_t)g * K + j) * ppb;
+                            for (uint32_t s = 0; s < ppb; s++) {
+                                if (xb + s >= w) break;
+                                const uint32_t smp = (byte >> (8u - depth * (s + 1u))) & mask;
+                                const uint32_t px = spec_pixel_sub(smp, ct, depth, t, L.pal, pal_bad);
+                                *reinterpret_cast<uint32_t *>(orow + (xb + s) * ostep) = px;
+                            }
+                        }
+                    } else {
+DEV_UNROLL
+                        for (uint32_t j = 0; j < K; j++) {
+                            const uint64_t x = (uint64_t)g * K + j;
+                            if (x >= w) break;
+                            const uint32_t lo = spec_get(R, j * (uint32_t)BPP, BPP < 4 ? (uint32_t)BPP : 4u);
+                            const uint32_t hi = BPP > 4 ? spec_get(R, j * (uint32_t)BPP + 4u, (uint32_t)BPP - 4u) : 0u;
+                            *reinterpret_cast<uint32_t *>(orow + x * ostep) = spec_pixel(lo, hi, ct, depth, t, L.pal, pal_bad);
+                        }
+                    }
+                }
+            }
+            // publish: after this block lane 63 has put the groups below T0 + kend - 63 into the ring
+            wave_mem_fence();
+            const int done_g = (int)(T0 + kend) - 63;
+            const uint32_t g63 = done_g < 0 ? 0u : ((uint32_t)done_g > ngroups ? ngroups : (uint32_t)done_g);
+            if (lane == 0) *(volatile uint32_t *)&L.progress[wv] = band * (ngroups + 1u) + g63;
+        }
+        if (stop) break;
+    }
+    if (__any(pal_bad != 0u) && lane == 0) atomicOr(&L.pal_bad, 1u);
+}
+
+__global__ void __launch_bounds__(64 * PNG_SPEC_NWD)
+debig_png_spec_defilter_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict__ rgba_arena,
+                               const debig_png_spec_task *__restrict__ tasks, debig_png_spec_result *__restrict__ results,
+                               uint32_t n_tasks)
+{
+    __shared__ PngSpecLds L;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = blockIdx.x; k < n_tasks; k += gridDim.x) {
+        const debig_png_spec_task t = tasks[k];
+        if (t.color_type == 3u) {
+            const uint32_t *pal = reinterpret_cast<const uint32_t *>(arena + t.pal_off);
+            for (uint32_t i = tid; i < 256u; i += 64u * PNG_SPEC_NWD) L.pal[i] = pal[i];
+        }
+        if (tid < PNG_SPEC_NWD) L.progress[tid] = 0u;
+        if (tid == 0) { L.first_bad = 0xffffffffu; L.pal_bad = 0u; }
+        __syncthreads();
+        switch (t.bpp_f) { /* workgroup-uniform */
+        case 1: png_spec_task<1>(L, arena, rgba_arena, t, tid); break;
+        case 2: png_spec_task<2>(L, arena, rgba_arena, t, tid); break;
+        case 3: png_spec_task<3>(L, arena, rgba_arena, t, tid); break;
+        case 4: png_spec_task<4>(L, arena, rgba_arena, t, tid); break;
+        case 6: png_spec_task<6>(L, arena, rgba_arena, t, tid); break;
+        case 8: png_spec_task<8>(L, arena, rgba_arena, t, tid); break;
+        default: if (tid == 0) L.first_bad = 0xfffffffeu; break;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const uint32_t fb = L.first_bad;
+            results[k].status = fb != 0xffffffffu ? DEBIG_PNG_SPEC_E_FILTER : L.pal_bad ? DEBIG_PNG_SPEC_E_PALETTE : 0u;
+            results[k].bad_row = fb;
+        }
+        __syncthreads();
+    }
+}

@@ -293,6 +293,39 @@ int debig_hip_png_decode_fused_batch(const void *d_in, void *d_streams_arena, co
                                      debig_png_result *d_png_results, uint32_t n, void *d_workspace,
                                      uint64_t workspace_bytes, void *hip_stream);
 
+/* One task of the general de-filter (csrc/png_spec_kernel.inc, behind debig_png_decode_batch in decode_png.h): one
+ * (image, Adam7 pass) sub-image of ANY colour type / bit depth the PNG specification allows -> RGBA8 pixels of the
+ * full image at (x0 + x dx, y0 + y dy).  A non-interlaced image is one task at (0, 0, 1, 1). */
+typedef struct debig_png_spec_task {
+    uint64_t stream_off;  /* first filter byte of the sub-image's h * (1 + rowbytes) scanline bytes, rel. to d_arena (>= 16) */
+    uint64_t rgba_off;    /* the FULL image's 4 * img_width * img_height output, rel. to d_rgba_arena (4-byte aligned) */
+    uint64_t pal_off;     /* colour type 3: 256 RGBA dwords (tRNS alpha folded in), rel. to d_arena (4-byte aligned)     */
+    uint64_t scratch_off; /* DEBIG_PNG_SPEC_SCRATCH_BYTES(...) of scratch, rel. to d_arena (16-byte aligned)             */
+    uint32_t width, height; /* of the sub-image (w_p, h_p >= 1)                                                          */
+    uint32_t img_width;     /* row pitch of the output in pixels                                                         */
+    uint32_t x0, y0, dx, dy;
+    uint8_t bpp_f;          /* filter unit max(1, channels * depth / 8): 1, 2, 3, 4, 6 or 8                              */
+    uint8_t depth, color_type, channels;
+    uint16_t key[3];        /* tRNS key (colour type 0: key[0]; 2: RGB), raw samples at full depth                      */
+    uint16_t has_key;
+    uint16_t n_pal;         /* palette entries; an index >= n_pal fails the task with DEBIG_PNG_SPEC_E_PALETTE           */
+    uint16_t reserved16;
+    uint32_t reserved;
+} debig_png_spec_task;
+
+typedef struct debig_png_spec_result {
+    uint32_t status;  /* 0, DEBIG_PNG_SPEC_E_FILTER or DEBIG_PNG_SPEC_E_PALETTE */
+    uint32_t bad_row; /* first row of the sub-image whose filter byte is > 4 (E_FILTER) */
+} debig_png_spec_result;
+enum { DEBIG_PNG_SPEC_E_FILTER = 1, DEBIG_PNG_SPEC_E_PALETTE = 2 };
+/* scratch of one task: the ring of de-filtered rows handed from band to band (4 rows of 16-byte groups) */
+#define DEBIG_PNG_SPEC_SCRATCH_BYTES(rowbytes) (4u * ((((uint64_t)(rowbytes) + 15u) / 16u) * 16u + 16u))
+
+/* De-filter n tasks (device pointers, asynchronous on hip_stream): one workgroup of four wavefronts per task.  d_arena
+ * must stay readable for 16 bytes past the end of every task's scanline bytes (rows are fetched as 16-byte pieces). */
+int debig_hip_png_spec_defilter_batch(void *d_arena, void *d_rgba_arena, const debig_png_spec_task *d_tasks,
+                                      debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

@@ -65,6 +65,69 @@ int debig_png_probe(const uint8_t *compressed_input, const uint64_t compressed_i
                     uint32_t *out_width, uint32_t *out_height, uint64_t *out_recipient_size,
                     uint64_t *out_zlib_size);
 
+/* ---- beyond the reference: spec-complete PNG batch decode ------------------------------
+ * decode_png() / debig_decode_png_batch above keep the reference's rules (colour types 2, 3, 6 at 8 bits, no
+ * interlacing, tRNS ignored, its P2 / P3 quirks unless DEBIG_STRICT=1).  debig_png_decode_batch decodes every PNG the
+ * specification allows to RGBA8 (4*w*h bytes, top-down, row-major):
+ *   - signature: all 8 bytes;
+ *   - chunks: IHDR first (exactly once); PLTE before the first IDAT; the IDAT chunks consecutive; IEND required, anything
+ *     after it ignored; an unknown critical chunk (first letter upper case) -> E_CHUNK, unknown ancillary chunks are
+ *     skipped; a chunk that runs past the end of the file -> E_CHUNK; the CRC of every chunk up to IEND is checked on
+ *     the GPU -> E_CRC;
+ *   - IHDR (13 bytes): (colour type, depth) in 0: 1 2 4 8 16 | 2: 8 16 | 3: 1 2 4 8 | 4: 8 16 | 6: 8 16; compression 0,
+ *     filter 0, interlace 0 or 1; 1 <= w, h <= 2^31 - 1; anything else -> E_IHDR.  out_caps[i] < 4wh -> E_OUTPUT;
+ *   - PLTE: required for colour type 3 and forbidden for 0 and 4 (E_CHUNK), ignored for 2 and 6; 1..256 entries,
+ *     length a multiple of 3, else E_PALETTE; a palette index >= the number of entries -> E_PALETTE (found on the GPU);
+ *   - tRNS (before the first IDAT): colour type 3: one alpha per palette entry, entries it does not cover get 255;
+ *     0: a 16-bit grey key, 2: an RGB key, compared against the raw sample at full depth (a match: alpha 0).  A tRNS
+ *     of the wrong length, before PLTE, or on colour type 4 / 6 is ignored;
+ *   - zlib: CM = 8, CINFO <= 7, FCHECK, no FDICT, else E_ZLIB.  The IDAT payloads are concatenated on the device and
+ *     inflated as plain RFC 1951 into exactly the scanline stream's size (per non-empty Adam7 pass
+ *     h_p * (1 + ceil(w_p * channels * depth / 8))): output past it -> E_DATA_LONG, short of it -> E_DATA_SHORT, any
+ *     other inflate failure -> E_INFLATE.  The Adler-32 trailer (at ceil(in_end_bits / 8)) is verified on the GPU;
+ *     missing or wrong -> E_ADLER.  Bytes after the trailer are ignored;
+ *     (The inflate is the library's shared one: a block of the reserved type 3 is skipped there, as by the
+ *     reference, so such a stream ends in E_DATA_SHORT or E_ADLER rather than E_INFLATE.)
+ *   - pixels: a filter type > 4 -> E_FILTER; 16-bit samples reduce to their high byte; 1/2/4-bit grey scales by
+ *     255/85/17; sub-byte samples are packed MSB first, every row starts on a byte boundary; grey -> (g, g, g, a).
+ *     Adam7 passes (x0, y0, dx, dy) = (0,0,8,8) (4,0,8,8) (0,4,4,8) (2,0,4,4) (0,2,2,4) (1,0,2,2) (0,1,1,2).
+ * Statuses are decided in this order: the chunk walk (in file order), missing PLTE / IDAT / IEND, zlib header, E_OUTPUT,
+ * CRC, inflate, Adler-32, filter types, palette indices.  On error outs[i] is unspecified; other files are not affected.
+ * Routing: non-interlaced 8-bit colour type 6, and 2 without a tRNS key, go through the tuned de-filter kernels of
+ * debig_decode_png_batch (spec output); everything else through the general kernel (debig_hip_png_spec_defilter_batch).
+ * DEBIG_PNG_FORCE_GENERAL sends every file through the general kernel (tests, measurements).
+ * Returns 0 or a device error code (then every status is unspecified). */
+typedef struct debig_png_info {
+    uint32_t width, height;
+    uint8_t bit_depth, color_type, interlace, has_trns;
+    uint32_t reserved;
+} debig_png_info;
+
+enum {
+    DEBIG_PNG_OK = 0,
+    DEBIG_PNG_E_SIGNATURE = 1,  /* not the 8-byte PNG signature                                 */
+    DEBIG_PNG_E_CHUNK = 2,      /* chunk layout / order, unknown critical chunk, truncated file   */
+    DEBIG_PNG_E_IHDR = 3,       /* IHDR length or field values                                    */
+    DEBIG_PNG_E_CRC = 4,        /* a chunk's CRC-32                                               */
+    DEBIG_PNG_E_ZLIB = 5,       /* zlib header                                                    */
+    DEBIG_PNG_E_INFLATE = 6,    /* the DEFLATE stream is damaged                                  */
+    DEBIG_PNG_E_ADLER = 7,      /* Adler-32 trailer missing or wrong                              */
+    DEBIG_PNG_E_DATA_SHORT = 8, /* the stream ends before the scanlines do                        */
+    DEBIG_PNG_E_DATA_LONG = 9,  /* the stream holds more than the scanlines                       */
+    DEBIG_PNG_E_FILTER = 10,    /* a filter type > 4                                              */
+    DEBIG_PNG_E_PALETTE = 11,   /* PLTE length, or a palette index past its entries               */
+    DEBIG_PNG_E_OUTPUT = 12     /* out_caps[i] < 4wh (or outs[i] NULL)                            */
+};
+
+/* Host only: signature, IHDR and the chunks up to the first IDAT -> *info (for sizing outs).  DEBIG_PNG_OK or the
+ * status of the first rule broken there; info is filled as far as it was read. */
+uint32_t debig_png_info_get(const uint8_t *p, uint64_t size, debig_png_info *info);
+
+#define DEBIG_PNG_FORCE_GENERAL 1u /* test / measurements: every image through the general kernel */
+int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                           const uint64_t *out_caps, uint32_t *status, debig_png_info *infos /* may be NULL */,
+                           uint32_t n, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

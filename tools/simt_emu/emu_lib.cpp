@@ -14,6 +14,7 @@
 #include "../../debigulator_amd/csrc/inflate_chunk_kernel.inc"
 #include "../../debigulator_amd/csrc/png_kernel.inc"
 #include "../../debigulator_amd/csrc/png_fused_kernel.inc"
+#include "../../debigulator_amd/csrc/png_spec_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -297,5 +298,13 @@ extern "C" int emu_checksum_batch(const void *arena, const debig_span *spans, ui
         EMU_LAUNCH(debig_checksum_tables_kernel, 1, CK_THREADS, t);
     }
     EMU_LAUNCH(debig_checksum_kernel, n, CK_THREADS, (const uint8_t *)arena, spans, out, n, kind, t);
+    return 0;
+}
+
+/* the general de-filter (png_spec_kernel.inc) as debig_hip_png_spec_defilter_batch launches it */
+extern "C" int emu_png_spec_defilter_batch(void *arena, void *rgba_arena, const debig_png_spec_task *tasks,
+                                           debig_png_spec_result *results, uint32_t n)
+{
+    if (n) EMU_LAUNCH(debig_png_spec_defilter_kernel, n, 64 * PNG_SPEC_NWD, (uint8_t *)arena, (uint8_t *)rgba_arena, tasks, results, n);
     return 0;
 }
