@@ -211,10 +211,6 @@ static DefaultWs *default_workspace(hipStream_t s)
     return w;
 }
 
-// one group of at most SPLIT_GROUP streams: plan, scan, lz, and debig_inflate_kernel for what the
-// pair handed back.  Returns 0, a hipError_t, or -1 when the workspace is too small to try.
-// what = 1: carve the workspace only (debig_split_plan_kernel), 2: scan + lz + hand-back over a
-// workspace already carved for exactly these descriptors, 3: both (one call does everything)
 // workgroups of debig_scanlz_queue_kernel the current device holds at once (per device, asked once)
 static uint32_t scanlz_resident_workgroups()
 {
@@ -255,6 +251,10 @@ static uint32_t pipe_big_tile_streams()
     return cap[dev];
 }
 
+// one group of at most SPLIT_GROUP streams: plan, scan, lz, and debig_inflate_kernel for what the
+// pair handed back.  Returns 0, a hipError_t, or -1 when the workspace is too small to try.
+// what = 1: carve the workspace only (debig_split_plan_kernel), 2: scan + lz + hand-back over a
+// workspace already carved for exactly these descriptors, 3: both (one call does everything)
 static int launch_split_group(hipStream_t s, const void *d_in, void *d_out, const debig_stream *d_streams,
                               debig_result *d_results, uint32_t n, const FixedTabs *tabs, void *ws, uint64_t ws_bytes,
                               int what = 3, int queued = 0)
@@ -271,10 +271,6 @@ static int launch_split_group(hipStream_t s, const void *d_in, void *d_out, cons
     if (what & 1)
         hipLaunchKernelGGL(debig_split_plan_kernel, dim3(1), dim3(1024), 0, s, d_streams, n, slots, total_rows, total_recs);
     if (!(what & 2)) return (int)hipGetLastError();
-#ifndef DEBIG_SPLIT_FUSED
-#define DEBIG_SPLIT_FUSED 1
-#endif
-#if DEBIG_SPLIT_FUSED
     const uint32_t cap = queued == 1 ? scanlz_resident_workgroups() : 0u;
     if (queued == 3) /* DEBIG_WAVES_STRAND_PIPE: the same two halves on two wavefronts of a workgroup, record by record */
     {   /* a 12 KB LZ77 tile while the device holds every stream at once with it (29 KB of LDS: 5 workgroups per CU) */
@@ -294,12 +290,6 @@ static int launch_split_group(hipStream_t s, const void *d_in, void *d_out, cons
     else
         hipLaunchKernelGGL(debig_scanlz_kernel, dim3(n), dim3(64), 0, s, (const uint8_t *)d_in, (uint8_t *)d_out, d_streams, n,
                            tabs->scan, slots, recs, rows, d_results);
-#else
-    hipLaunchKernelGGL(debig_scan_kernel, dim3(n), dim3(64), 0, s, (const uint8_t *)d_in, (uint8_t *)d_out, d_streams, n,
-                       tabs->scan, slots, recs, rows, d_results);
-    hipLaunchKernelGGL(debig_lz_kernel, dim3(n), dim3(64), 0, s, (uint8_t *)d_out, d_streams, d_results, n,
-                       (const debig_ws_slot *)slots, (const debig_ws_rec *)recs, (const uint32_t *)rows);
-#endif
     hipLaunchKernelGGL(debig_inflate_kernel, dim3(n), dim3(64), 0, s, (const uint8_t *)d_in, (uint8_t *)d_out, d_streams,
                        d_results, n, tabs->one, DEBIG_CLASS_RETRY);
     return (int)hipGetLastError();
@@ -607,15 +597,14 @@ static uint32_t mwg_resident_workgroups(int dev, uint32_t wpw)
     if (e && *e) return (uint32_t)strtoul(e, nullptr, 0);
     if (dev < 0 || dev >= 64) return 0u;
     static std::mutex m;
-    static uint32_t cap[64][3]; /* wpw = 2, 4, 8 */
-    const int k = wpw == 2u ? 0 : wpw == 4u ? 1 : 2;
+    static uint32_t cap[64][2]; /* wpw = 4, 8 */
+    const int k = wpw == 4u ? 0 : 1;
     std::lock_guard<std::mutex> lock(m);
     if (cap[dev][k] == 0) {
         DeviceGuard guard(dev);
         int per_cu = 0, cus = 0;
-        hipError_t rc = k == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, debig_png_defilter_kernel<2, 16, true>, 128, 0)
-                        : k == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, debig_png_defilter_kernel<4, 16, true>, 256, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, debig_png_defilter_kernel<8, 16, true>, 512, 0);
+        hipError_t rc = k == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, debig_png_defilter_kernel<4, 16, true, true>, 256, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, debig_png_defilter_kernel<8, 16, true, true>, 512, 0);
         if (rc != hipSuccess || per_cu <= 0) per_cu = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 0;
         // one workgroup per CU is what the measured shapes assume (and what 8 wavefronts' LDS allows); a device
@@ -634,21 +623,15 @@ int debig_hip_png_defilter_batch(const void *d_streams_arena, void *d_rgba_arena
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream)); /* kernels go to the stream's device */
     const uint32_t nwd = defilter_waves(n);
     hipStream_t s = (hipStream_t)hip_stream;
-    // few images: an image on several workgroups (CUs).  G workgroups of 4 wavefronts per image; all of
+    // few images: an image on several workgroups (CUs).  G workgroups of 4 or 8 wavefronts per image; all of
     // them must be resident together (87 KB of LDS: one per CU), so n * G stays within the CU count.
-    // DEBIG_DEFILTER_WGS = 1 turns it off, 2 / 4 / 8 force G (measurements).
+    // DEBIG_DEFILTER_WGS = 1 turns it off, 2 / 4 / 8 force G (tests, measurements).
     {
         static std::once_flag once;
-        static uint32_t env_g = 0, env_w = 0, env_blk = 0, env_px = 1;
+        static uint32_t env_g = 0;
         std::call_once(once, [] {
-            const char *ep = getenv("DEBIG_DEFILTER_PXSKEW"); /* 0: the group-skew step (measurements) */
-            if (ep && *ep) env_px = (uint32_t)strtoul(ep, nullptr, 0);
-            const char *eb = getenv("DEBIG_DEFILTER_BLK");
-            if (eb && *eb) env_blk = (uint32_t)strtoul(eb, nullptr, 0);
             const char *e = getenv("DEBIG_DEFILTER_WGS");
             if (e && *e) env_g = (uint32_t)strtoul(e, nullptr, 0);
-            e = getenv("DEBIG_DEFILTER_WG_WAVES"); /* 2 | 4 | 8 wavefronts per workgroup in that mode (measurements) */
-            if (e && *e) env_w = (uint32_t)strtoul(e, nullptr, 0);
         });
         // measured, 8192 x 8192 images (profiles/r03_defilter_wgs.txt): 32 images 43.6 -> 17.0 ms with 8 x 4
         // wavefronts, 64 images 46.6 -> 25.4 with 4 x 4, 128 images 54.6 -> 36.2 with 2 x 8
@@ -658,9 +641,8 @@ int debig_hip_png_defilter_batch(const void *d_streams_arena, void *d_rgba_arena
         // (and with the predictor of a row selected by masks in the 4-wavefront kernel: 16 images 7.4 ms, 32 images 11.2 ms
         // with 8 x 4 -- two wavefronts per SIMD prefer the branches and lose to it: 13.0)
         uint32_t g = n <= 16u ? 16u : n <= 32u ? 8u : n <= 64u ? 4u : n <= 128u ? 2u : 1u;
-        uint32_t wpw = n <= 32u ? 4u : 8u;
+        const uint32_t wpw = n <= 32u ? 4u : 8u;
         if (env_g) g = env_g;
-        if (env_w == 2u || env_w == 4u || env_w == 8u) wpw = env_w;
         if (g > 16u) g = 16u;
         if (g * wpw > PNG_GSYNC_STRIDE - 16u) g = (PNG_GSYNC_STRIDE - 16u) / wpw; /* progress words per image */
         // all n * G workgroups must be resident TOGETHER (the bands of an image are a ring of dependencies): the limit
@@ -677,26 +659,12 @@ int debig_hip_png_defilter_batch(const void *d_streams_arena, void *d_rgba_arena
             uint32_t *gsync = (uint32_t *)gw->ptr;
             hipError_t e = hipMemsetAsync(gsync, 0, (size_t)n * PNG_GSYNC_STRIDE * sizeof(uint32_t), s);
             if (e != hipSuccess) return (int)e;
-            if (wpw == 8u && env_px != 0u)
+            // lanes one PIXEL behind the row above (png_kernel.inc "PX"): the band below follows 32 macro-steps behind, not 79
+            if (wpw == 8u)
                 hipLaunchKernelGGL((debig_png_defilter_kernel<8, 16, true, true>), dim3(n * g), dim3(512), 0, s,
                                    (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images, d_results, n, g, gsync, 0u);
-            else if (wpw == 8u)
-                hipLaunchKernelGGL((debig_png_defilter_kernel<8, 16, true>), dim3(n * g), dim3(512), 0, s,
-                                   (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images, d_results, n, g, gsync, 0u);
-            else if (wpw == 2u)
-                hipLaunchKernelGGL((debig_png_defilter_kernel<2, 16, true>), dim3(n * g), dim3(128), 0, s,
-                                   (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images, d_results, n, g, gsync, 0u);
-            else if (env_blk == 32u) /* measurements: macro-steps per load phase (the share of the load phases in a band) */
-                hipLaunchKernelGGL((debig_png_defilter_kernel<4, 32, true>), dim3(n * g), dim3(256), 0, s,
-                                   (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images, d_results, n, g, gsync, 0u);
-            else if (env_blk == 8u)
-                hipLaunchKernelGGL((debig_png_defilter_kernel<4, 8, true>), dim3(n * g), dim3(256), 0, s,
-                                   (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images, d_results, n, g, gsync, 0u);
-            else if (env_px != 0u) /* lanes one PIXEL behind the row above (png_kernel.inc "PX"): the band below follows 32 macro-steps behind, not 79 */
-                hipLaunchKernelGGL((debig_png_defilter_kernel<4, 16, true, true>), dim3(n * g), dim3(256), 0, s,
-                                   (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images, d_results, n, g, gsync, 0u);
             else
-                hipLaunchKernelGGL((debig_png_defilter_kernel<4, 16, true>), dim3(n * g), dim3(256), 0, s,
+                hipLaunchKernelGGL((debig_png_defilter_kernel<4, 16, true, true>), dim3(n * g), dim3(256), 0, s,
                                    (const uint8_t *)d_streams_arena, (uint8_t *)d_rgba_arena, d_images, d_results, n, g, gsync, 0u);
             // Residency is the runtime's promise, not a guarantee (another stream's kernels may hold LDS when this
             // grid starts): a workgroup that waited in vain gave its image up as REDO after some tens of milliseconds,

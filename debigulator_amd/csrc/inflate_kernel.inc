@@ -207,7 +207,9 @@ template <int NW> DEV_INLINE uint32_t group_tid() { return threadIdx.x & (64u * 
 
 // Release / acquire of LDS data handed from one wavefront of the workgroup to another through
 // the pending-byte bitmap (resolve_matches): copied tile bytes must be visible before their
-// pending bits drop, and a reader that saw the bits clear must read the bytes after that.
+// pending bits drop, and a reader that saw the bits clear must read the bytes after that.  (Measured,
+// profiles/r04_mw_light_sync.txt: ordering them by the compiler alone, without the waits, has no effect
+// on any workload -- the waits are implied by the rounds' data dependencies anyway.)
 DEV_INLINE void lds_release_workgroup()
 {
 #ifndef DEBIG_EMU
@@ -218,25 +220,6 @@ DEV_INLINE void lds_acquire_workgroup()
 {
 #ifndef DEBIG_EMU
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#endif
-}
-
-// Ordering of LDS traffic WITHOUT waiting for it.  The LDS executes the DS instructions of a wavefront in the order they
-// were issued (lgkmcnt counts them down in order), and every wavefront of the workgroup talks to the same LDS: a store
-// issued before an atomic that drops a pending bit has happened before any other wavefront can see the bit dropped, and
-// a load issued behind the load that saw it dropped reads what that store left.  Nothing has to DRAIN for that -- a
-// workgroup-scope fence does drain (s_waitcnt vmcnt(0) lgkmcnt(0): the tile flush's stores in flight as well) -- only
-// the compiler must keep the order.  (The emulator's lanes are fibers: there this is a rendezvous.)
-#ifndef DEBIG_MW_LIGHT_SYNC
-#define DEBIG_MW_LIGHT_SYNC 0 /* measured (profiles/r04_mw_light_sync.txt): no effect on any workload -- the waits are implied by
-                                 the rounds' data dependencies anyway; the fences stay */
-#endif
-DEV_INLINE void wave_order()
-{
-#ifdef DEBIG_EMU
-    __wave_barrier();
-#else
-    asm volatile("" ::: "memory");
 #endif
 }
 
@@ -1219,8 +1202,7 @@ template <class LDS> DEV_INLINE int resolve_matches(LDS &S, OutState &O, uint32_
                 next = next + nfree < total ? next + nfree : total;
             }
             if (!__any(pending)) break;
-            if (DEBIG_MW_LIGHT_SYNC) wave_order();
-            else wave_sync<NW>(); /* copies and cleared bits of the previous round are visible */
+            wave_sync<NW>(); /* copies and cleared bits of the previous round are visible */
             const int ready = pending && !pend_any(S, chk_p, chk_n);
             if (!__any(ready)) {
                 // NW > 1: every source still belongs to another wavefront -- poll.  (With one
@@ -1235,8 +1217,7 @@ template <class LDS> DEV_INLINE int resolve_matches(LDS &S, OutState &O, uint32_
                 continue;
             }
             idle = 0;
-            if (DEBIG_MW_LIGHT_SYNC) wave_order();
-            else lds_acquire_workgroup(); /* the source bytes behind the cleared bits */
+            lds_acquire_workgroup(); /* the source bytes behind the cleared bits */
             const int src_in_lds = src_rel >= lds_rel0;
             const int simple = ready && len <= 16u && dist >= len;
             // (a) short, non-overlapping, source in the tile: by the lane itself
@@ -1253,11 +1234,8 @@ template <class LDS> DEV_INLINE int resolve_matches(LDS &S, OutState &O, uint32_
                 const uint32_t ld = wave_bcast_u32(dist, (uint32_t)sl);
                 copy_match_wave(S, O, lp, ll, ld);
             }
-            if (DEBIG_MW_LIGHT_SYNC) wave_order(); /* the copies are issued before the atomics that drop their pending bits */
-            else {
-                wave_sync<NW>(); /* the copied bytes are in LDS before their pending bits drop */
-                lds_release_workgroup();
-            }
+            wave_sync<NW>(); /* the copied bytes are in LDS before their pending bits drop */
+            lds_release_workgroup();
             if (ready) {
                 pend_clear(S, p, len);
                 pending = 0;

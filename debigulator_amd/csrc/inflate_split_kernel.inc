@@ -1,25 +1,25 @@
-// inflate_split_kernel.inc -- the throughput path: inflate as TWO kernels per batch.
+// inflate_split_kernel.inc -- the throughput path: inflate in two halves, both run by the wavefront
+// that owns the stream (debig_scanlz_kernel, one wavefront per stream).
 //
-//   debig_scan_kernel   (one wavefront per stream)  block headers, tables, the speculative segment
-//                       scan of inflate_kernel.inc (pass 1) -- and nothing else.  Once a window's
-//                       start/end chain is settled every lane has already decoded its segment's
-//                       symbols: they are kept, as 32-bit TOKENS in HBM, one row of 64 tokens per
-//                       symbol index (lane L's k-th symbol at row k, column L: the 64 lanes store
-//                       one coalesced 256-byte row per loop iteration).  Stored blocks are copied
-//                       straight to the recipient here.
-//   debig_lz_kernel     (one wavefront per stream)  reads the token rows back (coalesced, several
-//                       rows in flight: no table look-ups, no bit reader, no dependent LDS round
-//                       trips), places literals and match descriptors in an 8 KiB LDS tile, resolves
-//                       the LZ77 matches with the far/near machinery of inflate_kernel.inc and
-//                       flushes the tile with 16-byte stores.
+//   scan half   (scan_body)  block headers, tables, the speculative segment scan of inflate_kernel.inc
+//                            (pass 1) -- and nothing else.  Once a window's start/end chain is settled
+//                            every lane has already decoded its segment's symbols: they are kept, as
+//                            32-bit TOKENS in HBM, one row of 64 tokens per symbol index (lane L's k-th
+//                            symbol at row k, column L: the 64 lanes store one coalesced 256-byte row
+//                            per loop iteration).  Stored blocks are copied straight to the recipient here.
+//   LZ77 half   (lz_body)    reads the token rows back (coalesced, several rows in flight: no table
+//                            look-ups, no bit reader, no dependent LDS round trips), places literals and
+//                            match descriptors in an 8 KiB LDS tile, resolves the LZ77 matches with the
+//                            far/near machinery of inflate_kernel.inc and flushes the tile with 16-byte
+//                            stores.
 //
-// Why two kernels (measured on the one-kernel version, profiles/r01_*): every phase of the fused
+// Why two halves (measured on the one-pass version, profiles/r01_*): every phase of the one-pass
 // kernel was latency bound at 2 wavefronts per SIMD -- 219 VGPRs and 20 KB of LDS per wavefront,
 // the union of what the phases need -- and every symbol was decoded about 4 times (2 position
-// rounds, 1 full round, 1 emit pass).  Split, the scan needs window + tables (12.8 KB) and the
-// LZ77 kernel tile + bitmaps (13 KB): 3 wavefronts per SIMD each with far fewer registers, and
-// the emit pass becomes a replay of tokens.  The price is HBM traffic (tokens are written and
-// read once: about 1.5 x D each way) on a path that was using 7 % of the HBM bandwidth.
+// rounds, 1 full round, 1 emit pass).  Split, the emit pass becomes a replay of tokens.  The price
+// is HBM traffic (tokens are written and read once: about 1.5 x D each way) on a path that was
+// using 7 % of the HBM bandwidth.  (Round 2 ran the halves as two kernels; why they are fused now
+// is said above debig_scanlz_kernel.)
 //
 // What it replaces in the reference: src/inflate.c:786-1965, same observable behaviour as
 // debig_inflate_kernel (the two share every helper); streams that do not fit their share of the
@@ -235,7 +235,7 @@ debig_split_plan_kernel(const debig_stream *__restrict__ streams, uint32_t n, de
     }
 }
 
-// ------------------------------------------------------------------ scan kernel
+// ------------------------------------------------------------------ scan half
 // 16-bit table entries: the scan kernel's tables take 3 KB instead of 6 (with the 4.4 KB input
 // window: 9.4 KB of LDS per wavefront -> 16 wavefronts per CU).
 //   litlen: [3:0] code length l | [6:4] x = extra-bit count | [7] length code | [15:8] v
@@ -320,11 +320,7 @@ struct SegTok {
 #ifdef DEBIG_EMU
 DEV_INLINE void st_token(uint32_t *p, uint32_t v) { *p = v; }
 #else
-#if defined(DEBIG_TOK_POLICY) && DEBIG_TOK_POLICY == 1 /* experiment: default policy */
-DEV_INLINE void st_token(uint32_t *p, uint32_t v) { *p = v; }
-#else
 DEV_INLINE void st_token(uint32_t *p, uint32_t v) { __builtin_nontemporal_store(v, p); }
-#endif
 #endif
 
 // One symbol with every rare case handled (codes longer than the direct tables, no code at
@@ -799,20 +795,7 @@ DEV_INLINE void scan_body(ScanLds &S, const uint8_t *__restrict__ in_arena, uint
     (void)results;
 }
 
-__global__ void __launch_bounds__(64) DEBIG_SCAN_ATTRS
-debig_scan_kernel(const uint8_t *__restrict__ in_arena, uint8_t *__restrict__ out_arena,
-                  const debig_stream *__restrict__ streams, uint32_t n_streams,
-                  const uint32_t *__restrict__ fixed_tabs, debig_ws_slot *__restrict__ slots,
-                  debig_ws_rec *__restrict__ recs, uint32_t *__restrict__ rows, debig_result *results)
-{
-    __shared__ ScanLds S;
-    const uint32_t sid = blockIdx.x;
-    if (sid >= n_streams) return;
-    const debig_stream st = streams[sid];
-    scan_body<false>(S, in_arena, out_arena, st, sid, fixed_tabs, slots, recs, rows, results, 0ull, ~0ull, 1);
-}
-
-// ------------------------------------------------------------------ LZ77 kernel
+// ------------------------------------------------------------------ LZ77 half
 #ifndef DEBIG_PROFILE_LZ
 #define DEBIG_PROFILE_LZ 0
 #endif
@@ -944,11 +927,7 @@ template <class LDS> DEV_INLINE void lz_copy_match_wave(LDS &S, const OutState &
 #ifdef DEBIG_EMU
 DEV_INLINE uint32_t ld_token(const uint32_t *p) { return *p; }
 #else
-#if defined(DEBIG_TOK_POLICY) && DEBIG_TOK_POLICY == 1 /* experiment: default policy */
-DEV_INLINE uint32_t ld_token(const uint32_t *p) { return *p; }
-#else
 DEV_INLINE uint32_t ld_token(const uint32_t *p) { return __builtin_nontemporal_load(p); }
-#endif
 #endif
 // ---- match copies with unaligned accesses.  gfx950 runs in unaligned access mode (hipcc itself
 // emits unaligned ds_write_b64 / global_load_dword for packed structs), so a 3..16 byte match is
@@ -1155,56 +1134,6 @@ template <class LDS> DEV_INLINE void far_copy_u(LDS &S, OutState &O, uint32_t fr
     wave_local_sync();
 }
 
-// ---- whole-batch match lists.  The span-wise routines above pay a wave scan, two barriers and
-// one global-load round trip per 2048-byte span; with a tile that is re-anchored per batch there
-// are 3 spans and typically 400-600 far matches per batch: collected in ONE pass (lane L owns the
-// bitmap words 3L..3L+2, i.e. 96 consecutive tile bytes, so the list is in position order) and
-// gathered with all loads in flight at once.  More matches than S.mpos holds: the span-wise way.
-#ifndef LZ_FAR_DEPTH
-#define LZ_FAR_DEPTH 8
-#endif
-#ifndef DEBIG_LZ_BATCH_LISTS
-#define DEBIG_LZ_BATCH_LISTS 0 /* measured: 4-7 % slower than going span by span (register pressure) */
-#endif
-template <class LDS> DEV_INLINE uint32_t lz_collect(LDS &S, uint32_t *map, uint32_t from_rel, uint32_t to_rel)
-{
-    const uint32_t lane = lane_id();
-    uint32_t w[3], cnt = 0;
-DEV_UNROLL
-    for (uint32_t k = 0; k < 3; k++) {
-        const uint32_t wi = 3u * lane + k;
-        w[k] = span_word(map[wi], wi * 32u, from_rel, to_rel);
-        cnt += (uint32_t)__popc(w[k]);
-    }
-    uint32_t total;
-    uint32_t at = wave_excl_scan_u32(cnt, &total);
-    if (total > MPOS_CAP) return total; /* wave-uniform: the caller goes span by span, the map is untouched */
-DEV_UNROLL
-    for (uint32_t k = 0; k < 3; k++) {
-        const uint32_t wi = 3u * lane + k;
-        uint32_t ww = w[k];
-        while (ww) {
-            const uint32_t bit = (uint32_t)__ffs(ww) - 1u;
-            ww &= ww - 1u;
-            S.mpos[0][at++] = (uint16_t)(wi * 32u + bit);
-        }
-        map[wi] = 0; /* consumed */
-    }
-    return total;
-}
-
-template <class LDS> DEV_INLINE void lz_far_batch(LDS &S, OutState &O, uint32_t from_rel, uint32_t to_rel)
-{
-    static_assert(LDS::MAP_WORDS >= 192 || !DEBIG_LZ_BATCH_LISTS, "lane L reads map words 3L..3L+2");
-    if (!DEBIG_LZ_BATCH_LISTS) { far_copy_u(S, O, from_rel, to_rel); return; }
-    wave_local_sync();
-    const uint32_t total = lz_collect(S, S.farmap, from_rel, to_rel);
-    if (total > MPOS_CAP) { far_copy_u(S, O, from_rel, to_rel); return; }
-    wave_local_sync();
-    far_groups<LZ_FAR_DEPTH>(S, O, total);
-    wave_local_sync();
-}
-
 // copy_short_match of inflate_kernel.inc (3..16 bytes, non-overlapping, source in the LDS tile)
 // with two unaligned 8-byte reads and st_match_bytes
 template <class LDS> DEV_INLINE void copy_short_match_u(LDS &S, int mine, uint32_t p, uint32_t len, uint32_t sr)
@@ -1227,77 +1156,16 @@ template <class LDS> DEV_INLINE void copy_short_match_u(LDS &S, int mine, uint32
     }
 }
 
-// resolve_matches_groups of inflate_kernel.inc with copy_short_match_u
-// resolve the near matches listed (in position order) in S.mpos[0][0..total): groups of 64, a
-// match is copied once none of its source bytes is pending (resolve_matches_groups' inner loop)
-template <class LDS> DEV_INLINE void near_groups(LDS &S, OutState &O, uint32_t total)
-{
-    constexpr int NW = LDS::NW;
-    const uint32_t lane = lane_id();
-    const int64_t lds_rel0 = O.lds_from - O.tile_base; /* tile bytes below this are not in LDS */
-    for (uint32_t g = 0; g < total; g += 64) {
-        uint32_t q = g + lane;
-        int pending = q < total;
-        uint32_t p = 0, len = 0, dist = 1;
-        if (pending) {
-            p = S.mpos[LDS::NW == 1 ? 0u : wave_id()][q];
-            len = (uint32_t)S.tile[p] + 3u;
-            dist = ((uint32_t)S.tile[p + 1] | ((uint32_t)S.tile[p + 2] << 8)) + 1u;
-        }
-        const int64_t src_rel = (int64_t)p - (int64_t)dist;   /* tile relative, may be < 0 */
-        const uint32_t span_len = len < dist ? len : dist;     /* distinct source bytes   */
-        // part of the source range that lives in the LDS tile
-        int64_t t0 = src_rel > lds_rel0 ? src_rel : lds_rel0;
-        int64_t t1 = src_rel + (int64_t)span_len;
-        const uint32_t chk_p = (uint32_t)(t0 < t1 ? t0 : 0);
-        const uint32_t chk_n = (uint32_t)(t0 < t1 ? t1 - t0 : 0);
-        const int src_in_lds = src_rel >= lds_rel0;
-        wave_sync<NW>();
-        if (pending) pend_set(S, p, len);
-        wave_sync<NW>();
-        for (;;) {
-            if (!__any(pending)) break;
-            int ready = pending && !pend_any(S, chk_p, chk_n);
-            int simple = ready && len <= 16u && dist >= len;
-            // (a) short, non-overlapping, source in the tile
-            copy_short_match_u(S, simple && src_in_lds, p, len, (uint32_t)src_rel);
-            // (b) everything else (long, self-overlapping, straddling the flush point; matches
-            //     whose whole source is already flushed never get here: far_copy took them):
-            //     one match at a time, all 64 lanes copy
-            unsigned long long gm = __ballot(ready && !(simple && src_in_lds));
-            while (gm) {
-                int sl = __ffsll(gm) - 1;
-                gm &= gm - 1;
-                const uint32_t lp = wave_bcast_u32(p, (uint32_t)sl);
-                const uint32_t ll = wave_bcast_u32(len, (uint32_t)sl);
-                const uint32_t ld = wave_bcast_u32(dist, (uint32_t)sl);
-                lz_copy_match_wave(S, O, lp, ll, ld);
-            }
-            wave_sync<NW>();
-            if (ready) {
-                pend_clear(S, p, len);
-                pending = 0;
-            }
-            wave_sync<NW>();
-        }
-    }
-}
-
-// near_groups with the dependencies of a group kept in REGISTERS (round 4).  A group is 64 consecutive near matches
+// resolve_matches_groups of inflate_kernel.inc with copy_short_match_u, and the dependencies of a group kept in
+// REGISTERS instead of the pending bitmap (round 4).  A group is 64 consecutive near matches
 // in position order, and every group before it is finished when it starts: the only bytes of a match's source that can
 // still be pending are destinations of matches of the SAME group, i.e. of lanes below it -- and, positions being
 // sorted and destinations disjoint, of a contiguous range of lanes [lo, hi), found by two binary searches over the
 // lanes' start / end positions (six shuffle steps, both searches side by side).  A match is ready when none of those
 // lanes is pending: a ballot and two ANDs per round, against two pending-bitmap reads, one or two LDS atomics and two
-// waits per round and lane in near_groups -- whose rounds were a chain of four dependent LDS round trips
+// waits per round and lane with the bitmap -- whose rounds were a chain of four dependent LDS round trips
 // (pending bits -> source -> destination -> pending bits).  Here a round is source -> destination, and the next
 // round's reads may follow the writes at once (one wavefront: the LDS executes its instructions in order).
-#ifndef DEBIG_NEAR_REGDEPS
-#define DEBIG_NEAR_REGDEPS 1
-#endif
-#ifndef DEBIG_NEAR_RLE
-#define DEBIG_NEAR_RLE 1 /* runs of one byte (distance 1) without the general wavefront copy */
-#endif
 #if defined(DEBIG_PROFILE) && !defined(DEBIG_EMU)
 #define NPROF_T() __builtin_amdgcn_s_memtime()
 #define NPROF_ADD(i, t0) do { if (lane_id() == 0) S.nprof[i] += __builtin_amdgcn_s_memtime() - (t0); } while (0)
@@ -1358,7 +1226,7 @@ DEV_UNROLL
             copy_short_match_u(S, simple && src_in_lds, p, len, (uint32_t)src_rel);
             // (a') a short run of one byte (distance 1: 2.8 % of a photo's matches, the commonest kind that is not (a))
             int rle = 0;
-            if constexpr (LDS::ES == 1 && DEBIG_NEAR_RLE) {
+            if constexpr (LDS::ES == 1) {
                 rle = ready && dist == 1u && len <= 16u && src_in_lds;
                 if (rle) {
                     const uint32_t x = (uint32_t)S.tile[p - 1u] * 0x01010101u;
@@ -1376,7 +1244,7 @@ DEV_UNROLL
                 const uint32_t lp = wave_bcast_u32(p, (uint32_t)sl);
                 const uint32_t ll = wave_bcast_u32(len, (uint32_t)sl);
                 const uint32_t ld = wave_bcast_u32(dist, (uint32_t)sl);
-                if constexpr (LDS::ES == 1 && DEBIG_NEAR_RLE) {
+                if constexpr (LDS::ES == 1) {
                     if (ld == 1u && ll >= 8u && (int64_t)lp - 1 >= lds_rel0) { /* a long run (flat image areas: two thirds of such a
                                                                                   file's matches): eight bytes per lane */
                         const uint32_t x = (uint32_t)S.tile[lp - 1u] * 0x01010101u;
@@ -1414,93 +1282,20 @@ DEV_UNROLL
 // strand pipeline 20.3 -> 24.1 ms, 4096 x 64 KiB text 0.860 -> 0.911 ms -- the second match's state does not fit the 128
 // registers these kernels have, and a round's cost is its instructions as much as its latency.)
 
-// ---- the near matches of a span as a SWEEP in position order (round 4; measured and NOT the default).
-// near_groups resolves matches: 64 at a time, a round per level of the dependency chains inside the group, every
-// round a test of the pending bits of every source range, and every long or self-overlapping match a copy by the
-// whole wavefront, one after the other.  Real PNG data spends its time there: the reference's sample files have
-// 430 near matches per 5 KB tile in chains of a dozen levels and more (a filtered pixel repeats its neighbour:
-// distances of 1 .. 32 bytes), or 200-byte runs of one byte (tools/token_stats.py); 11 .. 17 cycles per output
-// byte, 74 % of the LZ77 half (profiles/r04_prof_strand_png_files.txt).
-// The sweep resolves BYTES instead: 64 consecutive positions of the tile at a time, one per lane, in position
-// order.  A lane finds the match that governs its position (the last start bit at or below it in the chunk's 64 map
-// bits, else the match carried over from the chunks before: at most one match reaches into a chunk from the left),
-// reads that match's descriptor, and knows its source position.  A source in an earlier chunk is final: one LDS
-// gather.  A source inside the chunk is another LANE: the lanes' pointers are doubled in registers (ds_bpermute; six
-// rounds reach any chain of 64, the loop ends as soon as nothing moves) and one last shuffle fetches every value
-// from the head of its chain.  About 55 instructions per 64 bytes whatever the matches look like -- but ONE chain
-// of about ten dependent LDS round trips per chunk with nothing to overlap them: measured (profiles/
-// r04_near_sweep_ab.txt) it is no faster on photo-like files (fs_angrymob 27.5 vs 28.2 ms) and slower everywhere
-// else (gimp_test 26.5 -> 41.7 ms, 4096 x 64 KiB text 0.874 -> 1.000 ms, 512 x 1 MiB text 4.06 -> 5.78 ms).  Kept
-// behind DEBIG_NEAR_SWEEP for the record; what it would need is several chunks in flight per wavefront.
-// (Descriptors are read before anything of the chunk is stored: they live in the first three positions of the
-// match they describe.)
-#ifndef DEBIG_NEAR_SWEEP
-#define DEBIG_NEAR_SWEEP 0
-#endif
-#ifndef DEBIG_NEAR_SWEEP_MIN
-#define DEBIG_NEAR_SWEEP_MIN 64u /* near matches in a 2048-element span from which the sweep takes it ... */
-#endif
-#ifndef DEBIG_NEAR_SWEEP_BYTES
-#define DEBIG_NEAR_SWEEP_BYTES 1024u /* ... or output elements of near matches in the span (runs, long copies) */
-#endif
-struct NearCarry { /* the last match that started in an earlier chunk: covers positions < end (0: none) */
-    uint32_t end, dist;
-};
-template <class LDS>
-DEV_INLINE void near_sweep_chunk(LDS &S, const OutState &O, const uint32_t c, const uint64_t M, NearCarry &carry)
-{
-    static_assert(LDS::NW == 1, "one wavefront per tile");
-    typedef typename LDS::Elem Elem;
-    const uint32_t lane = lane_id();
-    const int64_t lds_rel0 = O.lds_from - O.tile_base; /* tile elements below this are not in LDS */
-    const uint32_t b = c + lane;
-    const uint64_t Ml = M & (~0ull >> (63u - lane)); /* starts at or below my position */
-    const int has = Ml != 0ull;
-    const uint32_t m = has ? c + 63u - (uint32_t)__clzll((long long)Ml) : 0u;
-    uint32_t end = carry.end, dist = carry.dist;
-    if (has) {
-        const uint32_t len = (uint32_t)S.tile[m] + 3u;
-        dist = ((uint32_t)S.tile[m + 1] | ((uint32_t)S.tile[m + 2] << 8)) + 1u;
-        end = m + len;
-    }
-    const int is_m = b < end; /* (a match that starts below to_rel may end behind it: the general replay's tile carry) */
-    const int64_t src = (int64_t)b - (int64_t)dist;
-    uint32_t v = (uint32_t)S.tile[b];
-    uint32_t ptr = lane;
-    int in_hbm = 0;
-    if (is_m) {
-        if (src < lds_rel0) in_hbm = 1;                                  /* below the flush point: in L2 */
-        else if (src >= (int64_t)c) ptr = (uint32_t)(src - (int64_t)c); /* a lane to my left */
-        else v = (uint32_t)S.tile[src];                                  /* an earlier chunk: final */
-    }
-    if (__any(in_hbm)) {
-        if (in_hbm) v = (uint32_t)lz_ld_plane<LDS>(O, O.tile_base + src);
-    }
-    if (__any(ptr != lane)) {
-        for (int it = 0; it < 6; it++) {
-            const uint32_t pp = (uint32_t)__shfl((int)ptr, (int)ptr);
-            if (!__any(pp != ptr)) break;
-            ptr = pp;
-        }
-        v = (uint32_t)__shfl((int)v, (int)ptr);
-    }
-    if (is_m) S.tile[b] = (Elem)v;
-#ifdef DEBIG_EMU
-    __wave_barrier(); /* (the emulator's lanes are fibers: the next chunk reads what this one stored; on the GPU the LDS
-                         executes a wavefront's instructions in order) */
-#endif
-    if (M != 0ull) { /* the chunk's last start governs lane 63 */
-        carry.end = wave_bcast_u32(end, 63u);
-        carry.dist = wave_bcast_u32(dist, 63u);
-    }
-}
+// (Measured and not kept, profiles/r04_near_sweep_ab.txt: the near matches of a span as a SWEEP in position order -- 64
+// consecutive tile positions at a time, one per lane, each lane following its match's source back through the lanes to
+// its left by pointer doubling.  About 55 instructions per 64 bytes whatever the matches look like, but one chain of
+// about ten dependent LDS round trips per chunk with nothing to overlap them: no faster on photo-like files (fs_angrymob
+// 27.5 vs 28.2 ms) and slower everywhere else (gimp_test 26.5 -> 41.7 ms, 4096 x 64 KiB text 0.874 -> 1.000 ms, 512 x
+// 1 MiB text 4.06 -> 5.78 ms).  What it would need is several chunks in flight per wavefront.)
 
+// resolve_matches_groups of inflate_kernel.inc on one wavefront's tile: the near matches of each 2048-element span are
+// listed in position order and resolved by near_groups_r
 template <class LDS> DEV_INLINE void resolve_matches_groups_u(LDS &S, OutState &O, uint32_t from_rel, uint32_t to_rel)
 {
-    constexpr int NW = LDS::NW;
-    (void)NW;
+    static_assert(LDS::NW == 1, "one wavefront per tile");
     const uint32_t lane = lane_id();
-    wave_sync<NW>();
+    wave_local_sync();
     for (uint32_t span = from_rel >> 11; span < ((to_rel + 2047u) >> 11); span++) {
         uint32_t wbase = span * 64u + lane;
         uint32_t w = S.bitmap[wbase];
@@ -1514,57 +1309,18 @@ template <class LDS> DEV_INLINE void resolve_matches_groups_u(LDS &S, OutState &
         if (!__any(w != 0)) continue; /* no near match starts in this span */
         uint32_t total;
         uint32_t pre = wave_excl_scan_u32((uint32_t)__popc(w), &total);
-        uint32_t nel = 0; /* output elements of my word's matches */
         {
             uint32_t k = pre, ww = w;
             while (ww) {
                 uint32_t bit = (uint32_t)__ffs(ww) - 1u;
                 ww &= ww - 1u;
-                S.mpos[LDS::NW == 1 ? 0u : wave_id()][k++] = (uint16_t)(p0 + bit);
-                if (DEBIG_NEAR_SWEEP) nel += (uint32_t)S.tile[p0 + bit] + 3u;
+                S.mpos[0][k++] = (uint16_t)(p0 + bit);
             }
         }
-        if constexpr (DEBIG_NEAR_SWEEP && LDS::NW == 1) {
-            int sweep = total >= DEBIG_NEAR_SWEEP_MIN;
-            if (!sweep) {
-                uint32_t nel_total;
-                (void)wave_excl_scan_u32(nel, &nel_total);
-                sweep = nel_total >= DEBIG_NEAR_SWEEP_BYTES;
-            }
-            if (sweep) { /* wave-uniform */
-                NearCarry carry;
-                carry.end = 0; carry.dist = 1;
-                const uint32_t c0 = span << 11;
-                for (uint32_t k = 0; k < 32u; k++) {
-                    const uint64_t M = (uint64_t)wave_bcast_u32(w, 2u * k) | ((uint64_t)wave_bcast_u32(w, 2u * k + 1u) << 32);
-                    const uint32_t c = c0 + 64u * k;
-                    if (M == 0ull && carry.end <= c) continue; /* nothing of a near match in this chunk */
-                    near_sweep_chunk(S, O, c, M, carry);
-                }
-                for (uint32_t c = c0 + 2048u; carry.end > c; c += 64u) /* the last match's tail reaches into the next span */
-                    near_sweep_chunk(S, O, c, 0ull, carry);
-                wave_sync<NW>();
-                continue;
-            }
-        }
-        wave_sync<NW>();
-        if constexpr (DEBIG_NEAR_REGDEPS && LDS::NW == 1) near_groups_r(S, O, total);
-        else near_groups(S, O, total);
-        wave_sync<NW>(); /* S.mpos is rewritten by the next span */
+        wave_local_sync();
+        near_groups_r(S, O, total);
+        wave_local_sync(); /* S.mpos is rewritten by the next span */
     }
-    wave_sync<NW>();
-}
-
-
-template <class LDS> DEV_INLINE void lz_near_batch(LDS &S, OutState &O, uint32_t from_rel, uint32_t to_rel)
-{
-    if (!DEBIG_LZ_BATCH_LISTS) { resolve_matches_groups_u(S, O, from_rel, to_rel); return; }
-    wave_local_sync();
-    const uint32_t total = lz_collect(S, S.bitmap, from_rel, to_rel);
-    if (total > MPOS_CAP) { resolve_matches_groups_u(S, O, from_rel, to_rel); return; }
-    wave_local_sync();
-    if constexpr (DEBIG_NEAR_REGDEPS && LDS::NW == 1) near_groups_r(S, O, total);
-    else near_groups(S, O, total);
     wave_local_sync();
 }
 
@@ -1773,12 +1529,9 @@ DEV_INLINE uint32_t lz_body(LDS &S, OutState &O, const uint8_t *__restrict__ in_
             int64_t w_out1 = w_out0 + (int64_t)wave_bcast_u32(my_e, s0 + nseg - 1u);
             const uint32_t batch_s0 = s0;
             s0 += nseg;
-#ifndef DEBIG_LZ_DEFER_FENCE
-#define DEBIG_LZ_DEFER_FENCE 1
-#endif
             // the tile's stores stay in flight while the batch is replayed: the wait comes before the
             // first history read (far copy), behind the replay's own work
-            if (fast && w_out1 > O.tile_base + LDS::T2 && O.outpos > O.lds_from) lz_flush_all(S, O, !DEBIG_LZ_DEFER_FENCE);
+            if (fast && w_out1 > O.tile_base + LDS::T2 && O.outpos > O.lds_from) lz_flush_all(S, O, 0);
             if (fast && w_out1 <= O.tile_base + LDS::T2) {
                 // ---- fast replay
                 PROF_BEGIN();
@@ -1835,16 +1588,17 @@ DEV_UNROLL
                 }
                 const uint32_t from_rel = (uint32_t)(O.outpos - O.tile_base);
                 const uint32_t to_rel = (uint32_t)(w_out1 - O.tile_base);
-                if (DEBIG_LZ_DEFER_FENCE) { wave_mem_fence(); lz_publish(O); } /* the flushed tile is history now */
+                wave_mem_fence(); /* the flushed tile is history now */
+                lz_publish(O);
                 wave_local_sync();
                 PROF_BEGIN();
 #if !(defined(DEBIG_ABLATE) && (DEBIG_ABLATE & 1)) /* timing experiment: far copy skipped (wrong output) */
-                lz_far_batch(S, O, from_rel, to_rel);
+                far_copy_u(S, O, from_rel, to_rel);
 #endif
                 PROF_END(1);
                 PROF_BEGIN();
 #if !(defined(DEBIG_ABLATE) && (DEBIG_ABLATE & 2)) /* timing experiment: near resolve skipped (wrong output) */
-                lz_near_batch(S, O, from_rel, to_rel);
+                resolve_matches_groups_u(S, O, from_rel, to_rel);
 #endif
                 PROF_END(2);
                 if (status != DEBIG_OK) { /* drop the marks of matches at or beyond the failing position */
@@ -1997,8 +1751,7 @@ DEV_UNROLL
     return status;
 }
 
-// the LZ77 side of stream `sid` whose scan left `slot_state` (debig_lz_kernel: read from the slot;
-// debig_scanlz_kernel: handed over in a register)
+// the LZ77 side of stream `sid` whose scan left `slot_state` (handed over in a register)
 template <class LDS>
 DEV_INLINE void lz_stream(LDS &S, const uint32_t sid, const debig_ws_slot &slot, const uint32_t slot_state,
                           uint8_t *__restrict__ out_arena, const debig_stream *__restrict__ streams, debig_result *results,
@@ -2053,18 +1806,6 @@ DEV_INLINE void lz_stream(LDS &S, const uint32_t sid, const debig_ws_slot &slot,
 #endif
         results[sid] = r;
     }
-}
-
-__global__ void __launch_bounds__(64) DEBIG_LZ_ATTRS
-debig_lz_kernel(uint8_t *__restrict__ out_arena, const debig_stream *__restrict__ streams,
-                debig_result *results, uint32_t n_streams, const debig_ws_slot *__restrict__ slots,
-                const debig_ws_rec *__restrict__ recs, const uint32_t *__restrict__ rows)
-{
-    __shared__ LzLds S;
-    const uint32_t sid = blockIdx.x;
-    if (sid >= n_streams) return;
-    const debig_ws_slot slot = slots[sid];
-    lz_stream(S, sid, slot, slot.state, out_arena, streams, results, recs, rows);
 }
 
 // ---- both halves in ONE kernel: the wavefront that scanned a stream replays it.  The two halves are

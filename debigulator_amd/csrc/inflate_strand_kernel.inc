@@ -716,19 +716,6 @@ ST_NOUNROLL
                         uint32_t tot;
                         const uint32_t pre = wave_excl_scan_u32(est, &tot);
                         const uint32_t mx = wave_max_u32(est);
-#ifdef DEBIG_EMU
-                        if (getenv("DEBIG_EMU_ST_UNITS")) {
-                            for (uint32_t L = 0; L < 64; L++) {
-                                const uint32_t v = (uint32_t)__shfl((int)nlead, (int)L);
-                                if (lane == 0) fprintf(stderr, "%u%s", v, L == 63 ? " <- lead symbols\n" : " ");
-                            }
-                            for (uint32_t L = 0; L < 64; L++) {
-                                const uint32_t v = (uint32_t)__shfl((int)est, (int)L);
-                                if (lane == 0) fprintf(stderr, "%u%s", v, L == 63 ? " <- est\n" : " ");
-                            }
-                            if (lane == 0) fprintf(stderr, "mx %u tot %u segb %u\n", mx, tot, segb);
-                        }
-#endif
                         if ((uint64_t)mx * 64u * 8u <= (uint64_t)tot * 9u) break;     /* the densest strand is within 1/8 of the mean */
                         // boundary k at k / 64 of the estimated symbols: inside strand j, linearly
                         const uint32_t tk = (uint32_t)(((uint64_t)tot * lane) >> 6);
@@ -746,24 +733,10 @@ DEV_UNROLL
                         const uint32_t nb_next = (uint32_t)__shfl_down((int)nb, 1);
                         const uint32_t nxt = lane == 63u ? 64u * segb : nb_next;
                         const uint32_t gap = nxt - nb;
-#ifdef DEBIG_EMU
-                        if (getenv("DEBIG_EMU_ST_UNITS")) {
-                            uint32_t all[64], al2[64];
-                            for (uint32_t L = 0; L < 64; L++) { all[L] = (uint32_t)__shfl((int)nb, (int)L); al2[L] = (uint32_t)__shfl((int)j, (int)L); }
-                            if (lane == 0) { for (uint32_t L = 0; L < 64; L++) fprintf(stderr, "%u/%u ", all[L] >> 3, al2[L]); fprintf(stderr, "<- new boundary bytes / strand j; tot %u mx %u\n", tot, mx); }
-                        }
-#endif
                         // every strand must hold its lead and stay within what a unit header can address
                         if (__any(nxt <= nb || gap < lead_bits + 256u || gap > 8u * ST_STRAND_MAX)) break;
                         lo_w = (int64_t)nb;
                         hi_w = (int64_t)nxt;
-#ifdef DEBIG_EMU
-                        if (getenv("DEBIG_EMU_ST_UNITS")) {
-                            uint32_t all[64];
-                            for (uint32_t L = 0; L < 64; L++) all[L] = (uint32_t)__shfl((int)gap, (int)L);
-                            if (lane == 0) { for (uint32_t L = 0; L < 64; L++) fprintf(stderr, "%u ", all[L] >> 3); fprintf(stderr, "<- strand bytes after the cut\n"); }
-                        }
-#endif
                     }
                     PROF_END(1);
                     // ---- main pass
@@ -800,14 +773,6 @@ DEV_UNROLL
                     if (status != DEBIG_OK) break;
                     if (wave_bcast_u32(TA.ts, 0) != 0) kcut = 0;
                     n_main = u;
-#ifdef DEBIG_EMU
-                    if (getenv("DEBIG_EMU_ST_UNITS")) {
-                        for (uint32_t L = 0; L < 64; L++) {
-                            const uint32_t v = (uint32_t)__shfl((int)nu, (int)L);
-                            if (lane == 0) fprintf(stderr, "%u%s", v, L == 63 ? "\n" : " ");
-                        }
-                    }
-#endif
                     PROF_END(2);
                     PROF_BEGIN();
                     // the tail gate: a lane that stopped in front of its strand's end
@@ -872,14 +837,6 @@ DEV_UNROLL
                         }
                         if (status != DEBIG_OK) break;
                         n_patch = pu > n_patch ? pu : n_patch;
-#ifdef DEBIG_EMU
-                        if (getenv("DEBIG_EMU_ST_DEBUG")) {
-                            const unsigned long long nm = __ballot(need), sm = __ballot(need && synced), trm = __ballot(need && TR.ts != 0);
-                            if (lane == 0)
-                                fprintf(stderr, "  window %u seg %u main %u: redo round %u lanes %016llx synced %016llx term %016llx phases %u last %u\n",
-                                        n_windows, seg, n_main, round, nm, sm, trm, pu, last);
-                        }
-#endif
                         if (need) {
                             // a lane that stops exactly at the sync position between two phases
                             if (!synced && TR.ts == 0 && b.lp == sync_at) synced = 1u;
@@ -954,11 +911,6 @@ DEV_UNROLL
         end_bits = bitpos;
     }
 #undef ST_EMIT
-#ifdef DEBIG_EMU
-    if (lane == 0 && getenv("DEBIG_EMU_ST_DEBUG"))
-        fprintf(stderr, "strand sid %u: status %u blocks %u windows %u phases %u rows %u/%u recs %u/%u out %llu\n", sid, status, n_blocks,
-                n_windows, n_rounds, row_cur, slot.rows, rec_cur, slot.recs, (unsigned long long)outpos);
-#endif
     *state_out = status == DEBIG_E_RETRY ? (uint32_t)DEBIG_E_RETRY : (uint32_t)DEBIG_OK;
     if (lane == 0) {
         debig_ws_rec rr;
@@ -1117,7 +1069,8 @@ DEV_INLINE void lz_replay_units(LDS &S, OutState &O, const debig_ws_rec &rec, co
         // the matches of the whole tile are resolved.  (A round of 64 units is as little as 1 KB of literal-heavy
         // data: the far / near passes -- barriers, span scans -- must not be paid per round.)
         PROF_BEGIN();
-        if (O.outpos > O.lds_from) lz_flush_all(S, O, !DEBIG_LZ_DEFER_FENCE); /* the tile restarts at this batch's first byte */
+        // the tile restarts at this batch's first byte; its stores stay in flight until the fence before the far copy
+        if (O.outpos > O.lds_from) lz_flush_all(S, O, 0);
         const uint32_t b_rel0 = (uint32_t)(O.outpos - w_out0);
         const int32_t tb32 = O.tile_base > 70000 ? 70000 : (int32_t)O.tile_base;
         const int chk_far = tb32 < 32768; /* a distance can only be too far near the start */
@@ -1154,15 +1107,16 @@ DEV_INLINE void lz_replay_units(LDS &S, OutState &O, const debig_ws_rec &rec, co
         const uint32_t to_rel = (uint32_t)(w_out1 - O.tile_base);
         PROF_END(0);
         PROF_BEGIN();
-        if (DEBIG_LZ_DEFER_FENCE) { wave_mem_fence(); lz_publish(O); } /* the flushed tile is history now */
+        wave_mem_fence(); /* the flushed tile is history now */
+        lz_publish(O);
         wave_local_sync();
 #if !(defined(DEBIG_ABLATE) && (DEBIG_ABLATE & 1)) /* timing experiment: far copy skipped (wrong output) */
-        lz_far_batch(S, O, from_rel, to_rel);
+        far_copy_u(S, O, from_rel, to_rel);
 #endif
         PROF_END(1);
         PROF_BEGIN();
 #if !(defined(DEBIG_ABLATE) && (DEBIG_ABLATE & 2)) /* timing experiment: near resolve skipped (wrong output) */
-        lz_near_batch(S, O, from_rel, to_rel);
+        resolve_matches_groups_u(S, O, from_rel, to_rel);
 #endif
         PROF_END(2);
         if (status != DEBIG_OK) { /* drop the marks of matches at or beyond the failing position */

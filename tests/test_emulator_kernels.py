@@ -937,11 +937,11 @@ def test_strand_path_random_zlib_streams(emu, oracle):
             assert (good, final, out) == (eg, ef, eo), nw
 
 
-def test_near_sweep_variant_agrees_with_oracle(oracle):
-    """inflate_split_kernel.inc: the position-order near sweep (DEBIG_NEAR_SWEEP; measured, not the product's default) built
-    for EVERY span: zlib streams of text, runs and periodic data through the pair, the strand kernel, the pipeline and chunk
-    tasks (16-bit elements, matches that end behind the tile)"""
-    L = eb.load_emu(variant="sweep")
+def test_lz_half_on_mixed_zlib_streams_agrees_with_oracle(emu, oracle):
+    """inflate_split_kernel.inc, the LZ77 half: zlib streams of text, runs and periodic data at three levels and three
+    strategies (dense chains of near matches, long runs of one byte) through the pair, the strand kernel, the pipeline
+    and chunk tasks (16-bit elements, matches that end behind the tile)"""
+    L = emu
     rng = random.Random(77)
     raws, caps = [], []
     for it in range(10):

@@ -1,4 +1,4 @@
-# PMC passes over the scan / LZ77 kernel pair: tools/bench_variant.py $1 (kind) 4096 0x10
+# PMC passes over the fused scan / LZ77 kernel: tools/bench_variant.py $1 (kind) 4096 0x10
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 K=${1:-fixed}
@@ -19,7 +19,7 @@ pmc_pass $R/gpurun_out/pmcs_c_$K SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_IN
 cd $R
 python3 - <<PY
 import csv, glob, os
-for kern in ("debig_scanlz_kernel", "debig_scan_kernel", "debig_lz_kernel"):
+for kern in ("debig_scanlz_kernel",):
     print("==", kern)
     tot = {}
     for pas in "abc":

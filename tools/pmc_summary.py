@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Summarise the rocprofv3 --pmc CSVs made by tools/pmc_traffic.sh (bench.py: every step is the
 same batch) and write profiles/pmc_traffic.json for bench.py.  A step is several launches since
-round 2 (workspace plan, scan kernel, LZ77 kernel, the one-kernel path for handed-back streams):
+round 2 (workspace plan, the fused scan + LZ77 kernel, the one-kernel path for handed-back streams):
 the bytes of all debig_* kernels between two plan launches are one step."""
 import csv, glob, hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,7 +17,7 @@ for name in ("fetch", "write"):
     # steps: split at every plan kernel (or every one-kernel launch when the plan kernel is absent)
     steps, cur = [], []
     # round 3: the workspace is carved once per batch object, a step is scan + lz + hand-back
-    marker = next((m for m in ("debig_scanlz_kernel", "debig_scan_kernel", "debig_inflate_kernel")
+    marker = next((m for m in ("debig_scanlz_kernel", "debig_inflate_kernel")
                    if any(m in r["Kernel_Name"] for r in rows)), "debig_inflate_kernel")
     rows = [r for r in rows if "debig_split_plan_kernel" not in r["Kernel_Name"]]
     for r in rows:

@@ -109,29 +109,23 @@ extern "C" int emu_inflate_split_batch(const void *in, void *out, const debig_st
             else { if (in_cheap || (b && i < last_e)) return -3; last_e = i; }
         }
     }
-    if (getenv("DEBIG_EMU_TWO_KERNELS")) { /* the two halves as separate kernels (the chunk path's shape) */
-        EMU_LAUNCH(debig_scan_kernel, n, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
-        EMU_LAUNCH(debig_lz_kernel, n, 64, (uint8_t *)out, streams, results, n, (const debig_ws_slot *)slots,
-                   (const debig_ws_rec *)recs, (const uint32_t *)rows);
+    if (getenv("DEBIG_EMU_SPLIT_QUEUED")) {
+        // DEBIG_WAVES_SPLIT_QUEUED: fewer workgroups than streams, and twice (the queue counter carries on)
+        const uint32_t grid = n > 3u ? 3u : n;
+        const uint64_t *q = reinterpret_cast<const uint64_t *>(split_queue(slots, n));
+        EMU_LAUNCH(debig_scanlz_queue_kernel, grid, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
+        if (*q != (uint64_t)n) return -2; /* a launch adds exactly n to the queue counter */
+        EMU_LAUNCH(debig_scanlz_queue_kernel, grid, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
+        if (*q != 2u * (uint64_t)n) return -2;
+    } else if (getenv("DEBIG_EMU_STRAND_PIPE")) { /* DEBIG_WAVES_STRAND_PIPE: scan and LZ77 wavefronts side by side */
+        if (getenv("DEBIG_EMU_PIPE_BIG_TILE")) /* the 12 KB LZ77 tile (what the shim launches while the device holds every stream) */
+            EMU_LAUNCH(debig_strand_pipe_kernel<LzLdsBig>, n, 128, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
+        else
+            EMU_LAUNCH(debig_strand_pipe_kernel<LzLds>, n, 128, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
+    } else if (getenv("DEBIG_EMU_STRAND")) { /* DEBIG_WAVES_STRAND: the long-segment scan */
+        EMU_LAUNCH(debig_strand_kernel, n, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
     } else {
-        if (getenv("DEBIG_EMU_SPLIT_QUEUED")) {
-            // DEBIG_WAVES_SPLIT_QUEUED: fewer workgroups than streams, and twice (the queue counter carries on)
-            const uint32_t grid = n > 3u ? 3u : n;
-            const uint64_t *q = reinterpret_cast<const uint64_t *>(split_queue(slots, n));
-            EMU_LAUNCH(debig_scanlz_queue_kernel, grid, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
-            if (*q != (uint64_t)n) return -2; /* a launch adds exactly n to the queue counter */
-            EMU_LAUNCH(debig_scanlz_queue_kernel, grid, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
-            if (*q != 2u * (uint64_t)n) return -2;
-        } else if (getenv("DEBIG_EMU_STRAND_PIPE")) { /* DEBIG_WAVES_STRAND_PIPE: scan and LZ77 wavefronts side by side */
-            if (getenv("DEBIG_EMU_PIPE_BIG_TILE")) /* the 12 KB LZ77 tile (what the shim launches while the device holds every stream) */
-                EMU_LAUNCH(debig_strand_pipe_kernel<LzLdsBig>, n, 128, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
-            else
-                EMU_LAUNCH(debig_strand_pipe_kernel<LzLds>, n, 128, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
-        } else if (getenv("DEBIG_EMU_STRAND")) { /* DEBIG_WAVES_STRAND: the long-segment scan */
-            EMU_LAUNCH(debig_strand_kernel, n, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
-        } else {
-            EMU_LAUNCH(debig_scanlz_kernel, n, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
-        }
+        EMU_LAUNCH(debig_scanlz_kernel, n, 64, (const uint8_t *)in, (uint8_t *)out, streams, n, fts, slots, recs, rows, results);
     }
     uint32_t retried = 0;
     for (uint32_t i = 0; i < n; i++) retried += results[i].status == DEBIG_E_RETRY;
