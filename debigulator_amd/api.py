@@ -230,7 +230,36 @@ def _png_spec_lib():
     L.debig_png_info_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PngInfo)]
     L.debig_png_decode_batch.restype = C.c_int
     L.debig_png_decode_batch.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32]
+    L.debig_png_decode_batch_fmt.restype = C.c_int
+    L.debig_png_decode_batch_fmt.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.debig_png_out_layout.restype = C.c_uint64
+    L.debig_png_out_layout.argtypes = [C.POINTER(PngInfo), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     return L
+
+
+# include/decode_png.h: out_format = layout | depth
+PNG_MODES = {"rgba": 0, "rgb": 1, "gray": 2, "gray_alpha": 3, "native": 4}
+PNG_DEPTHS = {8: 0x00, 16: 0x10, "native": 0x20}
+
+
+def png_out_format(mode="rgba", depth=8):
+    """(mode, depth) -> the out_format of debig_png_decode_batch_fmt"""
+    if mode not in PNG_MODES:
+        raise ValueError(f"mode must be one of {sorted(PNG_MODES)}, not {mode!r}")
+    if isinstance(depth, bool) or depth not in PNG_DEPTHS:
+        raise ValueError(f"depth must be 8, 16 or 'native', not {depth!r}")
+    return PNG_MODES[mode] | PNG_DEPTHS[depth]
+
+
+def png_out_layout(info, mode="rgba", depth=8):
+    """the output of one image (info: a png_info dict) in (mode, depth) -> (channels, bytes_per_sample, nbytes)
+    (include/decode_png.h: debig_png_out_layout)"""
+    inf = PngInfo(**{k: info[k] for k in ("width", "height", "bit_depth", "color_type", "interlace", "has_trns")})
+    ch, bs = C.c_uint32(), C.c_uint32()
+    nbytes = _png_spec_lib().debig_png_out_layout(C.byref(inf), png_out_format(mode, depth), C.byref(ch), C.byref(bs))
+    if nbytes == 0:
+        raise ValueError(f"no output layout for {info}")
+    return ch.value, bs.value, int(nbytes)
 
 
 def png_info(data):
@@ -242,24 +271,32 @@ def png_info(data):
     return st, _info_dict(inf)
 
 
-def png_decode_batch(datas, force_general=False):
-    """every PNG the specification allows -> RGBA8 (include/decode_png.h: debig_png_decode_batch).
-    -> [(status, rgba ndarray (h, w, 4) or None, info dict)], status as in PNG_STATUS"""
+def png_decode_batch(datas, force_general=False, mode="rgba", depth=8):
+    """every PNG the specification allows -> pixels (include/decode_png.h: debig_png_decode_batch_fmt).
+    mode: "rgba" | "rgb" | "gray" | "gray_alpha" | "native" (as in the file); depth: 8 | 16 | "native" (16 for 16-bit
+    files, else 8).  -> [(status, ndarray (h, w, channels) of uint8 / uint16 or None, info dict)], status as in
+    PNG_STATUS.  The defaults give RGBA8, (h, w, 4) uint8."""
+    fmt = png_out_format(mode, depth)
     L = _png_spec_lib()
     n = len(datas)
     ins = [_u8(d) for d in datas]
-    shapes = []
+    outs, caps = [], []
     for a in ins:
         st, inf = png_info(a)
-        shapes.append((inf["height"], inf["width"]) if st == 0 else (0, 0))
-    outs = [np.empty((h, w, 4), dtype=np.uint8) if h * w else np.empty(4, dtype=np.uint8) for h, w in shapes]
+        if st == 0:
+            ch, bs, nbytes = png_out_layout(inf, mode, depth)
+            outs.append(np.empty((inf["height"], inf["width"], ch), dtype=np.uint16 if bs == 2 else np.uint8))
+            caps.append(nbytes)
+        else:
+            outs.append(np.empty(4, dtype=np.uint8))
+            caps.append(0)
     in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
     in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
     out_ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    caps = (C.c_uint64 * n)(*[4 * h * w for h, w in shapes])
+    caps = (C.c_uint64 * n)(*caps)
     status = (C.c_uint32 * n)()
     infos = (PngInfo * n)()
-    rc = L.debig_png_decode_batch(in_ptrs, in_sizes, out_ptrs, caps, status, infos, n,
-                                  PNG_FORCE_GENERAL if force_general else 0)
-    N.check(rc, "debig_png_decode_batch")
+    rc = L.debig_png_decode_batch_fmt(in_ptrs, in_sizes, out_ptrs, caps, status, infos, n,
+                                      PNG_FORCE_GENERAL if force_general else 0, fmt)
+    N.check(rc, "debig_png_decode_batch_fmt")
     return [(int(status[i]), outs[i] if status[i] == 0 else None, _info_dict(infos[i])) for i in range(n)]

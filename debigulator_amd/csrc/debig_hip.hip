@@ -712,6 +712,16 @@ int debig_hip_png_spec_defilter_batch(void *d_arena, void *d_rgba_arena, const d
     return (int)hipGetLastError();
 }
 
+int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
+                                          debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
+{
+    if (n == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    hipLaunchKernelGGL(debig_png_spec_defilter_fmt_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
+                       (uint8_t *)d_arena, (uint8_t *)d_out_arena, d_tasks, d_results, n);
+    return (int)hipGetLastError();
+}
+
 // inflate -> de-filter in one kernel (png_fused_kernel.inc).  Per group of at most SPLIT_GROUP
 // images: plan, the fused kernel, debig_inflate_kernel for the streams the scan handed back; then, over the whole
 // batch, the one-workgroup de-filter for the images of those streams (PNG_ROW_REDO) and the P3 kernel.

@@ -1,11 +1,12 @@
 /*
- * debig_png_info_get / debig_png_decode_batch (include/decode_png.h): every PNG the specification allows, to RGBA8.
- * Not a reference function.
+ * debig_png_info_get / debig_png_decode_batch / debig_png_decode_batch_fmt / debig_png_out_layout (include/decode_png.h):
+ * every PNG the specification allows, to RGBA8 or to the output format the caller asks for.  Not a reference function.
  *
  * Host side (plain C): the chunk walk and the rules decided by headers alone.  On the GPU: chunk CRC-32 and the
  * Adler-32 trailer (debig_hip_checksum_batch), the IDAT concatenation (debig_hip_gather), inflate (the batch inflate,
- * plain RFC 1951) and the de-filter -- the tuned kernels for non-interlaced 8-bit RGB / RGBA, the general kernel
- * (debig_hip_png_spec_defilter_batch: every colour type, depth, Adam7 pass, tRNS) for everything else.
+ * plain RFC 1951) and the de-filter -- the tuned kernels for non-interlaced 8-bit RGB / RGBA to RGBA8, the general
+ * kernel (debig_hip_png_spec_defilter_batch: every colour type, depth, Adam7 pass, tRNS) for the rest of RGBA8, and
+ * its output-format twin (debig_hip_png_spec_defilter_fmt_batch) for every image whose resolved format is not RGBA8.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -26,6 +27,8 @@ typedef struct spec_file {
     uint32_t n_pal;
     uint16_t key[3];
     uint32_t has_key, general;
+    uint32_t fmt;       /* resolved output format: layout (0..3) | DEBIG_PNG_FMT_16, 0 = RGBA8 */
+    uint64_t out_bytes; /* bytes of the output in that format */
     uint64_t scan;      /* scanline stream bytes */
     /* device layout */
     uint64_t file_off, in_off, out_off, pal_off, scratch_off, rgba_off;
@@ -193,14 +196,50 @@ DEBIG_API uint32_t debig_png_info_get(const uint8_t *p, uint64_t size, debig_png
     return st;
 }
 
+static int fmt_valid(uint32_t f) { return (f & ~0x3fu) == 0 && (f & 15u) <= DEBIG_PNG_FMT_NATIVE && (f & 0x30u) != 0x30u; }
+
+/* out_format -> the concrete layout (0..3) | DEBIG_PNG_FMT_16 of one image (out_format valid, info from the walk) */
+static uint32_t fmt_resolve(const debig_png_info *info, uint32_t out_format)
+{
+    uint32_t lay = out_format & 15u, d16 = out_format & 0x30u;
+    const uint32_t ct = info->color_type;
+    if (lay == DEBIG_PNG_FMT_NATIVE) {
+        if (ct == 0) lay = info->has_trns ? DEBIG_PNG_FMT_GRAY_ALPHA : DEBIG_PNG_FMT_GRAY;
+        else if (ct == 4) lay = DEBIG_PNG_FMT_GRAY_ALPHA;
+        else if (ct == 2 || ct == 3) lay = info->has_trns ? DEBIG_PNG_FMT_RGBA : DEBIG_PNG_FMT_RGB;
+        else lay = DEBIG_PNG_FMT_RGBA;
+    }
+    if (d16 == DEBIG_PNG_FMT_NATIVE_DEPTH) d16 = info->bit_depth == 16 ? DEBIG_PNG_FMT_16 : DEBIG_PNG_FMT_8;
+    return lay | d16;
+}
+static uint32_t fmt_channels(uint32_t fmt) { const uint32_t l = fmt & 15u; return l == 0 ? 4u : l == 1 ? 3u : l == 2 ? 1u : 2u; }
+/* w * h * bytes per pixel (w, h < 2^31), UINT64_MAX where that does not fit 64 bits */
+static uint64_t fmt_size(uint64_t w, uint64_t h, uint32_t fmt)
+{
+    const uint64_t wh = w * h, pb = (uint64_t)fmt_channels(fmt) * (fmt & DEBIG_PNG_FMT_16 ? 2u : 1u);
+    return wh > UINT64_MAX / pb ? UINT64_MAX : wh * pb;
+}
+
+DEBIG_API uint64_t debig_png_out_layout(const debig_png_info *info, uint32_t out_format, uint32_t *channels,
+                                        uint32_t *bytes_per_sample)
+{
+    if (!info || !fmt_valid(out_format) || !depth_ok(info->color_type, info->bit_depth)) return 0;
+    const uint32_t f = fmt_resolve(info, out_format), ch = fmt_channels(f), bs = f & DEBIG_PNG_FMT_16 ? 2u : 1u;
+    if (channels) *channels = ch;
+    if (bytes_per_sample) *bytes_per_sample = bs;
+    return fmt_size(info->width, info->height, f);
+}
+
 /* the host rules after the walk: zlib header, output size; and the sizes the device needs */
-static uint32_t spec_host_rules(spec_file *F, const uint8_t *in, uint8_t *out, uint64_t out_cap)
+static uint32_t spec_host_rules(spec_file *F, const uint8_t *in, uint8_t *out, uint64_t out_cap, uint32_t out_format)
 {
     if (F->z_total < 2) return DEBIG_PNG_E_ZLIB;
     const uint32_t cmf = z_byte(F, in, 0), flg = z_byte(F, in, 1);
     if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u || (flg & 0x20u)) return DEBIG_PNG_E_ZLIB;
-    const uint64_t w = F->info.width, h = F->info.height; /* < 2^31 each: 4wh fits */
-    if (!out || out_cap < 4u * w * h) return DEBIG_PNG_E_OUTPUT;
+    const uint64_t w = F->info.width, h = F->info.height;
+    F->fmt = fmt_resolve(&F->info, out_format);
+    F->out_bytes = fmt_size(w, h, F->fmt); /* UINT64_MAX (no buffer that large): E_OUTPUT */
+    if (!out || out_cap < F->out_bytes) return DEBIG_PNG_E_OUTPUT;
     const uint32_t ct = F->info.color_type, d = F->info.bit_depth, il = F->info.interlace;
     F->scan = 0;
     for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
@@ -215,6 +254,14 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
                                      const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n,
                                      uint32_t flags)
 {
+    return debig_png_decode_batch_fmt(inputs, input_sizes, outs, out_caps, status, infos, n, flags, 0);
+}
+
+DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                                         const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                         uint32_t flags, uint32_t out_format)
+{
+    if (!fmt_valid(out_format)) return DEBIG_PNG_BAD_FORMAT;
     if (n == 0) return 0;
     spec_file *F = (spec_file *)calloc(n, sizeof(spec_file));
     uint32_t *live = (uint32_t *)calloc(n, sizeof(uint32_t)); /* files still good, in order */
@@ -238,20 +285,21 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
     for (uint32_t i = 0; i < n; i++) {
         spec_file *f = &F[i];
         f->status = spec_walk(inputs[i], input_sizes[i], f, 0);
-        if (f->status == DEBIG_PNG_OK) f->status = spec_host_rules(f, inputs[i], outs[i], out_caps[i]);
+        if (f->status == DEBIG_PNG_OK) f->status = spec_host_rules(f, inputs[i], outs[i], out_caps[i], out_format);
         if (f->status == DEBIG_PNG_OK) live[m++] = i;
     }
     if (m == 0) goto report; /* nothing for the device */
     debig_ctx *c = debig_ctx_get(0);
     if (!c) { rc = 1; goto done; }
     /* ---- device layout: whole files (c->files); IDAT concatenations (c->in); per file in c->out the scanline stream
-     *      (+ 16 readable bytes), the palette and the scratch rings of its general-kernel tasks; RGBA (c->rgba) */
+     *      (+ 16 readable bytes), the palette and the scratch rings of its general-kernel tasks; pixels (c->rgba, each
+     *      image 16-byte aligned) */
     uint64_t files_total = 0, in_total = 0, out_total = 64, rgba_total = 0;
-    uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0;
+    uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0, n_ftasks = 0;
     for (uint32_t k = 0; k < m; k++) {
         spec_file *f = &F[live[k]];
         const uint32_t ct = f->info.color_type, d = f->info.bit_depth, il = f->info.interlace;
-        f->general = (flags & DEBIG_PNG_FORCE_GENERAL) || il || d != 8 || !(ct == 6 || (ct == 2 && !f->has_key));
+        f->general = (flags & DEBIG_PNG_FORCE_GENERAL) || f->fmt || il || d != 8 || !(ct == 6 || (ct == 2 && !f->has_key));
         f->file_off = files_total;
         files_total += debig_align16(input_sizes[live[k]]) + 16;
         f->in_off = in_total;
@@ -262,7 +310,7 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
         if (ct == 3) out_total += 1024;
         f->scratch_off = out_total;
         f->rgba_off = rgba_total;
-        rgba_total += debig_align16(4ull * f->info.width * f->info.height) + 16;
+        rgba_total += debig_align16(f->out_bytes) + 16;
         n_chunks += f->n_chunks;
         n_pieces += f->n_idat;
         if (f->general) {
@@ -272,6 +320,7 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
                 if (!wp || !hp) continue;
                 out_total += DEBIG_PNG_SPEC_SCRATCH_BYTES(row_bytes(wp, ct, d));
                 n_tasks++;
+                n_ftasks += f->fmt != 0;
             }
         } else {
             n_img++;
@@ -389,8 +438,10 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
         m = ns;
     }
     if (m == 0) goto report;
-    /* ---- de-filter: tuned kernels for non-interlaced 8-bit RGB / RGBA, the general kernel for the rest */
-    n_img = n_tasks = 0;
+    /* ---- de-filter: tuned kernels for non-interlaced 8-bit RGB / RGBA to RGBA8, the general kernel for the rest of
+     *      RGBA8 (tasks [0, n_tasks)), its output-format twin for every other format (tasks [n_tasks, n_tasks + n_ftasks)) */
+    const uint32_t f_base = n_tasks - n_ftasks;
+    n_img = n_tasks = n_ftasks = 0;
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = live[k];
         spec_file *f = &F[i];
@@ -412,7 +463,8 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
             pass_dims(f->info.width, f->info.height, il, p, g, &wp, &hp);
             if (!wp || !hp) continue;
             const uint64_t rb = row_bytes(wp, ct, d);
-            debig_png_spec_task *t = &tasks[n_tasks];
+            const uint32_t ti = f->fmt ? f_base + n_ftasks++ : n_tasks++;
+            debig_png_spec_task *t = &tasks[ti];
             t->stream_off = pos;
             t->rgba_off = f->rgba_off;
             t->pal_off = f->pal_off;
@@ -428,7 +480,8 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
             memcpy(t->key, f->key, sizeof t->key);
             t->has_key = (uint16_t)f->has_key;
             t->n_pal = (uint16_t)f->n_pal;
-            task_file[n_tasks++] = i;
+            t->out_fmt = (uint16_t)f->fmt;
+            task_file[ti] = i;
             pos += (uint64_t)hp * (1u + rb);
             scratch += DEBIG_PNG_SPEC_SCRATCH_BYTES(rb);
         }
@@ -442,31 +495,42 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
             (rc = debig_hip_memcpy_d2h(ires, c->imgres.ptr, (uint64_t)n_img * sizeof(debig_png_result), NULL)))
             goto done;
     }
+    if ((n_tasks || n_ftasks) && /* both task lists in one buffer, reserved before either launch */
+        ((rc = debig_devbuf_reserve(&c->spec_tasks, (uint64_t)(f_base + n_ftasks) * sizeof(debig_png_spec_task))) ||
+         (rc = debig_devbuf_reserve(&c->spec_res, (uint64_t)(f_base + n_ftasks) * sizeof(debig_png_spec_result)))))
+        goto done;
     if (n_tasks) {
-        if ((rc = debig_devbuf_reserve(&c->spec_tasks, (uint64_t)n_tasks * sizeof(debig_png_spec_task))) ||
-            (rc = debig_devbuf_reserve(&c->spec_res, (uint64_t)n_tasks * sizeof(debig_png_spec_result))) ||
-            (rc = debig_hip_memcpy_h2d(c->spec_tasks.ptr, tasks, (uint64_t)n_tasks * sizeof(debig_png_spec_task), NULL)) ||
+        if ((rc = debig_hip_memcpy_h2d(c->spec_tasks.ptr, tasks, (uint64_t)n_tasks * sizeof(debig_png_spec_task), NULL)) ||
             (rc = debig_hip_png_spec_defilter_batch(c->out.ptr, c->rgba.ptr, (const debig_png_spec_task *)c->spec_tasks.ptr,
                                                     (debig_png_spec_result *)c->spec_res.ptr, n_tasks, NULL)) ||
             (rc = debig_hip_memcpy_d2h(tres, c->spec_res.ptr, (uint64_t)n_tasks * sizeof(debig_png_spec_result), NULL)))
             goto done;
     }
+    if (n_ftasks) {
+        debig_png_spec_task *d_ft = (debig_png_spec_task *)c->spec_tasks.ptr + f_base;
+        debig_png_spec_result *d_fr = (debig_png_spec_result *)c->spec_res.ptr + f_base;
+        if ((rc = debig_hip_memcpy_h2d(d_ft, tasks + f_base, (uint64_t)n_ftasks * sizeof(debig_png_spec_task), NULL)) ||
+            (rc = debig_hip_png_spec_defilter_fmt_batch(c->out.ptr, c->rgba.ptr, d_ft, d_fr, n_ftasks, NULL)) ||
+            (rc = debig_hip_memcpy_d2h(tres + f_base, d_fr, (uint64_t)n_ftasks * sizeof(debig_png_spec_result), NULL)))
+            goto done;
+    }
     if ((rc = debig_hip_stream_sync(NULL))) goto done;
     for (uint32_t k = 0; k < n_img; k++)
         if (!ires[k].good) F[img_file[k]].status = DEBIG_PNG_E_FILTER;
-    for (uint32_t k = 0; k < n_tasks; k++) { /* a filter error anywhere in the image outranks a palette error */
+    for (uint32_t j = 0; j < n_tasks + n_ftasks; j++) { /* a filter error anywhere in the image outranks a palette error */
+        const uint32_t k = j < n_tasks ? j : f_base + (j - n_tasks);
         spec_file *f = &F[task_file[k]];
         if (tres[k].status == DEBIG_PNG_SPEC_E_FILTER) f->status = DEBIG_PNG_E_FILTER;
         else if (tres[k].status == DEBIG_PNG_SPEC_E_PALETTE && f->status == DEBIG_PNG_OK) f->status = DEBIG_PNG_E_PALETTE;
     }
-    /* ---- RGBA down */
+    /* ---- pixels down */
     {
         uint64_t last_end = 0;
         for (uint32_t k = 0; k < m; k++) {
             const uint32_t i = live[k];
             if (F[i].status != DEBIG_PNG_OK) continue;
             dn_dst[i] = outs[i];
-            dn_size[i] = 4ull * F[i].info.width * F[i].info.height;
+            dn_size[i] = F[i].out_bytes;
             dn_off[i] = F[i].rgba_off;
             if (dn_off[i] + dn_size[i] > last_end) last_end = dn_off[i] + dn_size[i];
         }

@@ -1,6 +1,7 @@
 // png_spec_kernel.inc -- the general PNG de-filter (include/decode_png.h: debig_png_decode_batch).
 //
-// Every colour type and bit depth the PNG specification allows, Adam7 passes and tRNS, to RGBA8.  One TASK is one
+// Every colour type and bit depth the PNG specification allows, Adam7 passes and tRNS, to RGBA8 (debig_png_spec_defilter_kernel)
+// or to any output format of decode_png.h (debig_png_spec_defilter_fmt_kernel, the same body with another store stage).  One TASK is one
 // (image, pass) sub-image (debig_png_spec_task); a non-interlaced image is one task placed at (0, 0, 1, 1).
 //
 // Mapping (what png_kernel.inc measured, generalised to a filter unit of BPP = 1, 2, 3, 4, 6 or 8 bytes):
@@ -122,7 +123,226 @@ DEV_INLINE uint32_t spec_pixel_sub(uint32_t s, uint32_t ct, uint32_t depth, cons
     return g * 0x010101u | (a << 24);
 }
 
+// RGBA8 (debig_png_spec_defilter_kernel): one dword per pixel, stored pixel by pixel (the code is in png_spec_task)
+struct PngSpecOutRgba8 {};
+DEV_INLINE uint32_t spec_out_bytes(PngSpecOutRgba8, const debig_png_spec_task &) { return 4u; }
+constexpr bool spec_out_rgba8(PngSpecOutRgba8) { return true; }
+
+// Any output format (debig_png_spec_defilter_fmt_kernel, t.out_fmt: include/decode_png.h DEBIG_PNG_FMT_*, resolved):
+// layout RGBA / RGB / GRAY / GRAY_ALPHA (bits 0..1), 16-bit little-endian samples (DEBIG_PNG_FMT_16 = 0x10) or 8-bit.
+// A pixel is first built as four 16-bit samples (8-bit sources times 257), then reduced to the output depth (the high
+// byte), then laid out: Y = (6968 R + 23434 G + 2366 B + 16384) >> 15 on the output-depth samples (the identity on grey
+// sources, where R = G = B), alpha dropped or kept.
+struct PngSpecOutFmt {};
+constexpr bool spec_out_rgba8(PngSpecOutFmt) { return false; }
+struct SpecPx16 { uint32_t r, g, b, a; };
+DEV_INLINE uint32_t spec_fmt_bytes(uint32_t f)
+{
+    const uint32_t lay = f & 3u;
+    return (lay == 0u ? 4u : lay == 1u ? 3u : lay == 2u ? 1u : 2u) << ((f >> 4) & 1u);
+}
+DEV_INLINE uint32_t spec_out_bytes(PngSpecOutFmt, const debig_png_spec_task &t) { return spec_fmt_bytes(t.out_fmt); }
+
+// spec_pixel at full depth
+DEV_INLINE SpecPx16 spec_pixel16(uint32_t lo, uint32_t hi, uint32_t ct, uint32_t depth, const debig_png_spec_task &t,
+                                 const uint32_t *pal, uint32_t &pal_bad)
+{
+    SpecPx16 p;
+    if (depth == 16u) {
+        const uint32_t s0 = ((lo & 0xffu) << 8) | ((lo >> 8) & 0xffu), s1 = ((lo >> 8) & 0xff00u) | (lo >> 24);
+        const uint32_t s2 = ((hi & 0xffu) << 8) | ((hi >> 8) & 0xffu), s3 = ((hi >> 8) & 0xff00u) | (hi >> 24);
+        if (ct == 0u || ct == 4u) {
+            p.r = p.g = p.b = s0;
+            p.a = ct == 4u ? s1 : t.has_key && s0 == t.key[0] ? 0u : 0xffffu;
+        } else {
+            p.r = s0; p.g = s1; p.b = s2;
+            p.a = ct == 6u ? s3 : t.has_key && s0 == t.key[0] && s1 == t.key[1] && s2 == t.key[2] ? 0u : 0xffffu;
+        }
+        return p;
+    }
+    const uint32_t b0 = lo & 0xffu, b1 = (lo >> 8) & 0xffu, b2 = (lo >> 16) & 0xffu, b3 = lo >> 24;
+    if (ct == 3u) {
+        pal_bad |= b0 >= t.n_pal;
+        const uint32_t e = pal[b0];
+        p.r = (e & 0xffu) * 257u; p.g = ((e >> 8) & 0xffu) * 257u; p.b = ((e >> 16) & 0xffu) * 257u; p.a = (e >> 24) * 257u;
+    } else if (ct == 0u || ct == 4u) {
+        p.r = p.g = p.b = b0 * 257u;
+        p.a = ct == 4u ? b1 * 257u : t.has_key && b0 == t.key[0] ? 0u : 0xffffu;
+    } else {
+        p.r = b0 * 257u; p.g = b1 * 257u; p.b = b2 * 257u;
+        p.a = ct == 6u ? b3 * 257u : t.has_key && b0 == t.key[0] && b1 == t.key[1] && b2 == t.key[2] ? 0u : 0xffffu;
+    }
+    return p;
+}
+// spec_pixel_sub at full depth
+DEV_INLINE SpecPx16 spec_pixel16_sub(uint32_t s, uint32_t ct, uint32_t depth, const debig_png_spec_task &t,
+                                     const uint32_t *pal, uint32_t &pal_bad)
+{
+    SpecPx16 p;
+    if (ct == 3u) {
+        pal_bad |= s >= t.n_pal;
+        const uint32_t e = pal[s];
+        p.r = (e & 0xffu) * 257u; p.g = ((e >> 8) & 0xffu) * 257u; p.b = ((e >> 16) & 0xffu) * 257u; p.a = (e >> 24) * 257u;
+        return p;
+    }
+    p.r = p.g = p.b = s * (depth == 1u ? 65535u : depth == 2u ? 21845u : 4369u); /* (255, 85, 17) * 257 */
+    p.a = t.has_key && s == t.key[0] ? 0u : 0xffffu;
+    return p;
+}
+// the pixel's bytes in output order, little-endian: lo = bytes 0..3, hi = bytes 4..7
+template <uint32_t F>
+DEV_INLINE void spec_fmt_pack(SpecPx16 p, uint32_t &lo, uint32_t &hi)
+{
+    constexpr uint32_t lay = F & 3u;
+    constexpr uint32_t sh = F & 0x10u ? 0u : 8u;
+    const uint32_t r = p.r >> sh, g = p.g >> sh, b = p.b >> sh, a = p.a >> sh;
+    const uint32_t y = (6968u * r + 23434u * g + 2366u * b + 16384u) >> 15;
+    if (F & 0x10u) {
+        lo = lay <= 1u ? r | (g << 16) : lay == 2u ? y : y | (a << 16);
+        hi = lay == 0u ? b | (a << 16) : lay == 1u ? b : 0u;
+    } else {
+        lo = lay == 0u ? r | (g << 8) | (b << 16) | (a << 24) : lay == 1u ? r | (g << 8) | (b << 16) : lay == 2u ? y : y | (a << 8);
+        hi = 0u;
+    }
+}
+// one pixel of PB bytes at p (p is aligned to PB for PB = 1, 2, 4, 8 and to 2 for PB = 6)
+template <uint32_t PB>
+DEV_INLINE void spec_store_px(uint8_t *p, uint32_t lo, uint32_t hi)
+{
+    if (PB == 1u) {
+        *p = (uint8_t)lo;
+    } else if (PB == 2u) {
+        *reinterpret_cast<uint16_t *>(p) = (uint16_t)lo;
+    } else if (PB == 3u) {
+        p[0] = (uint8_t)lo; p[1] = (uint8_t)(lo >> 8); p[2] = (uint8_t)(lo >> 16);
+    } else if (PB == 4u) {
+        *reinterpret_cast<uint32_t *>(p) = lo;
+    } else if (PB == 6u) {
+        uint16_t *q = reinterpret_cast<uint16_t *>(p);
+        q[0] = (uint16_t)lo; q[1] = (uint16_t)(lo >> 16); q[2] = (uint16_t)hi;
+    } else {
+        uint2 v;
+        v.x = lo; v.y = hi;
+        *reinterpret_cast<uint2 *>(p) = v;
+    }
+}
+// NB contiguous bytes (B: NB / 4 dwords, rounded up) at p, in the widest stores p's alignment allows
+template <uint32_t NB>
+DEV_INLINE void spec_store_run(uint8_t *p, const uint32_t *B)
+{
+    const uint32_t al = (uint32_t)reinterpret_cast<uintptr_t>(p) & 15u;
+    if (NB % 16u == 0u && al == 0u) {
+DEV_UNROLL
+        for (uint32_t i = 0; i < NB / 16u; i++) {
+            uint4 v;
+            v.x = B[4u * i]; v.y = B[4u * i + 1u]; v.z = B[4u * i + 2u]; v.w = B[4u * i + 3u];
+            *reinterpret_cast<uint4 *>(p + 16u * i) = v;
+        }
+    } else if (NB % 8u == 0u && (al & 7u) == 0u) {
+DEV_UNROLL
+        for (uint32_t i = 0; i < NB / 8u; i++) {
+            uint2 v;
+            v.x = B[2u * i]; v.y = B[2u * i + 1u];
+            *reinterpret_cast<uint2 *>(p + 8u * i) = v;
+        }
+    } else if (NB % 4u == 0u && (al & 3u) == 0u) {
+DEV_UNROLL
+        for (uint32_t i = 0; i < NB / 4u; i++) *reinterpret_cast<uint32_t *>(p + 4u * i) = B[i];
+    } else if (NB % 2u == 0u && (al & 1u) == 0u) {
+DEV_UNROLL
+        for (uint32_t i = 0; i < NB / 2u; i++) *reinterpret_cast<uint16_t *>(p + 2u * i) = (uint16_t)(B[i / 2u] >> (16u * (i & 1u)));
+    } else {
+DEV_UNROLL
+        for (uint32_t i = 0; i < NB; i++) p[i] = (uint8_t)(B[i / 4u] >> (8u * (i & 3u)));
+    }
+}
+// N pixels (lo / hi) that belong at x, x + dx, ...: one run when they are contiguous and all inside the row, else
+// pixel by pixel up to the row's end
+template <uint32_t PB, uint32_t N>
+DEV_INLINE void spec_store_pixels(uint8_t *orow, uint64_t x, uint32_t w, uint64_t ostep, uint32_t dx, const uint32_t *lo,
+                                  const uint32_t *hi)
+{
+    if (dx == 1u && x + N <= w) {
+        uint32_t B[(N * PB + 3u) / 4u + 1u];
+DEV_UNROLL
+        for (uint32_t i = 0; i < (N * PB + 3u) / 4u + 1u; i++) B[i] = 0u;
+DEV_UNROLL
+        for (uint32_t j = 0; j < N; j++) {
+            spec_put(B, j * PB, lo[j]);
+            if (PB > 4u) spec_put(B, j * PB + 4u, hi[j]);
+        }
+        spec_store_run<N * PB>(orow + x * PB, B);
+    } else {
+DEV_UNROLL
+        for (uint32_t j = 0; j < N; j++)
+            if (x + j < w) spec_store_px<PB>(orow + (x + j) * ostep, lo[j], hi[j]);
+    }
+}
+template <int BPP, uint32_t F, uint32_t DEPTH>
+DEV_INLINE void spec_fmt_group_sub(const uint32_t *R, int g, uint32_t w, uint32_t ct, const debig_png_spec_task &t,
+                                   const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep)
+{
+    constexpr uint32_t K = PngSpecShape<BPP>::K, CH = (F & 3u) == 0u ? 4u : (F & 3u) == 1u ? 3u : (F & 3u) == 2u ? 1u : 2u;
+    constexpr uint32_t PPB = 8u / DEPTH, PB = CH << ((F >> 4) & 1u);
+DEV_UNROLL
+    for (uint32_t j = 0; j < K; j++) {
+        const uint32_t byte = spec_get(R, j, 1u);
+        const uint64_t xb = ((uint64_t)g * K + j) * PPB;
+        if (xb >= w) break;
+        uint32_t lo[PPB], hi[PPB];
+DEV_UNROLL
+        for (uint32_t s = 0; s < PPB; s++) {
+            uint32_t bad = 0u;
+            const SpecPx16 p = spec_pixel16_sub((byte >> (8u - DEPTH * (s + 1u))) & ((1u << DEPTH) - 1u), ct, DEPTH, t, pal, bad);
+            pal_bad |= xb + s < w ? bad : 0u;
+            spec_fmt_pack<F>(p, lo[s], hi[s]);
+        }
+        spec_store_pixels<PB, PPB>(orow, xb, w, ostep, t.dx, lo, hi);
+    }
+}
+template <int BPP, uint32_t F>
+DEV_INLINE void spec_fmt_group(const uint32_t *R, int g, uint32_t w, uint32_t depth, uint32_t ct, const debig_png_spec_task &t,
+                               const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep)
+{
+    constexpr uint32_t K = PngSpecShape<BPP>::K, CH = (F & 3u) == 0u ? 4u : (F & 3u) == 1u ? 3u : (F & 3u) == 2u ? 1u : 2u;
+    constexpr uint32_t PB = CH << ((F >> 4) & 1u);
+    if (BPP == 1 && depth < 8u) {
+        if (depth == 1u) spec_fmt_group_sub<BPP, F, 1u>(R, g, w, ct, t, pal, pal_bad, orow, ostep);
+        else if (depth == 2u) spec_fmt_group_sub<BPP, F, 2u>(R, g, w, ct, t, pal, pal_bad, orow, ostep);
+        else spec_fmt_group_sub<BPP, F, 4u>(R, g, w, ct, t, pal, pal_bad, orow, ostep);
+        return;
+    }
+    const uint64_t x = (uint64_t)g * K;
+    uint32_t lo[K], hi[K];
+DEV_UNROLL
+    for (uint32_t j = 0; j < K; j++) {
+        uint32_t bad = 0u;
+        const uint32_t ulo = spec_get(R, j * (uint32_t)BPP, BPP < 4 ? (uint32_t)BPP : 4u);
+        const uint32_t uhi = BPP > 4 ? spec_get(R, j * (uint32_t)BPP + 4u, (uint32_t)BPP - 4u) : 0u;
+        const SpecPx16 p = spec_pixel16(ulo, uhi, ct, depth, t, pal, bad);
+        pal_bad |= x + j < w ? bad : 0u;
+        spec_fmt_pack<F>(p, lo[j], hi[j]);
+    }
+    spec_store_pixels<PB, K>(orow, x, w, ostep, t.dx, lo, hi);
+}
 template <int BPP>
+DEV_INLINE void spec_out_group(PngSpecOutFmt, const uint32_t *R, int g, uint32_t w, uint32_t depth, uint32_t ct,
+                               const debig_png_spec_task &t, const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow,
+                               uint64_t ostep)
+{
+    switch (t.out_fmt) { /* workgroup-uniform */
+    case 0x01u: spec_fmt_group<BPP, 0x01u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    case 0x02u: spec_fmt_group<BPP, 0x02u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    case 0x03u: spec_fmt_group<BPP, 0x03u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    case 0x10u: spec_fmt_group<BPP, 0x10u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    case 0x11u: spec_fmt_group<BPP, 0x11u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    case 0x12u: spec_fmt_group<BPP, 0x12u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    case 0x13u: spec_fmt_group<BPP, 0x13u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    default: spec_fmt_group<BPP, 0x00u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
+    }
+}
+
+template <int BPP, class O>
 DEV_INLINE void png_spec_task(PngSpecLds &L, uint8_t *__restrict__ arena, uint8_t *__restrict__ rgba_arena,
                               const debig_png_spec_task &t, const uint32_t tid)
 {
@@ -157,8 +377,8 @@ DEV_INLINE void png_spec_task(PngSpecLds &L, uint8_t *__restrict__ arena, uint8_
         const uint32_t *upring = ring + (pitch / 4u) * ((band + PNG_SPEC_NWD - 1u) % PNG_SPEC_NWD);
         uint32_t *myring = ring + (pitch / 4u) * (band % PNG_SPEC_NWD);
         const uint64_t out_y = (uint64_t)t.y0 + (uint64_t)(active ? row : 0u) * t.dy;
-        uint8_t *orow = out + (out_y * t.img_width + t.x0) * 4u;
-        const uint64_t ostep = 4u * (uint64_t)t.dx;
+        uint8_t *orow = out + (out_y * t.img_width + t.x0) * spec_out_bytes(O(), t);
+        const uint64_t ostep = spec_out_bytes(O(), t) * (uint64_t)t.dx;
         uint32_t R[GD + 1], a[ND], c[ND];
 DEV_UNROLL
         for (uint32_t i = 0; i <= GD; i++) R[i] = 0u;
@@ -251,28 +471,32 @@ DEV_UNROLL
                         for (uint32_t i = 0; i < GD; i++) myring[(uint32_t)g * GD + i] = R[i];
                     }
                     // ---- pixels: unpack / reduce / key / palette, strided Adam7 store
-                    if (BPP == 1 && depth < 8u) {
-                        const uint32_t mask = (1u << depth) - 1u;
+                    if constexpr (spec_out_rgba8(O())) {
+                        if (BPP == 1 && depth < 8u) {
+                            const uint32_t mask = (1u << depth) - 1u;
 DEV_UNROLL
-                        for (uint32_t j = 0; j < K; j++) {
-                            const uint32_t byte = spec_get(R, j, 1u);
-                            const uint64_t xb = ((uint64_t)g * K + j) * ppb;
-                            for (uint32_t s = 0; s < ppb; s++) {
-                                if (xb + s >= w) break;
-                                const uint32_t smp = (byte >> (8u - depth * (s + 1u))) & mask;
-                                const uint32_t px = spec_pixel_sub(smp, ct, depth, t, L.pal, pal_bad);
-                                *reinterpret_cast<uint32_t *>(orow + (xb + s) * ostep) = px;
+                            for (uint32_t j = 0; j < K; j++) {
+                                const uint32_t byte = spec_get(R, j, 1u);
+                                const uint64_t xb = ((uint64_t)g * K + j) * ppb;
+                                for (uint32_t s = 0; s < ppb; s++) {
+                                    if (xb + s >= w) break;
+                                    const uint32_t smp = (byte >> (8u - depth * (s + 1u))) & mask;
+                                    const uint32_t px = spec_pixel_sub(smp, ct, depth, t, L.pal, pal_bad);
+                                    *reinterpret_cast<uint32_t *>(orow + (xb + s) * ostep) = px;
+                                }
+                            }
+                        } else {
+DEV_UNROLL
+                            for (uint32_t j = 0; j < K; j++) {
+                                const uint64_t x = (uint64_t)g * K + j;
+                                if (x >= w) break;
+                                const uint32_t lo = spec_get(R, j * (uint32_t)BPP, BPP < 4 ? (uint32_t)BPP : 4u);
+                                const uint32_t hi = BPP > 4 ? spec_get(R, j * (uint32_t)BPP + 4u, (uint32_t)BPP - 4u) : 0u;
+                                *reinterpret_cast<uint32_t *>(orow + x * ostep) = spec_pixel(lo, hi, ct, depth, t, L.pal, pal_bad);
                             }
                         }
-                    } else {
-DEV_UNROLL
-                        for (uint32_t j = 0; j < K; j++) {
-                            const uint64_t x = (uint64_t)g * K + j;
-                            if (x >= w) break;
-                            const uint32_t lo = spec_get(R, j * (uint32_t)BPP, BPP < 4 ? (uint32_t)BPP : 4u);
-                            const uint32_t hi = BPP > 4 ? spec_get(R, j * (uint32_t)BPP + 4u, (uint32_t)BPP - 4u) : 0u;
-                            *reinterpret_cast<uint32_t *>(orow + x * ostep) = spec_pixel(lo, hi, ct, depth, t, L.pal, pal_bad);
-                        }
+                    } else { /* the output format of the task */
+                        spec_out_group<BPP>(O(), R, g, w, depth, ct, t, L.pal, pal_bad, orow, ostep);
                     }
                 }
             }
@@ -287,12 +511,11 @@ DEV_UNROLL
     if (__any(pal_bad != 0u) && lane == 0) atomicOr(&L.pal_bad, 1u);
 }
 
-__global__ void __launch_bounds__(64 * PNG_SPEC_NWD)
-debig_png_spec_defilter_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict__ rgba_arena,
+template <class O>
+DEV_INLINE void png_spec_tasks(PngSpecLds &L, uint8_t *__restrict__ arena, uint8_t *__restrict__ rgba_arena,
                                const debig_png_spec_task *__restrict__ tasks, debig_png_spec_result *__restrict__ results,
                                uint32_t n_tasks)
 {
-    __shared__ PngSpecLds L;
     const uint32_t tid = threadIdx.x;
     for (uint32_t k = blockIdx.x; k < n_tasks; k += gridDim.x) {
         const debig_png_spec_task t = tasks[k];
@@ -304,12 +527,12 @@ debig_png_spec_defilter_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict_
         if (tid == 0) { L.first_bad = 0xffffffffu; L.pal_bad = 0u; }
         __syncthreads();
         switch (t.bpp_f) { /* workgroup-uniform */
-        case 1: png_spec_task<1>(L, arena, rgba_arena, t, tid); break;
-        case 2: png_spec_task<2>(L, arena, rgba_arena, t, tid); break;
-        case 3: png_spec_task<3>(L, arena, rgba_arena, t, tid); break;
-        case 4: png_spec_task<4>(L, arena, rgba_arena, t, tid); break;
-        case 6: png_spec_task<6>(L, arena, rgba_arena, t, tid); break;
-        case 8: png_spec_task<8>(L, arena, rgba_arena, t, tid); break;
+        case 1: png_spec_task<1, O>(L, arena, rgba_arena, t, tid); break;
+        case 2: png_spec_task<2, O>(L, arena, rgba_arena, t, tid); break;
+        case 3: png_spec_task<3, O>(L, arena, rgba_arena, t, tid); break;
+        case 4: png_spec_task<4, O>(L, arena, rgba_arena, t, tid); break;
+        case 6: png_spec_task<6, O>(L, arena, rgba_arena, t, tid); break;
+        case 8: png_spec_task<8, O>(L, arena, rgba_arena, t, tid); break;
         default: if (tid == 0) L.first_bad = 0xfffffffeu; break;
         }
         __syncthreads();
@@ -320,4 +543,25 @@ debig_png_spec_defilter_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict_
         }
         __syncthreads();
     }
+}
+
+
+__global__ void __launch_bounds__(64 * PNG_SPEC_NWD)
+debig_png_spec_defilter_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict__ rgba_arena,
+                               const debig_png_spec_task *__restrict__ tasks, debig_png_spec_result *__restrict__ results,
+                               uint32_t n_tasks)
+{
+    __shared__ PngSpecLds L;
+    png_spec_tasks<PngSpecOutRgba8>(L, arena, rgba_arena, tasks, results, n_tasks);
+}
+
+// the same tasks to the output format each carries (t.out_fmt); a kernel of its own, so that the RGBA8 kernel keeps its
+// registers and its occupancy
+__global__ void __launch_bounds__(64 * PNG_SPEC_NWD)
+debig_png_spec_defilter_fmt_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict__ out_arena,
+                                   const debig_png_spec_task *__restrict__ tasks, debig_png_spec_result *__restrict__ results,
+                                   uint32_t n_tasks)
+{
+    __shared__ PngSpecLds L;
+    png_spec_tasks<PngSpecOutFmt>(L, arena, out_arena, tasks, results, n_tasks);
 }

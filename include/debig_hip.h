@@ -295,10 +295,11 @@ int debig_hip_png_decode_fused_batch(const void *d_in, void *d_streams_arena, co
 
 /* One task of the general de-filter (csrc/png_spec_kernel.inc, behind debig_png_decode_batch in decode_png.h): one
  * (image, Adam7 pass) sub-image of ANY colour type / bit depth the PNG specification allows -> RGBA8 pixels of the
- * full image at (x0 + x dx, y0 + y dy).  A non-interlaced image is one task at (0, 0, 1, 1). */
+ * full image at (x0 + x dx, y0 + y dy), or pixels of the format out_fmt (debig_hip_png_spec_defilter_fmt_batch).  A
+ * non-interlaced image is one task at (0, 0, 1, 1). */
 typedef struct debig_png_spec_task {
     uint64_t stream_off;  /* first filter byte of the sub-image's h * (1 + rowbytes) scanline bytes, rel. to d_arena (>= 16) */
-    uint64_t rgba_off;    /* the FULL image's 4 * img_width * img_height output, rel. to d_rgba_arena (4-byte aligned) */
+    uint64_t rgba_off;    /* the FULL image's output (img_width * img_height pixels), rel. to d_rgba_arena (16-byte aligned) */
     uint64_t pal_off;     /* colour type 3: 256 RGBA dwords (tRNS alpha folded in), rel. to d_arena (4-byte aligned)     */
     uint64_t scratch_off; /* DEBIG_PNG_SPEC_SCRATCH_BYTES(...) of scratch, rel. to d_arena (16-byte aligned)             */
     uint32_t width, height; /* of the sub-image (w_p, h_p >= 1)                                                          */
@@ -309,7 +310,7 @@ typedef struct debig_png_spec_task {
     uint16_t key[3];        /* tRNS key (colour type 0: key[0]; 2: RGB), raw samples at full depth                      */
     uint16_t has_key;
     uint16_t n_pal;         /* palette entries; an index >= n_pal fails the task with DEBIG_PNG_SPEC_E_PALETTE           */
-    uint16_t reserved16;
+    uint16_t out_fmt;       /* output format, resolved (decode_png.h DEBIG_PNG_FMT_*: layout 0..3 | DEBIG_PNG_FMT_16); 0 = RGBA8 */
     uint32_t reserved;
 } debig_png_spec_task;
 
@@ -325,6 +326,10 @@ enum { DEBIG_PNG_SPEC_E_FILTER = 1, DEBIG_PNG_SPEC_E_PALETTE = 2 };
  * must stay readable for 16 bytes past the end of every task's scanline bytes (rows are fetched as 16-byte pieces). */
 int debig_hip_png_spec_defilter_batch(void *d_arena, void *d_rgba_arena, const debig_png_spec_task *d_tasks,
                                       debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
+/* The same for tasks of any output format (each task's out_fmt; 0 is RGBA8, byte for byte as above): pixels of
+ * channels * bytes-per-sample bytes, rows of img_width pixels without padding, 16-bit samples little-endian. */
+int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
+                                          debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

@@ -116,7 +116,7 @@ enum {
     DEBIG_PNG_E_DATA_LONG = 9,  /* the stream holds more than the scanlines                       */
     DEBIG_PNG_E_FILTER = 10,    /* a filter type > 4                                              */
     DEBIG_PNG_E_PALETTE = 11,   /* PLTE length, or a palette index past its entries               */
-    DEBIG_PNG_E_OUTPUT = 12     /* out_caps[i] < 4wh (or outs[i] NULL)                            */
+    DEBIG_PNG_E_OUTPUT = 12     /* out_caps[i] < 4wh, or the size of the requested format (or outs[i] NULL) */
 };
 
 /* Host only: signature, IHDR and the chunks up to the first IDAT -> *info (for sizing outs).  DEBIG_PNG_OK or the
@@ -127,6 +127,48 @@ uint32_t debig_png_info_get(const uint8_t *p, uint64_t size, debig_png_info *inf
 int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
                            const uint64_t *out_caps, uint32_t *status, debig_png_info *infos /* may be NULL */,
                            uint32_t n, uint32_t flags);
+
+/* ---- output formats: out_format = layout | depth ---------------------------------------------------------------------
+ * layout:  DEBIG_PNG_FMT_RGBA (R, G, B, A), _RGB (R, G, B), _GRAY (Y), _GRAY_ALPHA (Y, A), or _NATIVE: per image, as in
+ *          the file -- colour type 0: GRAY, or GRAY_ALPHA with a tRNS key; 4: GRAY_ALPHA; 2 and 3: RGB, or RGBA with a
+ *          tRNS chunk; 6: RGBA.
+ * depth:   DEBIG_PNG_FMT_8 (uint8 samples), _16 (uint16, LITTLE-endian), or _NATIVE_DEPTH: 16 for 16-bit files, else 8
+ *          (palette and 1/2/4-bit grey files are 8-bit).
+ * out_format == 0 is RGBA8: exactly the output of debig_png_decode_batch.
+ * Per pixel, in this order:
+ *   1. the source samples at source precision P (16 for 16-bit files, else 8): 1/2/4-bit grey scaled to 8 bits by
+ *      255/85/17, palette entries 8-bit; alpha from colour types 4 and 6, or from a tRNS that applies (palette alpha,
+ *      255 for the entries it does not cover; a colour type 0/2 key: alpha 0 on a match, the maximum otherwise);
+ *   2. to the output depth D: 16 -> 8 keeps the high byte, 8 -> 16 is v * 257;
+ *   3. the layout, on the D-bit samples: grey from colour Y = (6968 R + 23434 G + 2366 B + 16384) >> 15; colour from
+ *      grey R = G = B = Y; missing alpha is the maximum (255 or 65535); an unwanted alpha is dropped (no compositing).
+ * Output: h rows of w * channels * D/8 bytes, top-down, no row padding. */
+enum {
+    DEBIG_PNG_FMT_RGBA = 0,
+    DEBIG_PNG_FMT_RGB = 1,
+    DEBIG_PNG_FMT_GRAY = 2,
+    DEBIG_PNG_FMT_GRAY_ALPHA = 3,
+    DEBIG_PNG_FMT_NATIVE = 4,
+    DEBIG_PNG_FMT_8 = 0x00,
+    DEBIG_PNG_FMT_16 = 0x10,
+    DEBIG_PNG_FMT_NATIVE_DEPTH = 0x20
+};
+#define DEBIG_PNG_BAD_FORMAT (-1) /* debig_png_decode_batch_fmt: out_format is not layout | depth of the tables above */
+
+/* Host only: the output of one image in out_format -- *channels (1..4) and *bytes_per_sample (1 or 2), either may be
+ * NULL -- and its size in bytes, w * h * channels * bytes_per_sample in 64 bits (UINT64_MAX where that does not fit).
+ * 0 for an invalid out_format (or an info without a valid colour type / depth).  Size outs[i] with debig_png_info_get and this call. */
+uint64_t debig_png_out_layout(const debig_png_info *info, uint32_t out_format, uint32_t *channels,
+                              uint32_t *bytes_per_sample);
+
+/* debig_png_decode_batch to out_format: the same statuses, in the same order, and the same flags; E_OUTPUT when
+ * out_caps[i] is smaller than debig_png_out_layout(&info, out_format, ...).  An out_format outside the tables returns
+ * DEBIG_PNG_BAD_FORMAT and writes nothing (no status either).  debig_png_decode_batch(...) is
+ * debig_png_decode_batch_fmt(..., 0).  Images whose resolved format is RGBA8 take the routing above; every other image
+ * goes through the general kernel's output-format twin (debig_hip_png_spec_defilter_fmt_batch). */
+int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                               const uint64_t *out_caps, uint32_t *status, debig_png_info *infos /* may be NULL */,
+                               uint32_t n, uint32_t flags, uint32_t out_format);
 
 #ifdef __cplusplus
 }

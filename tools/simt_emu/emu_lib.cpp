@@ -302,3 +302,11 @@ extern "C" int emu_png_spec_defilter_batch(void *arena, void *rgba_arena, const 
     if (n) EMU_LAUNCH(debig_png_spec_defilter_kernel, n, 64 * PNG_SPEC_NWD, (uint8_t *)arena, (uint8_t *)rgba_arena, tasks, results, n);
     return 0;
 }
+
+/* ... and its output-format twin, as debig_hip_png_spec_defilter_fmt_batch launches it */
+extern "C" int emu_png_spec_defilter_fmt_batch(void *arena, void *out_arena, const debig_png_spec_task *tasks,
+                                               debig_png_spec_result *results, uint32_t n)
+{
+    if (n) EMU_LAUNCH(debig_png_spec_defilter_fmt_kernel, n, 64 * PNG_SPEC_NWD, (uint8_t *)arena, (uint8_t *)out_arena, tasks, results, n);
+    return 0;
+}
