@@ -211,7 +211,7 @@ def gunzip_batch(datas, out_caps):
 
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
-              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output"}
+              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -300,3 +300,74 @@ def png_decode_batch(datas, force_general=False, mode="rgba", depth=8):
                                       PNG_FORCE_GENERAL if force_general else 0, fmt)
     N.check(rc, "debig_png_decode_batch_fmt")
     return [(int(status[i]), outs[i] if status[i] == 0 else None, _info_dict(infos[i])) for i in range(n)]
+
+
+class ApngFrame(C.Structure):  # include/decode_png.h: debig_apng_frame
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("x_off", C.c_uint32), ("y_off", C.c_uint32),
+                ("delay_num", C.c_uint16), ("delay_den", C.c_uint16), ("dispose_op", C.c_uint8), ("blend_op", C.c_uint8),
+                ("reserved", C.c_uint16)]
+
+
+class ApngInfo(C.Structure):  # include/decode_png.h: debig_apng_info
+    _fields_ = [("png", PngInfo), ("num_frames", C.c_uint32), ("num_plays", C.c_uint32),
+                ("default_is_frame", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_APNG_LIST_CAP = 1 << 16  # frames listed for a file that fails the walk (its num_frames is only what acTL claims)
+
+
+def _apng_lib():
+    L = _png_spec_lib()
+    L.debig_apng_info_get.restype = C.c_uint32
+    L.debig_apng_info_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ApngInfo), C.c_void_p, C.c_uint32]
+    L.debig_apng_decode_batch.restype = C.c_int
+    L.debig_apng_decode_batch.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32]
+    return L
+
+
+def apng_info(data):
+    """the whole chunk walk of a PNG or APNG, no CRCs (host only, include/decode_png.h: debig_apng_info_get) ->
+    (status, info): the png_info dict plus num_frames, num_plays, default_is_frame and frames, a list of dicts with x, y,
+    width, height, delay_num, delay_den, dispose and blend (a still PNG: one frame, the whole canvas)"""
+    d = _u8(data)
+    L = _apng_lib()
+    inf = ApngInfo()
+    st = L.debig_apng_info_get(d.ctypes.data, len(d), C.byref(inf), None, 0)
+    cap = inf.num_frames if st == 0 else min(inf.num_frames, _APNG_LIST_CAP)
+    frames = (ApngFrame * max(cap, 1))()
+    if cap:
+        L.debig_apng_info_get(d.ctypes.data, len(d), C.byref(inf), frames, cap)
+    out = _info_dict(inf.png)
+    out.update(num_frames=int(inf.num_frames), num_plays=int(inf.num_plays), default_is_frame=int(inf.default_is_frame))
+    out["frames"] = [{"x": int(f.x_off), "y": int(f.y_off), "width": int(f.width), "height": int(f.height),
+                      "delay_num": int(f.delay_num), "delay_den": int(f.delay_den), "dispose": int(f.dispose_op),
+                      "blend": int(f.blend_op)} for f in frames[:cap] if f.width]
+    return st, out
+
+
+def apng_decode_batch(datas, force_general=False):
+    """animated (and still) PNGs -> composited RGBA8 frames (include/decode_png.h: debig_apng_decode_batch) ->
+    [(status, ndarray (F, H, W, 4) uint8 or None, info dict as apng_info gives it)], status as in PNG_STATUS; frame k is
+    the canvas after frame k is rendered, before its dispose_op"""
+    L = _apng_lib()
+    n = len(datas)
+    ins = [_u8(d) for d in datas]
+    outs, caps, pre = [], [], []
+    for a in ins:
+        st, inf = apng_info(a)
+        pre.append(inf)
+        if st == 0:
+            outs.append(np.empty((inf["num_frames"], inf["height"], inf["width"], 4), dtype=np.uint8))
+            caps.append(outs[-1].nbytes)
+        else:
+            outs.append(np.empty(4, dtype=np.uint8))
+            caps.append(0)
+    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
+    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
+    out_ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    caps = (C.c_uint64 * n)(*caps)
+    status = (C.c_uint32 * n)()
+    rc = L.debig_apng_decode_batch(in_ptrs, in_sizes, out_ptrs, caps, status, None, n,
+                                   PNG_FORCE_GENERAL if force_general else 0)
+    N.check(rc, "debig_apng_decode_batch")
+    return [(int(status[i]), outs[i] if status[i] == 0 else None, pre[i]) for i in range(n)]

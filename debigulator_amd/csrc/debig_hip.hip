@@ -14,6 +14,7 @@
 #include "png_kernel.inc"
 #include "png_fused_kernel.inc"
 #include "png_spec_kernel.inc"
+#include "apng_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -719,6 +720,18 @@ int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, cons
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
     hipLaunchKernelGGL(debig_png_spec_defilter_fmt_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
                        (uint8_t *)d_arena, (uint8_t *)d_out_arena, d_tasks, d_results, n);
+    return (int)hipGetLastError();
+}
+
+// APNG compositing (apng_kernel.inc): one workgroup of 256 lanes per canvas slice; the grid is capped, the kernel loops
+int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena, const debig_apng_task *d_tasks,
+                                   uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_apng_composite_kernel, dim3(grid), dim3(APNG_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_frames_arena, (uint8_t *)d_out_arena, d_tasks, n_tasks);
     return (int)hipGetLastError();
 }
 

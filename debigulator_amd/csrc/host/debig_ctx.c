@@ -47,6 +47,8 @@ void debig_ctx_release_ptr(debig_ctx *c)
     buf_free(&c->copies);
     buf_free(&c->spec_tasks);
     buf_free(&c->spec_res);
+    buf_free(&c->anim);
+    buf_free(&c->anim_tasks);
     buf_free(&c->ws);
     buf_free(&c->dense);
     buf_free(&c->dense_list);

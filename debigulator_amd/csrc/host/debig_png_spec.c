@@ -12,27 +12,7 @@
 #include <string.h>
 #include "decode_png.h"
 #include "debig_ctx.h"
-
-typedef struct spec_piece { uint64_t off, len; } spec_piece;
-typedef struct spec_chunk { uint64_t off, len; uint32_t crc; } spec_chunk;
-
-typedef struct spec_file {
-    uint32_t status;
-    debig_png_info info;
-    uint32_t n_chunks, cap_chunks, n_idat, cap_idat;
-    spec_chunk *chunks; /* type + data spans and the CRCs stored in the file */
-    spec_piece *idat;   /* IDAT payloads, in file order */
-    uint64_t z_total;   /* bytes of the concatenated IDAT payloads (zlib header + DEFLATE + trailer) */
-    uint32_t pal[256];  /* RGBA, tRNS alpha folded in */
-    uint32_t n_pal;
-    uint16_t key[3];
-    uint32_t has_key, general;
-    uint32_t fmt;       /* resolved output format: layout (0..3) | DEBIG_PNG_FMT_16, 0 = RGBA8 */
-    uint64_t out_bytes; /* bytes of the output in that format */
-    uint64_t scan;      /* scanline stream bytes */
-    /* device layout */
-    uint64_t file_off, in_off, out_off, pal_off, scratch_off, rgba_off;
-} spec_file;
+#include "debig_png_spec.h"
 
 static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
 static const uint32_t adam7[7][4] = {{0, 0, 8, 8}, {4, 0, 8, 8}, {0, 4, 4, 8}, {2, 0, 4, 4}, {0, 2, 2, 4}, {1, 0, 2, 2}, {0, 1, 1, 2}};
@@ -71,6 +51,80 @@ static int grow(void **p, uint32_t *cap, uint32_t n, size_t elem)
     *cap = c;
     return 1;
 }
+int spec_grow(void **p, uint32_t *cap, uint32_t n, size_t elem) { return grow(p, cap, n, elem); }
+uint32_t spec_be32(const uint8_t *p) { return sbe32(p); }
+
+int spec_zlib_header_ok(uint32_t cmf, uint32_t flg)
+{
+    return (cmf & 15u) == 8u && (cmf >> 4) <= 7u && ((cmf << 8) | flg) % 31u == 0u && !(flg & 0x20u);
+}
+
+uint64_t spec_scan_bytes(const debig_png_info *info, uint32_t w, uint32_t h)
+{
+    const uint32_t ct = info->color_type, d = info->bit_depth, il = info->interlace;
+    uint64_t scan = 0;
+    for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
+        uint32_t g[4], wp, hp;
+        pass_dims(w, h, il, p, g, &wp, &hp);
+        if (wp && hp) scan += (uint64_t)hp * (1u + row_bytes(wp, ct, d));
+    }
+    return scan;
+}
+
+int spec_is_general(const spec_file *F, uint32_t flags)
+{
+    const uint32_t ct = F->info.color_type, d = F->info.bit_depth, il = F->info.interlace;
+    return (flags & DEBIG_PNG_FORCE_GENERAL) || F->fmt || il || d != 8 || !(ct == 6 || (ct == 2 && !F->has_key));
+}
+
+uint64_t spec_general_scratch(const debig_png_info *info, uint32_t w, uint32_t h, uint32_t *n_tasks)
+{
+    const uint32_t ct = info->color_type, d = info->bit_depth, il = info->interlace;
+    uint64_t bytes = 0;
+    *n_tasks = 0;
+    for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
+        uint32_t g[4], wp, hp;
+        pass_dims(w, h, il, p, g, &wp, &hp);
+        if (!wp || !hp) continue;
+        bytes += DEBIG_PNG_SPEC_SCRATCH_BYTES(row_bytes(wp, ct, d));
+        (*n_tasks)++;
+    }
+    return bytes;
+}
+
+uint32_t spec_image_tasks(const spec_file *F, uint32_t w, uint32_t h, uint64_t stream_off, uint64_t rgba_off,
+                          uint64_t scratch_off, debig_png_spec_task *tasks)
+{
+    const uint32_t ct = F->info.color_type, d = F->info.bit_depth, il = F->info.interlace;
+    uint64_t pos = stream_off, scratch = scratch_off;
+    uint32_t n = 0;
+    for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
+        uint32_t g[4], wp, hp;
+        pass_dims(w, h, il, p, g, &wp, &hp);
+        if (!wp || !hp) continue;
+        const uint64_t rb = row_bytes(wp, ct, d);
+        debig_png_spec_task *t = &tasks[n++];
+        t->stream_off = pos;
+        t->rgba_off = rgba_off;
+        t->pal_off = F->pal_off;
+        t->scratch_off = scratch;
+        t->width = wp;
+        t->height = hp;
+        t->img_width = w;
+        t->x0 = g[0]; t->y0 = g[1]; t->dx = g[2]; t->dy = g[3];
+        t->depth = (uint8_t)d;
+        t->color_type = (uint8_t)ct;
+        t->channels = (uint8_t)channels_of(ct);
+        t->bpp_f = (uint8_t)(t->channels * d / 8u ? t->channels * d / 8u : 1u);
+        memcpy(t->key, F->key, sizeof t->key);
+        t->has_key = (uint16_t)F->has_key;
+        t->n_pal = (uint16_t)F->n_pal;
+        t->out_fmt = (uint16_t)F->fmt;
+        pos += (uint64_t)hp * (1u + rb);
+        scratch += DEBIG_PNG_SPEC_SCRATCH_BYTES(rb);
+    }
+    return n;
+}
 
 /* byte k of the IDAT concatenation (k < z_total) */
 static uint8_t z_byte(const spec_file *F, const uint8_t *in, uint64_t k)
@@ -83,7 +137,7 @@ static uint8_t z_byte(const spec_file *F, const uint8_t *in, uint64_t k)
 }
 
 /* The chunk walk.  info_only: stop at the first IDAT (debig_png_info_get).  Returns a DEBIG_PNG_* status. */
-static uint32_t spec_walk(const uint8_t *in, uint64_t size, spec_file *F, int info_only)
+uint32_t spec_walk(const uint8_t *in, uint64_t size, spec_file *F, int info_only)
 {
     if (!in || size < 8 || memcmp(in, png_sig, 8)) return DEBIG_PNG_E_SIGNATURE;
     uint64_t pos = 8;
@@ -178,7 +232,7 @@ static uint32_t spec_walk(const uint8_t *in, uint64_t size, spec_file *F, int in
     return DEBIG_PNG_OK;
 }
 
-static void spec_free(spec_file *F)
+void spec_free(spec_file *F)
 {
     free(F->chunks);
     free(F->idat);
@@ -234,19 +288,12 @@ DEBIG_API uint64_t debig_png_out_layout(const debig_png_info *info, uint32_t out
 static uint32_t spec_host_rules(spec_file *F, const uint8_t *in, uint8_t *out, uint64_t out_cap, uint32_t out_format)
 {
     if (F->z_total < 2) return DEBIG_PNG_E_ZLIB;
-    const uint32_t cmf = z_byte(F, in, 0), flg = z_byte(F, in, 1);
-    if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u || (flg & 0x20u)) return DEBIG_PNG_E_ZLIB;
+    if (!spec_zlib_header_ok(z_byte(F, in, 0), z_byte(F, in, 1))) return DEBIG_PNG_E_ZLIB;
     const uint64_t w = F->info.width, h = F->info.height;
     F->fmt = fmt_resolve(&F->info, out_format);
     F->out_bytes = fmt_size(w, h, F->fmt); /* UINT64_MAX (no buffer that large): E_OUTPUT */
     if (!out || out_cap < F->out_bytes) return DEBIG_PNG_E_OUTPUT;
-    const uint32_t ct = F->info.color_type, d = F->info.bit_depth, il = F->info.interlace;
-    F->scan = 0;
-    for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
-        uint32_t g[4], wp, hp;
-        pass_dims((uint32_t)w, (uint32_t)h, il, p, g, &wp, &hp);
-        if (wp && hp) F->scan += (uint64_t)hp * (1u + row_bytes(wp, ct, d));
-    }
+    F->scan = spec_scan_bytes(&F->info, (uint32_t)w, (uint32_t)h);
     return DEBIG_PNG_OK;
 }
 
@@ -298,8 +345,8 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
     uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0, n_ftasks = 0;
     for (uint32_t k = 0; k < m; k++) {
         spec_file *f = &F[live[k]];
-        const uint32_t ct = f->info.color_type, d = f->info.bit_depth, il = f->info.interlace;
-        f->general = (flags & DEBIG_PNG_FORCE_GENERAL) || f->fmt || il || d != 8 || !(ct == 6 || (ct == 2 && !f->has_key));
+        const uint32_t ct = f->info.color_type;
+        f->general = spec_is_general(f, flags);
         f->file_off = files_total;
         files_total += debig_align16(input_sizes[live[k]]) + 16;
         f->in_off = in_total;
@@ -314,14 +361,10 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
         n_chunks += f->n_chunks;
         n_pieces += f->n_idat;
         if (f->general) {
-            for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
-                uint32_t g[4], wp, hp;
-                pass_dims(f->info.width, f->info.height, il, p, g, &wp, &hp);
-                if (!wp || !hp) continue;
-                out_total += DEBIG_PNG_SPEC_SCRATCH_BYTES(row_bytes(wp, ct, d));
-                n_tasks++;
-                n_ftasks += f->fmt != 0;
-            }
+            uint32_t nt;
+            out_total += spec_general_scratch(&f->info, f->info.width, f->info.height, &nt);
+            n_tasks += nt;
+            n_ftasks += f->fmt ? nt : 0u;
         } else {
             n_img++;
         }
@@ -445,7 +488,7 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = live[k];
         spec_file *f = &F[i];
-        const uint32_t ct = f->info.color_type, d = f->info.bit_depth, il = f->info.interlace;
+        const uint32_t ct = f->info.color_type;
         if (!f->general) {
             debig_png_image *im = &img[n_img];
             im->stream_off = f->out_off;
@@ -457,34 +500,11 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
             continue;
         }
         if (ct == 3 && (rc = debig_hip_memcpy_h2d((uint8_t *)c->out.ptr + f->pal_off, f->pal, 1024, NULL))) goto done;
-        uint64_t pos = f->out_off, scratch = f->scratch_off;
-        for (uint32_t p = 0; p < (il ? 7u : 1u); p++) {
-            uint32_t g[4], wp, hp;
-            pass_dims(f->info.width, f->info.height, il, p, g, &wp, &hp);
-            if (!wp || !hp) continue;
-            const uint64_t rb = row_bytes(wp, ct, d);
-            const uint32_t ti = f->fmt ? f_base + n_ftasks++ : n_tasks++;
-            debig_png_spec_task *t = &tasks[ti];
-            t->stream_off = pos;
-            t->rgba_off = f->rgba_off;
-            t->pal_off = f->pal_off;
-            t->scratch_off = scratch;
-            t->width = wp;
-            t->height = hp;
-            t->img_width = f->info.width;
-            t->x0 = g[0]; t->y0 = g[1]; t->dx = g[2]; t->dy = g[3];
-            t->depth = (uint8_t)d;
-            t->color_type = (uint8_t)ct;
-            t->channels = (uint8_t)channels_of(ct);
-            t->bpp_f = (uint8_t)(t->channels * d / 8u ? t->channels * d / 8u : 1u);
-            memcpy(t->key, f->key, sizeof t->key);
-            t->has_key = (uint16_t)f->has_key;
-            t->n_pal = (uint16_t)f->n_pal;
-            t->out_fmt = (uint16_t)f->fmt;
-            task_file[ti] = i;
-            pos += (uint64_t)hp * (1u + rb);
-            scratch += DEBIG_PNG_SPEC_SCRATCH_BYTES(rb);
-        }
+        const uint32_t t0 = f->fmt ? f_base + n_ftasks : n_tasks;
+        const uint32_t nt = spec_image_tasks(f, f->info.width, f->info.height, f->out_off, f->rgba_off, f->scratch_off, &tasks[t0]);
+        for (uint32_t j = 0; j < nt; j++) task_file[t0 + j] = i;
+        if (f->fmt) n_ftasks += nt;
+        else n_tasks += nt;
     }
     if (n_img) {
         if ((rc = debig_devbuf_reserve(&c->img, (uint64_t)n_img * sizeof(debig_png_image))) ||

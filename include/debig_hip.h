@@ -331,6 +331,34 @@ int debig_hip_png_spec_defilter_batch(void *d_arena, void *d_rgba_arena, const d
 int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
                                           debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
 
+/* APNG compositing (csrc/apng_kernel.inc, behind debig_apng_decode_batch in decode_png.h).  One frame of a file: its
+ * RGBA8 pixels (width * height dwords, rows without padding) and its place on the canvas. */
+typedef struct debig_apng_frame_desc {
+    uint64_t rgba_off;          /* the frame's pixels, rel. to d_frames_arena (4-byte aligned)              */
+    uint32_t x_off, y_off;      /* region on the canvas: x_off + width <= canvas width, the same for y      */
+    uint32_t width, height;     /* >= 1                                                                      */
+    uint8_t dispose_op;         /* 0 NONE, 1 BACKGROUND, 2 PREVIOUS (PREVIOUS on frame 0 acts as BACKGROUND) */
+    uint8_t blend_op;           /* 0 SOURCE, 1 OVER                                                          */
+    uint16_t reserved;
+    uint32_t reserved2;
+} debig_apng_frame_desc;
+
+/* One task: pixels [px0, px0 + n_px) of one file's canvas (n_px <= DEBIG_APNG_TASK_PX), through all of its frames. */
+typedef struct debig_apng_task {
+    uint64_t out_off;           /* the file's output: n_frames canvases of width * height * 4 bytes, rel. to d_out_arena (any alignment) */
+    uint64_t ftab_off;          /* the file's n_frames debig_apng_frame_desc, rel. to d_frames_arena (8-byte aligned) */
+    uint64_t px0;
+    uint32_t n_px;
+    uint32_t n_frames;          /* >= 1 */
+    uint32_t width, height;     /* the canvas */
+} debig_apng_task;
+#define DEBIG_APNG_TASK_PX 1024u /* pixels of one task: 256 lanes x 4 consecutive pixels */
+
+/* Composite n tasks (device pointers, asynchronous on hip_stream): one workgroup of 256 lanes per task, each lane a run
+ * of 4 consecutive canvas pixels held in registers through the file's frames (the APNG rules of decode_png.h). */
+int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena, const debig_apng_task *d_tasks,
+                                   uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

@@ -170,6 +170,63 @@ int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uint64_t *inp
                                const uint64_t *out_caps, uint32_t *status, debig_png_info *infos /* may be NULL */,
                                uint32_t n, uint32_t flags, uint32_t out_format);
 
+/* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
+ * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
+ * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when
+ *   - acTL comes after the first IDAT, comes more than once, is not 8 bytes long or has num_frames == 0;
+ *   - an fcTL is not 26 bytes long, has a width or height of 0, x_off + width > W or y_off + height > H (in 64 bits),
+ *     dispose_op > 2 or blend_op > 1;
+ *   - more than one fcTL comes before the first IDAT, or an fcTL before it is not the whole canvas at (0, 0);
+ *   - an fdAT comes before the first IDAT, is shorter than 4 bytes, or has no fcTL after the IDAT in front of it;
+ *   - a frame after the IDAT has no fdAT;
+ *   - the sequence numbers of fcTL and fdAT, in file order, are not 0, 1, 2, ...;
+ *   - the number of fcTL differs from acTL's num_frames.
+ * Every rule of debig_png_decode_batch still applies; the zlib header, inflate, data length and Adler-32 rules apply to
+ * each FRAME's stream: frame 0's is the IDAT concatenation when the IDAT image is frame 0 (an fcTL before the first
+ * IDAT), every other frame's the payloads of its fdAT chunks without their 4-byte sequence numbers, in file order.  A
+ * frame is decoded at its own width x height with the file's colour type, depth, palette, tRNS and interlace, to RGBA8 by
+ * the rules of debig_png_decode_batch.  An IDAT image that is not frame 0 is not decoded (its chunks' CRCs are checked).
+ * Statuses: the order of debig_png_decode_batch with E_ANIM directly after the chunk walk; E_OUTPUT when
+ * out_caps[i] < num_frames * w * h * 4; within one step the first failing frame decides (a filter error in any frame
+ * outranks a palette error in any frame).
+ * Compositing (APNG specification): the canvas starts as (0, 0, 0, 0); for frame k on its region R_k
+ *   1. dispose_op PREVIOUS: save the canvas on R_k (on frame 0 PREVIOUS counts as BACKGROUND);
+ *   2. blend_op SOURCE replaces R_k; OVER with source alpha sa: 255 takes the source, 0 keeps the canvas, otherwise
+ *      u = sa * 255, v = (255 - sa) * da, al = u + v, c = (sc * u + dc * v) / al per colour channel, a = al / 255
+ *      (unsigned integers, truncating division);
+ *   3. output frame k is the whole canvas;
+ *   4. dispose of R_k: NONE keeps it, BACKGROUND sets it to (0, 0, 0, 0), PREVIOUS restores what step 1 saved.
+ * Not provided: other output formats for animations, uncomposited frames, the default image when it is not a frame. */
+typedef struct debig_apng_frame {
+    uint32_t width, height, x_off, y_off;   /* fcTL region on the canvas                                             */
+    uint16_t delay_num, delay_den;          /* as stored (den 0 means 1/100 s by the APNG specification)              */
+    uint8_t dispose_op, blend_op;           /* as stored: 0 NONE / 1 BACKGROUND / 2 PREVIOUS; 0 SOURCE / 1 OVER       */
+    uint16_t reserved;
+} debig_apng_frame;
+
+typedef struct debig_apng_info {
+    debig_png_info png;        /* the canvas = IHDR, as debig_png_info_get fills it          */
+    uint32_t num_frames;       /* frames of the animation; 1 for a still PNG                 */
+    uint32_t num_plays;        /* acTL; 0 = forever (still PNG: 0)                            */
+    uint32_t default_is_frame; /* 1 when the IDAT image is frame 0 (or the file is still)     */
+    uint32_t reserved;
+} debig_apng_info;
+
+#define DEBIG_PNG_E_ANIM 13 /* acTL / fcTL / fdAT rules (list above) */
+
+/* Host only: the whole chunk walk (every fcTL), no CRCs.  DEBIG_PNG_OK or the first status of the walk, then E_ANIM;
+ * info is filled as far as it was read (num_frames: acTL's, 1 for a still file).  frames may be NULL, else it receives
+ * up to max_frames fcTL regions, in file order (a still file: one frame, the whole canvas, NONE / SOURCE). */
+uint32_t debig_apng_info_get(const uint8_t *p, uint64_t size, debig_apng_info *info, debig_apng_frame *frames,
+                             uint32_t max_frames);
+
+/* outs[i]: num_frames * w * h * 4 bytes; frame k (the canvas after frame k is rendered, before its dispose_op) at
+ * k * w * h * 4, RGBA8, rows top-down without padding.  flags: DEBIG_PNG_FORCE_GENERAL as for debig_png_decode_batch
+ * (the frames take that call's de-filter routing).  Returns 0 or a device error code (then every status is unspecified). */
+int debig_apng_decode_batch(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                            const uint64_t *out_caps, uint32_t *status, debig_apng_info *infos /* may be NULL */,
+                            uint32_t n, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include "../../debigulator_amd/csrc/png_kernel.inc"
 #include "../../debigulator_amd/csrc/png_fused_kernel.inc"
 #include "../../debigulator_amd/csrc/png_spec_kernel.inc"
+#include "../../debigulator_amd/csrc/apng_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -308,5 +309,15 @@ extern "C" int emu_png_spec_defilter_fmt_batch(void *arena, void *out_arena, con
                                                debig_png_spec_result *results, uint32_t n)
 {
     if (n) EMU_LAUNCH(debig_png_spec_defilter_fmt_kernel, n, 64 * PNG_SPEC_NWD, (uint8_t *)arena, (uint8_t *)out_arena, tasks, results, n);
+    return 0;
+}
+
+/* APNG compositing (apng_kernel.inc) as debig_hip_apng_composite_batch launches it (grid: 0 = one workgroup per task,
+ * else fewer workgroups that loop over the tasks) */
+extern "C" int emu_apng_composite_batch(const void *frames_arena, void *out_arena, const debig_apng_task *tasks, uint32_t n,
+                                        uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_apng_composite_kernel, grid, APNG_THREADS, (const uint8_t *)frames_arena, (uint8_t *)out_arena, tasks, n);
     return 0;
 }
