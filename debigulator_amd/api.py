@@ -232,6 +232,10 @@ def _png_spec_lib():
     L.debig_png_decode_batch.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32]
     L.debig_png_decode_batch_fmt.restype = C.c_int
     L.debig_png_decode_batch_fmt.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.debig_png_decode_batch_layout.restype = C.c_int
+    L.debig_png_decode_batch_layout.argtypes = [C.c_void_p] * 6 + [C.c_uint32] * 4
+    L.debig_png_decode_batch_dev.restype = C.c_int
+    L.debig_png_decode_batch_dev.argtypes = [C.c_void_p] * 7 + [C.c_uint32] * 4
     L.debig_png_out_layout.restype = C.c_uint64
     L.debig_png_out_layout.argtypes = [C.POINTER(PngInfo), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     return L
@@ -249,6 +253,17 @@ def png_out_format(mode="rgba", depth=8):
     if isinstance(depth, bool) or depth not in PNG_DEPTHS:
         raise ValueError(f"depth must be 8, 16 or 'native', not {depth!r}")
     return PNG_MODES[mode] | PNG_DEPTHS[depth]
+
+
+PNG_LAYOUTS = {"hwc": 0, "chw": 1}  # include/decode_png.h: DEBIG_PNG_LAYOUT_*
+PNG_BAD_FORMAT, PNG_BAD_ARG = -1, -2  # DEBIG_PNG_BAD_FORMAT, DEBIG_PNG_BAD_ARG
+
+
+def png_layout_code(layout="hwc"):
+    """layout -> the out_layout of debig_png_decode_batch_layout / _dev"""
+    if layout not in PNG_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(PNG_LAYOUTS)}, not {layout!r}")
+    return PNG_LAYOUTS[layout]
 
 
 def png_out_layout(info, mode="rgba", depth=8):
@@ -271,12 +286,14 @@ def png_info(data):
     return st, _info_dict(inf)
 
 
-def png_decode_batch(datas, force_general=False, mode="rgba", depth=8):
-    """every PNG the specification allows -> pixels (include/decode_png.h: debig_png_decode_batch_fmt).
+def png_decode_batch(datas, force_general=False, mode="rgba", depth=8, layout="hwc"):
+    """every PNG the specification allows -> pixels (include/decode_png.h: debig_png_decode_batch_fmt / _layout).
     mode: "rgba" | "rgb" | "gray" | "gray_alpha" | "native" (as in the file); depth: 8 | 16 | "native" (16 for 16-bit
-    files, else 8).  -> [(status, ndarray (h, w, channels) of uint8 / uint16 or None, info dict)], status as in
-    PNG_STATUS.  The defaults give RGBA8, (h, w, 4) uint8."""
+    files, else 8); layout: "hwc" (interleaved) | "chw" (channel planes).  -> [(status, ndarray (h, w, channels) -- or
+    (channels, h, w) for "chw" -- of uint8 / uint16 or None, info dict)], status as in PNG_STATUS.  The defaults give
+    RGBA8, (h, w, 4) uint8."""
     fmt = png_out_format(mode, depth)
+    lay = png_layout_code(layout)
     L = _png_spec_lib()
     n = len(datas)
     ins = [_u8(d) for d in datas]
@@ -285,7 +302,8 @@ def png_decode_batch(datas, force_general=False, mode="rgba", depth=8):
         st, inf = png_info(a)
         if st == 0:
             ch, bs, nbytes = png_out_layout(inf, mode, depth)
-            outs.append(np.empty((inf["height"], inf["width"], ch), dtype=np.uint16 if bs == 2 else np.uint8))
+            shape = (ch, inf["height"], inf["width"]) if lay else (inf["height"], inf["width"], ch)
+            outs.append(np.empty(shape, dtype=np.uint16 if bs == 2 else np.uint8))
             caps.append(nbytes)
         else:
             outs.append(np.empty(4, dtype=np.uint8))
@@ -296,10 +314,71 @@ def png_decode_batch(datas, force_general=False, mode="rgba", depth=8):
     caps = (C.c_uint64 * n)(*caps)
     status = (C.c_uint32 * n)()
     infos = (PngInfo * n)()
-    rc = L.debig_png_decode_batch_fmt(in_ptrs, in_sizes, out_ptrs, caps, status, infos, n,
-                                      PNG_FORCE_GENERAL if force_general else 0, fmt)
-    N.check(rc, "debig_png_decode_batch_fmt")
+    if lay:
+        rc = L.debig_png_decode_batch_layout(in_ptrs, in_sizes, out_ptrs, caps, status, infos, n,
+                                             PNG_FORCE_GENERAL if force_general else 0, fmt, lay)
+    else:
+        rc = L.debig_png_decode_batch_fmt(in_ptrs, in_sizes, out_ptrs, caps, status, infos, n,
+                                          PNG_FORCE_GENERAL if force_general else 0, fmt)
+    N.check(rc, "debig_png_decode_batch_layout" if lay else "debig_png_decode_batch_fmt")
     return [(int(status[i]), outs[i] if status[i] == 0 else None, _info_dict(infos[i])) for i in range(n)]
+
+
+def png_decode_batch_device(datas, mode="rgba", depth=8, layout="hwc", device="cuda:0", force_general=False):
+    """png_decode_batch with the pixels left on the GPU (include/decode_png.h: debig_png_decode_batch_dev): no pixel byte
+    goes to the host.  -> [(status, torch tensor or None, info dict)]; every tensor is a view of ONE torch.uint8 arena on
+    `device` (offsets multiples of 16), shaped (h, w, channels) or, with layout="chw", (channels, h, w).  16-bit results
+    have dtype torch.uint16 where the installed torch has it, else they are torch.int16 views of the same bits.  The call
+    returns after the work has finished.  The library works on the calling thread's current device: any other `device`
+    raises ValueError (select it with torch.cuda.set_device first)."""
+    import torch
+
+    fmt = png_out_format(mode, depth)
+    lay = png_layout_code(layout)
+    L = _png_spec_lib()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device must be a GPU, not {device!r}")
+    L.debig_hip_get_device.restype = C.c_int
+    cur = L.debig_hip_get_device()
+    if dev.index is not None and dev.index != cur:
+        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
+    dev = torch.device("cuda", cur)
+    n = len(datas)
+    ins = [_u8(d) for d in datas]
+    offs, caps, shapes, total = [], [], [], 0
+    for a in ins:
+        st, inf = png_info(a)
+        offs.append(total)
+        if st == 0:
+            ch, bs, nbytes = png_out_layout(inf, mode, depth)
+            shapes.append(((ch, inf["height"], inf["width"]) if lay else (inf["height"], inf["width"], ch), bs))
+            caps.append(nbytes)
+            total += (nbytes + 15) // 16 * 16
+        else:
+            shapes.append(None)
+            caps.append(0)
+    arena = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
+    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
+    status = (C.c_uint32 * n)()
+    infos = (PngInfo * n)()
+    rc = L.debig_png_decode_batch_dev(in_ptrs, in_sizes, arena.data_ptr(), (C.c_uint64 * n)(*offs),
+                                      (C.c_uint64 * n)(*caps), status, infos, n,
+                                      PNG_FORCE_GENERAL if force_general else 0, fmt, lay)
+    if rc in (PNG_BAD_FORMAT, PNG_BAD_ARG):
+        raise ValueError(f"debig_png_decode_batch_dev rejected its arguments ({rc})")
+    N.check(rc, "debig_png_decode_batch_dev")
+    u16 = getattr(torch, "uint16", torch.int16)
+    out = []
+    for i in range(n):
+        t = None
+        if status[i] == 0:
+            shape, bs = shapes[i]
+            t = arena[offs[i]: offs[i] + caps[i]]
+            t = (t.view(u16) if bs == 2 else t).view(shape)
+        out.append((int(status[i]), t, _info_dict(infos[i])))
+    return out
 
 
 class ApngFrame(C.Structure):  # include/decode_png.h: debig_apng_frame

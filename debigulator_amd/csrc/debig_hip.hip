@@ -723,6 +723,16 @@ int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, cons
     return (int)hipGetLastError();
 }
 
+int debig_hip_png_spec_defilter_planar_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
+                                             debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
+{
+    if (n == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    hipLaunchKernelGGL(debig_png_spec_defilter_planar_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
+                       (uint8_t *)d_arena, (uint8_t *)d_out_arena, d_tasks, d_results, n);
+    return (int)hipGetLastError();
+}
+
 // APNG compositing (apng_kernel.inc): one workgroup of 256 lanes per canvas slice; the grid is capped, the kernel loops
 int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena, const debig_apng_task *d_tasks,
                                    uint32_t n_tasks, void *hip_stream)

@@ -74,7 +74,7 @@ uint64_t spec_scan_bytes(const debig_png_info *info, uint32_t w, uint32_t h)
 int spec_is_general(const spec_file *F, uint32_t flags)
 {
     const uint32_t ct = F->info.color_type, d = F->info.bit_depth, il = F->info.interlace;
-    return (flags & DEBIG_PNG_FORCE_GENERAL) || F->fmt || il || d != 8 || !(ct == 6 || (ct == 2 && !F->has_key));
+    return (flags & DEBIG_PNG_FORCE_GENERAL) || F->fmt || F->planar || il || d != 8 || !(ct == 6 || (ct == 2 && !F->has_key));
 }
 
 uint64_t spec_general_scratch(const debig_png_info *info, uint32_t w, uint32_t h, uint32_t *n_tasks)
@@ -111,6 +111,7 @@ uint32_t spec_image_tasks(const spec_file *F, uint32_t w, uint32_t h, uint64_t s
         t->width = wp;
         t->height = hp;
         t->img_width = w;
+        t->img_height = h;
         t->x0 = g[0]; t->y0 = g[1]; t->dx = g[2]; t->dy = g[3];
         t->depth = (uint8_t)d;
         t->color_type = (uint8_t)ct;
@@ -285,14 +286,14 @@ DEBIG_API uint64_t debig_png_out_layout(const debig_png_info *info, uint32_t out
 }
 
 /* the host rules after the walk: zlib header, output size; and the sizes the device needs */
-static uint32_t spec_host_rules(spec_file *F, const uint8_t *in, uint8_t *out, uint64_t out_cap, uint32_t out_format)
+static uint32_t spec_host_rules(spec_file *F, const uint8_t *in, int have_out, uint64_t out_cap, uint32_t out_format)
 {
     if (F->z_total < 2) return DEBIG_PNG_E_ZLIB;
     if (!spec_zlib_header_ok(z_byte(F, in, 0), z_byte(F, in, 1))) return DEBIG_PNG_E_ZLIB;
     const uint64_t w = F->info.width, h = F->info.height;
     F->fmt = fmt_resolve(&F->info, out_format);
     F->out_bytes = fmt_size(w, h, F->fmt); /* UINT64_MAX (no buffer that large): E_OUTPUT */
-    if (!out || out_cap < F->out_bytes) return DEBIG_PNG_E_OUTPUT;
+    if (!have_out || out_cap < F->out_bytes) return DEBIG_PNG_E_OUTPUT;
     F->scan = spec_scan_bytes(&F->info, (uint32_t)w, (uint32_t)h);
     return DEBIG_PNG_OK;
 }
@@ -304,11 +305,20 @@ DEBIG_API int debig_png_decode_batch(const uint8_t *const *inputs, const uint64_
     return debig_png_decode_batch_fmt(inputs, input_sizes, outs, out_caps, status, infos, n, flags, 0);
 }
 
-DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
-                                         const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n,
-                                         uint32_t flags, uint32_t out_format)
+/* where the pixels go: host buffers (outs), or image i stays on the device at d_arena + d_offs[i] (outs NULL) */
+typedef struct spec_target {
+    uint8_t *const *outs;
+    void *d_arena;
+    const uint64_t *d_offs;
+} spec_target;
+
+typedef int (*spec_launch_fn)(void *, void *, const debig_png_spec_task *, debig_png_spec_result *, uint32_t, void *);
+
+/* the decode behind debig_png_decode_batch_fmt / _layout / _dev (out_format and out_layout valid) */
+static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_sizes, const spec_target *tg,
+                            const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags,
+                            uint32_t out_format, uint32_t out_layout)
 {
-    if (!fmt_valid(out_format)) return DEBIG_PNG_BAD_FORMAT;
     if (n == 0) return 0;
     spec_file *F = (spec_file *)calloc(n, sizeof(spec_file));
     uint32_t *live = (uint32_t *)calloc(n, sizeof(uint32_t)); /* files still good, in order */
@@ -332,17 +342,21 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
     for (uint32_t i = 0; i < n; i++) {
         spec_file *f = &F[i];
         f->status = spec_walk(inputs[i], input_sizes[i], f, 0);
-        if (f->status == DEBIG_PNG_OK) f->status = spec_host_rules(f, inputs[i], outs[i], out_caps[i], out_format);
-        if (f->status == DEBIG_PNG_OK) live[m++] = i;
+        if (f->status == DEBIG_PNG_OK)
+            f->status = spec_host_rules(f, inputs[i], tg->outs ? tg->outs[i] != NULL : 1, out_caps[i], out_format);
+        if (f->status == DEBIG_PNG_OK) {
+            f->planar = out_layout == DEBIG_PNG_LAYOUT_CHW && fmt_channels(f->fmt) > 1u; /* one channel: the same bytes */
+            live[m++] = i;
+        }
     }
     if (m == 0) goto report; /* nothing for the device */
     debig_ctx *c = debig_ctx_get(0);
     if (!c) { rc = 1; goto done; }
     /* ---- device layout: whole files (c->files); IDAT concatenations (c->in); per file in c->out the scanline stream
      *      (+ 16 readable bytes), the palette and the scratch rings of its general-kernel tasks; pixels (c->rgba, each
-     *      image 16-byte aligned) */
+     *      image 16-byte aligned), or the caller's device arena */
     uint64_t files_total = 0, in_total = 0, out_total = 64, rgba_total = 0;
-    uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0, n_ftasks = 0;
+    uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0, cnt[3] = {0, 0, 0}; /* cnt: tasks per de-filter kernel */
     for (uint32_t k = 0; k < m; k++) {
         spec_file *f = &F[live[k]];
         const uint32_t ct = f->info.color_type;
@@ -356,7 +370,7 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
         f->pal_off = out_total;
         if (ct == 3) out_total += 1024;
         f->scratch_off = out_total;
-        f->rgba_off = rgba_total;
+        f->rgba_off = tg->outs ? rgba_total : tg->d_offs[live[k]];
         rgba_total += debig_align16(f->out_bytes) + 16;
         n_chunks += f->n_chunks;
         n_pieces += f->n_idat;
@@ -364,7 +378,7 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
             uint32_t nt;
             out_total += spec_general_scratch(&f->info, f->info.width, f->info.height, &nt);
             n_tasks += nt;
-            n_ftasks += f->fmt ? nt : 0u;
+            cnt[f->planar ? 2 : f->fmt ? 1 : 0] += nt;
         } else {
             n_img++;
         }
@@ -391,7 +405,7 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
         goto done;
     }
     if ((rc = debig_devbuf_reserve(&c->files, files_total + 64)) || (rc = debig_devbuf_reserve(&c->in, in_total + 64)) ||
-        (rc = debig_devbuf_reserve(&c->out, out_total + 64)) || (rc = debig_devbuf_reserve(&c->rgba, rgba_total + 64)) ||
+        (rc = debig_devbuf_reserve(&c->out, out_total + 64)) || (tg->outs && (rc = debig_devbuf_reserve(&c->rgba, rgba_total + 64))) ||
         (rc = debig_devbuf_reserve(&c->spans, ((uint64_t)n_chunks + m) * sizeof(debig_span))) ||
         (rc = debig_devbuf_reserve(&c->crcs, ((uint64_t)n_chunks + m) * sizeof(uint32_t))) ||
         (rc = debig_devbuf_reserve(&c->copies, ((uint64_t)n_pieces + 1) * sizeof(debig_copy))))
@@ -481,10 +495,15 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
         m = ns;
     }
     if (m == 0) goto report;
-    /* ---- de-filter: tuned kernels for non-interlaced 8-bit RGB / RGBA to RGBA8, the general kernel for the rest of
-     *      RGBA8 (tasks [0, n_tasks)), its output-format twin for every other format (tasks [n_tasks, n_tasks + n_ftasks)) */
-    const uint32_t f_base = n_tasks - n_ftasks;
-    n_img = n_tasks = n_ftasks = 0;
+    /* ---- de-filter: tuned kernels for non-interlaced 8-bit RGB / RGBA to interleaved RGBA8; the general kernel for the
+     *      rest of interleaved RGBA8 (tasks [0, cnt[0])), its output-format twin for every other interleaved format (the
+     *      next cnt[1]) and the planar kernel for every channel-planar image of more than one channel (the last cnt[2]) */
+    static const spec_launch_fn launch[3] = {debig_hip_png_spec_defilter_batch, debig_hip_png_spec_defilter_fmt_batch,
+                                             debig_hip_png_spec_defilter_planar_batch};
+    void *pix = tg->outs ? c->rgba.ptr : tg->d_arena;
+    const uint32_t base[3] = {0, cnt[0], cnt[0] + cnt[1]};
+    uint32_t fill[3] = {0, 0, 0};
+    n_img = 0;
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = live[k];
         spec_file *f = &F[i];
@@ -500,56 +519,50 @@ DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uin
             continue;
         }
         if (ct == 3 && (rc = debig_hip_memcpy_h2d((uint8_t *)c->out.ptr + f->pal_off, f->pal, 1024, NULL))) goto done;
-        const uint32_t t0 = f->fmt ? f_base + n_ftasks : n_tasks;
+        const uint32_t cls = f->planar ? 2u : f->fmt ? 1u : 0u, t0 = base[cls] + fill[cls];
         const uint32_t nt = spec_image_tasks(f, f->info.width, f->info.height, f->out_off, f->rgba_off, f->scratch_off, &tasks[t0]);
         for (uint32_t j = 0; j < nt; j++) task_file[t0 + j] = i;
-        if (f->fmt) n_ftasks += nt;
-        else n_tasks += nt;
+        fill[cls] += nt;
     }
     if (n_img) {
         if ((rc = debig_devbuf_reserve(&c->img, (uint64_t)n_img * sizeof(debig_png_image))) ||
             (rc = debig_devbuf_reserve(&c->imgres, (uint64_t)n_img * sizeof(debig_png_result))) ||
             (rc = debig_hip_memcpy_h2d(c->img.ptr, img, (uint64_t)n_img * sizeof(debig_png_image), NULL)) ||
-            (rc = debig_hip_png_defilter_batch(c->out.ptr, c->rgba.ptr, (const debig_png_image *)c->img.ptr,
+            (rc = debig_hip_png_defilter_batch(c->out.ptr, pix, (const debig_png_image *)c->img.ptr,
                                                (debig_png_result *)c->imgres.ptr, n_img, NULL)) ||
             (rc = debig_hip_memcpy_d2h(ires, c->imgres.ptr, (uint64_t)n_img * sizeof(debig_png_result), NULL)))
             goto done;
     }
-    if ((n_tasks || n_ftasks) && /* both task lists in one buffer, reserved before either launch */
-        ((rc = debig_devbuf_reserve(&c->spec_tasks, (uint64_t)(f_base + n_ftasks) * sizeof(debig_png_spec_task))) ||
-         (rc = debig_devbuf_reserve(&c->spec_res, (uint64_t)(f_base + n_ftasks) * sizeof(debig_png_spec_result)))))
+    if ((fill[0] || fill[1] || fill[2]) && /* the task lists in one buffer, reserved before any launch */
+        ((rc = debig_devbuf_reserve(&c->spec_tasks, (uint64_t)(n_tasks + 1u) * sizeof(debig_png_spec_task))) ||
+         (rc = debig_devbuf_reserve(&c->spec_res, (uint64_t)(n_tasks + 1u) * sizeof(debig_png_spec_result)))))
         goto done;
-    if (n_tasks) {
-        if ((rc = debig_hip_memcpy_h2d(c->spec_tasks.ptr, tasks, (uint64_t)n_tasks * sizeof(debig_png_spec_task), NULL)) ||
-            (rc = debig_hip_png_spec_defilter_batch(c->out.ptr, c->rgba.ptr, (const debig_png_spec_task *)c->spec_tasks.ptr,
-                                                    (debig_png_spec_result *)c->spec_res.ptr, n_tasks, NULL)) ||
-            (rc = debig_hip_memcpy_d2h(tres, c->spec_res.ptr, (uint64_t)n_tasks * sizeof(debig_png_spec_result), NULL)))
-            goto done;
-    }
-    if (n_ftasks) {
-        debig_png_spec_task *d_ft = (debig_png_spec_task *)c->spec_tasks.ptr + f_base;
-        debig_png_spec_result *d_fr = (debig_png_spec_result *)c->spec_res.ptr + f_base;
-        if ((rc = debig_hip_memcpy_h2d(d_ft, tasks + f_base, (uint64_t)n_ftasks * sizeof(debig_png_spec_task), NULL)) ||
-            (rc = debig_hip_png_spec_defilter_fmt_batch(c->out.ptr, c->rgba.ptr, d_ft, d_fr, n_ftasks, NULL)) ||
-            (rc = debig_hip_memcpy_d2h(tres + f_base, d_fr, (uint64_t)n_ftasks * sizeof(debig_png_spec_result), NULL)))
+    for (uint32_t cls = 0; cls < 3; cls++) {
+        if (!fill[cls]) continue;
+        debig_png_spec_task *d_t = (debig_png_spec_task *)c->spec_tasks.ptr + base[cls];
+        debig_png_spec_result *d_r = (debig_png_spec_result *)c->spec_res.ptr + base[cls];
+        if ((rc = debig_hip_memcpy_h2d(d_t, tasks + base[cls], (uint64_t)fill[cls] * sizeof(debig_png_spec_task), NULL)) ||
+            (rc = launch[cls](c->out.ptr, pix, d_t, d_r, fill[cls], NULL)) ||
+            (rc = debig_hip_memcpy_d2h(tres + base[cls], d_r, (uint64_t)fill[cls] * sizeof(debig_png_spec_result), NULL)))
             goto done;
     }
     if ((rc = debig_hip_stream_sync(NULL))) goto done;
     for (uint32_t k = 0; k < n_img; k++)
         if (!ires[k].good) F[img_file[k]].status = DEBIG_PNG_E_FILTER;
-    for (uint32_t j = 0; j < n_tasks + n_ftasks; j++) { /* a filter error anywhere in the image outranks a palette error */
-        const uint32_t k = j < n_tasks ? j : f_base + (j - n_tasks);
-        spec_file *f = &F[task_file[k]];
-        if (tres[k].status == DEBIG_PNG_SPEC_E_FILTER) f->status = DEBIG_PNG_E_FILTER;
-        else if (tres[k].status == DEBIG_PNG_SPEC_E_PALETTE && f->status == DEBIG_PNG_OK) f->status = DEBIG_PNG_E_PALETTE;
-    }
-    /* ---- pixels down */
-    {
+    for (uint32_t cls = 0; cls < 3; cls++)
+        for (uint32_t j = 0; j < fill[cls]; j++) { /* a filter error anywhere in the image outranks a palette error */
+            const uint32_t k = base[cls] + j;
+            spec_file *f = &F[task_file[k]];
+            if (tres[k].status == DEBIG_PNG_SPEC_E_FILTER) f->status = DEBIG_PNG_E_FILTER;
+            else if (tres[k].status == DEBIG_PNG_SPEC_E_PALETTE && f->status == DEBIG_PNG_OK) f->status = DEBIG_PNG_E_PALETTE;
+        }
+    /* ---- pixels down (host buffers only) */
+    if (tg->outs) {
         uint64_t last_end = 0;
         for (uint32_t k = 0; k < m; k++) {
             const uint32_t i = live[k];
             if (F[i].status != DEBIG_PNG_OK) continue;
-            dn_dst[i] = outs[i];
+            dn_dst[i] = tg->outs[i];
             dn_size[i] = F[i].out_bytes;
             dn_off[i] = F[i].rgba_off;
             if (dn_off[i] + dn_size[i] > last_end) last_end = dn_off[i] + dn_size[i];
@@ -583,4 +596,56 @@ done:
     free(dn_size);
     free(dn_off);
     return rc;
+}
+
+DEBIG_API int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                                         const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                         uint32_t flags, uint32_t out_format)
+{
+    return debig_png_decode_batch_layout(inputs, input_sizes, outs, out_caps, status, infos, n, flags, out_format,
+                                         DEBIG_PNG_LAYOUT_HWC);
+}
+
+DEBIG_API int debig_png_decode_batch_layout(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                                            const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                            uint32_t flags, uint32_t out_format, uint32_t out_layout)
+{
+    if (!fmt_valid(out_format) || out_layout > DEBIG_PNG_LAYOUT_CHW) return DEBIG_PNG_BAD_FORMAT;
+    const spec_target tg = {outs, NULL, NULL};
+    return spec_decode_core(inputs, input_sizes, &tg, out_caps, status, infos, n, flags, out_format, out_layout);
+}
+
+typedef struct spec_region { uint64_t off, cap; } spec_region;
+static int by_off(const void *a, const void *b)
+{
+    const uint64_t x = ((const spec_region *)a)->off, y = ((const spec_region *)b)->off;
+    return x < y ? -1 : x > y;
+}
+
+DEBIG_API int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out_arena,
+                                         const uint64_t *out_offs, const uint64_t *out_caps, uint32_t *status,
+                                         debig_png_info *infos, uint32_t n, uint32_t flags, uint32_t out_format,
+                                         uint32_t out_layout)
+{
+    if (!fmt_valid(out_format) || out_layout > DEBIG_PNG_LAYOUT_CHW) return DEBIG_PNG_BAD_FORMAT;
+    if (n == 0) return 0;
+    /* the arguments on their own, before any file is looked at: arena, alignment, regions that do not overlap */
+    if (!d_out_arena || !out_offs || !out_caps) return DEBIG_PNG_BAD_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if ((out_offs[i] & 15u) || out_offs[i] + out_caps[i] < out_offs[i]) return DEBIG_PNG_BAD_ARG;
+    spec_region *reg = (spec_region *)malloc((size_t)n * sizeof(spec_region));
+    if (!reg) return 2; /* out of host memory, the code the core returns for it */
+    uint32_t r = 0;
+    for (uint32_t i = 0; i < n; i++)
+        if (out_caps[i]) { /* an empty region overlaps nothing */
+            reg[r].off = out_offs[i];
+            reg[r++].cap = out_caps[i];
+        }
+    qsort(reg, r, sizeof(spec_region), by_off);
+    int bad = 0;
+    for (uint32_t k = 0; k + 1 < r; k++) bad |= reg[k].off + reg[k].cap > reg[k + 1].off;
+    free(reg);
+    if (bad) return DEBIG_PNG_BAD_ARG;
+    const spec_target tg = {NULL, d_out_arena, out_offs};
+    return spec_decode_core(inputs, input_sizes, &tg, out_caps, status, infos, n, flags, out_format, out_layout);
 }

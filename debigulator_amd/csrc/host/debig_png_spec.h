@@ -21,6 +21,7 @@ typedef struct spec_file {
     uint32_t n_pal;
     uint16_t key[3];
     uint32_t has_key, general;
+    uint32_t planar;    /* channel planes (c, y, x) instead of interleaved pixels: the planar de-filter kernel */
     uint32_t fmt;       /* resolved output format: layout (0..3) | DEBIG_PNG_FMT_16, 0 = RGBA8 */
     uint64_t out_bytes; /* bytes of the output in that format */
     uint64_t scan;      /* scanline stream bytes */

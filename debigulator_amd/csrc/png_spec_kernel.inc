@@ -1,7 +1,8 @@
 // png_spec_kernel.inc -- the general PNG de-filter (include/decode_png.h: debig_png_decode_batch).
 //
 // Every colour type and bit depth the PNG specification allows, Adam7 passes and tRNS, to RGBA8 (debig_png_spec_defilter_kernel)
-// or to any output format of decode_png.h (debig_png_spec_defilter_fmt_kernel, the same body with another store stage).  One TASK is one
+// or to any output format of decode_png.h (debig_png_spec_defilter_fmt_kernel, the same body with another store stage; its
+// channel-planar form is debig_png_spec_defilter_planar_kernel).  One TASK is one
 // (image, pass) sub-image (debig_png_spec_task); a non-interlaced image is one task placed at (0, 0, 1, 1).
 //
 // Mapping (what png_kernel.inc measured, generalised to a filter unit of BPP = 1, 2, 3, 4, 6 or 8 bytes):
@@ -278,9 +279,41 @@ DEV_UNROLL
             if (x + j < w) spec_store_px<PB>(orow + (x + j) * ostep, lo[j], hi[j]);
     }
 }
-template <int BPP, uint32_t F, uint32_t DEPTH>
+// Channel-planar (debig_png_spec_defilter_planar_kernel): the same N pixels, channel c of each in plane c.  Here orow is
+// the pixel row in plane 0 and ostep the step of one sub-image pixel, both counted in bytes of ONE sample; plane is the
+// size of a plane in bytes.  Contiguous pixels inside the row are N consecutive samples in every plane: one run per plane
+// (a plane's base is only sample-aligned, so spec_store_run picks the width by the address); else sample by sample up to
+// the row's end.
+template <uint32_t F, uint32_t N>
+DEV_INLINE void spec_store_planar(uint8_t *orow, uint64_t plane, uint64_t x, uint32_t w, uint64_t ostep, uint32_t dx,
+                                  const uint32_t *lo, const uint32_t *hi)
+{
+    constexpr uint32_t CH = (F & 3u) == 0u ? 4u : (F & 3u) == 1u ? 3u : (F & 3u) == 2u ? 1u : 2u, BS = F & 0x10u ? 2u : 1u;
+    const bool run = dx == 1u && x + N <= w;
+DEV_UNROLL
+    for (uint32_t c = 0; c < CH; c++) {
+        uint8_t *p = orow + c * plane;
+        uint32_t s[N];
+DEV_UNROLL
+        for (uint32_t j = 0; j < N; j++)
+            s[j] = BS == 2u ? ((c < 2u ? lo[j] : hi[j]) >> (16u * (c & 1u))) & 0xffffu : (lo[j] >> (8u * c)) & 0xffu;
+        if (run) {
+            uint32_t B[(N * BS + 3u) / 4u];
+DEV_UNROLL
+            for (uint32_t i = 0; i < (N * BS + 3u) / 4u; i++) B[i] = 0u;
+DEV_UNROLL
+            for (uint32_t j = 0; j < N; j++) B[j * BS / 4u] |= s[j] << (8u * ((j * BS) & 3u));
+            spec_store_run<N * BS>(p + x * BS, B);
+        } else {
+DEV_UNROLL
+            for (uint32_t j = 0; j < N; j++)
+                if (x + j < w) spec_store_px<BS>(p + (x + j) * ostep, s[j], 0u);
+        }
+    }
+}
+template <int BPP, uint32_t F, uint32_t DEPTH, bool PL>
 DEV_INLINE void spec_fmt_group_sub(const uint32_t *R, int g, uint32_t w, uint32_t ct, const debig_png_spec_task &t,
-                                   const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep)
+                                   const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep, uint64_t plane)
 {
     constexpr uint32_t K = PngSpecShape<BPP>::K, CH = (F & 3u) == 0u ? 4u : (F & 3u) == 1u ? 3u : (F & 3u) == 2u ? 1u : 2u;
     constexpr uint32_t PPB = 8u / DEPTH, PB = CH << ((F >> 4) & 1u);
@@ -297,19 +330,20 @@ DEV_UNROLL
             pal_bad |= xb + s < w ? bad : 0u;
             spec_fmt_pack<F>(p, lo[s], hi[s]);
         }
-        spec_store_pixels<PB, PPB>(orow, xb, w, ostep, t.dx, lo, hi);
+        if constexpr (PL) spec_store_planar<F, PPB>(orow, plane, xb, w, ostep, t.dx, lo, hi);
+        else spec_store_pixels<PB, PPB>(orow, xb, w, ostep, t.dx, lo, hi);
     }
 }
-template <int BPP, uint32_t F>
+template <int BPP, uint32_t F, bool PL>
 DEV_INLINE void spec_fmt_group(const uint32_t *R, int g, uint32_t w, uint32_t depth, uint32_t ct, const debig_png_spec_task &t,
-                               const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep)
+                               const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep, uint64_t plane)
 {
     constexpr uint32_t K = PngSpecShape<BPP>::K, CH = (F & 3u) == 0u ? 4u : (F & 3u) == 1u ? 3u : (F & 3u) == 2u ? 1u : 2u;
     constexpr uint32_t PB = CH << ((F >> 4) & 1u);
     if (BPP == 1 && depth < 8u) {
-        if (depth == 1u) spec_fmt_group_sub<BPP, F, 1u>(R, g, w, ct, t, pal, pal_bad, orow, ostep);
-        else if (depth == 2u) spec_fmt_group_sub<BPP, F, 2u>(R, g, w, ct, t, pal, pal_bad, orow, ostep);
-        else spec_fmt_group_sub<BPP, F, 4u>(R, g, w, ct, t, pal, pal_bad, orow, ostep);
+        if (depth == 1u) spec_fmt_group_sub<BPP, F, 1u, PL>(R, g, w, ct, t, pal, pal_bad, orow, ostep, plane);
+        else if (depth == 2u) spec_fmt_group_sub<BPP, F, 2u, PL>(R, g, w, ct, t, pal, pal_bad, orow, ostep, plane);
+        else spec_fmt_group_sub<BPP, F, 4u, PL>(R, g, w, ct, t, pal, pal_bad, orow, ostep, plane);
         return;
     }
     const uint64_t x = (uint64_t)g * K;
@@ -323,23 +357,45 @@ DEV_UNROLL
         pal_bad |= x + j < w ? bad : 0u;
         spec_fmt_pack<F>(p, lo[j], hi[j]);
     }
-    spec_store_pixels<PB, K>(orow, x, w, ostep, t.dx, lo, hi);
+    if constexpr (PL) spec_store_planar<F, K>(orow, plane, x, w, ostep, t.dx, lo, hi);
+    else spec_store_pixels<PB, K>(orow, x, w, ostep, t.dx, lo, hi);
+}
+template <int BPP, bool PL>
+DEV_INLINE void spec_fmt_switch(const uint32_t *R, int g, uint32_t w, uint32_t depth, uint32_t ct, const debig_png_spec_task &t,
+                                const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep, uint64_t plane)
+{
+    switch (t.out_fmt) { /* workgroup-uniform */
+    case 0x01u: spec_fmt_group<BPP, 0x01u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    case 0x02u: spec_fmt_group<BPP, 0x02u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    case 0x03u: spec_fmt_group<BPP, 0x03u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    case 0x10u: spec_fmt_group<BPP, 0x10u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    case 0x11u: spec_fmt_group<BPP, 0x11u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    case 0x12u: spec_fmt_group<BPP, 0x12u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    case 0x13u: spec_fmt_group<BPP, 0x13u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    default: spec_fmt_group<BPP, 0x00u, PL>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane); break;
+    }
 }
 template <int BPP>
 DEV_INLINE void spec_out_group(PngSpecOutFmt, const uint32_t *R, int g, uint32_t w, uint32_t depth, uint32_t ct,
                                const debig_png_spec_task &t, const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow,
                                uint64_t ostep)
 {
-    switch (t.out_fmt) { /* workgroup-uniform */
-    case 0x01u: spec_fmt_group<BPP, 0x01u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    case 0x02u: spec_fmt_group<BPP, 0x02u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    case 0x03u: spec_fmt_group<BPP, 0x03u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    case 0x10u: spec_fmt_group<BPP, 0x10u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    case 0x11u: spec_fmt_group<BPP, 0x11u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    case 0x12u: spec_fmt_group<BPP, 0x12u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    case 0x13u: spec_fmt_group<BPP, 0x13u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    default: spec_fmt_group<BPP, 0x00u>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep); break;
-    }
+    spec_fmt_switch<BPP, false>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, 0u);
+}
+
+// Channel-planar output (debig_png_spec_defilter_planar_kernel): the pixels of PngSpecOutFmt, built by the same code, stored
+// as planes of img_height * img_width samples, one channel after the other without padding.  orow and ostep count in
+// samples here (spec_out_bytes is the size of ONE sample); the task carries the full image's height for the plane size.
+struct PngSpecOutPlanar {};
+constexpr bool spec_out_rgba8(PngSpecOutPlanar) { return false; }
+DEV_INLINE uint32_t spec_out_bytes(PngSpecOutPlanar, const debig_png_spec_task &t) { return 1u << ((t.out_fmt >> 4) & 1u); }
+template <int BPP>
+DEV_INLINE void spec_out_group(PngSpecOutPlanar, const uint32_t *R, int g, uint32_t w, uint32_t depth, uint32_t ct,
+                               const debig_png_spec_task &t, const uint32_t *pal, uint32_t &pal_bad, uint8_t *orow,
+                               uint64_t ostep)
+{
+    const uint64_t plane = ((uint64_t)t.img_height * t.img_width) << ((t.out_fmt >> 4) & 1u);
+    spec_fmt_switch<BPP, true>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane);
 }
 
 template <int BPP, class O>
@@ -564,4 +620,14 @@ debig_png_spec_defilter_fmt_kernel(uint8_t *__restrict__ arena, uint8_t *__restr
 {
     __shared__ PngSpecLds L;
     png_spec_tasks<PngSpecOutFmt>(L, arena, out_arena, tasks, results, n_tasks);
+}
+
+// ... and to channel planes (c, y, x) instead of interleaved pixels (t.out_fmt, t.img_height): again a kernel of its own
+__global__ void __launch_bounds__(64 * PNG_SPEC_NWD)
+debig_png_spec_defilter_planar_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict__ out_arena,
+                                      const debig_png_spec_task *__restrict__ tasks, debig_png_spec_result *__restrict__ results,
+                                      uint32_t n_tasks)
+{
+    __shared__ PngSpecLds L;
+    png_spec_tasks<PngSpecOutPlanar>(L, arena, out_arena, tasks, results, n_tasks);
 }

@@ -311,7 +311,7 @@ typedef struct debig_png_spec_task {
     uint16_t has_key;
     uint16_t n_pal;         /* palette entries; an index >= n_pal fails the task with DEBIG_PNG_SPEC_E_PALETTE           */
     uint16_t out_fmt;       /* output format, resolved (decode_png.h DEBIG_PNG_FMT_*: layout 0..3 | DEBIG_PNG_FMT_16); 0 = RGBA8 */
-    uint32_t reserved;
+    uint32_t img_height;    /* planar kernel only: rows of the FULL image (a plane is img_height * img_width samples); else unused */
 } debig_png_spec_task;
 
 typedef struct debig_png_spec_result {
@@ -330,6 +330,12 @@ int debig_hip_png_spec_defilter_batch(void *d_arena, void *d_rgba_arena, const d
  * channels * bytes-per-sample bytes, rows of img_width pixels without padding, 16-bit samples little-endian. */
 int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
                                           debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
+/* The same pixels channel-planar: sample c of pixel (x, y) at rgba_off + (c * img_height * img_width + y * img_width + x) *
+ * bytes-per-sample -- planes one after the other, no padding between planes or rows, 16-bit samples little-endian; every
+ * task needs img_height.  One-channel formats (GRAY) are the same bytes as above.  Only the image's
+ * channels * img_height * img_width * bytes-per-sample bytes are written. */
+int debig_hip_png_spec_defilter_planar_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
+                                             debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
 
 /* APNG compositing (csrc/apng_kernel.inc, behind debig_apng_decode_batch in decode_png.h).  One frame of a file: its
  * RGBA8 pixels (width * height dwords, rows without padding) and its place on the canvas. */

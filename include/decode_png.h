@@ -170,6 +170,38 @@ int debig_png_decode_batch_fmt(const uint8_t *const *inputs, const uint64_t *inp
                                const uint64_t *out_caps, uint32_t *status, debig_png_info *infos /* may be NULL */,
                                uint32_t n, uint32_t flags, uint32_t out_format);
 
+/* ---- channel-planar output and output that stays on the device --------------------------------------------------------
+ * out_layout: DEBIG_PNG_LAYOUT_HWC -- interleaved pixels, exactly debig_png_decode_batch_fmt -- or DEBIG_PNG_LAYOUT_CHW:
+ * sample c of pixel (x, y) at (c * h * w + y * w + x) * bytes_per_sample; the planes follow one another without padding,
+ * rows have no padding, 16-bit samples are little-endian.  The byte count is that of debig_png_out_layout.  Every image of
+ * more than one channel then goes through the planar de-filter kernel (debig_hip_png_spec_defilter_planar_batch), 8-bit
+ * RGB / RGBA files included; one-channel images are the same bytes in both layouts and keep their routing.  The layout is
+ * an argument of its own, never a bit of out_format.  Any other out_layout (or an invalid out_format) returns
+ * DEBIG_PNG_BAD_FORMAT and writes nothing. */
+enum { DEBIG_PNG_LAYOUT_HWC = 0, DEBIG_PNG_LAYOUT_CHW = 1 };
+#define DEBIG_PNG_BAD_ARG (-2) /* debig_png_decode_batch_dev: arena NULL, an offset not a multiple of 16, regions that overlap */
+
+/* debig_png_decode_batch_fmt with a layout: host buffers, the same statuses, order and flags. */
+int debig_png_decode_batch_layout(const uint8_t *const *inputs, const uint64_t *input_sizes, uint8_t *const *outs,
+                                  const uint64_t *out_caps, uint32_t *status, debig_png_info *infos /* may be NULL */,
+                                  uint32_t n, uint32_t flags, uint32_t out_format, uint32_t out_layout);
+
+/* The same with the pixels left on the device: image i at (uint8_t *)d_out_arena + out_offs[i], at most out_caps[i] bytes
+ * (E_OUTPUT is decided on the host from out_caps[i], as above).  d_out_arena is device memory of the current device.
+ * Checked first, on their own, before any file is looked at and before any device work: d_out_arena NULL with n > 0, an
+ * out_offs[i] that is not a multiple of 16, or two regions [out_offs[i], out_offs[i] + out_caps[i]) that overlap return
+ * DEBIG_PNG_BAD_ARG and leave status unwritten.  Statuses, their order and infos are those of debig_png_decode_batch_fmt.
+ * The call returns after the work has finished, so the pixels are visible to every stream; no pixel byte crosses the bus,
+ * only statuses, checksum words and result structs come down.
+ * What is written: the region of a file that fails on the host or before the de-filter (every status but E_FILTER and
+ * E_PALETTE) is untouched; the region of a file that fails in the de-filter holds unspecified bytes inside its own
+ * out_bytes = debig_png_out_layout(...); nothing outside [out_offs[i], out_offs[i] + out_bytes_i) of any file is written.
+ * Not provided: animated PNGs, inputs that are already on the device, an asynchronous variant on a caller's stream. */
+int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out_arena,
+                               const uint64_t *out_offs, const uint64_t *out_caps, uint32_t *status,
+                               debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags, uint32_t out_format,
+                               uint32_t out_layout);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

@@ -1,0 +1,255 @@
+"""The channel-planar store of the general PNG de-filter (csrc/png_spec_kernel.inc: debig_png_spec_defilter_planar_kernel)
+on the CPU lock-step emulator, plain and under ASan/UBSan.  Expected pixels: the numpy converter of
+tests/png_out_format_ref.py, transposed to (channels, h, w).  Every filter unit x every filter type x every concrete
+output format x interlace 0/1, widths 1..70, heights across the 64-row band edges, short palettes and tRNS keys, odd
+w * h (the planes of 8-bit outputs then start at odd addresses); every byte between and after the images must stay
+untouched; the filter-byte and palette-index statuses are those of the format twin on the same tasks."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import png_out_format_ref as F  # noqa: E402
+import png_spec_ref as R  # noqa: E402
+import test_emu_png_spec as T  # noqa: E402
+from emu_binding import load_emu  # noqa: E402
+
+
+class SpecTask(C.Structure):  # include/debig_hip.h: debig_png_spec_task (the former reserved word is img_height)
+    _fields_ = [("stream_off", C.c_uint64), ("rgba_off", C.c_uint64), ("pal_off", C.c_uint64), ("scratch_off", C.c_uint64),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("img_width", C.c_uint32),
+                ("x0", C.c_uint32), ("y0", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32),
+                ("bpp_f", C.c_uint8), ("depth", C.c_uint8), ("color_type", C.c_uint8), ("channels", C.c_uint8),
+                ("key", C.c_uint16 * 3), ("has_key", C.c_uint16), ("n_pal", C.c_uint16), ("out_fmt", C.c_uint16),
+                ("img_height", C.c_uint32)]
+
+
+assert C.sizeof(SpecTask) == C.sizeof(T.SpecTask) == 80
+assert SpecTask.img_height.offset == T.SpecTask.reserved.offset and SpecTask.out_fmt.offset == T.SpecTask.reserved16.offset
+
+CONCRETE = [lay | d for d in (F.D8, F.D16) for lay in (F.RGBA, F.RGB, F.GRAY, F.GRAY_ALPHA)]
+ALL_FMTS = CONCRETE + [F.NATIVE, F.NATIVE | F.D16, F.NATIVE | F.D_NATIVE]
+_LIB = {}
+FILL = 0xEE
+
+
+def _emu():
+    if "L" not in _LIB:
+        L = load_emu(asan=os.environ.get("DEBIG_SPEC_EMU_ASAN") == "1")
+        for name in ("emu_png_spec_defilter_planar_batch", "emu_png_spec_defilter_fmt_batch"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        _LIB["L"] = L
+    return _LIB["L"]
+
+
+def _has_trns(im):
+    return int(im.get("key") is not None) if im["ct"] in (0, 2) else int(im["ct"] == 3 and len(im.get("trns", b"")) > 0)
+
+
+def run_images(imgs, fmts, planar=True):
+    """imgs as test_emu_png_spec._image makes them, fmts: one out_format per image (NATIVE resolved here as the host does)
+    -> [(status list, pixels (channels, h, w) -- planar=False: the format twin, (h, w, channels) --, resolved format)];
+    asserts that no byte outside the images changed"""
+    arena = bytearray(64)
+    tasks, owners, offs, sizes, res_fmts = [], [], [], [], []
+    total = 0
+    for i, (im, fmt) in enumerate(zip(imgs, fmts)):
+        s = im["samples"]
+        h, w = s.shape[:2]
+        ct, depth, il = im["ct"], im["depth"], im.get("interlace", 0)
+        lay, bits = F.resolve(ct, depth, _has_trns(im), fmt)
+        rf = lay | (F.D16 if bits == 16 else F.D8)
+        res_fmts.append(rf)
+        nbytes = w * h * F.LAYOUT_CHANNELS[lay] * bits // 8
+        stream = R.scanlines(s, ct, depth, il, im.get("filters"))
+        pal_off = 0
+        if ct == 3:
+            pal_off = len(arena)
+            arena += R.full_palette(im["pal"], im.get("trns", b"")).tobytes()
+        base = len(arena)
+        arena += stream + bytes(T._a16(len(stream)) - len(stream) + 32)
+        offs.append(total)
+        sizes.append(nbytes)
+        pos = 0
+        for x0, y0, dx, dy, wp, hp in R.passes(w, h, il):
+            t = SpecTask()
+            t.stream_off, t.rgba_off, t.pal_off = base + pos, total, pal_off
+            t.width, t.height, t.img_width, t.img_height = wp, hp, w, h
+            t.x0, t.y0, t.dx, t.dy = x0, y0, dx, dy
+            t.bpp_f, t.depth, t.color_type, t.channels = R.bpp_f(ct, depth), depth, ct, R.CHANNELS[ct]
+            if im.get("key") is not None:
+                t.has_key = 1
+                for k, v in enumerate(im["key"]):
+                    t.key[k] = v
+            t.n_pal = len(im["pal"]) if ct == 3 else 0
+            t.out_fmt = rf
+            tasks.append(t)
+            owners.append(i)
+            pos += hp * (1 + R.row_bytes(wp, ct, depth))
+        total += T._a16(nbytes) + 16
+    for t in tasks:
+        rb = R.row_bytes(t.width, t.color_type, t.depth)
+        arena += bytes(T._a16(len(arena)) - len(arena))
+        t.scratch_off = len(arena)
+        arena += bytes(4 * (T._a16(rb) + 16))
+    arena += bytes(64)
+    a = np.frombuffer(bytes(arena), dtype=np.uint8).copy()
+    out = np.full(total + 64, FILL, dtype=np.uint8)
+    n = len(tasks)
+    TT = (SpecTask * n)(*tasks)
+    res = (T.SpecResult * n)()
+    fn = _emu().emu_png_spec_defilter_planar_batch if planar else _emu().emu_png_spec_defilter_fmt_batch
+    assert fn(a.ctypes.data, out.ctypes.data, TT, res, n) == 0
+    untouched = np.ones(len(out), dtype=bool)
+    result = []
+    for i, im in enumerate(imgs):
+        h, w = im["samples"].shape[:2]
+        lay, bits = res_fmts[i] & 15, 16 if res_fmts[i] & F.D16 else 8
+        ch = F.LAYOUT_CHANNELS[lay]
+        untouched[offs[i]: offs[i] + sizes[i]] = False
+        st = [(res[k].status, res[k].bad_row) for k in range(n) if owners[k] == i]
+        px = out[offs[i]: offs[i] + sizes[i]].view("<u2" if bits == 16 else np.uint8)
+        result.append((st, px.reshape((ch, h, w) if planar else (h, w, ch)), res_fmts[i]))
+    assert (out[untouched] == FILL).all(), "bytes outside the images were written"
+    return result
+
+
+def expected(im, fmt):
+    ct, depth = im["ct"], im["depth"]
+    pal = R.full_palette(im["pal"], im.get("trns", b""))[: len(im["pal"])] if ct == 3 else None
+    s = im["samples"]
+    if s.ndim == 2:
+        s = s[:, :, None]
+    return np.transpose(F.convert(s, ct, depth, im.get("key"), pal, fmt, has_trns=_has_trns(im)), (2, 0, 1))
+
+
+def _check(imgs, fmts):
+    for im, fmt, (st, px, rf) in zip(imgs, fmts, run_images(imgs, fmts)):
+        where = (im["ct"], im["depth"], im["samples"].shape, im.get("interlace"), hex(fmt))
+        assert all(s == (0, 0xFFFFFFFF) for s in st), (where, st)
+        exp = expected(im, fmt)
+        assert px.shape == exp.shape and px.dtype.itemsize == exp.dtype.itemsize, where
+        assert np.array_equal(px, exp), (where, np.argwhere(px != exp)[:4])
+
+
+@pytest.mark.parametrize("ct,depth", T.FORMATS)
+def test_every_unit_filter_type_and_format(ct, depth):
+    """every filter type on its own and mixed per row, interlaced and not, tRNS keys, to every output format (every
+    format in one launch: out_fmt is per task)"""
+    rng = np.random.default_rng(ct * 100 + depth + 2)
+    imgs, fmts = [], []
+    for k, fmt in enumerate(ALL_FMTS):
+        for ft in range(5):
+            imgs.append(T._image(rng, 21 + k, 9, ct, depth, 0, ft, key=ct in (0, 2) and (k + ft) % 2 == 0))
+            fmts.append(fmt)
+        imgs.append(T._image(rng, 19 + k, 17, ct, depth, 1, None, key=ct in (0, 2) and k % 2 == 0))
+        fmts.append(fmt)
+    _check(imgs, fmts)
+
+
+@pytest.mark.parametrize("ct,depth", [(0, 1), (0, 2), (0, 4), (3, 1), (3, 4), (2, 16), (6, 16), (4, 8), (2, 8), (6, 8), (0, 16)])
+def test_widths_1_to_70(ct, depth):
+    """every width 1..70 (sub-byte row tails, partial groups, empty Adam7 passes), concrete formats in rotation"""
+    rng = np.random.default_rng(19 + depth * 10 + ct)
+    imgs = [T._image(rng, w, 1 + (w % 7), ct, depth, w % 2, None, key=ct in (0, 2) and w % 3 == 0) for w in range(1, 71)]
+    fmts = [CONCRETE[(w + w // 8) % len(CONCRETE)] for w in range(1, 71)]
+    _check(imgs, fmts)
+
+
+@pytest.mark.parametrize("h", [63, 64, 65, 129])
+def test_heights_across_bands(h):
+    rng = np.random.default_rng(h + 2)
+    imgs = [T._image(rng, 45, h, 6, 16, 0, None), T._image(rng, 70, h, 0, 1, 0, 4), T._image(rng, 33, h, 2, 8, 1, None),
+            T._image(rng, 19, h, 3, 8, 0, 3), T._image(rng, 27, h, 4, 16, 1, None)]
+    for fmts in ([F.RGBA | F.D16] * 5, [F.RGB, F.GRAY_ALPHA, F.NATIVE | F.D_NATIVE, F.RGBA, F.GRAY_ALPHA | F.D16]):
+        _check(imgs, fmts)
+
+
+def test_short_palette_and_keys():
+    """a palette of fewer than 256 entries with a shorter tRNS (uncovered entries 255), 8- and 16-bit keys"""
+    rng = np.random.default_rng(22)
+    imgs, fmts = [], []
+    for fmt in ALL_FMTS:
+        p = T._image(rng, 23, 11, 3, 8, 0, None)
+        p["pal"] = p["pal"][:5] if len(p["pal"]) > 5 else p["pal"]
+        p["samples"] = (p["samples"] % len(p["pal"])).astype(np.uint8)
+        p["trns"] = bytes([0, 128, 7])[: len(p["pal"]) - 1]
+        imgs += [p, T._image(rng, 23, 11, 0, 16, 1, None, key=True), T._image(rng, 23, 11, 2, 16, 0, 2, key=True),
+                 T._image(rng, 23, 11, 0, 2, 0, 1, key=True)]
+        fmts += [fmt] * 4
+    _check(imgs, fmts)
+
+
+@pytest.mark.parametrize("w,h", [(7, 5), (37, 3), (1, 1), (3, 3), (65, 1), (9, 67)])
+def test_odd_plane_addresses(w, h):
+    """w * h odd: plane c of an 8-bit output starts at the odd address c * w * h, so the run stores fall back to bytes"""
+    rng = np.random.default_rng(w * 100 + h)
+    imgs, fmts = [], []
+    for ct, depth in T.FORMATS:
+        for il in (0, 1):
+            for fmt in (F.RGBA, F.RGB, F.GRAY_ALPHA, F.RGB | F.D16):
+                imgs.append(T._image(rng, w, h, ct, depth, il, None, key=ct in (0, 2)))
+                fmts.append(fmt)
+    _check(imgs, fmts)
+
+
+def test_equals_the_format_twin_transposed():
+    rng = np.random.default_rng(24)
+    imgs = [T._image(rng, w, h, ct, d, il, None, key=ct in (0, 2))
+            for (ct, d) in T.FORMATS for (w, h, il) in ((7, 5, 1), (37, 66, 0), (30, 13, 1))]
+    fmts = [ALL_FMTS[k % len(ALL_FMTS)] for k in range(len(imgs))]
+    a = run_images(imgs, fmts, planar=False)
+    b = run_images(imgs, fmts)
+    for (st0, px0, rf0), (st1, px1, rf1) in zip(a, b):
+        assert st0 == st1 and rf0 == rf1
+        assert np.array_equal(np.transpose(px0, (2, 0, 1)), px1)
+
+
+def test_error_statuses_equal_the_format_twin():
+    """the filter-byte and palette-index statuses are those of the format twin on the same tasks"""
+    rng = np.random.default_rng(6)
+    good = T._image(rng, 40, 70, 6, 8, 0, None)
+    bad_ft = T._image(rng, 40, 70, 0, 8, 0, lambda p, y: 5 if y == 66 else 1)
+    bad_il = T._image(rng, 21, 30, 2, 16, 1, lambda p, y: 7 if (p, y) == (4, 3) else 2)
+    pal = T._image(rng, 40, 70, 3, 8, 0, None)
+    pal["pal"] = pal["pal"][:3]
+    pal["samples"][30, 7] = 200
+    imgs, fmts = [good, bad_ft, bad_il, pal], [F.RGB | F.D16, F.RGB, F.RGBA | F.D16, F.NATIVE]
+    res = run_images(imgs, fmts)
+    twin = run_images(imgs, fmts, planar=False)
+    assert [r[0] for r in res] == [r[0] for r in twin]
+    assert res[0][0] == [(0, 0xFFFFFFFF)]
+    assert res[1][0][0] == (1, 66)
+    assert (1, 3) in res[2][0]
+    assert res[3][0][0][0] == 2
+    assert np.array_equal(res[0][1], expected(good, F.RGB | F.D16))
+
+
+def test_kernel_under_address_sanitizer():
+    """the same kernel source under ASan + UBSan (tools/simt_emu/libdebig_emu_asan.so), in a child process"""
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = r"""
+import sys, os
+sys.path.insert(0, os.path.join(%(root)r, "tests")); sys.path.insert(0, %(root)r)
+import numpy as np
+import test_emu_png_planar as E
+import test_emu_png_spec as T
+rng = np.random.default_rng(14)
+imgs, fmts = [], []
+for k, (ct, d) in enumerate(T.FORMATS):
+    for j, (w, h, il) in enumerate(((1, 1, 0), (3, 3, 1), (13, 66, 0), (9, 7, 1), (17, 3, 0))):
+        imgs.append(T._image(rng, w, h, ct, d, il, None, key=ct in (0, 2)))
+        fmts.append(E.ALL_FMTS[(k + j) %% len(E.ALL_FMTS)])
+E._check(imgs, fmts)
+print("asan ok")
+""" % {"root": root}
+    asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0", DEBIG_SPEC_EMU_ASAN="1")
+    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "asan ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]

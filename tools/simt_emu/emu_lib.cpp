@@ -312,6 +312,14 @@ extern "C" int emu_png_spec_defilter_fmt_batch(void *arena, void *out_arena, con
     return 0;
 }
 
+/* ... and the channel-planar one, as debig_hip_png_spec_defilter_planar_batch launches it */
+extern "C" int emu_png_spec_defilter_planar_batch(void *arena, void *out_arena, const debig_png_spec_task *tasks,
+                                                  debig_png_spec_result *results, uint32_t n)
+{
+    if (n) EMU_LAUNCH(debig_png_spec_defilter_planar_kernel, n, 64 * PNG_SPEC_NWD, (uint8_t *)arena, (uint8_t *)out_arena, tasks, results, n);
+    return 0;
+}
+
 /* APNG compositing (apng_kernel.inc) as debig_hip_apng_composite_batch launches it (grid: 0 = one workgroup per task,
  * else fewer workgroups that loop over the tasks) */
 extern "C" int emu_apng_composite_batch(const void *frames_arena, void *out_arena, const debig_apng_task *tasks, uint32_t n,
