@@ -211,7 +211,7 @@ def gunzip_batch(datas, out_caps):
 
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
-              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation"}
+              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -379,6 +379,116 @@ def png_decode_batch_device(datas, mode="rgba", depth=8, layout="hwc", device="c
             t = (t.view(u16) if bs == 2 else t).view(shape)
         out.append((int(status[i]), t, _info_dict(infos[i])))
     return out
+
+
+class PngBox(C.Structure):  # include/decode_png.h: debig_png_box
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
+
+
+class PngTensorDesc(C.Structure):  # include/decode_png.h: debig_png_tensor_desc
+    _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("out_format", C.c_uint32), ("out_layout", C.c_uint32),
+                ("dtype", C.c_uint32), ("resize_flags", C.c_uint32), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+PNG_TENSOR_DTYPES = {"uint": 0, "float32": 1, "float16": 2, "bfloat16": 3}  # include/decode_png.h: DEBIG_PNG_T_*
+PNG_RESIZE_ANTIALIAS = 1  # DEBIG_PNG_RESIZE_ANTIALIAS
+
+
+def png_tensor_desc(size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, antialias=True):
+    """the debig_png_tensor_desc of png_decode_batch_tensor's arguments (no GPU needed) -> (desc, channels, element bytes).
+    dtype: "float32" | "float16" | "bfloat16", or an integer result: "uint" ("uint8" with depth 8, "uint16" with depth 16)"""
+    if mode == "native" or depth == "native":
+        raise ValueError("png_decode_batch_tensor needs a concrete mode and depth: every image of the tensor has the same channels")
+    fmt = png_out_format(mode, depth)
+    lay = png_layout_code(layout)
+    if dtype in ("uint8", "uint16"):
+        if dtype != f"uint{depth}":
+            raise ValueError(f"dtype {dtype!r} needs depth={dtype[4:]}")
+        dtype = "uint"
+    if dtype not in PNG_TENSOR_DTYPES:
+        raise ValueError(f"dtype must be one of {sorted(PNG_TENSOR_DTYPES)}, 'uint8' or 'uint16', not {dtype!r}")
+    H, W = (int(v) for v in size)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"size must be (H, W) with 1 <= H, W <= 16384, not {size!r}")
+    ch = {0: 4, 1: 3, 2: 1, 3: 2}[fmt & 15]
+    d = PngTensorDesc(out_w=W, out_h=H, out_format=fmt, out_layout=lay, dtype=PNG_TENSOR_DTYPES[dtype],
+                      resize_flags=PNG_RESIZE_ANTIALIAS if antialias else 0)
+
+    def per_channel(v, name, default):
+        if v is None:
+            return [default] * ch
+        v = [float(x) for x in (v if hasattr(v, "__len__") else [v] * ch)]
+        if len(v) != ch:
+            raise ValueError(f"{name} needs {ch} values for mode {mode!r}, not {len(v)}")
+        return v
+
+    m, sd = per_channel(mean, "mean", 0.0), per_channel(std, "std", 1.0)
+    if (mean is not None or std is not None) and dtype == "uint":
+        raise ValueError("mean / std need a float dtype")
+    if any(x == 0.0 for x in sd):
+        raise ValueError("std must not be 0")
+    for k in range(4):
+        d.scale[k] = np.float32(1.0 / sd[k]) if k < ch else 1.0  # in float64, then float32
+        d.bias[k] = np.float32(-m[k] / sd[k]) if k < ch else 0.0
+    if not all(np.isfinite(d.scale[k]) and np.isfinite(d.bias[k]) for k in range(4)):
+        raise ValueError("mean / std give a non-finite scale or bias")
+    return d, ch, (depth // 8 if dtype == "uint" else 4 if dtype == "float32" else 2)
+
+
+def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
+                            antialias=True, device="cuda:0", fill=None, force_general=False):
+    """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
+    (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
+    (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
+    mean / std per channel, mean and std on the [0, 1] scale, absent: 1 and 0) or "uint" (uint8 for depth 8, uint16 for 16,
+    the latter as torch.int16 bits where torch has no uint16).  boxes: per image None or (x, y, w, h), the crop inside the
+    image.  The resize is bilinear with half-pixel centres, antialiased when it shrinks (what
+    torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=True) means, in Q14 integer weights).
+    The slot of a file whose status is not 0 is left as allocated, or holds `fill` when that is given.  Same device rule
+    as png_decode_batch_device."""
+    import torch
+
+    d, ch, es = png_tensor_desc(size, mode, depth, dtype, layout, mean, std, antialias)
+    L = _png_spec_lib()
+    L.debig_png_decode_batch_tensor.restype = C.c_int
+    L.debig_png_decode_batch_tensor.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device must be a GPU, not {device!r}")
+    L.debig_hip_get_device.restype = C.c_int
+    cur = L.debig_hip_get_device()
+    if dev.index is not None and dev.index != cur:
+        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
+    dev = torch.device("cuda", cur)
+    n = len(datas)
+    if boxes is not None and len(boxes) != n:
+        raise ValueError("boxes needs one entry (or None) per file")
+    H, W = d.out_h, d.out_w
+    tdt = {1: torch.float32, 2: torch.float16, 3: torch.bfloat16}.get(d.dtype)
+    if tdt is None:
+        tdt = torch.uint8 if es == 1 else getattr(torch, "uint16", torch.int16)
+    shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
+    if fill is None:
+        out = torch.empty(shape, dtype=tdt, device=dev)
+    elif tdt == getattr(torch, "uint16", None):  # (torch.full has no uint16 kernel: fill the same bits as int16)
+        out = torch.full(shape, int(np.array(fill, np.uint16).view(np.int16)), dtype=torch.int16, device=dev).view(tdt)
+    else:
+        out = torch.full(shape, fill, dtype=tdt, device=dev)
+    torch.cuda.synchronize(dev)  # the fill runs on torch's stream, the library on its own
+    ins = [_u8(x) for x in datas]
+    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
+    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
+    bx = None
+    if boxes is not None:
+        bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
+    status = (C.c_uint32 * n)()
+    infos = (PngInfo * n)()
+    rc = L.debig_png_decode_batch_tensor(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n,
+                                         PNG_FORCE_GENERAL if force_general else 0, C.byref(d))
+    if rc in (PNG_BAD_FORMAT, PNG_BAD_ARG):
+        raise ValueError(f"debig_png_decode_batch_tensor rejected its arguments ({rc})")
+    N.check(rc, "debig_png_decode_batch_tensor")
+    return [int(s) for s in status], out, [_info_dict(i) for i in infos]
 
 
 class ApngFrame(C.Structure):  # include/decode_png.h: debig_apng_frame

@@ -15,6 +15,7 @@
 #include "png_fused_kernel.inc"
 #include "png_spec_kernel.inc"
 #include "apng_kernel.inc"
+#include "png_resize_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -742,6 +743,18 @@ int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena
     const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
     hipLaunchKernelGGL(debig_apng_composite_kernel, dim3(grid), dim3(APNG_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_frames_arena, (uint8_t *)d_out_arena, d_tasks, n_tasks);
+    return (int)hipGetLastError();
+}
+
+// resize + normalise (png_resize_kernel.inc): one workgroup of 256 lanes per output tile; the grid is capped, the kernel loops
+int debig_hip_png_resize_batch(const void *d_src_arena, void *d_out, const debig_png_resize_task *d_tasks,
+                               const void *d_weights, uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_resize_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
     return (int)hipGetLastError();
 }
 

@@ -49,6 +49,9 @@ void debig_ctx_release_ptr(debig_ctx *c)
     buf_free(&c->spec_res);
     buf_free(&c->anim);
     buf_free(&c->anim_tasks);
+    buf_free(&c->rsz_src);
+    buf_free(&c->rsz_tasks);
+    buf_free(&c->rsz_weights);
     buf_free(&c->ws);
     buf_free(&c->dense);
     buf_free(&c->dense_list);

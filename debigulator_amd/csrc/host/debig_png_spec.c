@@ -1,6 +1,8 @@
 /*
  * debig_png_info_get / debig_png_decode_batch / debig_png_decode_batch_fmt / debig_png_out_layout (include/decode_png.h):
  * every PNG the specification allows, to RGBA8 or to the output format the caller asks for.  Not a reference function.
+ * debig_png_decode_batch_tensor (at the end of the file): the same decode into the context's own device arena, then one
+ * resize + normalise launch (debig_hip_png_resize_batch) into the caller's dense tensor.
  *
  * Host side (plain C): the chunk walk and the rules decided by headers alone.  On the GPU: chunk CRC-32 and the
  * Adler-32 trailer (debig_hip_checksum_batch), the IDAT concatenation (debig_hip_gather), inflate (the batch inflate,
@@ -310,11 +312,13 @@ typedef struct spec_target {
     uint8_t *const *outs;
     void *d_arena;
     const uint64_t *d_offs;
+    uint64_t own_bytes;        /* != 0: the arena is the context's own (c->rsz_src, reserved here to own_bytes), d_arena unused */
+    const uint32_t *pre_status; /* may be NULL; pre_status[i] != 0: file i ends with that status once its walk has filled info */
 } spec_target;
 
 typedef int (*spec_launch_fn)(void *, void *, const debig_png_spec_task *, debig_png_spec_result *, uint32_t, void *);
 
-/* the decode behind debig_png_decode_batch_fmt / _layout / _dev (out_format and out_layout valid) */
+/* the decode behind debig_png_decode_batch_fmt / _layout / _dev / _tensor (out_format and out_layout valid) */
 static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_sizes, const spec_target *tg,
                             const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags,
                             uint32_t out_format, uint32_t out_layout)
@@ -342,7 +346,9 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
     for (uint32_t i = 0; i < n; i++) {
         spec_file *f = &F[i];
         f->status = spec_walk(inputs[i], input_sizes[i], f, 0);
-        if (f->status == DEBIG_PNG_OK)
+        if (tg->pre_status && tg->pre_status[i])
+            f->status = tg->pre_status[i];
+        else if (f->status == DEBIG_PNG_OK)
             f->status = spec_host_rules(f, inputs[i], tg->outs ? tg->outs[i] != NULL : 1, out_caps[i], out_format);
         if (f->status == DEBIG_PNG_OK) {
             f->planar = out_layout == DEBIG_PNG_LAYOUT_CHW && fmt_channels(f->fmt) > 1u; /* one channel: the same bytes */
@@ -406,6 +412,7 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
     }
     if ((rc = debig_devbuf_reserve(&c->files, files_total + 64)) || (rc = debig_devbuf_reserve(&c->in, in_total + 64)) ||
         (rc = debig_devbuf_reserve(&c->out, out_total + 64)) || (tg->outs && (rc = debig_devbuf_reserve(&c->rgba, rgba_total + 64))) ||
+        (tg->own_bytes && (rc = debig_devbuf_reserve(&c->rsz_src, tg->own_bytes))) ||
         (rc = debig_devbuf_reserve(&c->spans, ((uint64_t)n_chunks + m) * sizeof(debig_span))) ||
         (rc = debig_devbuf_reserve(&c->crcs, ((uint64_t)n_chunks + m) * sizeof(uint32_t))) ||
         (rc = debig_devbuf_reserve(&c->copies, ((uint64_t)n_pieces + 1) * sizeof(debig_copy))))
@@ -500,7 +507,7 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
      *      next cnt[1]) and the planar kernel for every channel-planar image of more than one channel (the last cnt[2]) */
     static const spec_launch_fn launch[3] = {debig_hip_png_spec_defilter_batch, debig_hip_png_spec_defilter_fmt_batch,
                                              debig_hip_png_spec_defilter_planar_batch};
-    void *pix = tg->outs ? c->rgba.ptr : tg->d_arena;
+    void *pix = tg->outs ? c->rgba.ptr : tg->own_bytes ? c->rsz_src.ptr : tg->d_arena;
     const uint32_t base[3] = {0, cnt[0], cnt[0] + cnt[1]};
     uint32_t fill[3] = {0, 0, 0};
     n_img = 0;
@@ -611,7 +618,7 @@ DEBIG_API int debig_png_decode_batch_layout(const uint8_t *const *inputs, const 
                                             uint32_t flags, uint32_t out_format, uint32_t out_layout)
 {
     if (!fmt_valid(out_format) || out_layout > DEBIG_PNG_LAYOUT_CHW) return DEBIG_PNG_BAD_FORMAT;
-    const spec_target tg = {outs, NULL, NULL};
+    const spec_target tg = {outs, NULL, NULL, 0, NULL};
     return spec_decode_core(inputs, input_sizes, &tg, out_caps, status, infos, n, flags, out_format, out_layout);
 }
 
@@ -646,6 +653,256 @@ DEBIG_API int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uin
     for (uint32_t k = 0; k + 1 < r; k++) bad |= reg[k].off + reg[k].cap > reg[k + 1].off;
     free(reg);
     if (bad) return DEBIG_PNG_BAD_ARG;
-    const spec_target tg = {NULL, d_out_arena, out_offs};
+    const spec_target tg = {NULL, d_out_arena, out_offs, 0, NULL};
     return spec_decode_core(inputs, input_sizes, &tg, out_caps, status, infos, n, flags, out_format, out_layout);
+}
+
+/* ---- debig_png_decode_batch_tensor: crop + resize + normalise into one dense device tensor (decode_png.h) ---------------- */
+
+#define RSZ_MAX_TAPS 129u /* antialias is refused beyond a scale of 64: 2 * 64 + 1 taps */
+#define RSZ_MAX_IMAGE_BYTES ((uint64_t)1 << 31)
+
+DEBIG_API uint32_t debig_png_resize_weights(uint32_t cl, uint32_t L, uint32_t antialias, uint32_t X, uint32_t *first,
+                                            int16_t *w, uint32_t w_cap)
+{
+    if (cl == 0 || L == 0 || L > 16384u || X >= L || !first || !w) return 0;
+    const int64_t l2 = 2 * (int64_t)L;
+    if (!antialias || cl <= L) {
+        int64_t num = (2 * (int64_t)X + 1) * cl - L;
+        const int64_t top = ((int64_t)cl - 1) * l2;
+        num = num < 0 ? 0 : num > top ? top : num;
+        const int64_t i0 = num / l2, r = num % l2, w1 = (r * 16384 + L) / l2;
+        *first = (uint32_t)i0;
+        if (i0 == (int64_t)cl - 1) {
+            if (w_cap < 1) return 0;
+            w[0] = 16384;
+            return 1;
+        }
+        if (w_cap < 2) return 0;
+        w[0] = (int16_t)(16384 - w1);
+        w[1] = (int16_t)w1;
+        return 2;
+    }
+    if ((uint64_t)cl > 64u * (uint64_t)L) return 0;
+    const int64_t c = (2 * (int64_t)X + 1) * cl, reach = 2 * (int64_t)cl;
+    int64_t j = c - reach > 0 ? (c - reach) / l2 : 0; /* (2j + 1) L <= c - 2 cl + L: at or left of the first tap */
+    if (j > 0) j--;
+#define RSZ_N(j) (reach - ((2 * (j) + 1) * (int64_t)L > c ? (2 * (j) + 1) * (int64_t)L - c : c - (2 * (j) + 1) * (int64_t)L))
+    while (j < (int64_t)cl && RSZ_N(j) <= 0) j++;
+    int64_t nn[RSZ_MAX_TAPS], T = 0, best = 0;
+    uint32_t cnt = 0, best_k = 0;
+    for (; j < (int64_t)cl && RSZ_N(j) > 0; j++) {
+        if (cnt == RSZ_MAX_TAPS) return 0;
+        if (cnt == 0) *first = (uint32_t)j;
+        nn[cnt] = RSZ_N(j);
+        T += nn[cnt];
+        if (nn[cnt] > best) { best = nn[cnt]; best_k = cnt; }
+        cnt++;
+    }
+#undef RSZ_N
+    if (cnt == 0 || cnt > w_cap) return 0;
+    int64_t sum = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+        const int64_t q = (nn[k] * 16384 + T / 2) / T;
+        w[k] = (int16_t)q;
+        sum += q;
+    }
+    w[best_k] = (int16_t)(w[best_k] + (16384 - sum));
+    return cnt;
+}
+
+/* the axis tables of one call (include/debig_hip.h: layout), one per distinct (cl, L) */
+typedef struct rsz_axis { uint32_t cl, max_taps; uint64_t off; } rsz_axis;
+typedef struct rsz_tables {
+    uint8_t *buf;
+    uint64_t len, cap;
+    rsz_axis *ax;
+    uint32_t n_ax, cap_ax, L, aa;
+} rsz_tables;
+
+/* the table of crop length cl (made on first use) -> its index, or -1 (out of memory) */
+static int64_t rsz_axis_get(rsz_tables *T, uint32_t cl)
+{
+    for (uint32_t k = 0; k < T->n_ax; k++)
+        if (T->ax[k].cl == cl) return k;
+    if (!grow((void **)&T->ax, &T->cap_ax, T->n_ax, sizeof(rsz_axis))) return -1;
+    const uint32_t L = T->L;
+    int16_t w[RSZ_MAX_TAPS];
+    uint32_t first, mt = 1;
+    for (uint32_t X = 0; X < L; X++) {
+        const uint32_t cnt = debig_png_resize_weights(cl, L, T->aa, X, &first, w, RSZ_MAX_TAPS);
+        if (cnt > mt) mt = cnt;
+    }
+    const uint64_t bytes = (8u + 8u * (uint64_t)L + 2u * (uint64_t)L * mt + 7u) & ~(uint64_t)7u;
+    if (T->len + bytes > T->cap) {
+        uint64_t nc = T->cap ? T->cap : 4096;
+        while (nc < T->len + bytes) nc *= 2;
+        uint8_t *q = (uint8_t *)realloc(T->buf, nc);
+        if (!q) return -1;
+        T->buf = q;
+        T->cap = nc;
+    }
+    uint8_t *base = T->buf + T->len;
+    memset(base, 0, bytes);
+    uint32_t *hdr = (uint32_t *)base;
+    int16_t *wt = (int16_t *)(base + 8u + 8u * (uint64_t)L);
+    hdr[0] = mt;
+    hdr[1] = L;
+    for (uint32_t X = 0; X < L; X++) {
+        hdr[3 + 2 * X] = debig_png_resize_weights(cl, L, T->aa, X, &hdr[2 + 2 * X], wt + (uint64_t)X * mt, mt);
+    }
+    rsz_axis *a = &T->ax[T->n_ax];
+    a->cl = cl;
+    a->max_taps = mt;
+    a->off = T->len;
+    T->len += bytes;
+    return T->n_ax++;
+}
+
+static int rsz_finite(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return (u & 0x7f800000u) != 0x7f800000u;
+}
+
+DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                            const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                            uint32_t flags, const debig_png_tensor_desc *desc)
+{
+    /* the arguments on their own, before any file is looked at */
+    if (n == 0) return 0;
+    if (!desc || !d_out || ((uintptr_t)d_out & 15u)) return DEBIG_PNG_BAD_ARG;
+    const uint32_t fmt = desc->out_format;
+    if ((fmt & ~0x13u) || (fmt & 15u) > DEBIG_PNG_FMT_GRAY_ALPHA || desc->out_layout > DEBIG_PNG_LAYOUT_CHW) return DEBIG_PNG_BAD_FORMAT;
+    if (desc->dtype > DEBIG_PNG_T_BF16 || (desc->resize_flags & ~DEBIG_PNG_RESIZE_ANTIALIAS) || desc->out_w == 0 ||
+        desc->out_w > 16384u || desc->out_h == 0 || desc->out_h > 16384u)
+        return DEBIG_PNG_BAD_ARG;
+    if (desc->dtype != DEBIG_PNG_T_UINT)
+        for (int k = 0; k < 4; k++)
+            if (!rsz_finite(desc->scale[k]) || !rsz_finite(desc->bias[k])) return DEBIG_PNG_BAD_ARG;
+    const uint32_t aa = desc->resize_flags & DEBIG_PNG_RESIZE_ANTIALIAS, W = desc->out_w, H = desc->out_h;
+    const uint32_t ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u, sb = bits / 8u;
+    const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? sb : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
+    const uint64_t slot = (uint64_t)H * W * ch * es;
+
+    uint32_t *pre = (uint32_t *)calloc(n, sizeof(uint32_t));
+    uint64_t *offs = (uint64_t *)calloc(n, sizeof(uint64_t)), *caps = (uint64_t *)calloc(n, sizeof(uint64_t));
+    debig_png_box *box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
+    debig_png_info *inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
+    debig_png_resize_task *tasks = NULL;
+    rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa};
+    int rc = 2;
+    if (!pre || !offs || !caps || !box || !inf) goto done;
+    /* ---- IHDR, the box, the image's place in the context's arena */
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        spec_file f0;
+        memset(&f0, 0, sizeof f0);
+        const uint32_t st = spec_walk(inputs[i], input_sizes[i], &f0, 1);
+        spec_free(&f0);
+        offs[i] = total;
+        const uint64_t iw = f0.info.width, ih = f0.info.height;
+        if (iw == 0) continue; /* no valid IHDR: the walk's status stands */
+        debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
+        if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
+        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih ||
+            (aa && ((uint64_t)b.w > 64u * (uint64_t)W || (uint64_t)b.h > 64u * (uint64_t)H))) {
+            pre[i] = DEBIG_PNG_E_BOX;
+            continue;
+        }
+        box[i] = b;
+        if (st != DEBIG_PNG_OK) continue;
+        const uint64_t sz = fmt_size(iw, ih, fmt);
+        if (sz > RSZ_MAX_IMAGE_BYTES) continue; /* caps[i] stays 0: E_OUTPUT */
+        caps[i] = sz;
+        total += debig_align16(sz) + 16;
+    }
+    {
+        const spec_target tg = {NULL, NULL, offs, total + 64, pre};
+        if ((rc = spec_decode_core(inputs, input_sizes, &tg, caps, status, inf, n, flags, fmt, DEBIG_PNG_LAYOUT_HWC))) goto done;
+    }
+    if (infos) memcpy(infos, inf, (size_t)n * sizeof(debig_png_info));
+    /* ---- the tiles of every decoded image */
+    uint64_t n_tasks = 0;
+    uint32_t cap_tasks = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status[i] != DEBIG_PNG_OK) continue;
+        const int64_t ax = rsz_axis_get(&TX, box[i].w), ay = rsz_axis_get(&TY, box[i].h);
+        if (ax < 0 || ay < 0) { rc = 2; goto done; }
+        const uint32_t mtx = TX.ax[ax].max_taps, mty = TY.ax[ay].max_taps;
+        const uint32_t *ey = (const uint32_t *)(TY.buf + TY.ax[ay].off) + 2;
+        uint32_t tw = W < DEBIG_PNG_RESIZE_TILE_W ? W : DEBIG_PNG_RESIZE_TILE_W;
+        if (tw > DEBIG_PNG_RESIZE_WX_CAP / mtx) tw = DEBIG_PNG_RESIZE_WX_CAP / mtx;
+        if (tw > DEBIG_PNG_RESIZE_HQ_CAP / (mty * ch)) tw = DEBIG_PNG_RESIZE_HQ_CAP / (mty * ch);
+        debig_png_resize_task proto;
+        memset(&proto, 0, sizeof proto);
+        proto.src_off = offs[i] + ((uint64_t)box[i].y * inf[i].width + box[i].x) * ch * sb;
+        proto.out_off = (uint64_t)i * slot;
+        proto.wx_off = TX.ax[ax].off; /* (the vertical tables follow the horizontal ones: fixed up below) */
+        proto.wy_off = TY.ax[ay].off;
+        proto.src_pitch = inf[i].width * ch;
+        proto.out_sx = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? 1u : ch;
+        proto.out_sy = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? W : W * ch;
+        proto.out_sc = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? H * W : 1u;
+        proto.channels = (uint8_t)ch;
+        proto.bits = (uint8_t)bits;
+        proto.dtype = (uint8_t)desc->dtype;
+        for (uint32_t k = 0; k < 4; k++) {
+            proto.a[k] = (float)((double)desc->scale[k] / ((double)((1u << bits) - 1u) * (double)(1u << (30u - bits))));
+            proto.b[k] = desc->bias[k];
+        }
+        for (uint32_t y0 = 0; y0 < H;) {
+            uint32_t lo = ey[2 * y0], hi = ey[2 * y0] + ey[2 * y0 + 1], th = 1;
+            while (y0 + th < H && th < 64u) {
+                const uint32_t f = ey[2 * (y0 + th)], e = f + ey[2 * (y0 + th) + 1];
+                const uint32_t nlo = f < lo ? f : lo, nhi = e > hi ? e : hi;
+                if ((uint64_t)(nhi - nlo) * tw * ch > DEBIG_PNG_RESIZE_HQ_CAP) break;
+                lo = nlo;
+                hi = nhi;
+                th++;
+            }
+            for (uint32_t x0 = 0; x0 < W; x0 += tw) {
+                if (n_tasks >= 0x7fffffffu) { rc = 2; goto done; }
+                if (!grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof(debig_png_resize_task))) { rc = 2; goto done; }
+                debig_png_resize_task *t = &tasks[n_tasks++];
+                *t = proto;
+                t->tile_x = x0;
+                t->tile_y = y0;
+                t->tile_w = W - x0 < tw ? W - x0 : tw;
+                t->tile_h = th;
+                t->src_y0 = lo;
+                t->src_rows = hi - lo;
+            }
+            y0 += th;
+        }
+    }
+    rc = 0;
+    if (n_tasks == 0) goto done;
+    for (uint64_t k = 0; k < n_tasks; k++) tasks[k].wy_off += TX.len;
+    {
+        debig_ctx *c = debig_ctx_get(0);
+        if (!c) { rc = 1; goto done; }
+        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_resize_task))) ||
+            (rc = debig_devbuf_reserve(&c->rsz_weights, TX.len + TY.len)) ||
+            (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, tasks, n_tasks * sizeof(debig_png_resize_task), NULL)) ||
+            (rc = debig_hip_memcpy_h2d(c->rsz_weights.ptr, TX.buf, TX.len, NULL)) ||
+            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + TX.len, TY.buf, TY.len, NULL)) ||
+            (rc = debig_hip_png_resize_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_task *)c->rsz_tasks.ptr,
+                                             c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)) ||
+            (rc = debig_hip_stream_sync(NULL)))
+            goto done;
+    }
+done:
+    free(pre);
+    free(offs);
+    free(caps);
+    free(box);
+    free(inf);
+    free(tasks);
+    free(TX.buf);
+    free(TX.ax);
+    free(TY.buf);
+    free(TY.ax);
+    return rc;
 }

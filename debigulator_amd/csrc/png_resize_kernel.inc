@@ -1,0 +1,144 @@
+// png_resize_kernel.inc -- crop + bilinear / antialiased resize + normalise of decoded PNG pixels into one dense tensor
+// (include/decode_png.h: debig_png_decode_batch_tensor; include/debig_hip.h: debig_hip_png_resize_batch).
+//
+// The arithmetic is fixed by decode_png.h: Q14 integer weights made on the host, a horizontal pass rounded to 16 bits, a
+// vertical pass into 30 bits, then ONE conversion.  Every sum is an integer sum, so no result depends on its order.
+//
+// One TASK is a tile of tile_w x tile_h output pixels of one image; one workgroup of 256 lanes per task:
+//   - the tile's slice of the horizontal weights (and each column's first tap / tap count) is staged in LDS;
+//   - pass 1: item i = (source row r, column x, channel c), c fastest, lanes along i: the lanes of one row read runs of
+//     `channels` adjacent samples that lie scale * channels samples apart and walk right with the tap loop, so the lines
+//     of a source row are fetched from HBM once and re-read from L1; Hq goes to LDS as 16-bit at index i (lanes write
+//     adjacent halfwords);
+//   - pass 2: lanes along the output row -- (x, c) with c fastest when the output's channel stride is 1 (HWC: the lanes'
+//     stores are adjacent elements), else x fastest inside a channel (CHW: a run of tile_w adjacent elements per plane
+//     row); the tap loop walks DOWN the Hq rows, so the lanes of a wavefront read adjacent (HWC) or `channels`-strided
+//     (CHW) halfwords of one LDS row: no column walk, no padding needed;
+//   - the vertical weights are uniform over a row of lanes and come from memory.
+// LDS: 24 KB of Hq + 8 KB of weights + 512 B of column tables = 33,280 B per workgroup.  The host sizes the tile so that
+// it fits; a task that does not is skipped (never indexed out of range).  No cross-workgroup communication, no atomics.
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs inflate_kernel.inc in front of it.
+
+#define RSZ_THREADS 256u
+
+struct RszLds {
+    uint16_t hq[DEBIG_PNG_RESIZE_HQ_CAP];
+    int16_t wx[DEBIG_PNG_RESIZE_WX_CAP];
+    uint32_t fx[DEBIG_PNG_RESIZE_TILE_W], cx[DEBIG_PNG_RESIZE_TILE_W];
+};
+
+// e / ch for ch in 1..4 without a run-time division
+DEV_INLINE uint32_t rsz_div_ch(uint32_t e, uint32_t ch) { return ch == 3u ? e / 3u : e >> (ch >> 1); }
+
+// float32 bits -> float16 bits, round to nearest even (finite values that round past 65504 and infinities -> infinity)
+DEV_INLINE uint32_t rsz_f16_bits(uint32_t x)
+{
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x >= 0x7f800000u) return sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u);
+    if (x >= 0x477ff000u) return sign | 0x7c00u;
+    if (x < 0x38800000u) { // below 2^-14: a float16 subnormal (units of 2^-24) or zero
+        const uint32_t sh = 126u - (x >> 23);
+        if (sh > 25u) return sign;
+        const uint32_t m = (x & 0x7fffffu) | 0x800000u, half = 1u << (sh - 1u), rem = m & ((1u << sh) - 1u);
+        uint32_t r = m >> sh;
+        if (rem > half || (rem == half && (r & 1u))) r++;
+        return sign | r;
+    }
+    uint32_t r = (x - 0x38000000u) >> 13;
+    const uint32_t rem = x & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (r & 1u))) r++;
+    return sign | r;
+}
+
+// (float)v * a + b as two separately rounded operations (never one fused multiply-add), as float32 bits
+DEV_INLINE uint32_t rsz_affine_bits(uint32_t v, float a, float b)
+{
+#ifndef DEBIG_EMU
+#pragma clang fp contract(off)
+#endif
+    const float m = (float)v * a;
+    const float f = m + b;
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    return u;
+}
+
+__global__ void __launch_bounds__(RSZ_THREADS)
+debig_png_resize_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                        const debig_png_resize_task *__restrict__ tasks, const uint8_t *__restrict__ weights,
+                        uint32_t n_tasks)
+{
+    __shared__ RszLds lds;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
+        const debig_png_resize_task t = tasks[ti];
+        const uint32_t *tx = reinterpret_cast<const uint32_t *>(weights + t.wx_off);
+        const uint32_t *ty = reinterpret_cast<const uint32_t *>(weights + t.wy_off);
+        const uint32_t mtx = tx[0], mty = ty[0], ch = t.channels, twc = t.tile_w * ch;
+        const int16_t *wxg = reinterpret_cast<const int16_t *>(tx + 2u + 2u * tx[1]);
+        const int16_t *wyg = reinterpret_cast<const int16_t *>(ty + 2u + 2u * ty[1]);
+        // (uniform over the workgroup: every lane skips, or none)
+        if (t.tile_w == 0u || t.tile_w > DEBIG_PNG_RESIZE_TILE_W || ch == 0u || ch > 4u ||
+            (uint64_t)t.tile_w * mtx > DEBIG_PNG_RESIZE_WX_CAP || (uint64_t)t.src_rows * twc > DEBIG_PNG_RESIZE_HQ_CAP)
+            continue;
+        __syncthreads(); // the previous task's pass 2 has read its LDS
+        if (tid < t.tile_w) {
+            lds.fx[tid] = tx[2u + 2u * (t.tile_x + tid)];
+            lds.cx[tid] = tx[3u + 2u * (t.tile_x + tid)];
+        }
+        for (uint32_t i = tid; i < t.tile_w * mtx; i += RSZ_THREADS) lds.wx[i] = wxg[(uint64_t)t.tile_x * mtx + i];
+        __syncthreads();
+        // ---- pass 1: Hq[r][x][c] = (sum_k wx[x][k] * s[r][fx[x] + k][c] + 2^(P-3)) >> (P-2)
+        const uint32_t n1 = t.src_rows * twc, sh1 = (uint32_t)t.bits - 2u, rnd1 = 1u << ((uint32_t)t.bits - 3u);
+        {
+            uint32_t r = tid / twc, e = tid - r * twc;
+            const uint32_t dr = RSZ_THREADS / twc, de = RSZ_THREADS - dr * twc;
+            for (uint32_t i = tid; i < n1; i += RSZ_THREADS) {
+                const uint32_t x = rsz_div_ch(e, ch), c = e - x * ch, cnt = lds.cx[x];
+                const uint64_t s0 = (uint64_t)(t.src_y0 + r) * t.src_pitch + (uint64_t)lds.fx[x] * ch + c;
+                const int16_t *w = &lds.wx[x * mtx];
+                uint32_t acc = 0u;
+                if (t.bits == 8u) {
+                    const uint8_t *p = src + t.src_off + s0;
+                    for (uint32_t k = 0; k < cnt; k++) acc += (uint32_t)w[k] * p[(uint64_t)k * ch];
+                } else {
+                    const uint16_t *p = reinterpret_cast<const uint16_t *>(src + t.src_off) + s0;
+                    for (uint32_t k = 0; k < cnt; k++) acc += (uint32_t)w[k] * p[(uint64_t)k * ch];
+                }
+                lds.hq[i] = (uint16_t)((acc + rnd1) >> sh1);
+                r += dr;
+                e += de;
+                if (e >= twc) { e -= twc; r++; }
+            }
+        }
+        __syncthreads();
+        // ---- pass 2: v = sum_k wy[Y][k] * Hq[fy[Y] + k][x][c], then the one conversion
+        const uint32_t n2 = t.tile_h * twc, planar = t.out_sc != 1u;
+        for (uint32_t i = tid; i < n2; i += RSZ_THREADS) {
+            const uint32_t yy = i / twc, e = i - yy * twc;
+            uint32_t x, c;
+            if (planar) { c = e / t.tile_w; x = e - c * t.tile_w; }
+            else { x = rsz_div_ch(e, ch); c = e - x * ch; }
+            const uint32_t Y = t.tile_y + yy, fy = ty[2u + 2u * Y], cnt = ty[3u + 2u * Y];
+            const int16_t *w = wyg + (uint64_t)Y * mty;
+            const uint16_t *h = &lds.hq[(fy - t.src_y0) * twc + x * ch + c];
+            uint32_t v = 0u;
+            for (uint32_t k = 0; k < cnt; k++) v += (uint32_t)w[k] * h[k * twc];
+            const uint64_t el = (uint64_t)(t.tile_x + x) * t.out_sx + (uint64_t)Y * t.out_sy + (uint64_t)c * t.out_sc;
+            uint8_t *o = out + t.out_off;
+            if (t.dtype == 0u) { // DEBIG_PNG_T_UINT
+                if (t.bits == 8u) o[el] = (uint8_t)((v + (1u << 21)) >> 22);
+                else reinterpret_cast<uint16_t *>(o)[el] = (uint16_t)((v + (1u << 13)) >> 14);
+            } else {
+                // a[] / b[] by a select chain: a run-time index into the by-value task struct would go through scratch
+                const float a = c == 0u ? t.a[0] : c == 1u ? t.a[1] : c == 2u ? t.a[2] : t.a[3];
+                const float b = c == 0u ? t.b[0] : c == 1u ? t.b[1] : c == 2u ? t.b[2] : t.b[3];
+                const uint32_t u = rsz_affine_bits(v, a, b);
+                if (t.dtype == 1u) reinterpret_cast<uint32_t *>(o)[el] = u;                                  // F32
+                else if (t.dtype == 2u) reinterpret_cast<uint16_t *>(o)[el] = (uint16_t)rsz_f16_bits(u);      // F16
+                else reinterpret_cast<uint16_t *>(o)[el] = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); // BF16
+            }
+        }
+    }
+}

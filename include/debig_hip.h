@@ -365,6 +365,35 @@ typedef struct debig_apng_task {
 int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena, const debig_apng_task *d_tasks,
                                    uint32_t n_tasks, void *hip_stream);
 
+/* Resize + normalise (csrc/png_resize_kernel.inc, behind debig_png_decode_batch_tensor in decode_png.h).  One task: a tile
+ * of tile_w x tile_h output pixels (all channels) of one image, one workgroup.  The tile is chosen on the host so that
+ * the horizontally filtered rows it needs (src_rows rows of tile_w * channels 16-bit values) fit DEBIG_PNG_RESIZE_HQ_CAP
+ * and its slice of the horizontal weights fits DEBIG_PNG_RESIZE_WX_CAP; a task that breaks a bound is skipped. */
+typedef struct debig_png_resize_task {
+    uint64_t src_off;       /* sample (0, 0) of the CROP, in bytes rel. to d_src_arena (aligned to the sample size)         */
+    uint64_t out_off;       /* the image's slot, in bytes rel. to d_out (aligned to the element size)                       */
+    uint64_t wx_off, wy_off; /* the axis tables of the crop's width / height, in bytes rel. to d_weights (8-byte aligned)    */
+    uint32_t src_pitch;     /* samples from one source row to the next                                                       */
+    uint32_t tile_x, tile_y, tile_w, tile_h; /* output pixels; tile_w <= DEBIG_PNG_RESIZE_TILE_W                              */
+    uint32_t src_y0, src_rows; /* crop rows [src_y0, src_y0 + src_rows) hold every vertical tap of the tile's rows          */
+    uint32_t out_sx, out_sy, out_sc; /* output strides of x, y and the channel, in ELEMENTS (HWC: C, W*C, 1; CHW: 1, W, H*W) */
+    uint8_t channels;       /* 1..4, interleaved in the source                                                               */
+    uint8_t bits;           /* P: 8 (uint8 samples) or 16 (uint16, little-endian)                                            */
+    uint8_t dtype;          /* decode_png.h DEBIG_PNG_T_*: UINT (uint8 for P = 8, uint16 for P = 16), F32, F16, BF16          */
+    uint8_t reserved;
+    float a[4], b[4];       /* float dtypes: element = (float)v * a[c] + b[c], two rounded operations (decode_png.h)         */
+} debig_png_resize_task;
+/* An axis table (crop length cl -> L outputs): uint32 max_taps, L; then L pairs of uint32 (first tap, tap count); then
+ * L * max_taps int16 Q14 weights, output X's at X * max_taps.  Built on the host by the integer rule of decode_png.h. */
+#define DEBIG_PNG_RESIZE_TILE_W 64u
+#define DEBIG_PNG_RESIZE_HQ_CAP 12288u /* 16-bit values of one tile's horizontally filtered rows (24 KB of LDS) */
+#define DEBIG_PNG_RESIZE_WX_CAP 4096u  /* int16 weights of one tile's columns (8 KB of LDS) */
+
+/* Resize n_tasks tiles (device pointers, asynchronous on hip_stream): pass 1 filters the tile's source rows horizontally
+ * into LDS, pass 2 filters them vertically, converts and stores.  Nothing but the tiles' own output elements is written. */
+int debig_hip_png_resize_batch(const void *d_src_arena, void *d_out, const debig_png_resize_task *d_tasks,
+                               const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

@@ -202,6 +202,59 @@ int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *inp
                                debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags, uint32_t out_format,
                                uint32_t out_layout);
 
+/* ---- one resized, normalised tensor for the whole batch -------------------------------------------------------------------
+ * debig_png_decode_batch_tensor: bytes of n PNG files in, one dense tensor of n images of out_h x out_w pixels in device
+ * memory out.  Image i occupies slot = out_h * out_w * channels * sizeof(element) bytes at (uint8_t *)d_out + i * slot, laid out
+ * HWC (y, x, c) or CHW (c, y, x) without padding.  The pixels are decoded (steps 1 - 3 above, out_format concrete: no NATIVE
+ * layout or depth) into an arena of the library's own on the device, then ONE launch crops, resizes and converts all images
+ * (debig_hip_png_resize_batch); the call returns after the work has finished.  Nothing crosses the bus but the files, the task
+ * and weight tables, statuses and checksum words.
+ *
+ * The arithmetic is integer up to the final conversion, so that no result depends on a summation order.  P is the source
+ * precision (8 or 16: the depth of out_format), the crop is boxes[i] (w == 0 && h == 0, or boxes NULL: the whole image).
+ * Weights of one axis (crop length cl, output length L, output coordinate X; Q14: >= 0, their sum exactly 16384):
+ *   - interpolating (antialias off, or cl <= L): num = clamp((2X + 1) cl - L, 0, (cl - 1) 2L), i0 = num div 2L, r = num mod 2L,
+ *     w1 = (r * 16384 + L) div 2L; taps {i0: 16384 - w1, i0 + 1: w1}, or the single tap {cl - 1: 16384} when i0 == cl - 1
+ *     (half-pixel centres; the edges clamp inside the CROP, not the image);
+ *   - antialiased (DEBIG_PNG_RESIZE_ANTIALIAS and cl > L; a triangle filter as wide as the scale): c = (2X + 1) cl; for source
+ *     index j in [0, cl): n_j = 2 cl - |(2j + 1) L - c|; the taps are the j with n_j > 0; T = sum n_j,
+ *     w_j = (n_j * 16384 + T div 2) div T; then 16384 - sum w_j is added to the tap with the largest n_j (the lowest such j).
+ * Two passes, horizontal first:  h = sum wx_k s_k;  Hq = (h + (1 << (P - 3))) >> (P - 2)  (< 2^16);  v = sum wy_k Hq_k  (< 2^30),
+ * the sample times 2^(30 - P).  The element of channel c:
+ *   - DEBIG_PNG_T_UINT (uint8 for P = 8, uint16 for P = 16):  (v + (1 << (29 - P))) >> (30 - P);
+ *   - DEBIG_PNG_T_F32:  (float)v, times A_c, plus B_c -- each step rounded to nearest even on its own, never a fused
+ *     multiply-add -- with A_c = (float)((double)scale[c] / ((2^P - 1) * 2^(30 - P))) and B_c = bias[c]: sample01 * scale + bias;
+ *   - DEBIG_PNG_T_F16 / _BF16:  that float32 converted with round to nearest even.
+ * With out_w == w and out_h == h the UINT output is the cropped decode exactly, antialias on or off.  Alpha is resized like
+ * any other channel: there is NO premultiplication.
+ * Checked first, before any file is looked at (status unwritten): an out_format with a NATIVE layout or depth or an unknown
+ * out_layout -> DEBIG_PNG_BAD_FORMAT; desc or d_out NULL with n > 0, d_out not 16-byte aligned, an unknown dtype or
+ * resize_flags bit, out_w or out_h 0 or above 16384, a non-finite scale / bias with a float dtype -> DEBIG_PNG_BAD_ARG.
+ * Per image: the statuses of debig_png_decode_batch_fmt in their order, and DEBIG_PNG_E_BOX, decided as soon as IHDR has been
+ * read (it outranks every status found later in the file): a box with exactly one of w, h zero, a box that leaves the image
+ * (64-bit sums), or antialias with cl > 64 L on either axis (that bounds the taps at 129 and keeps the corrected weight
+ * positive).  E_OUTPUT: the decoded image is larger than 2^31 bytes.  A file with any non-zero status leaves its slot
+ * untouched; nothing outside d_out[0 .. n * slot) is written.
+ * Not provided: other filters (bicubic, nearest), flips, colour jitter, animated PNGs, inputs already on the device, an
+ * asynchronous variant. */
+typedef struct debig_png_box { uint32_t x, y, w, h; } debig_png_box; /* w == 0 && h == 0: the whole image */
+enum { DEBIG_PNG_T_UINT = 0, DEBIG_PNG_T_F32 = 1, DEBIG_PNG_T_F16 = 2, DEBIG_PNG_T_BF16 = 3 };
+#define DEBIG_PNG_RESIZE_ANTIALIAS 1u
+#define DEBIG_PNG_E_BOX 14 /* the crop box (rules above) */
+typedef struct debig_png_tensor_desc {
+    uint32_t out_w, out_h, out_format /* concrete: no NATIVE layout or depth */, out_layout /* DEBIG_PNG_LAYOUT_HWC | _CHW */;
+    uint32_t dtype, resize_flags;
+    float scale[4], bias[4]; /* float dtypes only */
+} debig_png_tensor_desc;
+int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                  const debig_png_box *boxes /* may be NULL */, uint32_t *status,
+                                  debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                  const debig_png_tensor_desc *desc);
+/* Host only: the taps of output coordinate X by the rule above -> their number (0: cl or L zero, L > 16384, X >= L, more
+ * than w_cap taps, or antialias with cl > 64 L); *first = the first tap's source index, w[0 .. count) the Q14 weights. */
+uint32_t debig_png_resize_weights(uint32_t cl, uint32_t L, uint32_t antialias, uint32_t X, uint32_t *first, int16_t *w,
+                                  uint32_t w_cap);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

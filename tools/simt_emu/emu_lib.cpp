@@ -16,6 +16,7 @@
 #include "../../debigulator_amd/csrc/png_fused_kernel.inc"
 #include "../../debigulator_amd/csrc/png_spec_kernel.inc"
 #include "../../debigulator_amd/csrc/apng_kernel.inc"
+#include "../../debigulator_amd/csrc/png_resize_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -327,5 +328,16 @@ extern "C" int emu_apng_composite_batch(const void *frames_arena, void *out_aren
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_apng_composite_kernel, grid, APNG_THREADS, (const uint8_t *)frames_arena, (uint8_t *)out_arena, tasks, n);
+    return 0;
+}
+
+/* resize + normalise (png_resize_kernel.inc) as debig_hip_png_resize_batch launches it (grid: 0 = one workgroup per task,
+ * else fewer workgroups that loop over the tasks) */
+extern "C" int emu_png_resize_batch(const void *src_arena, void *out, const debig_png_resize_task *tasks, const void *weights,
+                                    uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_resize_kernel, grid, RSZ_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)weights, n);
     return 0;
 }
