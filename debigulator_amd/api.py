@@ -435,8 +435,51 @@ def png_tensor_desc(size, mode="rgb", depth=8, dtype="float32", layout="chw", me
     return d, ch, (depth // 8 if dtype == "uint" else 4 if dtype == "float32" else 2)
 
 
+class PngAlphaDesc(C.Structure):  # include/decode_png.h: debig_png_alpha_desc
+    _fields_ = [("mode", C.c_uint32), ("background", C.c_uint16 * 4), ("reserved", C.c_uint32)]
+
+
+PNG_ALPHA_MODES = {"straight": 0, "premultiplied": 1, "over": 2}  # include/decode_png.h: DEBIG_PNG_ALPHA_*
+
+
+def png_alpha_desc(alpha="straight", background=None, mode="rgb", depth=8):
+    """the debig_png_alpha_desc of png_decode_batch_tensor's alpha / background arguments (no GPU needed), or None for
+    alpha="straight".  "over" needs mode "rgb" or "gray" (the tensor's channels) and composites over `background`: one value
+    per output channel on the [0, 1] scale (a number: every channel; None: 1.0, white), stored as round(x * (2^depth - 1));
+    "premultiplied" needs mode "rgba" or "gray_alpha"."""
+    if alpha not in PNG_ALPHA_MODES:
+        raise ValueError(f"alpha must be one of {sorted(PNG_ALPHA_MODES)}, not {alpha!r}")
+    if alpha == "straight":
+        if background is not None:
+            raise ValueError("background needs alpha='over'")
+        return None
+    if depth not in (8, 16):
+        raise ValueError("alpha needs a concrete depth (8 or 16)")
+    d = PngAlphaDesc(mode=PNG_ALPHA_MODES[alpha])
+    if alpha == "premultiplied":
+        if mode not in ("rgba", "gray_alpha"):
+            raise ValueError(f"alpha='premultiplied' needs mode 'rgba' or 'gray_alpha', not {mode!r}")
+        if background is not None:
+            raise ValueError("background needs alpha='over'")
+        return d
+    if mode not in ("rgb", "gray"):
+        raise ValueError(f"alpha='over' needs mode 'rgb' or 'gray' (the channels of the tensor), not {mode!r}")
+    ch = 3 if mode == "rgb" else 1
+    if background is None:
+        background = 1.0
+    bg = [float(x) for x in (background if hasattr(background, "__len__") else [background] * ch)]
+    if len(bg) != ch:
+        raise ValueError(f"background needs {ch} values for mode {mode!r}, not {len(bg)}")
+    if not all(0.0 <= x <= 1.0 for x in bg):  # (a NaN fails every comparison)
+        raise ValueError(f"background values must lie in [0, 1], not {bg!r}")
+    for k, x in enumerate(bg):
+        d.background[k] = int(round(x * ((1 << depth) - 1)))
+    return d
+
+
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
-                            antialias=True, device="cuda:0", fill=None, force_general=False):
+                            antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
+                            background=None):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
     (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
@@ -445,13 +488,20 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     image.  The resize is bilinear with half-pixel centres, antialiased when it shrinks (what
     torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=True) means, in Q14 integer weights).
     The slot of a file whose status is not 0 is left as allocated, or holds `fill` when that is given.  Same device rule
-    as png_decode_batch_device."""
+    as png_decode_batch_device.
+    alpha: "straight" (the default: alpha is dropped or resized like a colour channel, no premultiplication), "over"
+    (mode "rgb" / "gray": the file's alpha composites the pixels over `background`, per output channel on the [0, 1]
+    scale, default white, inside the resize launch) or "premultiplied" (mode "rgba" / "gray_alpha": premultiplied colour
+    and plain alpha, filtered in premultiplied space) -- debig_png_decode_batch_tensor_alpha, see png_alpha_desc."""
     import torch
 
     d, ch, es = png_tensor_desc(size, mode, depth, dtype, layout, mean, std, antialias)
+    ad = png_alpha_desc(alpha, background, mode, depth)
     L = _png_spec_lib()
     L.debig_png_decode_batch_tensor.restype = C.c_int
     L.debig_png_decode_batch_tensor.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
+    L.debig_png_decode_batch_tensor_alpha.restype = C.c_int
+    L.debig_png_decode_batch_tensor_alpha.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError(f"device must be a GPU, not {device!r}")
@@ -483,8 +533,12 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
         bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
     status = (C.c_uint32 * n)()
     infos = (PngInfo * n)()
-    rc = L.debig_png_decode_batch_tensor(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n,
-                                         PNG_FORCE_GENERAL if force_general else 0, C.byref(d))
+    if ad is None:
+        rc = L.debig_png_decode_batch_tensor(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n,
+                                             PNG_FORCE_GENERAL if force_general else 0, C.byref(d))
+    else:
+        rc = L.debig_png_decode_batch_tensor_alpha(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n,
+                                                   PNG_FORCE_GENERAL if force_general else 0, C.byref(d), C.byref(ad))
     if rc in (PNG_BAD_FORMAT, PNG_BAD_ARG):
         raise ValueError(f"debig_png_decode_batch_tensor rejected its arguments ({rc})")
     N.check(rc, "debig_png_decode_batch_tensor")

@@ -766,12 +766,9 @@ static int rsz_finite(float f)
     return (u & 0x7f800000u) != 0x7f800000u;
 }
 
-DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                            const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n,
-                                            uint32_t flags, const debig_png_tensor_desc *desc)
+/* the argument checks of debig_png_decode_batch_tensor (n > 0): 0, DEBIG_PNG_BAD_FORMAT or DEBIG_PNG_BAD_ARG */
+static int tensor_args_check(const void *d_out, const debig_png_tensor_desc *desc)
 {
-    /* the arguments on their own, before any file is looked at */
-    if (n == 0) return 0;
     if (!desc || !d_out || ((uintptr_t)d_out & 15u)) return DEBIG_PNG_BAD_ARG;
     const uint32_t fmt = desc->out_format;
     if ((fmt & ~0x13u) || (fmt & 15u) > DEBIG_PNG_FMT_GRAY_ALPHA || desc->out_layout > DEBIG_PNG_LAYOUT_CHW) return DEBIG_PNG_BAD_FORMAT;
@@ -781,16 +778,38 @@ DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const 
     if (desc->dtype != DEBIG_PNG_T_UINT)
         for (int k = 0; k < 4; k++)
             if (!rsz_finite(desc->scale[k]) || !rsz_finite(desc->bias[k])) return DEBIG_PNG_BAD_ARG;
+    return 0;
+}
+
+#define RSZ_TASK_FIELDS (offsetof(debig_png_resize_task, b) + sizeof(((debig_png_resize_task *)0)->b)) /* without tail padding */
+_Static_assert(offsetof(debig_png_resize_alpha_task, mode) == RSZ_TASK_FIELDS &&
+                   offsetof(debig_png_resize_alpha_task, b) == offsetof(debig_png_resize_task, b) &&
+                   sizeof(debig_png_resize_alpha_task) == 128,
+               "debig_png_resize_alpha_task starts with the fields of debig_png_resize_task");
+
+/* debig_png_decode_batch_tensor (amode == DEBIG_PNG_ALPHA_STRAIGHT: bg unused) and debig_png_decode_batch_tensor_alpha behind
+ * their argument checks.  With alpha the pixels are decoded WITH their alpha (dfmt: 4 or 2 channels) and the tiles go to the
+ * alpha kernel, which writes the channels of desc->out_format. */
+static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
+                       uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                       uint32_t amode, const uint16_t *bg)
+{
+    /* fmt: the format decoded into the arena (ch channels); oc: the channels of the tensor */
+    uint32_t fmt = desc->out_format;
+    const uint32_t oc = fmt_channels(fmt);
+    if (amode == DEBIG_PNG_ALPHA_OVER)
+        fmt = (fmt & ~15u) | ((fmt & 15u) == DEBIG_PNG_FMT_RGB ? DEBIG_PNG_FMT_RGBA : DEBIG_PNG_FMT_GRAY_ALPHA);
     const uint32_t aa = desc->resize_flags & DEBIG_PNG_RESIZE_ANTIALIAS, W = desc->out_w, H = desc->out_h;
     const uint32_t ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u, sb = bits / 8u;
     const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? sb : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
-    const uint64_t slot = (uint64_t)H * W * ch * es;
+    const uint64_t slot = (uint64_t)H * W * oc * es;
 
     uint32_t *pre = (uint32_t *)calloc(n, sizeof(uint32_t));
     uint64_t *offs = (uint64_t *)calloc(n, sizeof(uint64_t)), *caps = (uint64_t *)calloc(n, sizeof(uint64_t));
     debig_png_box *box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
     debig_png_info *inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
     debig_png_resize_task *tasks = NULL;
+    debig_png_resize_alpha_task *atasks = NULL;
     rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa};
     int rc = 2;
     if (!pre || !offs || !caps || !box || !inf) goto done;
@@ -842,8 +861,8 @@ DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const 
         proto.wx_off = TX.ax[ax].off; /* (the vertical tables follow the horizontal ones: fixed up below) */
         proto.wy_off = TY.ax[ay].off;
         proto.src_pitch = inf[i].width * ch;
-        proto.out_sx = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? 1u : ch;
-        proto.out_sy = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? W : W * ch;
+        proto.out_sx = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? 1u : oc;
+        proto.out_sy = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? W : W * oc;
         proto.out_sc = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? H * W : 1u;
         proto.channels = (uint8_t)ch;
         proto.bits = (uint8_t)bits;
@@ -880,7 +899,31 @@ DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const 
     rc = 0;
     if (n_tasks == 0) goto done;
     for (uint64_t k = 0; k < n_tasks; k++) tasks[k].wy_off += TX.len;
-    {
+    if (amode != DEBIG_PNG_ALPHA_STRAIGHT) {
+        /* the alpha kernel's task: the plain one (channels: the source's) + mode, channel counts, background */
+        atasks = (debig_png_resize_alpha_task *)calloc(n_tasks, sizeof(debig_png_resize_alpha_task));
+        if (!atasks) { rc = 2; goto done; }
+        for (uint64_t k = 0; k < n_tasks; k++) {
+            debig_png_resize_alpha_task *t = &atasks[k];
+            memcpy(t, &tasks[k], RSZ_TASK_FIELDS);
+            t->mode = amode;
+            t->src_channels = (uint8_t)ch;
+            t->out_channels = (uint8_t)oc;
+            if (amode == DEBIG_PNG_ALPHA_OVER)
+                for (uint32_t j = 0; j < oc; j++) t->bg[j] = bg[j];
+        }
+        debig_ctx *c = debig_ctx_get(0);
+        if (!c) { rc = 1; goto done; }
+        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_resize_alpha_task))) ||
+            (rc = debig_devbuf_reserve(&c->rsz_weights, TX.len + TY.len)) ||
+            (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, atasks, n_tasks * sizeof(debig_png_resize_alpha_task), NULL)) ||
+            (rc = debig_hip_memcpy_h2d(c->rsz_weights.ptr, TX.buf, TX.len, NULL)) ||
+            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + TX.len, TY.buf, TY.len, NULL)) ||
+            (rc = debig_hip_png_resize_alpha_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_alpha_task *)c->rsz_tasks.ptr,
+                                                   c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)) ||
+            (rc = debig_hip_stream_sync(NULL)))
+            goto done;
+    } else {
         debig_ctx *c = debig_ctx_get(0);
         if (!c) { rc = 1; goto done; }
         if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_resize_task))) ||
@@ -900,9 +943,45 @@ done:
     free(box);
     free(inf);
     free(tasks);
+    free(atasks);
     free(TX.buf);
     free(TX.ax);
     free(TY.buf);
     free(TY.ax);
     return rc;
+}
+
+DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                            const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                            uint32_t flags, const debig_png_tensor_desc *desc)
+{
+    /* the arguments on their own, before any file is looked at */
+    if (n == 0) return 0;
+    const int bad = tensor_args_check(d_out, desc);
+    if (bad) return bad;
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL);
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                  const debig_png_box *boxes, uint32_t *status, debig_png_info *infos,
+                                                  uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                                                  const debig_png_alpha_desc *alpha)
+{
+    /* the checks of debig_png_decode_batch_tensor first and unchanged, then alpha's; all before any file is looked at */
+    if (n == 0) return 0;
+    const int bad = tensor_args_check(d_out, desc);
+    if (bad) return bad;
+    uint32_t amode = DEBIG_PNG_ALPHA_STRAIGHT;
+    if (alpha) {
+        const uint32_t lay = desc->out_format & 15u, bits = desc->out_format & DEBIG_PNG_FMT_16 ? 16u : 8u;
+        amode = alpha->mode;
+        if (amode > DEBIG_PNG_ALPHA_OVER || alpha->reserved != 0) return DEBIG_PNG_BAD_ARG;
+        if (amode == DEBIG_PNG_ALPHA_PREMULTIPLIED && lay != DEBIG_PNG_FMT_RGBA && lay != DEBIG_PNG_FMT_GRAY_ALPHA) return DEBIG_PNG_BAD_ARG;
+        if (amode == DEBIG_PNG_ALPHA_OVER) {
+            if (lay != DEBIG_PNG_FMT_RGB && lay != DEBIG_PNG_FMT_GRAY) return DEBIG_PNG_BAD_ARG;
+            for (uint32_t k = 0; k < fmt_channels(desc->out_format); k++)
+                if (alpha->background[k] > (1u << bits) - 1u) return DEBIG_PNG_BAD_ARG;
+        }
+    }
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL);
 }

@@ -142,3 +142,159 @@ debig_png_resize_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ o
         }
     }
 }
+
+// ---- the same with alpha: premultiply in pass 1, filter premultiplied, composite over a background in pass 2 -----------------
+// (include/decode_png.h: debig_png_decode_batch_tensor_alpha; include/debig_hip.h: debig_hip_png_resize_alpha_batch).
+// The source is RGBA or GRAY_ALPHA (SC = 4 or 2 interleaved samples, alpha last).  The tile, the weight tables and the LDS
+// are those of the kernel above; what differs is the unit of work, a PIXEL instead of a sample:
+//   - pass 1: item i = (source row r, column x), lanes along i; a tap loads the whole pixel with one naturally aligned load
+//     (b16 GA8, b32 RGBA8 / GA16, b64 RGBA16), premultiplies p_c = (s_c * alpha + (M >> 1)) div M in registers (a division
+//     by a constant: a multiply and a shift) and adds into SC sums; the pixel's SC Hq halfwords go to LDS as one b32 / b64 at
+//     index i * SC;
+//   - pass 2: item = output pixel (yy, x), lanes along x; a tap reads the pixel's SC halfwords as one b32 / b64; OVER forms
+//     v'_c = v_c + (bg_c * (Vmax - v_alpha) + (M >> 1)) div M with the 32-bit identity of the header (t = q M + r) and
+//     stores SC - 1 channels, PREMULTIPLIED stores all SC; a wavefront writes a run of adjacent elements per plane row (CHW)
+//     or adjacent pixels of out_channels elements (HWC).
+// No scratch (every per-channel array is indexed by unrolled constants), no atomics, nothing shared between workgroups.
+
+#ifdef DEBIG_EMU
+#define RSZ_UNROLL
+#else
+#define RSZ_UNROLL _Pragma("unroll")
+#endif
+#define RSZ_ALPHA_PREMULTIPLIED 1u // decode_png.h: DEBIG_PNG_ALPHA_PREMULTIPLIED
+#define RSZ_ALPHA_OVER 2u          // decode_png.h: DEBIG_PNG_ALPHA_OVER
+
+template <uint32_t P, uint32_t SC> struct RszPixel;
+template <> struct RszPixel<8u, 2u> { typedef uint16_t load_t; };
+template <> struct RszPixel<8u, 4u> { typedef uint32_t load_t; };
+template <> struct RszPixel<16u, 2u> { typedef uint32_t load_t; };
+template <> struct RszPixel<16u, 4u> { typedef uint64_t load_t; };
+template <uint32_t SC> struct RszHqWord;
+template <> struct RszHqWord<2u> { typedef uint32_t word_t; };
+template <> struct RszHqWord<4u> { typedef uint64_t word_t; };
+
+// one element of output channel c (a compile-time constant at every call: the selects fold away)
+DEV_INLINE void rsz_alpha_store(const debig_png_resize_alpha_task &t, uint8_t *o, uint64_t el, uint32_t v, uint32_t c)
+{
+    if (t.dtype == 0u) { // DEBIG_PNG_T_UINT
+        if (t.bits == 8u) o[el] = (uint8_t)((v + (1u << 21)) >> 22);
+        else reinterpret_cast<uint16_t *>(o)[el] = (uint16_t)((v + (1u << 13)) >> 14);
+    } else {
+        const float a = c == 0u ? t.a[0] : c == 1u ? t.a[1] : c == 2u ? t.a[2] : t.a[3];
+        const float b = c == 0u ? t.b[0] : c == 1u ? t.b[1] : c == 2u ? t.b[2] : t.b[3];
+        const uint32_t u = rsz_affine_bits(v, a, b);
+        if (t.dtype == 1u) reinterpret_cast<uint32_t *>(o)[el] = u;                                  // F32
+        else if (t.dtype == 2u) reinterpret_cast<uint16_t *>(o)[el] = (uint16_t)rsz_f16_bits(u);      // F16
+        else reinterpret_cast<uint16_t *>(o)[el] = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); // BF16
+    }
+}
+
+// the two passes of one tile for source precision P and SC source channels; the weights of the tile are in LDS already
+template <uint32_t P, uint32_t SC>
+DEV_INLINE void rsz_alpha_tile(RszLds &lds, const debig_png_resize_alpha_task &t, const uint8_t *__restrict__ src,
+                               uint8_t *__restrict__ out, const uint32_t *ty, const int16_t *wyg, uint32_t mtx, uint32_t mty,
+                               uint32_t tid)
+{
+    typedef typename RszPixel<P, SC>::load_t load_t;
+    typedef typename RszHqWord<SC>::word_t word_t;
+    constexpr uint32_t M = (1u << P) - 1u, HALF = M >> 1, S = 30u - P, VMAX = M << S;
+    const uint32_t tw = t.tile_w;
+    word_t *hqw = reinterpret_cast<word_t *>(lds.hq);
+    // ---- pass 1: Hq[r][x][c] = (sum_k wx[x][k] * p[r][fx[x] + k][c] + 2^(P-3)) >> (P-2), p premultiplied
+    {
+        const uint32_t n1 = t.src_rows * tw;
+        uint32_t r = tid / tw, x = tid - r * tw;
+        const uint32_t dr = RSZ_THREADS / tw, dx = RSZ_THREADS - dr * tw;
+        for (uint32_t i = tid; i < n1; i += RSZ_THREADS) {
+            const uint32_t cnt = lds.cx[x];
+            const int16_t *w = &lds.wx[x * mtx];
+            const load_t *p = reinterpret_cast<const load_t *>(src + t.src_off + (uint64_t)(t.src_y0 + r) * t.src_pitch * (P / 8u)) + lds.fx[x];
+            uint32_t acc[SC];
+RSZ_UNROLL
+            for (uint32_t c = 0; c < SC; c++) acc[c] = 0u;
+            for (uint32_t k = 0; k < cnt; k++) {
+                const load_t px = p[k];
+                const uint32_t wk = (uint32_t)w[k], al = (uint32_t)(px >> ((SC - 1u) * P)) & M;
+RSZ_UNROLL
+                for (uint32_t c = 0; c + 1u < SC; c++) acc[c] += wk * ((((uint32_t)(px >> (c * P)) & M) * al + HALF) / M);
+                acc[SC - 1u] += wk * al;
+            }
+            word_t h = 0;
+RSZ_UNROLL
+            for (uint32_t c = 0; c < SC; c++) h |= (word_t)((acc[c] + (1u << (P - 3u))) >> (P - 2u)) << (16u * c);
+            hqw[i] = h;
+            r += dr;
+            x += dx;
+            if (x >= tw) { x -= tw; r++; }
+        }
+    }
+    __syncthreads();
+    // ---- pass 2: v_c = sum_k wy[Y][k] * Hq[fy[Y] + k][x][c]; OVER adds the background's share; the one conversion
+    const uint32_t n2 = t.tile_h * tw, over = t.mode == RSZ_ALPHA_OVER;
+    for (uint32_t i = tid; i < n2; i += RSZ_THREADS) {
+        const uint32_t yy = i / tw, x = i - yy * tw;
+        const uint32_t Y = t.tile_y + yy, fy = ty[2u + 2u * Y], cnt = ty[3u + 2u * Y];
+        const int16_t *w = wyg + (uint64_t)Y * mty;
+        const word_t *h = &hqw[(fy - t.src_y0) * tw + x];
+        uint32_t v[SC];
+RSZ_UNROLL
+        for (uint32_t c = 0; c < SC; c++) v[c] = 0u;
+        for (uint32_t k = 0; k < cnt; k++) {
+            const word_t hk = h[k * tw];
+            const uint32_t wk = (uint32_t)w[k];
+RSZ_UNROLL
+            for (uint32_t c = 0; c < SC; c++) v[c] += wk * ((uint32_t)(hk >> (16u * c)) & 0xffffu);
+        }
+        const uint64_t el = (uint64_t)(t.tile_x + x) * t.out_sx + (uint64_t)Y * t.out_sy;
+        uint8_t *o = out + t.out_off;
+        if (over) {
+            const uint32_t tr = VMAX - v[SC - 1u], q = tr / M, rm = tr - q * M; // v_alpha <= Vmax (weights >= 0, sum 2^14)
+RSZ_UNROLL
+            for (uint32_t c = 0; c + 1u < SC; c++) {
+                const uint32_t b = t.bg[c];
+                rsz_alpha_store(t, o, el + (uint64_t)c * t.out_sc, v[c] + b * q + (b * rm + HALF) / M, c);
+            }
+        } else {
+RSZ_UNROLL
+            for (uint32_t c = 0; c < SC; c++) rsz_alpha_store(t, o, el + (uint64_t)c * t.out_sc, v[c], c);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RSZ_THREADS)
+debig_png_resize_alpha_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                              const debig_png_resize_alpha_task *__restrict__ tasks, const uint8_t *__restrict__ weights,
+                              uint32_t n_tasks)
+{
+    __shared__ __attribute__((aligned(16))) RszLds lds;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
+        const debig_png_resize_alpha_task t = tasks[ti];
+        const uint32_t *tx = reinterpret_cast<const uint32_t *>(weights + t.wx_off);
+        const uint32_t *ty = reinterpret_cast<const uint32_t *>(weights + t.wy_off);
+        const uint32_t mtx = tx[0], mty = ty[0], sc = t.channels;
+        const int16_t *wxg = reinterpret_cast<const int16_t *>(tx + 2u + 2u * tx[1]);
+        const int16_t *wyg = reinterpret_cast<const int16_t *>(ty + 2u + 2u * ty[1]);
+        // (uniform over the workgroup: every lane skips, or none)
+        if (t.tile_w == 0u || t.tile_w > DEBIG_PNG_RESIZE_TILE_W || (sc != 2u && sc != 4u) || t.src_channels != sc ||
+            (t.bits != 8u && t.bits != 16u) || t.dtype > 3u ||
+            !((t.mode == RSZ_ALPHA_OVER && t.out_channels == sc - 1u) || (t.mode == RSZ_ALPHA_PREMULTIPLIED && t.out_channels == sc)) ||
+            (uint64_t)t.tile_w * mtx > DEBIG_PNG_RESIZE_WX_CAP || (uint64_t)t.src_rows * t.tile_w * sc > DEBIG_PNG_RESIZE_HQ_CAP)
+            continue;
+        __syncthreads(); // the previous task's pass 2 has read its LDS
+        if (tid < t.tile_w) {
+            lds.fx[tid] = tx[2u + 2u * (t.tile_x + tid)];
+            lds.cx[tid] = tx[3u + 2u * (t.tile_x + tid)];
+        }
+        for (uint32_t i = tid; i < t.tile_w * mtx; i += RSZ_THREADS) lds.wx[i] = wxg[(uint64_t)t.tile_x * mtx + i];
+        __syncthreads();
+        if (t.bits == 8u) {
+            if (sc == 4u) rsz_alpha_tile<8u, 4u>(lds, t, src, out, ty, wyg, mtx, mty, tid);
+            else rsz_alpha_tile<8u, 2u>(lds, t, src, out, ty, wyg, mtx, mty, tid);
+        } else {
+            if (sc == 4u) rsz_alpha_tile<16u, 4u>(lds, t, src, out, ty, wyg, mtx, mty, tid);
+            else rsz_alpha_tile<16u, 2u>(lds, t, src, out, ty, wyg, mtx, mty, tid);
+        }
+    }
+}

@@ -394,6 +394,31 @@ typedef struct debig_png_resize_task {
 int debig_hip_png_resize_batch(const void *d_src_arena, void *d_out, const debig_png_resize_task *d_tasks,
                                const void *d_weights, uint32_t n_tasks, void *hip_stream);
 
+/* The same with alpha (debig_png_resize_alpha_kernel, behind debig_png_decode_batch_tensor_alpha in decode_png.h): the source
+ * is RGBA or GRAY_ALPHA, premultiplied as it is read, filtered premultiplied, and either stored with its alpha
+ * (PREMULTIPLIED: out_channels == src_channels) or composited over bg (OVER: out_channels == src_channels - 1).  The first
+ * 108 bytes are the fields of debig_png_resize_task with the same meaning; `channels` is the SOURCE channel count (2 or 4,
+ * alpha last), the output strides and a[] / b[] are those of the OUTPUT channels.  The tile bounds are the ones above, on
+ * the source channel count: src_rows * tile_w * src_channels <= DEBIG_PNG_RESIZE_HQ_CAP; a task that breaks a bound, or
+ * whose mode and channel counts do not go together, is skipped. */
+typedef struct debig_png_resize_alpha_task {
+    uint64_t src_off, out_off, wx_off, wy_off;
+    uint32_t src_pitch;     /* SAMPLES from one source row to the next (image width * src_channels)                          */
+    uint32_t tile_x, tile_y, tile_w, tile_h;
+    uint32_t src_y0, src_rows;
+    uint32_t out_sx, out_sy, out_sc; /* in elements of the OUTPUT (HWC: out_channels, W * out_channels, 1; CHW: 1, W, H*W)    */
+    uint8_t channels;       /* == src_channels                                                                                */
+    uint8_t bits, dtype, reserved;
+    float a[4], b[4];       /* indexed by output channel                                                                      */
+    uint32_t mode;          /* decode_png.h: DEBIG_PNG_ALPHA_PREMULTIPLIED or _OVER (STRAIGHT is the plain kernel's)          */
+    uint8_t src_channels;   /* 4 (R, G, B, A) or 2 (Y, A)                                                                     */
+    uint8_t out_channels;   /* OVER: src_channels - 1; PREMULTIPLIED: src_channels                                            */
+    uint16_t reserved2;
+    uint16_t bg[4];         /* OVER: the background per output channel at precision P, 0 .. 2^P - 1                           */
+} debig_png_resize_alpha_task;
+int debig_hip_png_resize_alpha_batch(const void *d_src_arena, void *d_out, const debig_png_resize_alpha_task *d_tasks,
+                                     const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

@@ -226,7 +226,7 @@ int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *inp
  *     multiply-add -- with A_c = (float)((double)scale[c] / ((2^P - 1) * 2^(30 - P))) and B_c = bias[c]: sample01 * scale + bias;
  *   - DEBIG_PNG_T_F16 / _BF16:  that float32 converted with round to nearest even.
  * With out_w == w and out_h == h the UINT output is the cropped decode exactly, antialias on or off.  Alpha is resized like
- * any other channel: there is NO premultiplication.
+ * any other channel: there is NO premultiplication (debig_png_decode_batch_tensor_alpha below composites or premultiplies).
  * Checked first, before any file is looked at (status unwritten): an out_format with a NATIVE layout or depth or an unknown
  * out_layout -> DEBIG_PNG_BAD_FORMAT; desc or d_out NULL with n > 0, d_out not 16-byte aligned, an unknown dtype or
  * resize_flags bit, out_w or out_h 0 or above 16384, a non-finite scale / bias with a float dtype -> DEBIG_PNG_BAD_ARG.
@@ -254,6 +254,49 @@ int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const uint64_t *
  * than w_cap taps, or antialias with cl > 64 L); *first = the first tap's source index, w[0 .. count) the Q14 weights. */
 uint32_t debig_png_resize_weights(uint32_t cl, uint32_t L, uint32_t antialias, uint32_t X, uint32_t *first, int16_t *w,
                                   uint32_t w_cap);
+
+/* ---- the same tensor with the alpha channel honoured: composited over a background, or premultiplied --------------------
+ * debig_png_decode_batch_tensor drops an unwanted alpha and filters straight (un-premultiplied) samples: with out_format RGB
+ * a transparent file shows whatever colours its encoder left under the transparent pixels, and a shrinking resize of RGBA
+ * lets those hidden colours bleed into the edges of opaque shapes.  debig_png_decode_batch_tensor_alpha takes the same
+ * arguments, in the same order, and an alpha descriptor:
+ *   - alpha == NULL or mode DEBIG_PNG_ALPHA_STRAIGHT: exactly debig_png_decode_batch_tensor;
+ *   - DEBIG_PNG_ALPHA_OVER: desc->out_format must have layout RGB or GRAY; that is the tensor's channel set (3 or 1).  The
+ *     library decodes into its arena as RGBA (for RGB) or GRAY_ALPHA (for GRAY) at the same depth by steps 1 - 3 above, and
+ *     the resize launch (debig_hip_png_resize_alpha_batch) composites over background[c], one integer sample per OUTPUT
+ *     channel at precision P;
+ *   - DEBIG_PNG_ALPHA_PREMULTIPLIED: out_format must have layout RGBA or GRAY_ALPHA; the tensor holds premultiplied colour
+ *     and plain alpha, filtered in premultiplied space.
+ * The arithmetic, integer up to the one final conversion.  M = 2^P - 1, S = 30 - P, Vmax = M << S:
+ *   1. premultiply every source pixel of the crop (colour s_c, alpha al):  p_c = (s_c * al + (M >> 1)) div M,  p_alpha = al;
+ *   2. filter: the two passes above on p -- the same Q14 axis tables, the same Hq rounding, the same tile rules -> v_c, v_alpha;
+ *   3. PREMULTIPLIED: element c is the conversion above of v_c, for every channel, alpha included;
+ *   4. OVER: t = Vmax - v_alpha;  v'_c = v_c + (b_c * t + (M >> 1)) div M  (the product in 64 bits; in 32 bits, with
+ *      t = q M + r:  b q + (b r + (M >> 1)) div M);  element c is the conversion above of v'_c.
+ * scale[c] / bias[c] are indexed by OUTPUT channel.  p_c <= al, hence v_c <= v_alpha <= Vmax and v'_c <= Vmax: no clamp is
+ * needed anywhere.  A fully opaque image gives, bit for bit, debig_png_decode_batch_tensor's RGB / GRAY result in OVER mode
+ * and its RGBA / GRAY_ALPHA result in PREMULTIPLIED mode; a fully transparent one gives v'_c = b_c << S exactly.
+ * Limits: premultiplying at P bits means that colour under a very low alpha keeps few bits (at alpha 1 of 255 a colour is 0
+ * or 1).  That is what Pillow's "RGBa" resize does; it is harmless for OVER, whose output scales with alpha, and it is why
+ * straight (un-premultiplied) output of a premultiplied resize is not offered.
+ * Checked before any file is looked at, with status unwritten: every check of debig_png_decode_batch_tensor first and
+ * unchanged; then DEBIG_PNG_BAD_ARG for an unknown mode, reserved != 0, a mode / layout pairing other than the ones above,
+ * or, in OVER mode, a used background[c] above 2^P - 1.
+ * Per image: statuses and their order, the E_BOX rule, the infos and the untouched slot of a failed file are those of
+ * debig_png_decode_batch_tensor; E_OUTPUT is judged on the size of the format actually decoded (4 or 2 channels).
+ * Not provided: un-premultiplied RGBA output of a premultiplied resize (it needs a division per pixel); compositing in the
+ * calls that do not resize (debig_png_decode_batch_fmt, _layout, _dev); bKGD / gAMA handling (the background is the
+ * caller's, the samples are composited as stored); animated PNGs. */
+enum { DEBIG_PNG_ALPHA_STRAIGHT = 0, DEBIG_PNG_ALPHA_PREMULTIPLIED = 1, DEBIG_PNG_ALPHA_OVER = 2 };
+typedef struct debig_png_alpha_desc {
+    uint32_t mode;
+    uint16_t background[4];   /* OVER: one integer sample per OUTPUT channel at precision P, 0 .. 2^P - 1 */
+    uint32_t reserved;        /* 0 */
+} debig_png_alpha_desc;
+int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                        const debig_png_box *boxes /* may be NULL */, uint32_t *status,
+                                        debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                        const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha /* may be NULL */);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
