@@ -477,9 +477,27 @@ def png_alpha_desc(alpha="straight", background=None, mode="rgb", depth=8):
     return d
 
 
+class PngFilterDesc(C.Structure):  # include/decode_png.h: debig_png_filter_desc
+    _fields_ = [("filter", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PNG_FILTERS = {"bilinear": 0, "bicubic": 1, "nearest": 2}  # include/decode_png.h: DEBIG_PNG_FILTER_*
+
+
+def png_filter_desc(filter="bilinear"):
+    """the debig_png_filter_desc of png_decode_batch_tensor's filter argument (no GPU needed), or None for "bilinear" (the
+    calls without a filter).  "bicubic": the Keys kernel with a = -1/2, antialiased when it shrinks (at most 32 x per axis);
+    "nearest": the source sample at the output pixel's centre, antialias ignored."""
+    if filter not in PNG_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(PNG_FILTERS)}, not {filter!r}")
+    if filter == "bilinear":
+        return None
+    return PngFilterDesc(filter=PNG_FILTERS[filter])
+
+
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
                             antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
-                            background=None):
+                            background=None, filter="bilinear"):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
     (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
@@ -492,11 +510,18 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     alpha: "straight" (the default: alpha is dropped or resized like a colour channel, no premultiplication), "over"
     (mode "rgb" / "gray": the file's alpha composites the pixels over `background`, per output channel on the [0, 1]
     scale, default white, inside the resize launch) or "premultiplied" (mode "rgba" / "gray_alpha": premultiplied colour
-    and plain alpha, filtered in premultiplied space) -- debig_png_decode_batch_tensor_alpha, see png_alpha_desc."""
+    and plain alpha, filtered in premultiplied space) -- debig_png_decode_batch_tensor_alpha, see png_alpha_desc.
+    filter: "bilinear" (the default: the calls above, unchanged), "bicubic" (the Keys kernel with a = -1/2, clipped to the
+    crop and renormalised, antialiased when it shrinks: what Pillow's BICUBIC and interpolate(mode="bicubic",
+    antialias=True) mean, in Q14 integer weights with signed sums and clamps to [0, 1] of full scale; a crop more than 32
+    times the output on an axis is E_BOX) or "nearest" (the source sample at the output pixel's centre, torch's
+    "nearest-exact"; antialias is ignored) -- debig_png_decode_batch_tensor_filter, see png_filter_desc.  Every alpha mode
+    goes with every filter."""
     import torch
 
     d, ch, es = png_tensor_desc(size, mode, depth, dtype, layout, mean, std, antialias)
     ad = png_alpha_desc(alpha, background, mode, depth)
+    fd = png_filter_desc(filter)
     L = _png_spec_lib()
     L.debig_png_decode_batch_tensor.restype = C.c_int
     L.debig_png_decode_batch_tensor.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
@@ -533,7 +558,13 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
         bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
     status = (C.c_uint32 * n)()
     infos = (PngInfo * n)()
-    if ad is None:
+    if fd is not None:
+        L.debig_png_decode_batch_tensor_filter.restype = C.c_int
+        L.debig_png_decode_batch_tensor_filter.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_tensor_filter(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n,
+                                                    PNG_FORCE_GENERAL if force_general else 0, C.byref(d),
+                                                    C.byref(ad) if ad is not None else None, C.byref(fd))
+    elif ad is None:
         rc = L.debig_png_decode_batch_tensor(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n,
                                              PNG_FORCE_GENERAL if force_general else 0, C.byref(d))
     else:

@@ -770,6 +770,18 @@ int debig_hip_png_resize_alpha_batch(const void *d_src_arena, void *d_out, const
     return (int)hipGetLastError();
 }
 
+// ... and the signed filter (bicubic: weights of either sign), straight or with alpha: the same grid rule
+int debig_hip_png_resize_cubic_batch(const void *d_src_arena, void *d_out, const debig_png_resize_cubic_task *d_tasks,
+                                     const void *d_weights, uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_resize_cubic_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
+    return (int)hipGetLastError();
+}
+
 // inflate -> de-filter in one kernel (png_fused_kernel.inc).  Per group of at most SPLIT_GROUP
 // images: plan, the fused kernel, debig_inflate_kernel for the streams the scan handed back; then, over the whole
 // batch, the one-workgroup de-filter for the images of those streams (PNG_ROW_REDO) and the P3 kernel.

@@ -711,13 +711,67 @@ DEBIG_API uint32_t debig_png_resize_weights(uint32_t cl, uint32_t L, uint32_t an
     return cnt;
 }
 
+/* the Keys kernel (a = -1/2) times 2^29 at the distance m / D (decode_png.h: BICUBIC); m < 2 D */
+static int64_t rsz_cubic_n(int64_t m, int64_t D)
+{
+    const int64_t u = (m * 65536) / D;
+    const int64_t p = u <= 65536 ? 3 * u * u * u - 327680 * u * u + ((int64_t)1 << 49)
+                                 : -u * u * u + 327680 * u * u - ((int64_t)1 << 35) * u + ((int64_t)1 << 50);
+    return p >= 0 ? p >> 20 : -((-p + 1048575) >> 20); /* an arithmetic shift: floor(p / 2^20) */
+}
+
+DEBIG_API uint32_t debig_png_resize_weights_filter(uint32_t filter, uint32_t cl, uint32_t L, uint32_t antialias, uint32_t X,
+                                                   uint32_t *first, int16_t *w, uint32_t w_cap)
+{
+    if (filter == DEBIG_PNG_FILTER_BILINEAR) return debig_png_resize_weights(cl, L, antialias, X, first, w, w_cap);
+    if (cl == 0 || L == 0 || L > 16384u || X >= L || !first || !w) return 0;
+    const int64_t l2 = 2 * (int64_t)L, c = (2 * (int64_t)X + 1) * cl;
+    if (filter == DEBIG_PNG_FILTER_NEAREST) {
+        if (w_cap < 1) return 0;
+        *first = (uint32_t)(c / l2);
+        w[0] = 16384;
+        return 1;
+    }
+    if (filter != DEBIG_PNG_FILTER_BICUBIC) return 0;
+    const int shrink = antialias && cl > L;
+    if (shrink && (uint64_t)cl > 32u * (uint64_t)L) return 0;
+    const int64_t D = shrink ? 2 * (int64_t)cl : l2, reach = 2 * D;
+#define RSZ_M(j) ((2 * (j) + 1) * (int64_t)L > c ? (2 * (j) + 1) * (int64_t)L - c : c - (2 * (j) + 1) * (int64_t)L)
+    int64_t j = c - reach > 0 ? (c - reach) / l2 : 0; /* (2j + 1) L <= c - 2 D + L: at or left of the first tap */
+    if (j > 0) j--;
+    while (j < (int64_t)cl && RSZ_M(j) >= reach) j++;
+    int64_t nn[RSZ_MAX_TAPS], T = 0, best = 0;
+    uint32_t cnt = 0, best_k = 0;
+    for (; j < (int64_t)cl && RSZ_M(j) < reach; j++) {
+        if (cnt == RSZ_MAX_TAPS) return 0;
+        if (cnt == 0) *first = (uint32_t)j;
+        nn[cnt] = rsz_cubic_n(RSZ_M(j), D);
+        T += nn[cnt];
+        if (cnt == 0 || nn[cnt] > best) { best = nn[cnt]; best_k = cnt; }
+        cnt++;
+    }
+#undef RSZ_M
+    if (cnt == 0 || cnt > w_cap || T <= 0) return 0;
+    int64_t q[RSZ_MAX_TAPS], sum = 0, abs_sum = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+        const int64_t num = nn[k] * 16384 + (T >> 1);
+        q[k] = num >= 0 ? num / T : -((-num + T - 1) / T); /* floor */
+        sum += q[k];
+    }
+    q[best_k] += 16384 - sum;
+    for (uint32_t k = 0; k < cnt; k++) abs_sum += q[k] < 0 ? -q[k] : q[k];
+    if (abs_sum > 32768) return 0;
+    for (uint32_t k = 0; k < cnt; k++) w[k] = (int16_t)q[k];
+    return cnt;
+}
+
 /* the axis tables of one call (include/debig_hip.h: layout), one per distinct (cl, L) */
 typedef struct rsz_axis { uint32_t cl, max_taps; uint64_t off; } rsz_axis;
 typedef struct rsz_tables {
     uint8_t *buf;
     uint64_t len, cap;
     rsz_axis *ax;
-    uint32_t n_ax, cap_ax, L, aa;
+    uint32_t n_ax, cap_ax, L, aa, filter;
 } rsz_tables;
 
 /* the table of crop length cl (made on first use) -> its index, or -1 (out of memory) */
@@ -730,7 +784,7 @@ static int64_t rsz_axis_get(rsz_tables *T, uint32_t cl)
     int16_t w[RSZ_MAX_TAPS];
     uint32_t first, mt = 1;
     for (uint32_t X = 0; X < L; X++) {
-        const uint32_t cnt = debig_png_resize_weights(cl, L, T->aa, X, &first, w, RSZ_MAX_TAPS);
+        const uint32_t cnt = debig_png_resize_weights_filter(T->filter, cl, L, T->aa, X, &first, w, RSZ_MAX_TAPS);
         if (cnt > mt) mt = cnt;
     }
     const uint64_t bytes = (8u + 8u * (uint64_t)L + 2u * (uint64_t)L * mt + 7u) & ~(uint64_t)7u;
@@ -749,7 +803,7 @@ static int64_t rsz_axis_get(rsz_tables *T, uint32_t cl)
     hdr[0] = mt;
     hdr[1] = L;
     for (uint32_t X = 0; X < L; X++) {
-        hdr[3 + 2 * X] = debig_png_resize_weights(cl, L, T->aa, X, &hdr[2 + 2 * X], wt + (uint64_t)X * mt, mt);
+        hdr[3 + 2 * X] = debig_png_resize_weights_filter(T->filter, cl, L, T->aa, X, &hdr[2 + 2 * X], wt + (uint64_t)X * mt, mt);
     }
     rsz_axis *a = &T->ax[T->n_ax];
     a->cl = cl;
@@ -786,13 +840,22 @@ _Static_assert(offsetof(debig_png_resize_alpha_task, mode) == RSZ_TASK_FIELDS &&
                    offsetof(debig_png_resize_alpha_task, b) == offsetof(debig_png_resize_task, b) &&
                    sizeof(debig_png_resize_alpha_task) == 128,
                "debig_png_resize_alpha_task starts with the fields of debig_png_resize_task");
+_Static_assert(sizeof(debig_png_resize_cubic_task) == sizeof(debig_png_resize_alpha_task) &&
+                   offsetof(debig_png_resize_cubic_task, mode) == offsetof(debig_png_resize_alpha_task, mode) &&
+                   offsetof(debig_png_resize_cubic_task, src_channels) == offsetof(debig_png_resize_alpha_task, src_channels) &&
+                   offsetof(debig_png_resize_cubic_task, out_channels) == offsetof(debig_png_resize_alpha_task, out_channels) &&
+                   offsetof(debig_png_resize_cubic_task, bg) == offsetof(debig_png_resize_alpha_task, bg) &&
+                   offsetof(debig_png_resize_cubic_task, b) == offsetof(debig_png_resize_alpha_task, b),
+               "debig_png_resize_cubic_task has the layout of debig_png_resize_alpha_task (tensor_core fills both through one)");
 
-/* debig_png_decode_batch_tensor (amode == DEBIG_PNG_ALPHA_STRAIGHT: bg unused) and debig_png_decode_batch_tensor_alpha behind
- * their argument checks.  With alpha the pixels are decoded WITH their alpha (dfmt: 4 or 2 channels) and the tiles go to the
- * alpha kernel, which writes the channels of desc->out_format. */
+/* debig_png_decode_batch_tensor (amode == DEBIG_PNG_ALPHA_STRAIGHT: bg unused), debig_png_decode_batch_tensor_alpha and
+ * debig_png_decode_batch_tensor_filter behind their argument checks.  With alpha the pixels are decoded WITH their alpha (dfmt:
+ * 4 or 2 channels) and the tiles go to the alpha kernel, which writes the channels of desc->out_format.  The filter picks the
+ * weight rule and the E_BOX scale; BICUBIC tiles, of every alpha mode, go to the signed kernel (debig_hip_png_resize_cubic_batch),
+ * NEAREST ones to the kernels of BILINEAR. */
 static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
                        uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
-                       uint32_t amode, const uint16_t *bg)
+                       uint32_t amode, const uint16_t *bg, uint32_t filter)
 {
     /* fmt: the format decoded into the arena (ch channels); oc: the channels of the tensor */
     uint32_t fmt = desc->out_format;
@@ -810,7 +873,10 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     debig_png_info *inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
     debig_png_resize_task *tasks = NULL;
     debig_png_resize_alpha_task *atasks = NULL;
-    rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa};
+    rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa, filter}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa, filter};
+    /* the largest antialiased scale (decode_png.h); NEAREST ignores the flag */
+    const uint64_t max_scale = filter == DEBIG_PNG_FILTER_BICUBIC ? 32u : 64u;
+    const uint32_t aa_box = filter == DEBIG_PNG_FILTER_NEAREST ? 0u : aa;
     int rc = 2;
     if (!pre || !offs || !caps || !box || !inf) goto done;
     /* ---- IHDR, the box, the image's place in the context's arena */
@@ -826,7 +892,7 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
         debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
         if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
         if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih ||
-            (aa && ((uint64_t)b.w > 64u * (uint64_t)W || (uint64_t)b.h > 64u * (uint64_t)H))) {
+            (aa_box && ((uint64_t)b.w > max_scale * (uint64_t)W || (uint64_t)b.h > max_scale * (uint64_t)H))) {
             pre[i] = DEBIG_PNG_E_BOX;
             continue;
         }
@@ -899,8 +965,9 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     rc = 0;
     if (n_tasks == 0) goto done;
     for (uint64_t k = 0; k < n_tasks; k++) tasks[k].wy_off += TX.len;
-    if (amode != DEBIG_PNG_ALPHA_STRAIGHT) {
-        /* the alpha kernel's task: the plain one (channels: the source's) + mode, channel counts, background */
+    if (amode != DEBIG_PNG_ALPHA_STRAIGHT || filter == DEBIG_PNG_FILTER_BICUBIC) {
+        /* the alpha kernel's task, and the signed kernel's of the same layout: the plain one (channels: the source's) + mode,
+         * channel counts, background */
         atasks = (debig_png_resize_alpha_task *)calloc(n_tasks, sizeof(debig_png_resize_alpha_task));
         if (!atasks) { rc = 2; goto done; }
         for (uint64_t k = 0; k < n_tasks; k++) {
@@ -919,8 +986,11 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
             (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, atasks, n_tasks * sizeof(debig_png_resize_alpha_task), NULL)) ||
             (rc = debig_hip_memcpy_h2d(c->rsz_weights.ptr, TX.buf, TX.len, NULL)) ||
             (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + TX.len, TY.buf, TY.len, NULL)) ||
-            (rc = debig_hip_png_resize_alpha_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_alpha_task *)c->rsz_tasks.ptr,
-                                                   c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)) ||
+            (rc = filter == DEBIG_PNG_FILTER_BICUBIC
+                      ? debig_hip_png_resize_cubic_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_cubic_task *)c->rsz_tasks.ptr,
+                                                         c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
+                      : debig_hip_png_resize_alpha_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_alpha_task *)c->rsz_tasks.ptr,
+                                                         c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)) ||
             (rc = debig_hip_stream_sync(NULL)))
             goto done;
     } else {
@@ -959,16 +1029,13 @@ DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const 
     if (n == 0) return 0;
     const int bad = tensor_args_check(d_out, desc);
     if (bad) return bad;
-    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL);
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL, DEBIG_PNG_FILTER_BILINEAR);
 }
 
-DEBIG_API int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                                  const debig_png_box *boxes, uint32_t *status, debig_png_info *infos,
-                                                  uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
-                                                  const debig_png_alpha_desc *alpha)
+/* the checks of debig_png_decode_batch_tensor_alpha (n > 0): those of debig_png_decode_batch_tensor first and unchanged, then
+ * alpha's; all before any file is looked at -> 0 and *mode, or the call's return value */
+static int tensor_alpha_check(const void *d_out, const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha, uint32_t *mode)
 {
-    /* the checks of debig_png_decode_batch_tensor first and unchanged, then alpha's; all before any file is looked at */
-    if (n == 0) return 0;
     const int bad = tensor_args_check(d_out, desc);
     if (bad) return bad;
     uint32_t amode = DEBIG_PNG_ALPHA_STRAIGHT;
@@ -983,5 +1050,34 @@ DEBIG_API int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, 
                 if (alpha->background[k] > (1u << bits) - 1u) return DEBIG_PNG_BAD_ARG;
         }
     }
-    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL);
+    *mode = amode;
+    return 0;
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                  const debig_png_box *boxes, uint32_t *status, debig_png_info *infos,
+                                                  uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                                                  const debig_png_alpha_desc *alpha)
+{
+    if (n == 0) return 0;
+    uint32_t amode;
+    const int bad = tensor_alpha_check(d_out, desc, alpha, &amode);
+    if (bad) return bad;
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
+                       DEBIG_PNG_FILTER_BILINEAR);
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                   const debig_png_box *boxes, uint32_t *status, debig_png_info *infos,
+                                                   uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                                                   const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter)
+{
+    /* every check of debig_png_decode_batch_tensor_alpha first and unchanged, then the filter's */
+    if (n == 0) return 0;
+    uint32_t amode;
+    const int bad = tensor_alpha_check(d_out, desc, alpha, &amode);
+    if (bad) return bad;
+    if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
+                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR);
 }

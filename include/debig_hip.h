@@ -419,6 +419,31 @@ typedef struct debig_png_resize_alpha_task {
 int debig_hip_png_resize_alpha_batch(const void *d_src_arena, void *d_out, const debig_png_resize_alpha_task *d_tasks,
                                      const void *d_weights, uint32_t n_tasks, void *hip_stream);
 
+/* The signed filter (debig_png_resize_cubic_kernel, behind debig_png_decode_batch_tensor_filter with DEBIG_PNG_FILTER_BICUBIC
+ * in decode_png.h): weights of either sign, signed sums, a biased 16-bit intermediate and the clamps of the header.  The
+ * task has the layout of debig_png_resize_alpha_task, field for field, and covers all three alpha modes:
+ *   - mode STRAIGHT: 1..4 source channels, out_channels == src_channels, no premultiplication;
+ *   - mode PREMULTIPLIED / OVER: as the alpha task (2 or 4 source channels, alpha last).
+ * The axis tables, the tile bounds (on the source channel count) and the LDS are those of the kernels above; a task that
+ * breaks a bound, or whose mode, channel counts, depth or dtype do not go together, is skipped. */
+typedef struct debig_png_resize_cubic_task {
+    uint64_t src_off, out_off, wx_off, wy_off;
+    uint32_t src_pitch;     /* SAMPLES from one source row to the next (image width * src_channels)                          */
+    uint32_t tile_x, tile_y, tile_w, tile_h;
+    uint32_t src_y0, src_rows;
+    uint32_t out_sx, out_sy, out_sc; /* in elements of the OUTPUT                                                             */
+    uint8_t channels;       /* == src_channels                                                                                */
+    uint8_t bits, dtype, reserved;
+    float a[4], b[4];       /* indexed by output channel                                                                      */
+    uint32_t mode;          /* decode_png.h: DEBIG_PNG_ALPHA_STRAIGHT, _PREMULTIPLIED or _OVER                                */
+    uint8_t src_channels;   /* STRAIGHT: 1..4; else 4 (R, G, B, A) or 2 (Y, A)                                                */
+    uint8_t out_channels;   /* OVER: src_channels - 1; else src_channels                                                      */
+    uint16_t reserved2;
+    uint16_t bg[4];         /* OVER: the background per output channel at precision P, 0 .. 2^P - 1                           */
+} debig_png_resize_cubic_task;
+int debig_hip_png_resize_cubic_batch(const void *d_src_arena, void *d_out, const debig_png_resize_cubic_task *d_tasks,
+                                     const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

@@ -235,8 +235,8 @@ int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *inp
  * (64-bit sums), or antialias with cl > 64 L on either axis (that bounds the taps at 129 and keeps the corrected weight
  * positive).  E_OUTPUT: the decoded image is larger than 2^31 bytes.  A file with any non-zero status leaves its slot
  * untouched; nothing outside d_out[0 .. n * slot) is written.
- * Not provided: other filters (bicubic, nearest), flips, colour jitter, animated PNGs, inputs already on the device, an
- * asynchronous variant. */
+ * Not provided: flips, colour jitter, animated PNGs, inputs already on the device, an asynchronous variant; other filters than
+ * bilinear are debig_png_decode_batch_tensor_filter's (below). */
 typedef struct debig_png_box { uint32_t x, y, w, h; } debig_png_box; /* w == 0 && h == 0: the whole image */
 enum { DEBIG_PNG_T_UINT = 0, DEBIG_PNG_T_F32 = 1, DEBIG_PNG_T_F16 = 2, DEBIG_PNG_T_BF16 = 3 };
 #define DEBIG_PNG_RESIZE_ANTIALIAS 1u
@@ -297,6 +297,55 @@ int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, const uint
                                         const debig_png_box *boxes /* may be NULL */, uint32_t *status,
                                         debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
                                         const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha /* may be NULL */);
+
+/* ---- the same tensor through another filter: bicubic or nearest ---------------------------------------------------------
+ * debig_png_decode_batch_tensor_filter takes the arguments of debig_png_decode_batch_tensor_alpha, in the same order, and a
+ * filter descriptor.  filter == NULL or DEBIG_PNG_FILTER_BILINEAR is exactly debig_png_decode_batch_tensor_alpha: the same code
+ * path, the same kernels, the same bytes.  All three alpha modes work with all three filters.  The old two calls are
+ * unchanged (they still refuse resize_flags bit 1 and above).
+ * Weights of one axis (crop length cl, output length L, output coordinate X; Q14, their sum exactly 16384):
+ *   - DEBIG_PNG_FILTER_NEAREST: one tap, source index ((2X + 1) cl) div 2L, weight 16384.  The antialias flag is ignored (no
+ *     E_BOX arises from scale).  The tiles run through the kernels of the bilinear filter; a single weight of 16384 makes both
+ *     passes exact, so the UINT output is the chosen source sample ("nearest-exact" with half-pixel centres).
+ *   - DEBIG_PNG_FILTER_BICUBIC: the Keys kernel with a = -1/2 (Pillow's BICUBIC; torch's bicubic with antialias=True), as wide
+ *     as the scale when it shrinks with antialias; taps are clipped to the CROP and renormalised (no border replication).
+ *     D = 2 cl when antialias is on and cl > L, else 2 L.  For source index j in [0, cl): m_j = |(2j + 1) L - (2X + 1) cl|; the
+ *     taps are the j with m_j < 2 D (a contiguous run; a tap may carry the weight 0).  u = (m_j * 65536) div D;
+ *     p = 3 u^3 - 327680 u^2 + 2^49 for u <= 65536, else p = -u^3 + 327680 u^2 - 2^35 u + 2^50 (signed 64 bits, every term
+ *     below 2^55); n_j = p >> 20 (arithmetic); T = sum n_j; w_j = floor((n_j * 16384 + (T >> 1)) / T), floor toward minus
+ *     infinity; then 16384 - sum w_j is added to the tap with the largest n_j (the lowest such j).  E_BOX when antialias is on
+ *     and cl > 32 L on either axis (that bounds the taps at 129).  Over every cl, L in 1 .. 69 and 300 larger pairs: T > 0, at
+ *     most 128 taps, weights in [-2032, 18416], sum |w_j| <= 20788 (cl = 14, L = 13); cl == L gives 16384 on the pixel itself
+ *     and 0 on its neighbours, so an unscaled UINT output is the crop at P = 8 (at P = 16 see the intermediate below).
+ * The signed passes (BICUBIC only; NEAREST and BILINEAR use the unsigned ones above).  M = 2^P - 1:
+ *   - pass 1: h = sum wx_k s_k in signed 32 bits (|h| <= 20788 * 65535 < 2^31);
+ *   - the intermediate: Hq = clamp(((h + 2^(P-2)) >> (P-1)) + 16384, 0, 65535), stored as uint16 (>> arithmetic): the sample at
+ *     scale 2^15, biased, covering [-0.5, 1.5) of full scale.  The clamp is part of the definition; with sum |w| <= 20788 it is
+ *     never reached.  At P = 16 it keeps 15 of the sample's 16 bits: an unscaled UINT output is min(2 * ((s + 1) >> 1), M);
+ *   - pass 2: v = sum wy_k Hq_k - 2^28, signed (sum wy = 16384 exactly, so the bias leaves as one constant; |v| < 2^31);
+ *   - v30 = clamp(v, 0, M << (29 - P)) << 1, and from there the ONE conversion above, unchanged: UINT, F32 (a separately
+ *     rounded multiply and add), F16, BF16;
+ *   - with alpha: premultiply exactly as above, filter as here; v30_alpha is clamped to [0, Vmax] first, then every v30_c to
+ *     [0, v30_alpha] (with negative lobes v_c <= v_alpha no longer holds by itself); then the OVER formula or the PREMULTIPLIED
+ *     output above.  A fully opaque file gives the plain bicubic result of its colour channels bit for bit, a fully
+ *     transparent one the background exactly.
+ * Checked before any file is looked at, with status unwritten: every check of debig_png_decode_batch_tensor_alpha first and
+ * unchanged; then DEBIG_PNG_BAD_ARG for an unknown filter or reserved != 0.  Per image: statuses, their order, the untouched
+ * slot of a failed file and infos are those of debig_png_decode_batch_tensor_alpha, with the E_BOX scale rule of the filter.
+ * Not provided: Lanczos and other kernels, the a = -3/4 variant, border replication, flips, colour jitter, animated PNGs,
+ * inputs already on the device, an asynchronous variant. */
+enum { DEBIG_PNG_FILTER_BILINEAR = 0, DEBIG_PNG_FILTER_BICUBIC = 1, DEBIG_PNG_FILTER_NEAREST = 2 };
+typedef struct debig_png_filter_desc { uint32_t filter; uint32_t reserved; /* 0 */ } debig_png_filter_desc;
+int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                         const debig_png_box *boxes /* may be NULL */, uint32_t *status,
+                                         debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                         const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha /* may be NULL */,
+                                         const debig_png_filter_desc *filter /* may be NULL */);
+/* Host only: debig_png_resize_weights for a filter (BILINEAR: that call itself) -> the number of taps; 0 as there, for an
+ * unknown filter, for BICUBIC antialiased with cl > 32 L, or where T <= 0 or sum |w| > 32768 (neither occurs in the sweep
+ * above). */
+uint32_t debig_png_resize_weights_filter(uint32_t filter, uint32_t cl, uint32_t L, uint32_t antialias, uint32_t X,
+                                         uint32_t *first, int16_t *w, uint32_t w_cap);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

@@ -351,3 +351,13 @@ extern "C" int emu_png_resize_alpha_batch(const void *src_arena, void *out, cons
                       (const uint8_t *)weights, n);
     return 0;
 }
+
+/* ... and the signed (bicubic) filter, as debig_hip_png_resize_cubic_batch launches it */
+extern "C" int emu_png_resize_cubic_batch(const void *src_arena, void *out, const debig_png_resize_cubic_task *tasks,
+                                          const void *weights, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_resize_cubic_kernel, grid, RSZ_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)weights, n);
+    return 0;
+}
