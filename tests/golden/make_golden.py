@@ -62,6 +62,34 @@ def corrupt_corpus():
     print("corpus_corrupt.json:", len(keep), "cases; reference deaths:", w.crashes)
 
 
+def token_corpus():
+    """8. token-made streams (tests/token_fuzz.py: golden_subset) through the reference: matches at the
+    base and the top of distance codes up to 32 768, distance = bytes produced and one more (:1843-1852
+    with the partial final size), overlapping copies, far matches into stored blocks, a match that ends
+    on recipient_size.  Build A answers the streams it decodes, in a child process: its overlapping copy
+    asserts that the output stays strictly below recipient_size (:1889), so the overlapping match that
+    ends exactly there goes through build B, like the failing streams (as in corrupt_corpus)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import token_fuzz as tf
+    from ref_worker import RefWorker
+
+    w = RefWorker()
+    keep = []
+    for c in tf.golden_subset():
+        which = "A" if c.legal else "B"
+        r = w.inflate(which, c.raw, c.cap)
+        if r is None and which == "A":
+            which = "B"
+            r = w.inflate(which, c.raw, c.cap)
+        good, final, digest = r
+        assert (good, final, digest) == (int(c.legal), len(c.plain), sha(c.plain)), c.name
+        keep.append({"name": c.name, "raw_hex": c.raw.hex(), "recipient_size": c.cap, "good": int(good), "final": final,
+                     "out_sha256": digest, "oracle": which})
+    w.close()
+    json.dump(keep, open(os.path.join(HERE, "corpus_tokens.json"), "w"))
+    print("corpus_tokens.json:", len(keep), "cases; reference deaths:", w.crashes)
+
+
 def vs_reference():
     """7. the reference's answers (digests) to exactly the inputs of tests/test_oracle_vs_reference.py, recorded by
     running that module's tests against the live reference (build A in process, build B in a child process)."""
@@ -85,6 +113,8 @@ def main():
         return corrupt_corpus()
     if "--only-vs-reference" in sys.argv:
         return vs_reference()
+    if "--only-tokens" in sys.argv:
+        return token_corpus()
     A = binding.Reference("A")  # silent, asserts on (canonical)
     B = binding.Reference("B")  # silent, asserts off (inputs on which A aborts)
 
@@ -175,6 +205,7 @@ def main():
     json.dump(pngs, open(os.path.join(HERE, "png_synth.json"), "w"))
     corrupt_corpus()
     vs_reference()
+    token_corpus()
     print("golden fixtures written:", sorted(os.listdir(HERE)))
 
 

@@ -41,6 +41,22 @@ def test_corrupt_corpus_failure_semantics(oracle):
         assert (good, final, sha(out)) == (c["good"], c["final"], c["out_sha256"])
 
 
+def test_token_corpus_distance_edges(oracle):
+    """reference-made answers for token-made streams (tests/token_fuzz.py: golden_subset): distances up
+    to 32 768, distance = bytes produced and one more, overlap, far matches into stored blocks, a match
+    that ends on recipient_size -- and the generator still writes the very same streams"""
+    import token_fuzz as tf
+
+    corpus = json.load(open(os.path.join(GOLD, "corpus_tokens.json")))
+    assert len(corpus) >= 36 and sum(c["good"] == 0 for c in corpus) >= 4
+    for c in corpus:
+        good, final, out, st = oracle.inflate(bytes.fromhex(c["raw_hex"]), c["recipient_size"], want_stats=True)
+        assert st.ub_flags == 0
+        assert (good, final, sha(out)) == (c["good"], c["final"], c["out_sha256"]), c["name"]
+    assert [(c.name, c.raw.hex(), c.cap) for c in tf.golden_subset()] == \
+        [(c["name"], c["raw_hex"], c["recipient_size"]) for c in corpus]
+
+
 def test_resources_png_and_gz(oracle):
     gold = json.load(open(os.path.join(GOLD, "resources.json")))
     files = sorted(glob.glob(os.path.join(GOLD, "resources", "*.png")))
