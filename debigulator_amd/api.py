@@ -211,7 +211,7 @@ def gunzip_batch(datas, out_caps):
 
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
-              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box"}
+              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box", 15: "label"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -573,6 +573,87 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     if rc in (PNG_BAD_FORMAT, PNG_BAD_ARG):
         raise ValueError(f"debig_png_decode_batch_tensor rejected its arguments ({rc})")
     N.check(rc, "debig_png_decode_batch_tensor")
+    return [int(s) for s in status], out, [_info_dict(i) for i in infos]
+
+
+class PngLabelDesc(C.Structure):  # include/decode_png.h: debig_png_label_desc
+    _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("dtype", C.c_uint32), ("reserved", C.c_uint32),
+                ("lut", C.POINTER(C.c_int32))]
+
+
+PNG_LABEL_DTYPES = {"uint8": 0, "uint16": 1, "int32": 2, "int64": 3}  # include/decode_png.h: DEBIG_PNG_L_*
+
+
+def png_label_desc(size, dtype="int64", lut=None):
+    """the debig_png_label_desc of png_decode_batch_labels' arguments (no GPU needed) -> (desc, element bytes).  The desc
+    keeps the 256 int32 of `lut` alive (desc._lut)."""
+    if dtype not in PNG_LABEL_DTYPES:
+        raise ValueError(f"dtype must be one of {sorted(PNG_LABEL_DTYPES)}, not {dtype!r}")
+    H, W = (int(v) for v in size)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"size must be (H, W) with 1 <= H, W <= 16384, not {size!r}")
+    d = PngLabelDesc(out_w=W, out_h=H, dtype=PNG_LABEL_DTYPES[dtype])
+    if lut is not None:
+        table = np.asarray(lut)
+        if table.shape != (256,) or table.dtype.kind not in "iu":
+            raise ValueError("lut needs 256 integers")
+        top = {"uint8": 255, "uint16": 65535}.get(dtype, 2 ** 31 - 1)
+        low = 0 if dtype in ("uint8", "uint16") else -2 ** 31
+        if int(table.min()) < low or int(table.max()) > top:
+            raise ValueError(f"lut entries must lie in [{low}, {top}] for dtype {dtype!r}")
+        d._lut = np.ascontiguousarray(table, dtype=np.int32)
+        d.lut = d._lut.ctypes.data_as(C.POINTER(C.c_int32))
+    return d, 1 << PNG_LABEL_DTYPES[dtype]
+
+
+def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fill=None, device="cuda:0"):
+    """bytes of N label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
+    debig_png_decode_batch_labels) -> (statuses, tensor, infos).  The label of a pixel is its palette index (colour type 3)
+    or its raw grey sample (colour type 0, 1 to 16 bits): nothing is scaled, PLTE colours and tRNS are ignored.  size =
+    (H, W); boxes: per image None or (x, y, w, h), the crop inside the image; the pick is the source pixel under the output
+    pixel's centre -- the grid of png_decode_batch_tensor(filter="nearest") with the same box.  lut: 256 integers, the
+    element is lut[label] (an id -> train-id remap; 16-bit files take none).  dtype: "uint8" | "uint16" | "int32" | "int64";
+    uint16 comes as torch.int16 bits where torch has no uint16.  Colour types 2, 4 and 6, a 16-bit file with dtype "uint8" or
+    with a lut: status 15 ("label").  The slot of a file whose status is not 0 is left as allocated, or holds `fill` when that
+    is given.  Same device rule as png_decode_batch_device."""
+    import torch
+
+    d, es = png_label_desc(size, dtype, lut)
+    L = _png_spec_lib()
+    L.debig_png_decode_batch_labels.restype = C.c_int
+    L.debig_png_decode_batch_labels.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device must be a GPU, not {device!r}")
+    L.debig_hip_get_device.restype = C.c_int
+    cur = L.debig_hip_get_device()
+    if dev.index is not None and dev.index != cur:
+        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
+    dev = torch.device("cuda", cur)
+    n = len(datas)
+    if boxes is not None and len(boxes) != n:
+        raise ValueError("boxes needs one entry (or None) per file")
+    tdt = {"uint8": torch.uint8, "uint16": getattr(torch, "uint16", torch.int16), "int32": torch.int32, "int64": torch.int64}[dtype]
+    shape = (n, d.out_h, d.out_w)
+    if fill is None:
+        out = torch.empty(shape, dtype=tdt, device=dev)
+    elif tdt == getattr(torch, "uint16", None):  # (torch.full has no uint16 kernel: fill the same bits as int16)
+        out = torch.full(shape, int(np.array(fill, np.uint16).view(np.int16)), dtype=torch.int16, device=dev).view(tdt)
+    else:
+        out = torch.full(shape, fill, dtype=tdt, device=dev)
+    torch.cuda.synchronize(dev)  # the fill runs on torch's stream, the library on its own
+    ins = [_u8(x) for x in datas]
+    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
+    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
+    bx = None
+    if boxes is not None:
+        bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
+    status = (C.c_uint32 * n)()
+    infos = (PngInfo * n)()
+    rc = L.debig_png_decode_batch_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n, 0, C.byref(d))
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"debig_png_decode_batch_labels rejected its arguments ({rc})")
+    N.check(rc, "debig_png_decode_batch_labels")
     return [int(s) for s in status], out, [_info_dict(i) for i in infos]
 
 

@@ -16,6 +16,7 @@
 #include "png_spec_kernel.inc"
 #include "apng_kernel.inc"
 #include "png_resize_kernel.inc"
+#include "png_label_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -734,6 +735,17 @@ int debig_hip_png_spec_defilter_planar_batch(void *d_arena, void *d_out_arena, c
     return (int)hipGetLastError();
 }
 
+// ... and to raw labels (palette indices, grey samples as stored): colour types 3 and 0 only
+int debig_hip_png_spec_defilter_index_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
+                                            debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
+{
+    if (n == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    hipLaunchKernelGGL(debig_png_spec_defilter_index_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
+                       (uint8_t *)d_arena, (uint8_t *)d_out_arena, d_tasks, d_results, n);
+    return (int)hipGetLastError();
+}
+
 // APNG compositing (apng_kernel.inc): one workgroup of 256 lanes per canvas slice; the grid is capped, the kernel loops
 int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena, const debig_apng_task *d_tasks,
                                    uint32_t n_tasks, void *hip_stream)
@@ -779,6 +791,19 @@ int debig_hip_png_resize_cubic_batch(const void *d_src_arena, void *d_out, const
     const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
     hipLaunchKernelGGL(debig_png_resize_cubic_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
+    return (int)hipGetLastError();
+}
+
+// crop + nearest pick + remap + widening of raw labels (png_label_kernel.inc): one workgroup of 256 lanes per run of output
+// rows; the same grid rule
+int debig_hip_png_label_gather_batch(const void *d_src_arena, void *d_out, const debig_png_label_task *d_tasks,
+                                     const void *d_tables, const int32_t *d_lut, uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_label_gather_kernel, dim3(grid), dim3(LBL_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_lut, n_tasks);
     return (int)hipGetLastError();
 }
 

@@ -1,8 +1,10 @@
 /*
  * debig_png_info_get / debig_png_decode_batch / debig_png_decode_batch_fmt / debig_png_out_layout (include/decode_png.h):
  * every PNG the specification allows, to RGBA8 or to the output format the caller asks for.  Not a reference function.
- * debig_png_decode_batch_tensor (at the end of the file): the same decode into the context's own device arena, then one
+ * debig_png_decode_batch_tensor (towards the end of the file): the same decode into the context's own device arena, then one
  * resize + normalise launch (debig_hip_png_resize_batch) into the caller's dense tensor.
+ * debig_png_decode_batch_labels (at the end of the file): palette indices and raw grey samples into that arena
+ * (debig_hip_png_spec_defilter_index_batch), then one crop + nearest + remap + widen launch (debig_hip_png_label_gather_batch).
  *
  * Host side (plain C): the chunk walk and the rules decided by headers alone.  On the GPU: chunk CRC-32 and the
  * Adler-32 trailer (debig_hip_checksum_batch), the IDAT concatenation (debig_hip_gather), inflate (the batch inflate,
@@ -314,6 +316,7 @@ typedef struct spec_target {
     const uint64_t *d_offs;
     uint64_t own_bytes;        /* != 0: the arena is the context's own (c->rsz_src, reserved here to own_bytes), d_arena unused */
     const uint32_t *pre_status; /* may be NULL; pre_status[i] != 0: file i ends with that status once its walk has filled info */
+    uint32_t labels;           /* != 0 (debig_png_decode_batch_labels): every file through the raw-label de-filter kernel */
 } spec_target;
 
 typedef int (*spec_launch_fn)(void *, void *, const debig_png_spec_task *, debig_png_spec_result *, uint32_t, void *);
@@ -362,11 +365,11 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
      *      (+ 16 readable bytes), the palette and the scratch rings of its general-kernel tasks; pixels (c->rgba, each
      *      image 16-byte aligned), or the caller's device arena */
     uint64_t files_total = 0, in_total = 0, out_total = 64, rgba_total = 0;
-    uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0, cnt[3] = {0, 0, 0}; /* cnt: tasks per de-filter kernel */
+    uint32_t n_chunks = 0, n_pieces = 0, n_tasks = 0, n_img = 0, cnt[4] = {0, 0, 0, 0}; /* cnt: tasks per de-filter kernel */
     for (uint32_t k = 0; k < m; k++) {
         spec_file *f = &F[live[k]];
         const uint32_t ct = f->info.color_type;
-        f->general = spec_is_general(f, flags);
+        f->general = tg->labels || spec_is_general(f, flags);
         f->file_off = files_total;
         files_total += debig_align16(input_sizes[live[k]]) + 16;
         f->in_off = in_total;
@@ -384,7 +387,7 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
             uint32_t nt;
             out_total += spec_general_scratch(&f->info, f->info.width, f->info.height, &nt);
             n_tasks += nt;
-            cnt[f->planar ? 2 : f->fmt ? 1 : 0] += nt;
+            cnt[tg->labels ? 3 : f->planar ? 2 : f->fmt ? 1 : 0] += nt;
         } else {
             n_img++;
         }
@@ -504,12 +507,13 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
     if (m == 0) goto report;
     /* ---- de-filter: tuned kernels for non-interlaced 8-bit RGB / RGBA to interleaved RGBA8; the general kernel for the
      *      rest of interleaved RGBA8 (tasks [0, cnt[0])), its output-format twin for every other interleaved format (the
-     *      next cnt[1]) and the planar kernel for every channel-planar image of more than one channel (the last cnt[2]) */
-    static const spec_launch_fn launch[3] = {debig_hip_png_spec_defilter_batch, debig_hip_png_spec_defilter_fmt_batch,
-                                             debig_hip_png_spec_defilter_planar_batch};
+     *      next cnt[1]) and the planar kernel for every channel-planar image of more than one channel (the next cnt[2]);
+     *      in a label call every file is general and goes to the raw-label kernel (cnt[3], the other three empty) */
+    static const spec_launch_fn launch[4] = {debig_hip_png_spec_defilter_batch, debig_hip_png_spec_defilter_fmt_batch,
+                                             debig_hip_png_spec_defilter_planar_batch, debig_hip_png_spec_defilter_index_batch};
     void *pix = tg->outs ? c->rgba.ptr : tg->own_bytes ? c->rsz_src.ptr : tg->d_arena;
-    const uint32_t base[3] = {0, cnt[0], cnt[0] + cnt[1]};
-    uint32_t fill[3] = {0, 0, 0};
+    const uint32_t base[4] = {0, cnt[0], cnt[0] + cnt[1], cnt[0] + cnt[1] + cnt[2]};
+    uint32_t fill[4] = {0, 0, 0, 0};
     n_img = 0;
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = live[k];
@@ -525,8 +529,8 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
             img_file[n_img++] = i;
             continue;
         }
-        if (ct == 3 && (rc = debig_hip_memcpy_h2d((uint8_t *)c->out.ptr + f->pal_off, f->pal, 1024, NULL))) goto done;
-        const uint32_t cls = f->planar ? 2u : f->fmt ? 1u : 0u, t0 = base[cls] + fill[cls];
+        if (ct == 3 && !tg->labels && (rc = debig_hip_memcpy_h2d((uint8_t *)c->out.ptr + f->pal_off, f->pal, 1024, NULL))) goto done;
+        const uint32_t cls = tg->labels ? 3u : f->planar ? 2u : f->fmt ? 1u : 0u, t0 = base[cls] + fill[cls];
         const uint32_t nt = spec_image_tasks(f, f->info.width, f->info.height, f->out_off, f->rgba_off, f->scratch_off, &tasks[t0]);
         for (uint32_t j = 0; j < nt; j++) task_file[t0 + j] = i;
         fill[cls] += nt;
@@ -540,11 +544,11 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
             (rc = debig_hip_memcpy_d2h(ires, c->imgres.ptr, (uint64_t)n_img * sizeof(debig_png_result), NULL)))
             goto done;
     }
-    if ((fill[0] || fill[1] || fill[2]) && /* the task lists in one buffer, reserved before any launch */
+    if ((fill[0] || fill[1] || fill[2] || fill[3]) && /* the task lists in one buffer, reserved before any launch */
         ((rc = debig_devbuf_reserve(&c->spec_tasks, (uint64_t)(n_tasks + 1u) * sizeof(debig_png_spec_task))) ||
          (rc = debig_devbuf_reserve(&c->spec_res, (uint64_t)(n_tasks + 1u) * sizeof(debig_png_spec_result)))))
         goto done;
-    for (uint32_t cls = 0; cls < 3; cls++) {
+    for (uint32_t cls = 0; cls < 4; cls++) {
         if (!fill[cls]) continue;
         debig_png_spec_task *d_t = (debig_png_spec_task *)c->spec_tasks.ptr + base[cls];
         debig_png_spec_result *d_r = (debig_png_spec_result *)c->spec_res.ptr + base[cls];
@@ -556,7 +560,7 @@ static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_
     if ((rc = debig_hip_stream_sync(NULL))) goto done;
     for (uint32_t k = 0; k < n_img; k++)
         if (!ires[k].good) F[img_file[k]].status = DEBIG_PNG_E_FILTER;
-    for (uint32_t cls = 0; cls < 3; cls++)
+    for (uint32_t cls = 0; cls < 4; cls++)
         for (uint32_t j = 0; j < fill[cls]; j++) { /* a filter error anywhere in the image outranks a palette error */
             const uint32_t k = base[cls] + j;
             spec_file *f = &F[task_file[k]];
@@ -618,7 +622,7 @@ DEBIG_API int debig_png_decode_batch_layout(const uint8_t *const *inputs, const 
                                             uint32_t flags, uint32_t out_format, uint32_t out_layout)
 {
     if (!fmt_valid(out_format) || out_layout > DEBIG_PNG_LAYOUT_CHW) return DEBIG_PNG_BAD_FORMAT;
-    const spec_target tg = {outs, NULL, NULL, 0, NULL};
+    const spec_target tg = {outs, NULL, NULL, 0, NULL, 0};
     return spec_decode_core(inputs, input_sizes, &tg, out_caps, status, infos, n, flags, out_format, out_layout);
 }
 
@@ -653,7 +657,7 @@ DEBIG_API int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uin
     for (uint32_t k = 0; k + 1 < r; k++) bad |= reg[k].off + reg[k].cap > reg[k + 1].off;
     free(reg);
     if (bad) return DEBIG_PNG_BAD_ARG;
-    const spec_target tg = {NULL, d_out_arena, out_offs, 0, NULL};
+    const spec_target tg = {NULL, d_out_arena, out_offs, 0, NULL, 0};
     return spec_decode_core(inputs, input_sizes, &tg, out_caps, status, infos, n, flags, out_format, out_layout);
 }
 
@@ -904,7 +908,7 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
         total += debig_align16(sz) + 16;
     }
     {
-        const spec_target tg = {NULL, NULL, offs, total + 64, pre};
+        const spec_target tg = {NULL, NULL, offs, total + 64, pre, 0};
         if ((rc = spec_decode_core(inputs, input_sizes, &tg, caps, status, inf, n, flags, fmt, DEBIG_PNG_LAYOUT_HWC))) goto done;
     }
     if (infos) memcpy(infos, inf, (size_t)n * sizeof(debig_png_info));
@@ -1080,4 +1084,158 @@ DEBIG_API int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs,
     if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
                        filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR);
+}
+
+/* ---- debig_png_decode_batch_labels: palette indices / raw grey samples -> one dense integer class-map tensor (decode_png.h) - */
+
+#define LBL_TASK_ELEMS 16384u /* output elements of one gather task (a run of whole rows; one row when it is wider) */
+
+/* the index table of one axis (crop length cl -> L outputs: ((2X + 1) cl) div 2L, 64-bit on the host) appended to *buf,
+ * 16-byte aligned; one table per distinct cl.  -> its offset, or UINT64_MAX (out of memory) */
+typedef struct lbl_axis { uint32_t cl; uint64_t off; } lbl_axis;
+typedef struct lbl_tables { uint32_t *buf; uint64_t len, cap; /* in uint32 */ lbl_axis *ax; uint32_t n_ax, cap_ax, L; } lbl_tables;
+static uint64_t lbl_axis_get(lbl_tables *T, uint32_t cl)
+{
+    for (uint32_t k = 0; k < T->n_ax; k++)
+        if (T->ax[k].cl == cl) return T->ax[k].off;
+    if (!grow((void **)&T->ax, &T->cap_ax, T->n_ax, sizeof(lbl_axis))) return UINT64_MAX;
+    const uint64_t words = ((uint64_t)T->L + 3u) & ~(uint64_t)3u;
+    if (T->len + words > T->cap) {
+        uint64_t nc = T->cap ? T->cap : 1024;
+        while (nc < T->len + words) nc *= 2;
+        uint32_t *q = (uint32_t *)realloc(T->buf, nc * sizeof(uint32_t));
+        if (!q) return UINT64_MAX;
+        T->buf = q;
+        T->cap = nc;
+    }
+    uint32_t *t = T->buf + T->len;
+    for (uint64_t X = 0; X < words; X++) t[X] = X < T->L ? (uint32_t)(((2u * X + 1u) * cl) / (2u * (uint64_t)T->L)) : 0u;
+    T->ax[T->n_ax].cl = cl;
+    T->ax[T->n_ax].off = T->len * sizeof(uint32_t);
+    T->n_ax++;
+    T->len += words;
+    return T->ax[T->n_ax - 1].off;
+}
+
+DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                            const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                            uint32_t flags, const debig_png_label_desc *desc)
+{
+    /* the arguments on their own, before any file is looked at */
+    if (n == 0) return 0;
+    if (!desc || !d_out || ((uintptr_t)d_out & 15u)) return DEBIG_PNG_BAD_ARG;
+    if (desc->out_w == 0 || desc->out_w > 16384u || desc->out_h == 0 || desc->out_h > 16384u || desc->dtype > DEBIG_PNG_L_I64 ||
+        desc->reserved != 0)
+        return DEBIG_PNG_BAD_ARG;
+    if (desc->lut && desc->dtype <= DEBIG_PNG_L_U16)
+        for (uint32_t k = 0; k < 256; k++)
+            if (desc->lut[k] < 0 || desc->lut[k] > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)) return DEBIG_PNG_BAD_ARG;
+    const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
+    const uint64_t slot = (uint64_t)H * W * es;
+
+    uint32_t *pre = (uint32_t *)calloc(n, sizeof(uint32_t));
+    uint64_t *offs = (uint64_t *)calloc(n, sizeof(uint64_t)), *caps = (uint64_t *)calloc(n, sizeof(uint64_t));
+    debig_png_box *box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
+    debig_png_info *inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
+    debig_png_label_task *tasks = NULL;
+    lbl_tables TX = {NULL, 0, 0, NULL, 0, 0, W}, TY = {NULL, 0, 0, NULL, 0, 0, H};
+    int rc = 2;
+    if (!pre || !offs || !caps || !box || !inf) goto done;
+    /* ---- IHDR: E_LABEL, then the box; the image's place in the context's arena */
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        spec_file f0;
+        memset(&f0, 0, sizeof f0);
+        const uint32_t st = spec_walk(inputs[i], input_sizes[i], &f0, 1);
+        spec_free(&f0);
+        offs[i] = total;
+        const uint64_t iw = f0.info.width, ih = f0.info.height;
+        if (iw == 0) continue; /* no valid IHDR: the walk's status stands */
+        const uint32_t ct = f0.info.color_type, d = f0.info.bit_depth;
+        if ((ct != 0 && ct != 3) || (d == 16 && (desc->dtype == DEBIG_PNG_L_U8 || desc->lut))) {
+            pre[i] = DEBIG_PNG_E_LABEL;
+            continue;
+        }
+        debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
+        if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
+        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih) {
+            pre[i] = DEBIG_PNG_E_BOX;
+            continue;
+        }
+        box[i] = b;
+        if (st != DEBIG_PNG_OK) continue;
+        const uint64_t sz = fmt_size(iw, ih, DEBIG_PNG_FMT_GRAY | (d == 16 ? DEBIG_PNG_FMT_16 : DEBIG_PNG_FMT_8));
+        if (sz > RSZ_MAX_IMAGE_BYTES) continue; /* caps[i] stays 0: E_OUTPUT */
+        caps[i] = sz;
+        total += debig_align16(sz) + 16;
+    }
+    {
+        /* one element per pixel, as wide as the file's samples: the size rules of GRAY at the file's own depth */
+        const spec_target tg = {NULL, NULL, offs, total + 64, pre, 1};
+        if ((rc = spec_decode_core(inputs, input_sizes, &tg, caps, status, inf, n, flags,
+                                   DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, DEBIG_PNG_LAYOUT_HWC)))
+            goto done;
+    }
+    if (infos) memcpy(infos, inf, (size_t)n * sizeof(debig_png_info));
+    /* ---- the row runs of every decoded image */
+    const uint32_t run = W >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / W;
+    uint64_t n_tasks = 0;
+    uint32_t cap_tasks = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status[i] != DEBIG_PNG_OK) continue;
+        const uint64_t ox = lbl_axis_get(&TX, box[i].w), oy = lbl_axis_get(&TY, box[i].h);
+        if (ox == UINT64_MAX || oy == UINT64_MAX) { rc = 2; goto done; }
+        const uint32_t sb = inf[i].bit_depth == 16 ? 2u : 1u;
+        for (uint32_t y0 = 0; y0 < H; y0 += run) {
+            if (n_tasks >= 0x7fffffffu) { rc = 2; goto done; }
+            if (!grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof(debig_png_label_task))) { rc = 2; goto done; }
+            debig_png_label_task *t = &tasks[n_tasks++];
+            memset(t, 0, sizeof *t);
+            t->src_off = offs[i] + ((uint64_t)box[i].y * inf[i].width + box[i].x) * sb;
+            t->out_off = (uint64_t)i * slot;
+            t->sx_off = ox; /* (the vertical tables follow the horizontal ones, the LUT comes first: fixed up below) */
+            t->sy_off = oy;
+            t->src_pitch = inf[i].width;
+            t->out_w = W;
+            t->out_h = H;
+            t->row0 = y0;
+            t->rows = H - y0 < run ? H - y0 : run;
+            t->src_bytes = (uint8_t)sb;
+            t->dtype = (uint8_t)desc->dtype;
+        }
+    }
+    rc = 0;
+    if (n_tasks == 0) goto done;
+    {
+        const uint64_t lut_bytes = 1024, tx_bytes = TX.len * sizeof(uint32_t), ty_bytes = TY.len * sizeof(uint32_t);
+        for (uint64_t k = 0; k < n_tasks; k++) {
+            tasks[k].sx_off += lut_bytes;
+            tasks[k].sy_off += lut_bytes + tx_bytes;
+        }
+        debig_ctx *c = debig_ctx_get(0);
+        if (!c) { rc = 1; goto done; }
+        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_label_task))) ||
+            (rc = debig_devbuf_reserve(&c->rsz_weights, lut_bytes + tx_bytes + ty_bytes)) ||
+            (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, tasks, n_tasks * sizeof(debig_png_label_task), NULL)) ||
+            (desc->lut && (rc = debig_hip_memcpy_h2d(c->rsz_weights.ptr, desc->lut, lut_bytes, NULL))) ||
+            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + lut_bytes, TX.buf, tx_bytes, NULL)) ||
+            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + lut_bytes + tx_bytes, TY.buf, ty_bytes, NULL)) ||
+            (rc = debig_hip_png_label_gather_batch(c->rsz_src.ptr, d_out, (const debig_png_label_task *)c->rsz_tasks.ptr,
+                                                   c->rsz_weights.ptr, desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL,
+                                                   (uint32_t)n_tasks, NULL)) ||
+            (rc = debig_hip_stream_sync(NULL)))
+            goto done;
+    }
+done:
+    free(pre);
+    free(offs);
+    free(caps);
+    free(box);
+    free(inf);
+    free(tasks);
+    free(TX.buf);
+    free(TX.ax);
+    free(TY.buf);
+    free(TY.ax);
+    return rc;
 }

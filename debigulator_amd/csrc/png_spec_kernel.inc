@@ -2,7 +2,8 @@
 //
 // Every colour type and bit depth the PNG specification allows, Adam7 passes and tRNS, to RGBA8 (debig_png_spec_defilter_kernel)
 // or to any output format of decode_png.h (debig_png_spec_defilter_fmt_kernel, the same body with another store stage; its
-// channel-planar form is debig_png_spec_defilter_planar_kernel).  One TASK is one
+// channel-planar form is debig_png_spec_defilter_planar_kernel; debig_png_spec_defilter_index_kernel stores raw labels --
+// palette indices and grey samples as stored -- for debig_png_decode_batch_labels).  One TASK is one
 // (image, pass) sub-image (debig_png_spec_task); a non-interlaced image is one task placed at (0, 0, 1, 1).
 //
 // Mapping (what png_kernel.inc measured, generalised to a filter unit of BPP = 1, 2, 3, 4, 6 or 8 bytes):
@@ -398,6 +399,58 @@ DEV_INLINE void spec_out_group(PngSpecOutPlanar, const uint32_t *R, int g, uint3
     spec_fmt_switch<BPP, true>(R, g, w, depth, ct, t, pal, pal_bad, orow, ostep, plane);
 }
 
+// Raw labels (debig_png_spec_defilter_index_kernel, behind debig_png_decode_batch_labels of decode_png.h): colour types 3 and 0
+// only, hence BPP 1 (depths 1..8) or 2 (16-bit grey).  One ELEMENT per pixel -- the palette index or the grey sample as the
+// file stores it, nothing scaled, PLTE colours and tRNS unused -- of one byte for depths up to 8 and one little-endian uint16
+// for depth 16 (spec_out_bytes is the element).  Sub-byte samples are unpacked MSB first by constant shifts; where dx == 1 the
+// elements of a byte (depth < 8) or of the whole group go out as one run (spec_store_pixels), else one by one at the Adam7
+// stride.  The palette is never read: only n_pal bounds the index (pal_bad, as in the other policies).
+struct PngSpecOutIndex {};
+constexpr bool spec_out_rgba8(PngSpecOutIndex) { return false; }
+DEV_INLINE uint32_t spec_out_bytes(PngSpecOutIndex, const debig_png_spec_task &t) { return t.depth == 16u ? 2u : 1u; }
+template <uint32_t DEPTH>
+DEV_INLINE void spec_index_group_sub(const uint32_t *R, int g, uint32_t w, uint32_t lim, uint32_t dx, uint32_t &pal_bad,
+                                     uint8_t *orow, uint64_t ostep)
+{
+    constexpr uint32_t K = PngSpecShape<1>::K, PPB = 8u / DEPTH;
+DEV_UNROLL
+    for (uint32_t j = 0; j < K; j++) {
+        const uint32_t byte = spec_get(R, j, 1u);
+        const uint64_t xb = ((uint64_t)g * K + j) * PPB;
+        if (xb >= w) break;
+        uint32_t s[PPB];
+DEV_UNROLL
+        for (uint32_t k = 0; k < PPB; k++) {
+            s[k] = (byte >> (8u - DEPTH * (k + 1u))) & ((1u << DEPTH) - 1u);
+            pal_bad |= xb + k < w && s[k] >= lim ? 1u : 0u;
+        }
+        spec_store_pixels<1u, PPB>(orow, xb, w, ostep, dx, s, s);
+    }
+}
+template <int BPP>
+DEV_INLINE void spec_out_group(PngSpecOutIndex, const uint32_t *R, int g, uint32_t w, uint32_t depth, uint32_t ct,
+                               const debig_png_spec_task &t, const uint32_t *, uint32_t &pal_bad, uint8_t *orow, uint64_t ostep)
+{
+    static_assert(BPP == 1 || BPP == 2, "labels are one sample of at most 16 bits per pixel");
+    constexpr uint32_t K = PngSpecShape<BPP>::K;
+    const uint32_t lim = ct == 3u ? t.n_pal : 0x10000u; /* grey samples have no bound */
+    if (BPP == 1 && depth < 8u) {
+        if (depth == 1u) spec_index_group_sub<1u>(R, g, w, lim, t.dx, pal_bad, orow, ostep);
+        else if (depth == 2u) spec_index_group_sub<2u>(R, g, w, lim, t.dx, pal_bad, orow, ostep);
+        else spec_index_group_sub<4u>(R, g, w, lim, t.dx, pal_bad, orow, ostep);
+        return;
+    }
+    const uint64_t x = (uint64_t)g * K;
+    uint32_t s[K];
+DEV_UNROLL
+    for (uint32_t j = 0; j < K; j++) {
+        const uint32_t u = spec_get(R, j * (uint32_t)BPP, (uint32_t)BPP);
+        s[j] = BPP == 2 ? ((u & 0xffu) << 8) | (u >> 8) : u; /* the stream is big-endian */
+        pal_bad |= x + j < w && s[j] >= lim ? 1u : 0u;
+    }
+    spec_store_pixels<(uint32_t)BPP, K>(orow, x, w, ostep, t.dx, s, s);
+}
+
 template <int BPP, class O>
 DEV_INLINE void png_spec_task(PngSpecLds &L, uint8_t *__restrict__ arena, uint8_t *__restrict__ rgba_arena,
                               const debig_png_spec_task &t, const uint32_t tid)
@@ -630,4 +683,33 @@ debig_png_spec_defilter_planar_kernel(uint8_t *__restrict__ arena, uint8_t *__re
 {
     __shared__ PngSpecLds L;
     png_spec_tasks<PngSpecOutPlanar>(L, arena, out_arena, tasks, results, n_tasks);
+}
+
+// ... and to raw labels (PngSpecOutIndex): colour types 3 and 0 only, so the body is instantiated for the filter units 1 and 2
+// alone and the palette is not staged; every other task fails with the internal guard.  A kernel of its own once more: the
+// kernels above keep their code, registers and occupancy.
+__global__ void __launch_bounds__(64 * PNG_SPEC_NWD)
+debig_png_spec_defilter_index_kernel(uint8_t *__restrict__ arena, uint8_t *__restrict__ out_arena,
+                                     const debig_png_spec_task *__restrict__ tasks, debig_png_spec_result *__restrict__ results,
+                                     uint32_t n_tasks)
+{
+    __shared__ PngSpecLds L;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = blockIdx.x; k < n_tasks; k += gridDim.x) {
+        const debig_png_spec_task t = tasks[k];
+        if (tid < PNG_SPEC_NWD) L.progress[tid] = 0u;
+        if (tid == 0) { L.first_bad = 0xffffffffu; L.pal_bad = 0u; }
+        __syncthreads();
+        const bool label = (t.color_type == 0u || t.color_type == 3u) && t.channels == 1u; /* workgroup-uniform */
+        if (label && t.bpp_f == 1u && t.depth <= 8u) png_spec_task<1, PngSpecOutIndex>(L, arena, out_arena, t, tid);
+        else if (label && t.bpp_f == 2u && t.depth == 16u) png_spec_task<2, PngSpecOutIndex>(L, arena, out_arena, t, tid);
+        else if (tid == 0) L.first_bad = 0xfffffffeu;
+        __syncthreads();
+        if (tid == 0) {
+            const uint32_t fb = L.first_bad;
+            results[k].status = fb != 0xffffffffu ? DEBIG_PNG_SPEC_E_FILTER : L.pal_bad ? DEBIG_PNG_SPEC_E_PALETTE : 0u;
+            results[k].bad_row = fb;
+        }
+        __syncthreads();
+    }
 }

@@ -337,6 +337,14 @@ int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, cons
 int debig_hip_png_spec_defilter_planar_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
                                              debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
 
+/* The same tasks to raw labels (debig_png_spec_defilter_index_kernel, behind debig_png_decode_batch_labels in decode_png.h):
+ * colour types 3 and 0 only (any other task fails as if its filter byte were bad).  One element per pixel at
+ * rgba_off + ((y0 + y dy) * img_width + x0 + x dx) * element size: the palette index or the grey sample as stored, one byte
+ * for depths up to 8, one little-endian uint16 for depth 16 -- the element size follows from `depth`.  pal_off, key, has_key
+ * and out_fmt are not read; an index >= n_pal still fails the task with DEBIG_PNG_SPEC_E_PALETTE. */
+int debig_hip_png_spec_defilter_index_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
+                                            debig_png_spec_result *d_results, uint32_t n, void *hip_stream);
+
 /* APNG compositing (csrc/apng_kernel.inc, behind debig_apng_decode_batch in decode_png.h).  One frame of a file: its
  * RGBA8 pixels (width * height dwords, rows without padding) and its place on the canvas. */
 typedef struct debig_apng_frame_desc {
@@ -443,6 +451,28 @@ typedef struct debig_png_resize_cubic_task {
 } debig_png_resize_cubic_task;
 int debig_hip_png_resize_cubic_batch(const void *d_src_arena, void *d_out, const debig_png_resize_cubic_task *d_tasks,
                                      const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
+/* Crop + nearest pick + remap + widening of raw labels (csrc/png_label_kernel.inc, behind debig_png_decode_batch_labels in
+ * decode_png.h).  One task: the output rows [row0, row0 + rows) of one image, one workgroup of 256 lanes.  Element (X, Y) of
+ * the image is the source label at sy[Y] * src_pitch + sx[X] (counted in labels from src_off), through the call's LUT when it
+ * has one, stored as `dtype`.  A task that breaks a bound -- sizes, a table offset that is not a multiple of 16, a dtype of
+ * one byte or a LUT with two-byte labels -- is skipped. */
+typedef struct debig_png_label_task {
+    uint64_t src_off;        /* label (0, 0) of the CROP, in bytes rel. to d_src_arena (aligned to src_bytes)                 */
+    uint64_t out_off;        /* the image's slot, in bytes rel. to d_out (aligned to the element size)                        */
+    uint64_t sx_off, sy_off; /* out_w / out_h uint32 indices inside the crop, in bytes rel. to d_tables (16-byte aligned)     */
+    uint32_t src_pitch;      /* labels from one source row to the next (the image's width)                                    */
+    uint32_t out_w, out_h;   /* 1 .. 16384                                                                                    */
+    uint32_t row0, rows;     /* row0 + rows <= out_h                                                                          */
+    uint8_t src_bytes;       /* 1, or 2 (little-endian uint16)                                                                */
+    uint8_t dtype;           /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                       */
+    uint16_t reserved;
+} debig_png_label_task;
+/* Gather n_tasks row runs (device pointers, asynchronous on hip_stream).  d_lut: 256 int32 in device memory, staged in LDS
+ * once per workgroup, or NULL (the element is the label itself; two-byte labels need NULL).  Nothing but the tasks' own
+ * output elements is written. */
+int debig_hip_png_label_gather_batch(const void *d_src_arena, void *d_out, const debig_png_label_task *d_tasks,
+                                     const void *d_tables, const int32_t *d_lut, uint32_t n_tasks, void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

@@ -347,6 +347,48 @@ int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs, const uin
 uint32_t debig_png_resize_weights_filter(uint32_t filter, uint32_t cl, uint32_t L, uint32_t antialias, uint32_t X,
                                          uint32_t *first, int16_t *w, uint32_t w_cap);
 
+/* ---- label maps: palette indices and raw grey samples as one integer class-map tensor -------------------------------------
+ * Segmentation masks come as palette PNGs or as 1/2/4/8/16-bit grey PNGs, and what a trainer needs from them is the palette
+ * index or the grey sample itself -- which every call above destroys (a palette pixel goes through PLTE, 1/2/4-bit grey is
+ * scaled by 255/85/17, 16-bit grey keeps its high byte).  debig_png_decode_batch_labels: bytes of n PNG files in, one dense
+ * (n, out_h, out_w) tensor of `dtype` in device memory out; image i at (uint8_t *)d_out + i * out_h * out_w * sizeof(element),
+ * no padding.  The call returns after the work has finished.
+ *   - The label of a source pixel: colour type 3: the palette index (depths 1, 2, 4, 8); colour type 0: the raw sample as an
+ *     unsigned number (depths 1, 2, 4, 8, 16).  Nothing is scaled; PLTE colours and any tRNS are ignored (infos[i].has_trns is
+ *     still what debig_png_info_get reports); Adam7 files give the labels of their non-interlaced twins.
+ *   - Geometry: the crop is boxes[i] with the box rules of debig_png_decode_batch_tensor (crop cw x chh at (bx, by)); output
+ *     (X, Y) takes the source pixel (bx + ((2X + 1) cw) div 2 out_w, by + ((2Y + 1) chh) div 2 out_h) -- exactly the tap of
+ *     DEBIG_PNG_FILTER_NEAREST, so a mask decoded here and an image decoded by debig_png_decode_batch_tensor_filter with the
+ *     same box share one grid, whatever filter the image uses.
+ *   - Value: lut[label] with a lut (256 int32 in HOST memory, read before the call returns), else the label; stored as dtype
+ *     (int32 / int64 sign-extend a negative lut entry, e.g. an ignore index of -1).
+ * The labels are de-filtered into the library's own device arena, one element per pixel (debig_hip_png_spec_defilter_index_batch:
+ * every label file goes through it, none through the tuned kernels), then ONE launch crops, picks, remaps and widens all images
+ * (debig_hip_png_label_gather_batch).
+ * Checked first, before any file is looked at (status unwritten, DEBIG_PNG_BAD_ARG): desc or d_out NULL with n > 0, d_out not
+ * 16-byte aligned, out_w or out_h 0 or above 16384, an unknown dtype, reserved != 0, a lut entry outside the dtype's range
+ * (U8: 0 .. 255, U16: 0 .. 65535).  flags keeps its meaning (DEBIG_PNG_FORCE_GENERAL is accepted and changes nothing here).
+ * Per image: the chunk walk's statuses first; as soon as IHDR has been read DEBIG_PNG_E_LABEL is decided -- colour type 2, 4
+ * or 6; a 16-bit file with dtype U8; a 16-bit file with a lut -- then DEBIG_PNG_E_BOX, and both outrank anything found later in
+ * the file; then the statuses of debig_png_decode_batch_fmt in their order (E_PALETTE for an index >= the PLTE entries stays,
+ * found on the GPU; E_OUTPUT: the raw labels are larger than 2^31 bytes).  A file with a non-zero status leaves its slot
+ * untouched; nothing outside d_out[0 .. n * slot) is written.
+ * Not provided: label output to host buffers or at each file's own size, colour -> class lookup for RGB-coded masks, LUTs for
+ * 16-bit sources, boundary / ignore-ring generation, flips, animated PNGs, inputs already on the device, an asynchronous
+ * variant. */
+#define DEBIG_PNG_E_LABEL 15 /* not a label file for this call (rules above) */
+enum { DEBIG_PNG_L_U8 = 0, DEBIG_PNG_L_U16 = 1, DEBIG_PNG_L_I32 = 2, DEBIG_PNG_L_I64 = 3 };
+typedef struct debig_png_label_desc {
+    uint32_t out_w, out_h;   /* 1 .. 16384 */
+    uint32_t dtype;          /* DEBIG_PNG_L_* */
+    uint32_t reserved;       /* 0 */
+    const int32_t *lut;      /* host memory, 256 entries, or NULL */
+} debig_png_label_desc;
+int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                  const debig_png_box *boxes /* may be NULL */, uint32_t *status,
+                                  debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                  const debig_png_label_desc *desc);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

@@ -17,6 +17,7 @@
 #include "../../debigulator_amd/csrc/png_spec_kernel.inc"
 #include "../../debigulator_amd/csrc/apng_kernel.inc"
 #include "../../debigulator_amd/csrc/png_resize_kernel.inc"
+#include "../../debigulator_amd/csrc/png_label_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -321,6 +322,14 @@ extern "C" int emu_png_spec_defilter_planar_batch(void *arena, void *out_arena, 
     return 0;
 }
 
+/* ... and the raw-label one (palette indices, grey samples as stored), as debig_hip_png_spec_defilter_index_batch launches it */
+extern "C" int emu_png_spec_defilter_index_batch(void *arena, void *out_arena, const debig_png_spec_task *tasks,
+                                                 debig_png_spec_result *results, uint32_t n)
+{
+    if (n) EMU_LAUNCH(debig_png_spec_defilter_index_kernel, n, 64 * PNG_SPEC_NWD, (uint8_t *)arena, (uint8_t *)out_arena, tasks, results, n);
+    return 0;
+}
+
 /* APNG compositing (apng_kernel.inc) as debig_hip_apng_composite_batch launches it (grid: 0 = one workgroup per task,
  * else fewer workgroups that loop over the tasks) */
 extern "C" int emu_apng_composite_batch(const void *frames_arena, void *out_arena, const debig_apng_task *tasks, uint32_t n,
@@ -359,5 +368,16 @@ extern "C" int emu_png_resize_cubic_batch(const void *src_arena, void *out, cons
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_resize_cubic_kernel, grid, RSZ_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
                       (const uint8_t *)weights, n);
+    return 0;
+}
+
+/* crop + nearest pick + remap + widening of raw labels (png_label_kernel.inc) as debig_hip_png_label_gather_batch launches it
+ * (lut: 256 int32 or NULL; grid: 0 = one workgroup per task, else fewer workgroups that loop over the tasks) */
+extern "C" int emu_png_label_gather_batch(const void *src_arena, void *out, const debig_png_label_task *tasks, const void *tables,
+                                          const int32_t *lut, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_gather_kernel, grid, LBL_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)tables, lut, n);
     return 0;
 }
