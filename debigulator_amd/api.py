@@ -657,6 +657,133 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     return [int(s) for s in status], out, [_info_dict(i) for i in infos]
 
 
+class PngColorMap(C.Structure):  # include/decode_png.h: debig_png_color_map
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("keys", C.POINTER(C.c_uint32)), ("values", C.POINTER(C.c_int32))]
+
+
+class PngColorLabelDesc(C.Structure):  # include/decode_png.h: debig_png_color_label_desc
+    _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("dtype", C.c_uint32), ("mode", C.c_uint32), ("missing", C.c_int32),
+                ("n_maps", C.c_uint32), ("maps", C.POINTER(PngColorMap)), ("reserved", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+PNG_CL_PACK, PNG_CL_MAP = 0, 1  # include/decode_png.h: DEBIG_PNG_CL_*
+PNG_CMAP_MAX = 2048  # DEBIG_PNG_CMAP_MAX
+
+
+def png_pack_rgb(rgb):
+    """(..., 3) integers R, G, B in 0 .. 255 -> the packed colours R | G << 8 | B << 16 the colour-label call looks up"""
+    a = np.asarray(rgb)
+    if a.ndim < 1 or a.shape[-1] != 3 or a.dtype.kind not in "iu":
+        raise ValueError("colours need a last axis of 3 integers")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 255):
+        raise ValueError("colour components must lie in 0 .. 255")
+    a = a.astype(np.uint32)
+    return a[..., 0] | (a[..., 1] << 8) | (a[..., 2] << 16)
+
+
+def _png_color_map_arrays(colors):
+    """one map -- a dict {(r, g, b): value} or a pair (keys, values), keys packed or (m, 3) RGB -> (uint32 keys, int32 values);
+    what the arrays hold (range, distinct keys, the size limit) is the C call's to judge"""
+    if isinstance(colors, dict):
+        keys = png_pack_rgb(np.array(list(colors.keys()), dtype=np.int64).reshape(len(colors), 3))
+        values = np.array(list(colors.values()))
+    elif isinstance(colors, tuple) and len(colors) == 2:
+        keys, values = np.asarray(colors[0]), np.asarray(colors[1])
+        if keys.ndim == 2:
+            keys = png_pack_rgb(keys)
+    else:
+        raise ValueError("a colour map is a dict {(r, g, b): value} or a pair (keys, values)")
+    if keys.ndim != 1 or values.shape != keys.shape or (keys.size and (keys.dtype.kind not in "iu" or values.dtype.kind not in "iu")):
+        raise ValueError("a colour map needs as many integer values as keys")
+    if keys.size and (int(keys.min()) < 0 or int(keys.max()) > 0xFFFFFFFF or int(values.min()) < -2 ** 31 or int(values.max()) > 2 ** 31 - 1):
+        raise ValueError("colour keys are uint32 and values int32")
+    return np.ascontiguousarray(keys, dtype=np.uint32), np.ascontiguousarray(values, dtype=np.int32)
+
+
+def png_color_label_desc(size, colors=None, missing=-1, dtype="int64", n=None):
+    """the debig_png_color_label_desc of png_decode_batch_color_labels' arguments (no GPU needed) -> (desc, element bytes).
+    colors: None (PACK), one map, or a list of n maps (n: the number of files).  The desc keeps the arrays alive (desc._keep)."""
+    if dtype not in PNG_LABEL_DTYPES:
+        raise ValueError(f"dtype must be one of {sorted(PNG_LABEL_DTYPES)}, not {dtype!r}")
+    H, W = (int(v) for v in size)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"size must be (H, W) with 1 <= H, W <= 16384, not {size!r}")
+    d = PngColorLabelDesc(out_w=W, out_h=H, dtype=PNG_LABEL_DTYPES[dtype], mode=PNG_CL_PACK)
+    if colors is None:
+        if dtype not in ("int32", "int64"):
+            raise ValueError("packed colours (colors=None) need dtype 'int32' or 'int64'")
+        return d, 1 << PNG_LABEL_DTYPES[dtype]
+    if isinstance(colors, list):
+        if n is None or len(colors) != n:
+            raise ValueError("a list of colour maps needs one map per file")
+        maps = [_png_color_map_arrays(m) for m in colors]
+    else:
+        maps = [_png_color_map_arrays(colors)]
+    if not -2 ** 31 <= int(missing) <= 2 ** 31 - 1:
+        raise ValueError("missing must be an int32")
+    arr = (PngColorMap * max(len(maps), 1))()
+    for m, (k, v) in zip(arr, maps):
+        m.n = len(k)
+        m.keys = k.ctypes.data_as(C.POINTER(C.c_uint32))
+        m.values = v.ctypes.data_as(C.POINTER(C.c_int32))
+    d._keep = (arr, maps)
+    d.mode, d.missing, d.n_maps, d.maps = PNG_CL_MAP, int(missing), len(maps), arr
+    return d, 1 << PNG_LABEL_DTYPES[dtype]
+
+
+def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="int64", boxes=None, fill=None, device="cuda:0"):
+    """bytes of N colour-coded label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
+    debig_png_decode_batch_color_labels) -> (statuses, tensor, infos, unmatched).  The colour of a pixel is what
+    png_decode_batch(mode="rgb") gives for it (palette files through PLTE, grey replicated, alpha and tRNS dropped), packed as
+    R | G << 8 | B << 16.  colors=None: the element is the packed colour itself (COCO panoptic's rgb2id; dtype "int32" or
+    "int64").  colors = a dict {(r, g, b): value} or a pair (keys, values) -- keys packed, or (m, 3) RGB; at most 2048 distinct
+    colours --: the element is the colour's value, or `missing`; a list of N of those gives every file its own map (COCO
+    panoptic's per-image segment id -> category tables, with keys packed as the segment ids are).  unmatched[i]: how many
+    elements of image i took `missing`.  size, boxes, fill, dtype, the device rule and the grid are those of
+    png_decode_batch_labels; 16-bit files have status 15 ("label")."""
+    import torch
+
+    n = len(datas)
+    d, es = png_color_label_desc(size, colors, missing, dtype, n)
+    L = _png_spec_lib()
+    L.debig_png_decode_batch_color_labels.restype = C.c_int
+    L.debig_png_decode_batch_color_labels.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device must be a GPU, not {device!r}")
+    L.debig_hip_get_device.restype = C.c_int
+    cur = L.debig_hip_get_device()
+    if dev.index is not None and dev.index != cur:
+        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
+    dev = torch.device("cuda", cur)
+    if boxes is not None and len(boxes) != n:
+        raise ValueError("boxes needs one entry (or None) per file")
+    tdt = {"uint8": torch.uint8, "uint16": getattr(torch, "uint16", torch.int16), "int32": torch.int32, "int64": torch.int64}[dtype]
+    shape = (n, d.out_h, d.out_w)
+    if fill is None:
+        out = torch.empty(shape, dtype=tdt, device=dev)
+    elif tdt == getattr(torch, "uint16", None):  # (torch.full has no uint16 kernel: fill the same bits as int16)
+        out = torch.full(shape, int(np.array(fill, np.uint16).view(np.int16)), dtype=torch.int16, device=dev).view(tdt)
+    else:
+        out = torch.full(shape, fill, dtype=tdt, device=dev)
+    torch.cuda.synchronize(dev)  # the fill runs on torch's stream, the library on its own
+    ins = [_u8(x) for x in datas]
+    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
+    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
+    bx = None
+    if boxes is not None:
+        bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
+    status = (C.c_uint32 * n)()
+    infos = (PngInfo * n)()
+    unmatched = (C.c_uint32 * n)()
+    rc = L.debig_png_decode_batch_color_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, unmatched, n, 0,
+                                               C.byref(d))
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"debig_png_decode_batch_color_labels rejected its arguments ({rc})")
+    N.check(rc, "debig_png_decode_batch_color_labels")
+    return [int(s) for s in status], out, [_info_dict(i) for i in infos], [int(u) for u in unmatched]
+
+
 class ApngFrame(C.Structure):  # include/decode_png.h: debig_apng_frame
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("x_off", C.c_uint32), ("y_off", C.c_uint32),
                 ("delay_num", C.c_uint16), ("delay_den", C.c_uint16), ("dispose_op", C.c_uint8), ("blend_op", C.c_uint8),

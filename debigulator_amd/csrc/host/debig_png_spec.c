@@ -5,6 +5,8 @@
  * resize + normalise launch (debig_hip_png_resize_batch) into the caller's dense tensor.
  * debig_png_decode_batch_labels (at the end of the file): palette indices and raw grey samples into that arena
  * (debig_hip_png_spec_defilter_index_batch), then one crop + nearest + remap + widen launch (debig_hip_png_label_gather_batch).
+ * debig_png_decode_batch_color_labels (after it): RGB8 into that arena, then one crop + nearest + pack + colour lookup + widen
+ * launch (debig_hip_png_color_label_batch).
  *
  * Host side (plain C): the chunk walk and the rules decided by headers alone.  On the GPU: chunk CRC-32 and the
  * Adler-32 trailer (debig_hip_checksum_batch), the IDAT concatenation (debig_hip_gather), inflate (the batch inflate,
@@ -1228,6 +1230,211 @@ DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const 
     }
 done:
     free(pre);
+    free(offs);
+    free(caps);
+    free(box);
+    free(inf);
+    free(tasks);
+    free(TX.buf);
+    free(TX.ax);
+    free(TY.buf);
+    free(TY.ax);
+    return rc;
+}
+
+/* ---- debig_png_decode_batch_color_labels: RGB-coded masks -> one dense integer class-map tensor (decode_png.h) --------------- */
+
+/* the smallest table of a map of n keys (include/debig_hip.h): a power of two, >= 2 n, >= 2 */
+static uint32_t cmap_slots(uint32_t n)
+{
+    uint32_t s = 2;
+    while (s < 2u * n) s *= 2;
+    return s;
+}
+
+DEBIG_API uint32_t debig_png_color_map_table(const debig_png_color_map *map, uint32_t *table, uint32_t cap_slots)
+{
+    if (!map || !table || map->n > DEBIG_PNG_CMAP_MAX || (map->n && (!map->keys || !map->values))) return 0;
+    const uint32_t slots = cmap_slots(map->n);
+    if (slots > cap_slots) return 0;
+    for (uint32_t k = 0; k < map->n; k++)
+        if (map->keys[k] > 0xFFFFFFu) return 0;
+    /* (two equal keys are found while the table fills: it is the caller's only once it is whole) */
+    uint32_t tmp[2u * DEBIG_PNG_CMAP_MAX_SLOTS];
+    for (uint32_t s = 0; s < slots; s++) { tmp[2u * s] = DEBIG_PNG_CMAP_EMPTY; tmp[2u * s + 1u] = 0u; }
+    for (uint32_t k = 0; k < map->n; k++) {
+        const uint32_t key = map->keys[k];
+        uint32_t s = DEBIG_PNG_CMAP_SLOT(key, slots);
+        while (tmp[2u * s] != DEBIG_PNG_CMAP_EMPTY) { /* (n <= slots / 2: an unused slot exists) */
+            if (tmp[2u * s] == key) return 0;
+            s = (s + 1u) & (slots - 1u);
+        }
+        tmp[2u * s] = key;
+        tmp[2u * s + 1u] = (uint32_t)map->values[k];
+    }
+    memcpy(table, tmp, (size_t)slots * 8u);
+    return slots;
+}
+
+DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                  const debig_png_box *boxes, uint32_t *status, debig_png_info *infos,
+                                                  uint32_t *unmatched, uint32_t n, uint32_t flags,
+                                                  const debig_png_color_label_desc *desc)
+{
+    /* the arguments on their own, before any file is looked at: the label call's, then the mode's and the maps' */
+    if (n == 0) return 0;
+    if (!desc || !d_out || ((uintptr_t)d_out & 15u)) return DEBIG_PNG_BAD_ARG;
+    if (desc->out_w == 0 || desc->out_w > 16384u || desc->out_h == 0 || desc->out_h > 16384u || desc->dtype > DEBIG_PNG_L_I64 ||
+        desc->reserved != 0 || desc->mode > DEBIG_PNG_CL_MAP)
+        return DEBIG_PNG_BAD_ARG;
+    const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
+    if (!map_mode && (desc->dtype < DEBIG_PNG_L_I32 || desc->n_maps != 0)) return DEBIG_PNG_BAD_ARG;
+    if (map_mode && ((desc->n_maps != 1 && desc->n_maps != n) || !desc->maps)) return DEBIG_PNG_BAD_ARG;
+    const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
+    const uint64_t slot = (uint64_t)H * W * es;
+
+    uint32_t *mtab = NULL;          /* the maps' tables, one behind the other */
+    uint64_t *moff = NULL;          /* table k: at moff[k] bytes, mslots[k] slots */
+    uint32_t *mslots = NULL, *pre = NULL, *cnt = NULL;
+    uint64_t *offs = NULL, *caps = NULL;
+    debig_png_box *box = NULL;
+    debig_png_info *inf = NULL;
+    debig_png_color_label_task *tasks = NULL;
+    lbl_tables TX = {NULL, 0, 0, NULL, 0, 0, W}, TY = {NULL, 0, 0, NULL, 0, 0, H};
+    uint64_t map_bytes = 0;
+    int rc = 2;
+    if (map_mode) {
+        const int64_t top = desc->dtype == DEBIG_PNG_L_U8 ? 255 : desc->dtype == DEBIG_PNG_L_U16 ? 65535 : INT32_MAX;
+        const int64_t low = desc->dtype <= DEBIG_PNG_L_U16 ? 0 : INT32_MIN;
+        if (desc->missing < low || desc->missing > top) return DEBIG_PNG_BAD_ARG;
+        uint64_t total_slots = 0;
+        for (uint32_t k = 0; k < n_maps; k++) {
+            const debig_png_color_map *m = &desc->maps[k];
+            if (m->n > DEBIG_PNG_CMAP_MAX || (m->n && (!m->keys || !m->values))) return DEBIG_PNG_BAD_ARG;
+            for (uint32_t j = 0; j < m->n; j++)
+                if (m->values[j] < low || m->values[j] > top) return DEBIG_PNG_BAD_ARG;
+            total_slots += cmap_slots(m->n);
+        }
+        mtab = (uint32_t *)malloc((size_t)total_slots * 8u);
+        moff = (uint64_t *)calloc(n_maps, sizeof(uint64_t));
+        mslots = (uint32_t *)calloc(n_maps, sizeof(uint32_t));
+        if (!mtab || !moff || !mslots) goto done;
+        for (uint32_t k = 0; k < n_maps; k++) {
+            moff[k] = map_bytes;
+            mslots[k] = debig_png_color_map_table(&desc->maps[k], mtab + map_bytes / 4u, DEBIG_PNG_CMAP_MAX_SLOTS);
+            if (mslots[k] == 0) { rc = DEBIG_PNG_BAD_ARG; goto done; } /* a key above 0xFFFFFF, or two equal keys */
+            map_bytes += (uint64_t)mslots[k] * 8u;
+        }
+    }
+    pre = (uint32_t *)calloc(n, sizeof(uint32_t));
+    cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
+    offs = (uint64_t *)calloc(n, sizeof(uint64_t));
+    caps = (uint64_t *)calloc(n, sizeof(uint64_t));
+    box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
+    inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
+    if (!pre || !cnt || !offs || !caps || !box || !inf) goto done;
+    /* ---- IHDR: E_LABEL (16-bit), then the box; the image's place in the context's arena */
+    const uint32_t fmt = DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        spec_file f0;
+        memset(&f0, 0, sizeof f0);
+        const uint32_t st = spec_walk(inputs[i], input_sizes[i], &f0, 1);
+        spec_free(&f0);
+        offs[i] = total;
+        const uint64_t iw = f0.info.width, ih = f0.info.height;
+        if (iw == 0) continue; /* no valid IHDR: the walk's status stands */
+        if (f0.info.bit_depth == 16) {
+            pre[i] = DEBIG_PNG_E_LABEL;
+            continue;
+        }
+        debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
+        if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
+        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih) {
+            pre[i] = DEBIG_PNG_E_BOX;
+            continue;
+        }
+        box[i] = b;
+        if (st != DEBIG_PNG_OK) continue;
+        const uint64_t sz = fmt_size(iw, ih, fmt);
+        if (sz > RSZ_MAX_IMAGE_BYTES) continue; /* caps[i] stays 0: E_OUTPUT */
+        caps[i] = sz;
+        total += debig_align16(sz) + 16;
+    }
+    {
+        const spec_target tg = {NULL, NULL, offs, total + 64, pre, 0};
+        if ((rc = spec_decode_core(inputs, input_sizes, &tg, caps, status, inf, n, flags, fmt, DEBIG_PNG_LAYOUT_HWC))) goto done;
+    }
+    if (infos) memcpy(infos, inf, (size_t)n * sizeof(debig_png_info));
+    if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
+    /* ---- the row runs of every decoded image */
+    const uint32_t run = W >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / W;
+    uint64_t n_tasks = 0;
+    uint32_t cap_tasks = 0;
+    rc = 2;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status[i] != DEBIG_PNG_OK) continue;
+        const uint64_t ox = lbl_axis_get(&TX, box[i].w), oy = lbl_axis_get(&TY, box[i].h);
+        if (ox == UINT64_MAX || oy == UINT64_MAX) goto done;
+        const uint32_t mk = n_maps == 1 ? 0u : i;
+        for (uint32_t y0 = 0; y0 < H; y0 += run) {
+            if (n_tasks >= 0x7fffffffu) goto done;
+            if (!grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof(debig_png_color_label_task))) goto done;
+            debig_png_color_label_task *t = &tasks[n_tasks++];
+            memset(t, 0, sizeof *t);
+            t->src_off = offs[i] + ((uint64_t)box[i].y * inf[i].width + box[i].x) * 3u;
+            t->out_off = (uint64_t)i * slot;
+            t->sx_off = ox; /* (the maps' tables come first, then the horizontal, then the vertical tables: fixed up below) */
+            t->sy_off = oy;
+            t->src_pitch = inf[i].width;
+            t->out_w = W;
+            t->out_h = H;
+            t->row0 = y0;
+            t->rows = H - y0 < run ? H - y0 : run;
+            t->dtype = (uint8_t)desc->dtype;
+            t->mode = (uint8_t)desc->mode;
+            t->image = i;
+            if (map_mode) {
+                t->map_off = moff[mk];
+                t->map_slots = mslots[mk];
+                t->missing = desc->missing;
+            }
+        }
+    }
+    rc = 0;
+    if (n_tasks == 0) goto done;
+    {
+        const uint64_t tx_bytes = TX.len * sizeof(uint32_t), ty_bytes = TY.len * sizeof(uint32_t);
+        const uint64_t cnt_off = map_bytes + tx_bytes + ty_bytes, cnt_bytes = (uint64_t)n * sizeof(uint32_t); /* (16-byte aligned) */
+        for (uint64_t k = 0; k < n_tasks; k++) {
+            tasks[k].sx_off += map_bytes;
+            tasks[k].sy_off += map_bytes + tx_bytes;
+        }
+        debig_ctx *c = debig_ctx_get(0);
+        if (!c) { rc = 1; goto done; }
+        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_color_label_task))) ||
+            (rc = debig_devbuf_reserve(&c->rsz_weights, cnt_off + cnt_bytes)))
+            goto done;
+        uint8_t *d_tab = (uint8_t *)c->rsz_weights.ptr;
+        uint32_t *d_cnt = map_mode ? (uint32_t *)(d_tab + cnt_off) : NULL;
+        if ((rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, tasks, n_tasks * sizeof(debig_png_color_label_task), NULL)) ||
+            (map_bytes && (rc = debig_hip_memcpy_h2d(d_tab, mtab, map_bytes, NULL))) ||
+            (rc = debig_hip_memcpy_h2d(d_tab + map_bytes, TX.buf, tx_bytes, NULL)) ||
+            (rc = debig_hip_memcpy_h2d(d_tab + map_bytes + tx_bytes, TY.buf, ty_bytes, NULL)) ||
+            (d_cnt && (rc = debig_hip_memset(d_cnt, 0, cnt_bytes, NULL))) ||
+            (rc = debig_hip_png_color_label_batch(c->rsz_src.ptr, d_out, (const debig_png_color_label_task *)c->rsz_tasks.ptr, d_tab,
+                                                  d_cnt, (uint32_t)n_tasks, NULL)) ||
+            (d_cnt && (rc = debig_hip_memcpy_d2h(cnt, d_cnt, cnt_bytes, NULL))) ||
+            (rc = debig_hip_stream_sync(NULL)))
+            goto done;
+        if (unmatched && map_mode) memcpy(unmatched, cnt, (size_t)n * sizeof(uint32_t));
+    }
+done:
+    free(mtab);
+    free(moff);
+    free(mslots);
+    free(pre);
+    free(cnt);
     free(offs);
     free(caps);
     free(box);

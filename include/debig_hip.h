@@ -474,6 +474,50 @@ typedef struct debig_png_label_task {
 int debig_hip_png_label_gather_batch(const void *d_src_arena, void *d_out, const debig_png_label_task *d_tasks,
                                      const void *d_tables, const int32_t *d_lut, uint32_t n_tasks, void *hip_stream);
 
+/* Crop + nearest pick + colour pack + colour -> class lookup + widening of decoded RGB8 masks (csrc/png_color_label_kernel.inc,
+ * behind debig_png_decode_batch_color_labels in decode_png.h).  Tasks, workgroups and the sx / sy tables are those of the raw-label
+ * gather above; the source is interleaved RGB8, three bytes per pixel at any alignment.  Element (X, Y) of the image comes from
+ * the pixel at sy[Y] * src_pitch + sx[X] (counted in pixels from src_off), key = R | G << 8 | B << 16:
+ *   mode 0 (DEBIG_PNG_CL_PACK): the key itself, dtype int32 or int64;
+ *   mode 1 (DEBIG_PNG_CL_MAP):  the value of the key in the task's table, else `missing`; every element that takes `missing`
+ *                               adds one to d_unmatched[image].
+ * THE TABLE of a colour map of n <= DEBIG_PNG_CMAP_MAX distinct keys, so that a device-pointer caller can build one: `slots`
+ * pairs of uint32 (key, value), side by side, 8 bytes per slot, 16-byte aligned in d_tables; slots is a power of two,
+ * >= 2 n, >= 2 and <= DEBIG_PNG_CMAP_MAX_SLOTS (the host takes the smallest); an unused slot holds the key
+ * DEBIG_PNG_CMAP_EMPTY, which no 24-bit key equals.  A key lives in the first unused slot of the sequence
+ * DEBIG_PNG_CMAP_SLOT(key, slots), + 1, + 2, ... (mod slots) at the time it is inserted (linear probing); the value is the
+ * int32 as its bits.  A lookup walks that sequence until it finds the key (hit), an unused slot (miss), or has looked at
+ * `slots` slots (miss): it terminates on any contents.  The workgroup stages the table in LDS (at most 32 KB), again only when
+ * map_off or map_slots differ from the task it did before.
+ * A task that breaks a bound -- the sizes and table offsets of the raw-label task, an unknown dtype or mode, PACK with a dtype
+ * of one or two bytes, MAP with a slot count that is no power of two, below 2 or above DEBIG_PNG_CMAP_MAX_SLOTS, with a map_off
+ * that is no multiple of 16 or without d_unmatched -- is skipped.  src_off, out_off and image are the caller's word, as
+ * everywhere in this header. */
+#define DEBIG_PNG_CMAP_MAX_SLOTS 4096u
+#define DEBIG_PNG_CMAP_EMPTY 0xFFFFFFFFu
+#define DEBIG_PNG_CMAP_SLOT(key, slots) ((((uint32_t)(key) * 0x9E3779B1u) >> 20) & ((slots) - 1u))
+typedef struct debig_png_color_label_task {
+    uint64_t src_off;        /* pixel (0, 0) of the CROP, in bytes rel. to d_src_arena (any alignment)                        */
+    uint64_t out_off;        /* the image's slot, in bytes rel. to d_out (aligned to the element size)                        */
+    uint64_t sx_off, sy_off; /* out_w / out_h uint32 indices inside the crop, in bytes rel. to d_tables (16-byte aligned)     */
+    uint64_t map_off;        /* MAP: the image's table, in bytes rel. to d_tables (16-byte aligned)                           */
+    uint32_t src_pitch;      /* pixels from one source row to the next (the image's width)                                    */
+    uint32_t out_w, out_h;   /* 1 .. 16384                                                                                    */
+    uint32_t row0, rows;     /* row0 + rows <= out_h                                                                          */
+    uint32_t map_slots;      /* MAP: slots of the table                                                                       */
+    int32_t missing;         /* MAP: the element of a colour that is not in the table                                         */
+    uint32_t image;          /* MAP: the image's counter in d_unmatched                                                       */
+    uint8_t dtype;           /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                       */
+    uint8_t mode;            /* decode_png.h DEBIG_PNG_CL_*                                                                   */
+    uint16_t reserved;
+    uint32_t reserved2;
+} debig_png_color_label_task;
+/* n_tasks row runs (device pointers, asynchronous on hip_stream).  d_unmatched: one uint32 per image, zeroed by the caller;
+ * one atomic add per wavefront and task; may be NULL when every task is PACK.  Nothing but the tasks' own output elements and
+ * counters is written. */
+int debig_hip_png_color_label_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_task *d_tasks,
+                                    const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

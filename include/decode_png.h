@@ -373,9 +373,9 @@ uint32_t debig_png_resize_weights_filter(uint32_t filter, uint32_t cl, uint32_t 
  * the file; then the statuses of debig_png_decode_batch_fmt in their order (E_PALETTE for an index >= the PLTE entries stays,
  * found on the GPU; E_OUTPUT: the raw labels are larger than 2^31 bytes).  A file with a non-zero status leaves its slot
  * untouched; nothing outside d_out[0 .. n * slot) is written.
- * Not provided: label output to host buffers or at each file's own size, colour -> class lookup for RGB-coded masks, LUTs for
- * 16-bit sources, boundary / ignore-ring generation, flips, animated PNGs, inputs already on the device, an asynchronous
- * variant. */
+ * Not provided: label output to host buffers or at each file's own size, LUTs for 16-bit sources, boundary / ignore-ring
+ * generation, flips, animated PNGs, inputs already on the device, an asynchronous variant.  (Colour -> class lookup for
+ * RGB-coded masks: debig_png_decode_batch_color_labels below.) */
 #define DEBIG_PNG_E_LABEL 15 /* not a label file for this call (rules above) */
 enum { DEBIG_PNG_L_U8 = 0, DEBIG_PNG_L_U16 = 1, DEBIG_PNG_L_I32 = 2, DEBIG_PNG_L_I64 = 3 };
 typedef struct debig_png_label_desc {
@@ -388,6 +388,67 @@ int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *
                                   const debig_png_box *boxes /* may be NULL */, uint32_t *status,
                                   debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
                                   const debig_png_label_desc *desc);
+
+/* ---- colour-coded label maps: RGB-coded masks as one integer class-map tensor -----------------------------------------------
+ * A large share of segmentation data stores the class as a COLOUR: COCO panoptic packs the segment id as R + 256 G + 65536 B,
+ * Cityscapes *_color.png, Mapillary, ADE20K colour masks and most annotation-tool exports use a fixed list of RGB colours, one
+ * per class, and image optimisers re-save either kind as palette or RGBA files.  debig_png_decode_batch_color_labels: bytes of
+ * n PNG files in, one dense (n, out_h, out_w) tensor of `dtype` in device memory out, laid out as debig_png_decode_batch_labels
+ * lays it out.  The call returns after the work has finished.
+ *   - The colour of a source pixel: the three bytes debig_png_decode_batch_fmt(..., DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8) gives
+ *     for it, whatever the file's colour type: palette files go through PLTE, grey is replicated (1/2/4-bit grey scaled as that
+ *     call scales it), alpha and tRNS are dropped, Adam7 files give the colours of their non-interlaced twins.  The packed
+ *     colour is key = R | G << 8 | B << 16.
+ *   - Geometry: exactly that of debig_png_decode_batch_labels -- the box rules, the pick (bx + ((2X + 1) cw) div 2 out_w,
+ *     by + ((2Y + 1) chh) div 2 out_h), d_out 16-byte aligned.
+ *   - Value, mode DEBIG_PNG_CL_PACK: the element is key (COCO's rgb2id); dtype I32 or I64.
+ *   - Value, mode DEBIG_PNG_CL_MAP: the element is values[k] where keys[k] == key in the image's map -- maps[0] for every image
+ *     when n_maps == 1, maps[i] for image i when n_maps == n --, else `missing`; int32 / int64 sign-extend.  Maps are HOST
+ *     memory, read before the call returns; the keys of one map are distinct.
+ *   - unmatched (may be NULL): unmatched[i] is the exact number of OUTPUT elements of image i whose colour was not in its map
+ *     (antialiased mask edges show up here); 0 in PACK mode and for a file with a non-zero status.
+ * The colours are de-filtered as RGB8 into the library's own device arena (the route of debig_png_decode_batch_tensor), then ONE
+ * launch picks, packs, looks up and widens all images (debig_hip_png_color_label_batch; the lookup is an open-addressing table
+ * per map, made on the host once per call, staged in LDS: include/debig_hip.h).
+ * Checked first, before any file is looked at (status, unmatched and tensor unwritten, DEBIG_PNG_BAD_ARG): the cases of
+ * debig_png_decode_batch_labels (desc or d_out NULL with n > 0, d_out not 16-byte aligned, out_w or out_h 0 or above 16384, an
+ * unknown dtype, reserved != 0); an unknown mode; PACK with dtype U8 or U16; PACK with n_maps != 0; MAP with n_maps neither 1
+ * nor n, or maps NULL; a map with n > DEBIG_PNG_CMAP_MAX, or n > 0 and keys or values NULL; a key above 0xFFFFFF; two equal
+ * keys in one map; a value or `missing` outside the range of dtype U8 (0 .. 255) or U16 (0 .. 65535).
+ * Per image: the chunk walk's statuses first; as soon as IHDR has been read DEBIG_PNG_E_LABEL iff the file is 16-bit (its high
+ * byte would pass for a colour silently), then DEBIG_PNG_E_BOX, and both outrank anything found later in the file; then the
+ * statuses of debig_png_decode_batch_fmt in their order (E_PALETTE; E_OUTPUT: more than 2^31 decoded RGB8 bytes).  A file with
+ * a non-zero status leaves its slot untouched; nothing outside d_out[0 .. n * slot) is written.
+ * Not provided: arithmetic decodings other than PACK (e.g. ADE20K's R / 10 * 256 + G), maps above DEBIG_PNG_CMAP_MAX entries,
+ * 16-bit sources, nearest-colour matching for unmatched pixels, host-buffer output, flips, animated PNGs, inputs already on the
+ * device, an asynchronous variant. */
+#define DEBIG_PNG_CMAP_MAX 2048u
+enum { DEBIG_PNG_CL_PACK = 0, DEBIG_PNG_CL_MAP = 1 };
+typedef struct debig_png_color_map {      /* host memory, read before the call returns */
+    uint32_t n;                           /* 0 .. DEBIG_PNG_CMAP_MAX */
+    uint32_t reserved;                    /* (not read) */
+    const uint32_t *keys;                 /* packed colours R | G << 8 | B << 16, distinct, <= 0xFFFFFF */
+    const int32_t *values;
+} debig_png_color_map;
+typedef struct debig_png_color_label_desc {
+    uint32_t out_w, out_h;                /* 1 .. 16384 */
+    uint32_t dtype;                       /* DEBIG_PNG_L_* */
+    uint32_t mode;                        /* DEBIG_PNG_CL_* */
+    int32_t  missing;                     /* MAP: the element of a colour that is not in the image's map */
+    uint32_t n_maps;                      /* MAP: 1 (one map for every image) or n (maps[i] is image i's); PACK: 0 */
+    const debig_png_color_map *maps;
+    uint32_t reserved;                    /* 0 */
+    uint32_t reserved2;                   /* (not read) */
+} debig_png_color_label_desc;
+int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                        const debig_png_box *boxes /* may be NULL */, uint32_t *status,
+                                        debig_png_info *infos /* may be NULL */, uint32_t *unmatched /* may be NULL */,
+                                        uint32_t n, uint32_t flags, const debig_png_color_label_desc *desc);
+/* Host only: the lookup table of one map as the call uploads it (include/debig_hip.h: debig_png_color_label_task has the
+ * layout, the slot function and the probe rule) -> its slot count, and 2 * slots uint32 (key, value pairs) in table; 0 and
+ * nothing written for a map the call refuses (map NULL, n > DEBIG_PNG_CMAP_MAX, n > 0 with a NULL array, a key above
+ * 0xFFFFFF, two equal keys) or when cap_slots is too small (4096 always suffices). */
+uint32_t debig_png_color_map_table(const debig_png_color_map *map, uint32_t *table, uint32_t cap_slots);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

@@ -18,6 +18,7 @@
 #include "../../debigulator_amd/csrc/apng_kernel.inc"
 #include "../../debigulator_amd/csrc/png_resize_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_kernel.inc"
+#include "../../debigulator_amd/csrc/png_color_label_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -379,5 +380,16 @@ extern "C" int emu_png_label_gather_batch(const void *src_arena, void *out, cons
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_label_gather_kernel, grid, LBL_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
                       (const uint8_t *)tables, lut, n);
+    return 0;
+}
+
+/* crop + nearest pick + colour pack + colour -> class lookup + widening of RGB8 masks (png_color_label_kernel.inc) as
+ * debig_hip_png_color_label_batch launches it (unmatched: one zeroed uint32 per image, or NULL; grid as above) */
+extern "C" int emu_png_color_label_batch(const void *src_arena, void *out, const debig_png_color_label_task *tasks,
+                                         const void *tables, uint32_t *unmatched, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_color_label_kernel, grid, CLBL_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)tables, unmatched, n);
     return 0;
 }
