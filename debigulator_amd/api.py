@@ -336,14 +336,7 @@ def png_decode_batch_device(datas, mode="rgba", depth=8, layout="hwc", device="c
     fmt = png_out_format(mode, depth)
     lay = png_layout_code(layout)
     L = _png_spec_lib()
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"device must be a GPU, not {device!r}")
-    L.debig_hip_get_device.restype = C.c_int
-    cur = L.debig_hip_get_device()
-    if dev.index is not None and dev.index != cur:
-        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
-    dev = torch.device("cuda", cur)
+    dev = _png_device(L, device)
     n = len(datas)
     ins = [_u8(d) for d in datas]
     offs, caps, shapes, total = [], [], [], 0
@@ -383,6 +376,49 @@ def png_decode_batch_device(datas, mode="rgba", depth=8, layout="hwc", device="c
 
 class PngBox(C.Structure):  # include/decode_png.h: debig_png_box
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
+
+
+def _png_device(L, device):
+    """the device rule of png_decode_batch_device and the dense-tensor calls -> the current device as a torch.device"""
+    import torch
+
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device must be a GPU, not {device!r}")
+    L.debig_hip_get_device.restype = C.c_int
+    cur = L.debig_hip_get_device()
+    if dev.index is not None and dev.index != cur:
+        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
+    return torch.device("cuda", cur)
+
+
+def _png_dense_out(shape, tdt, fill, dev):
+    """the one tensor of a dense-tensor call: as allocated, or holding `fill`, once that fill has finished"""
+    import torch
+
+    if fill is None:
+        out = torch.empty(shape, dtype=tdt, device=dev)
+    elif tdt == getattr(torch, "uint16", None):  # (torch.full has no uint16 kernel: fill the same bits as int16)
+        out = torch.full(shape, int(np.array(fill, np.uint16).view(np.int16)), dtype=torch.int16, device=dev).view(tdt)
+    else:
+        out = torch.full(shape, fill, dtype=tdt, device=dev)
+    torch.cuda.synchronize(dev)  # the fill runs on torch's stream, the library on its own
+    return out
+
+
+def _png_batch_args(datas, boxes):
+    """the per-file arguments of a dense-tensor call -> in_ptrs, in_sizes, boxes (or None), status, infos; in_ptrs keeps
+    the bytes it points to alive"""
+    n = len(datas)
+    if boxes is not None and len(boxes) != n:
+        raise ValueError("boxes needs one entry (or None) per file")
+    ins = [_u8(x) for x in datas]
+    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
+    in_ptrs._ins = ins
+    bx = None
+    if boxes is not None:
+        bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
+    return in_ptrs, (C.c_uint64 * n)(*[len(a) for a in ins]), bx, (C.c_uint32 * n)(), (PngInfo * n)()
 
 
 class PngTensorDesc(C.Structure):  # include/decode_png.h: debig_png_tensor_desc
@@ -527,37 +563,16 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     L.debig_png_decode_batch_tensor.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
     L.debig_png_decode_batch_tensor_alpha.restype = C.c_int
     L.debig_png_decode_batch_tensor_alpha.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"device must be a GPU, not {device!r}")
-    L.debig_hip_get_device.restype = C.c_int
-    cur = L.debig_hip_get_device()
-    if dev.index is not None and dev.index != cur:
-        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
-    dev = torch.device("cuda", cur)
+    dev = _png_device(L, device)
     n = len(datas)
-    if boxes is not None and len(boxes) != n:
-        raise ValueError("boxes needs one entry (or None) per file")
+    args = _png_batch_args(datas, boxes)
     H, W = d.out_h, d.out_w
     tdt = {1: torch.float32, 2: torch.float16, 3: torch.bfloat16}.get(d.dtype)
     if tdt is None:
         tdt = torch.uint8 if es == 1 else getattr(torch, "uint16", torch.int16)
     shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
-    if fill is None:
-        out = torch.empty(shape, dtype=tdt, device=dev)
-    elif tdt == getattr(torch, "uint16", None):  # (torch.full has no uint16 kernel: fill the same bits as int16)
-        out = torch.full(shape, int(np.array(fill, np.uint16).view(np.int16)), dtype=torch.int16, device=dev).view(tdt)
-    else:
-        out = torch.full(shape, fill, dtype=tdt, device=dev)
-    torch.cuda.synchronize(dev)  # the fill runs on torch's stream, the library on its own
-    ins = [_u8(x) for x in datas]
-    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
-    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
-    bx = None
-    if boxes is not None:
-        bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
-    status = (C.c_uint32 * n)()
-    infos = (PngInfo * n)()
+    out = _png_dense_out(shape, tdt, fill, dev)
+    in_ptrs, in_sizes, bx, status, infos = args
     if fd is not None:
         L.debig_png_decode_batch_tensor_filter.restype = C.c_int
         L.debig_png_decode_batch_tensor_filter.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -622,34 +637,12 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     L = _png_spec_lib()
     L.debig_png_decode_batch_labels.restype = C.c_int
     L.debig_png_decode_batch_labels.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"device must be a GPU, not {device!r}")
-    L.debig_hip_get_device.restype = C.c_int
-    cur = L.debig_hip_get_device()
-    if dev.index is not None and dev.index != cur:
-        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
-    dev = torch.device("cuda", cur)
+    dev = _png_device(L, device)
     n = len(datas)
-    if boxes is not None and len(boxes) != n:
-        raise ValueError("boxes needs one entry (or None) per file")
+    args = _png_batch_args(datas, boxes)
     tdt = {"uint8": torch.uint8, "uint16": getattr(torch, "uint16", torch.int16), "int32": torch.int32, "int64": torch.int64}[dtype]
-    shape = (n, d.out_h, d.out_w)
-    if fill is None:
-        out = torch.empty(shape, dtype=tdt, device=dev)
-    elif tdt == getattr(torch, "uint16", None):  # (torch.full has no uint16 kernel: fill the same bits as int16)
-        out = torch.full(shape, int(np.array(fill, np.uint16).view(np.int16)), dtype=torch.int16, device=dev).view(tdt)
-    else:
-        out = torch.full(shape, fill, dtype=tdt, device=dev)
-    torch.cuda.synchronize(dev)  # the fill runs on torch's stream, the library on its own
-    ins = [_u8(x) for x in datas]
-    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
-    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
-    bx = None
-    if boxes is not None:
-        bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
-    status = (C.c_uint32 * n)()
-    infos = (PngInfo * n)()
+    out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
+    in_ptrs, in_sizes, bx, status, infos = args
     rc = L.debig_png_decode_batch_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n, 0, C.byref(d))
     if rc == PNG_BAD_ARG:
         raise ValueError(f"debig_png_decode_batch_labels rejected its arguments ({rc})")
@@ -748,33 +741,11 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     L = _png_spec_lib()
     L.debig_png_decode_batch_color_labels.restype = C.c_int
     L.debig_png_decode_batch_color_labels.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p]
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"device must be a GPU, not {device!r}")
-    L.debig_hip_get_device.restype = C.c_int
-    cur = L.debig_hip_get_device()
-    if dev.index is not None and dev.index != cur:
-        raise ValueError(f"device {device!r} is not the current device (cuda:{cur}), on which the library works")
-    dev = torch.device("cuda", cur)
-    if boxes is not None and len(boxes) != n:
-        raise ValueError("boxes needs one entry (or None) per file")
+    dev = _png_device(L, device)
+    args = _png_batch_args(datas, boxes)
     tdt = {"uint8": torch.uint8, "uint16": getattr(torch, "uint16", torch.int16), "int32": torch.int32, "int64": torch.int64}[dtype]
-    shape = (n, d.out_h, d.out_w)
-    if fill is None:
-        out = torch.empty(shape, dtype=tdt, device=dev)
-    elif tdt == getattr(torch, "uint16", None):  # (torch.full has no uint16 kernel: fill the same bits as int16)
-        out = torch.full(shape, int(np.array(fill, np.uint16).view(np.int16)), dtype=torch.int16, device=dev).view(tdt)
-    else:
-        out = torch.full(shape, fill, dtype=tdt, device=dev)
-    torch.cuda.synchronize(dev)  # the fill runs on torch's stream, the library on its own
-    ins = [_u8(x) for x in datas]
-    in_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in ins])
-    in_sizes = (C.c_uint64 * n)(*[len(a) for a in ins])
-    bx = None
-    if boxes is not None:
-        bx = (PngBox * n)(*[PngBox(*[int(v) for v in b]) if b is not None else PngBox(0, 0, 0, 0) for b in boxes])
-    status = (C.c_uint32 * n)()
-    infos = (PngInfo * n)()
+    out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
+    in_ptrs, in_sizes, bx, status, infos = args
     unmatched = (C.c_uint32 * n)()
     rc = L.debig_png_decode_batch_color_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, unmatched, n, 0,
                                                C.byref(d))

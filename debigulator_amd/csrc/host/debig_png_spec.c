@@ -6,7 +6,8 @@
  * debig_png_decode_batch_labels (at the end of the file): palette indices and raw grey samples into that arena
  * (debig_hip_png_spec_defilter_index_batch), then one crop + nearest + remap + widen launch (debig_hip_png_label_gather_batch).
  * debig_png_decode_batch_color_labels (after it): RGB8 into that arena, then one crop + nearest + pack + colour lookup + widen
- * launch (debig_hip_png_color_label_batch).
+ * launch (debig_hip_png_color_label_batch).  These three share one staging path (stage_decode: IHDR rules, box, arena place,
+ * decode) and one way to the device (dev_tables_place, dev_upload), between the tensor call's checks and its core.
  *
  * Host side (plain C): the chunk walk and the rules decided by headers alone.  On the GPU: chunk CRC-32 and the
  * Adler-32 trailer (debig_hip_checksum_batch), the IDAT concatenation (debig_hip_gather), inflate (the batch inflate,
@@ -323,7 +324,8 @@ typedef struct spec_target {
 
 typedef int (*spec_launch_fn)(void *, void *, const debig_png_spec_task *, debig_png_spec_result *, uint32_t, void *);
 
-/* the decode behind debig_png_decode_batch_fmt / _layout / _dev / _tensor (out_format and out_layout valid) */
+/* the decode behind debig_png_decode_batch_fmt / _layout / _dev and, through stage_decode, behind _tensor / _tensor_alpha /
+ * _tensor_filter / _labels / _color_labels (out_format and out_layout valid) */
 static int spec_decode_core(const uint8_t *const *inputs, const uint64_t *input_sizes, const spec_target *tg,
                             const uint64_t *out_caps, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags,
                             uint32_t out_format, uint32_t out_layout)
@@ -854,6 +856,111 @@ _Static_assert(sizeof(debig_png_resize_cubic_task) == sizeof(debig_png_resize_al
                    offsetof(debig_png_resize_cubic_task, b) == offsetof(debig_png_resize_alpha_task, b),
                "debig_png_resize_cubic_task has the layout of debig_png_resize_alpha_task (tensor_core fills both through one)");
 
+/* ---- the staging path of the tensor, label and colour-label calls: IHDR, the crop box and the image's place in the context's
+ *      own arena (c->rsz_src), then the decode into it; and the way their tasks and tables reach the device ------------------- */
+
+/* what the three calls' staging differs in */
+typedef struct stage_rule {
+    uint32_t fmt;          /* the arena's format; GRAY | NATIVE_DEPTH (labels): one element per pixel, as wide as the file's samples */
+    uint32_t labels;       /* spec_target.labels */
+    uint32_t index_only;   /* != 0: colour types 2, 4 and 6 are E_LABEL */
+    uint32_t no16;         /* != 0: a 16-bit file is E_LABEL */
+    uint64_t max_w, max_h; /* max_w != 0: a crop wider / taller than this is E_BOX (the antialiased resize) */
+} stage_rule;
+
+/* per file: the status decided from IHDR (0: none), the image's place and size in the arena, the resolved box, the walk's info */
+typedef struct stage {
+    uint32_t *pre;
+    uint64_t *offs, *caps;
+    debig_png_box *box;
+    debig_png_info *inf;
+} stage;
+
+static void stage_free(stage *S)
+{
+    free(S->pre);
+    free(S->offs);
+    free(S->caps);
+    free(S->box);
+    free(S->inf);
+}
+
+/* IHDR -> E_LABEL, then E_BOX, then the walk's own error, then the size cap; the decode of what is left into the arena.
+ * -> 0 (status and infos written; S filled, the caller's to stage_free either way) or the call's return value */
+static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inputs, const uint64_t *input_sizes,
+                        const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags)
+{
+    S->pre = (uint32_t *)calloc(n, sizeof(uint32_t));
+    S->offs = (uint64_t *)calloc(n, sizeof(uint64_t));
+    S->caps = (uint64_t *)calloc(n, sizeof(uint64_t));
+    S->box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
+    S->inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
+    if (!S->pre || !S->offs || !S->caps || !S->box || !S->inf) return 2;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        spec_file f0;
+        memset(&f0, 0, sizeof f0);
+        const uint32_t st = spec_walk(inputs[i], input_sizes[i], &f0, 1);
+        spec_free(&f0);
+        S->offs[i] = total;
+        const uint64_t iw = f0.info.width, ih = f0.info.height;
+        if (iw == 0) continue; /* no valid IHDR: the walk's status stands */
+        const uint32_t ct = f0.info.color_type;
+        if ((R->index_only && ct != 0 && ct != 3) || (R->no16 && f0.info.bit_depth == 16)) {
+            S->pre[i] = DEBIG_PNG_E_LABEL;
+            continue;
+        }
+        debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
+        if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
+        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih ||
+            (R->max_w && (b.w > R->max_w || b.h > R->max_h))) {
+            S->pre[i] = DEBIG_PNG_E_BOX;
+            continue;
+        }
+        S->box[i] = b;
+        if (st != DEBIG_PNG_OK) continue;
+        const uint64_t sz = fmt_size(iw, ih, fmt_resolve(&f0.info, R->fmt));
+        if (sz > RSZ_MAX_IMAGE_BYTES) continue; /* caps[i] stays 0: E_OUTPUT */
+        S->caps[i] = sz;
+        total += debig_align16(sz) + 16;
+    }
+    const spec_target tg = {NULL, NULL, S->offs, total + 64, S->pre, R->labels};
+    const int rc = spec_decode_core(inputs, input_sizes, &tg, S->caps, status, S->inf, n, flags, R->fmt, DEBIG_PNG_LAYOUT_HWC);
+    if (rc == 0 && infos) memcpy(infos, S->inf, (size_t)n * sizeof(debig_png_info));
+    return rc;
+}
+
+/* a host table of one launch and where it lands in c->rsz_weights; src NULL: the space only, nothing copied */
+typedef struct dev_table { const void *src; uint64_t bytes, off; } dev_table;
+
+/* the tables one behind the other, in their order: every off.  Tasks are built with these offsets, after it. */
+static void dev_tables_place(dev_table *tab, uint32_t n_tab)
+{
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n_tab; k++) {
+        tab[k].off = at;
+        at += tab[k].bytes;
+    }
+}
+
+/* n_tasks tasks of elem bytes -> c->rsz_tasks, the placed tables -> c->rsz_weights.  -> the context (the launch, which follows
+ * on the same stream, takes its pointers from it), or NULL and *rc */
+static debig_ctx *dev_upload(const void *tasks, uint64_t n_tasks, size_t elem, const dev_table *tab, uint32_t n_tab, int *rc)
+{
+    debig_ctx *c = debig_ctx_get(0);
+    *rc = 1;
+    if (!c) return NULL;
+    if ((*rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * elem)) ||
+        (*rc = debig_devbuf_reserve(&c->rsz_weights, tab[n_tab - 1].off + tab[n_tab - 1].bytes)) ||
+        (*rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, tasks, n_tasks * elem, NULL)))
+        return NULL;
+    for (uint32_t k = 0; k < n_tab; k++)
+        if (tab[k].src && tab[k].bytes &&
+            (*rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + tab[k].off, tab[k].src, tab[k].bytes, NULL)))
+            return NULL;
+    return c;
+}
+
 /* debig_png_decode_batch_tensor (amode == DEBIG_PNG_ALPHA_STRAIGHT: bg unused), debig_png_decode_batch_tensor_alpha and
  * debig_png_decode_batch_tensor_filter behind their argument checks.  With alpha the pixels are decoded WITH their alpha (dfmt:
  * 4 or 2 channels) and the tiles go to the alpha kernel, which writes the channels of desc->out_format.  The filter picks the
@@ -872,67 +979,44 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     const uint32_t ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u, sb = bits / 8u;
     const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? sb : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
     const uint64_t slot = (uint64_t)H * W * oc * es;
-
-    uint32_t *pre = (uint32_t *)calloc(n, sizeof(uint32_t));
-    uint64_t *offs = (uint64_t *)calloc(n, sizeof(uint64_t)), *caps = (uint64_t *)calloc(n, sizeof(uint64_t));
-    debig_png_box *box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
-    debig_png_info *inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
-    debig_png_resize_task *tasks = NULL;
-    debig_png_resize_alpha_task *atasks = NULL;
-    rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa, filter}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa, filter};
+    /* the plain kernel's task, or the alpha kernel's and the signed kernel's of one layout: the plain one (channels: the
+     * source's) + mode, channel counts, background */
+    const int plain = amode == DEBIG_PNG_ALPHA_STRAIGHT && filter != DEBIG_PNG_FILTER_BICUBIC;
+    const size_t elem = plain ? sizeof(debig_png_resize_task) : sizeof(debig_png_resize_alpha_task);
     /* the largest antialiased scale (decode_png.h); NEAREST ignores the flag */
     const uint64_t max_scale = filter == DEBIG_PNG_FILTER_BICUBIC ? 32u : 64u;
-    const uint32_t aa_box = filter == DEBIG_PNG_FILTER_NEAREST ? 0u : aa;
-    int rc = 2;
-    if (!pre || !offs || !caps || !box || !inf) goto done;
-    /* ---- IHDR, the box, the image's place in the context's arena */
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        spec_file f0;
-        memset(&f0, 0, sizeof f0);
-        const uint32_t st = spec_walk(inputs[i], input_sizes[i], &f0, 1);
-        spec_free(&f0);
-        offs[i] = total;
-        const uint64_t iw = f0.info.width, ih = f0.info.height;
-        if (iw == 0) continue; /* no valid IHDR: the walk's status stands */
-        debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
-        if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
-        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih ||
-            (aa_box && ((uint64_t)b.w > max_scale * (uint64_t)W || (uint64_t)b.h > max_scale * (uint64_t)H))) {
-            pre[i] = DEBIG_PNG_E_BOX;
-            continue;
-        }
-        box[i] = b;
-        if (st != DEBIG_PNG_OK) continue;
-        const uint64_t sz = fmt_size(iw, ih, fmt);
-        if (sz > RSZ_MAX_IMAGE_BYTES) continue; /* caps[i] stays 0: E_OUTPUT */
-        caps[i] = sz;
-        total += debig_align16(sz) + 16;
-    }
-    {
-        const spec_target tg = {NULL, NULL, offs, total + 64, pre, 0};
-        if ((rc = spec_decode_core(inputs, input_sizes, &tg, caps, status, inf, n, flags, fmt, DEBIG_PNG_LAYOUT_HWC))) goto done;
-    }
-    if (infos) memcpy(infos, inf, (size_t)n * sizeof(debig_png_info));
+    const int aa_box = aa && filter != DEBIG_PNG_FILTER_NEAREST;
+    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H};
+
+    stage S = {NULL, NULL, NULL, NULL, NULL};
+    uint8_t *tasks = NULL;
+    rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa, filter}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa, filter};
+    int rc;
+    if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
+    /* ---- the axis tables of every decoded image, then their places behind one another */
+    rc = 2;
+    for (uint32_t i = 0; i < n; i++)
+        if (status[i] == DEBIG_PNG_OK && (rsz_axis_get(&TX, S.box[i].w) < 0 || rsz_axis_get(&TY, S.box[i].h) < 0)) goto done;
+    dev_table tab[2] = {{TX.buf, TX.len, 0}, {TY.buf, TY.len, 0}};
+    dev_tables_place(tab, 2);
     /* ---- the tiles of every decoded image */
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (status[i] != DEBIG_PNG_OK) continue;
-        const int64_t ax = rsz_axis_get(&TX, box[i].w), ay = rsz_axis_get(&TY, box[i].h);
-        if (ax < 0 || ay < 0) { rc = 2; goto done; }
-        const uint32_t mtx = TX.ax[ax].max_taps, mty = TY.ax[ay].max_taps;
-        const uint32_t *ey = (const uint32_t *)(TY.buf + TY.ax[ay].off) + 2;
+        const rsz_axis *ax = &TX.ax[rsz_axis_get(&TX, S.box[i].w)], *ay = &TY.ax[rsz_axis_get(&TY, S.box[i].h)];
+        const uint32_t mtx = ax->max_taps, mty = ay->max_taps;
+        const uint32_t *ey = (const uint32_t *)(TY.buf + ay->off) + 2;
         uint32_t tw = W < DEBIG_PNG_RESIZE_TILE_W ? W : DEBIG_PNG_RESIZE_TILE_W;
         if (tw > DEBIG_PNG_RESIZE_WX_CAP / mtx) tw = DEBIG_PNG_RESIZE_WX_CAP / mtx;
         if (tw > DEBIG_PNG_RESIZE_HQ_CAP / (mty * ch)) tw = DEBIG_PNG_RESIZE_HQ_CAP / (mty * ch);
-        debig_png_resize_task proto;
+        debig_png_resize_alpha_task proto; /* (the plain task: its first elem bytes) */
         memset(&proto, 0, sizeof proto);
-        proto.src_off = offs[i] + ((uint64_t)box[i].y * inf[i].width + box[i].x) * ch * sb;
+        proto.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * ch * sb;
         proto.out_off = (uint64_t)i * slot;
-        proto.wx_off = TX.ax[ax].off; /* (the vertical tables follow the horizontal ones: fixed up below) */
-        proto.wy_off = TY.ax[ay].off;
-        proto.src_pitch = inf[i].width * ch;
+        proto.wx_off = tab[0].off + ax->off;
+        proto.wy_off = tab[1].off + ay->off;
+        proto.src_pitch = S.inf[i].width * ch;
         proto.out_sx = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? 1u : oc;
         proto.out_sy = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? W : W * oc;
         proto.out_sc = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? H * W : 1u;
@@ -943,6 +1027,11 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
             proto.a[k] = (float)((double)desc->scale[k] / ((double)((1u << bits) - 1u) * (double)(1u << (30u - bits))));
             proto.b[k] = desc->bias[k];
         }
+        proto.mode = amode;
+        proto.src_channels = (uint8_t)ch;
+        proto.out_channels = (uint8_t)oc;
+        if (amode == DEBIG_PNG_ALPHA_OVER)
+            for (uint32_t j = 0; j < oc; j++) proto.bg[j] = bg[j];
         for (uint32_t y0 = 0; y0 < H;) {
             uint32_t lo = ey[2 * y0], hi = ey[2 * y0] + ey[2 * y0 + 1], th = 1;
             while (y0 + th < H && th < 64u) {
@@ -954,10 +1043,9 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
                 th++;
             }
             for (uint32_t x0 = 0; x0 < W; x0 += tw) {
-                if (n_tasks >= 0x7fffffffu) { rc = 2; goto done; }
-                if (!grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof(debig_png_resize_task))) { rc = 2; goto done; }
-                debig_png_resize_task *t = &tasks[n_tasks++];
-                *t = proto;
+                if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
+                debig_png_resize_task *t = (debig_png_resize_task *)(tasks + n_tasks++ * elem);
+                memcpy(t, &proto, elem);
                 t->tile_x = x0;
                 t->tile_y = y0;
                 t->tile_w = W - x0 < tw ? W - x0 : tw;
@@ -970,56 +1058,21 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     }
     rc = 0;
     if (n_tasks == 0) goto done;
-    for (uint64_t k = 0; k < n_tasks; k++) tasks[k].wy_off += TX.len;
-    if (amode != DEBIG_PNG_ALPHA_STRAIGHT || filter == DEBIG_PNG_FILTER_BICUBIC) {
-        /* the alpha kernel's task, and the signed kernel's of the same layout: the plain one (channels: the source's) + mode,
-         * channel counts, background */
-        atasks = (debig_png_resize_alpha_task *)calloc(n_tasks, sizeof(debig_png_resize_alpha_task));
-        if (!atasks) { rc = 2; goto done; }
-        for (uint64_t k = 0; k < n_tasks; k++) {
-            debig_png_resize_alpha_task *t = &atasks[k];
-            memcpy(t, &tasks[k], RSZ_TASK_FIELDS);
-            t->mode = amode;
-            t->src_channels = (uint8_t)ch;
-            t->out_channels = (uint8_t)oc;
-            if (amode == DEBIG_PNG_ALPHA_OVER)
-                for (uint32_t j = 0; j < oc; j++) t->bg[j] = bg[j];
-        }
-        debig_ctx *c = debig_ctx_get(0);
-        if (!c) { rc = 1; goto done; }
-        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_resize_alpha_task))) ||
-            (rc = debig_devbuf_reserve(&c->rsz_weights, TX.len + TY.len)) ||
-            (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, atasks, n_tasks * sizeof(debig_png_resize_alpha_task), NULL)) ||
-            (rc = debig_hip_memcpy_h2d(c->rsz_weights.ptr, TX.buf, TX.len, NULL)) ||
-            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + TX.len, TY.buf, TY.len, NULL)) ||
-            (rc = filter == DEBIG_PNG_FILTER_BICUBIC
-                      ? debig_hip_png_resize_cubic_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_cubic_task *)c->rsz_tasks.ptr,
-                                                         c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
-                      : debig_hip_png_resize_alpha_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_alpha_task *)c->rsz_tasks.ptr,
-                                                         c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)) ||
-            (rc = debig_hip_stream_sync(NULL)))
-            goto done;
-    } else {
-        debig_ctx *c = debig_ctx_get(0);
-        if (!c) { rc = 1; goto done; }
-        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_resize_task))) ||
-            (rc = debig_devbuf_reserve(&c->rsz_weights, TX.len + TY.len)) ||
-            (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, tasks, n_tasks * sizeof(debig_png_resize_task), NULL)) ||
-            (rc = debig_hip_memcpy_h2d(c->rsz_weights.ptr, TX.buf, TX.len, NULL)) ||
-            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + TX.len, TY.buf, TY.len, NULL)) ||
-            (rc = debig_hip_png_resize_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_task *)c->rsz_tasks.ptr,
-                                             c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)) ||
-            (rc = debig_hip_stream_sync(NULL)))
-            goto done;
-    }
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, 2, &rc);
+    if (!c) goto done;
+    const void *d_tasks = c->rsz_tasks.ptr;
+    if ((rc = filter == DEBIG_PNG_FILTER_BICUBIC
+                  ? debig_hip_png_resize_cubic_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_cubic_task *)d_tasks,
+                                                     c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
+              : plain ? debig_hip_png_resize_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_task *)d_tasks,
+                                                   c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
+                      : debig_hip_png_resize_alpha_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_alpha_task *)d_tasks,
+                                                         c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)))
+        goto done;
+    rc = debig_hip_stream_sync(NULL);
 done:
-    free(pre);
-    free(offs);
-    free(caps);
-    free(box);
-    free(inf);
+    stage_free(&S);
     free(tasks);
-    free(atasks);
     free(TX.buf);
     free(TX.ax);
     free(TY.buf);
@@ -1119,6 +1172,64 @@ static uint64_t lbl_axis_get(lbl_tables *T, uint32_t cl)
     return T->ax[T->n_ax - 1].off;
 }
 
+/* the row-run tasks of the label and the colour-label call: both kernels' tasks (elem bytes) start with src_off, out_off,
+ * sx_off, sy_off and hold row0 and rows side by side (at row_at) */
+typedef struct lbl_head { uint64_t src_off, out_off, sx_off, sy_off; } lbl_head;
+_Static_assert(offsetof(debig_png_label_task, sy_off) == offsetof(lbl_head, sy_off) &&
+                   offsetof(debig_png_color_label_task, sy_off) == offsetof(lbl_head, sy_off) &&
+                   offsetof(debig_png_label_task, rows) == offsetof(debig_png_label_task, row0) + 4 &&
+                   offsetof(debig_png_color_label_task, rows) == offsetof(debig_png_color_label_task, row0) + 4,
+               "the fields lbl_runs fills lie alike in both label tasks");
+typedef struct lbl_job {
+    uint8_t *tasks;
+    uint64_t n_tasks;
+    uint32_t cap_tasks, W, H;
+    size_t elem, row_at;
+    lbl_tables TX, TY;
+    dev_table *tx, *ty; /* their places among the call's tables */
+} lbl_job;
+
+/* the axis tables of every decoded image -> *tx, *ty (not placed yet).  -> 0 or 2 */
+static int lbl_axes(lbl_job *J, const stage *S, const uint32_t *status, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; i++)
+        if (status[i] == DEBIG_PNG_OK &&
+            (lbl_axis_get(&J->TX, S->box[i].w) == UINT64_MAX || lbl_axis_get(&J->TY, S->box[i].h) == UINT64_MAX))
+            return 2;
+    J->tx->src = J->TX.buf;
+    J->tx->bytes = J->TX.len * sizeof(uint32_t);
+    J->ty->src = J->TY.buf;
+    J->ty->bytes = J->TY.len * sizeof(uint32_t);
+    return 0;
+}
+
+/* the row runs of one decoded image (px bytes per pixel in the arena): copies of *proto, the caller's task with everything but
+ * the fields named above filled in.  -> 0 or 2 */
+static int lbl_runs(lbl_job *J, const stage *S, uint32_t i, uint32_t px, uint64_t slot, void *proto)
+{
+    const uint32_t run = J->W >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / J->W;
+    const lbl_head h = {S->offs[i] + ((uint64_t)S->box[i].y * S->inf[i].width + S->box[i].x) * px, (uint64_t)i * slot,
+                        J->tx->off + lbl_axis_get(&J->TX, S->box[i].w), J->ty->off + lbl_axis_get(&J->TY, S->box[i].h)};
+    memcpy(proto, &h, sizeof h);
+    for (uint32_t y0 = 0; y0 < J->H; y0 += run) {
+        if (J->n_tasks >= 0x7fffffffu || !grow((void **)&J->tasks, &J->cap_tasks, (uint32_t)J->n_tasks, J->elem)) return 2;
+        uint8_t *t = J->tasks + J->n_tasks++ * J->elem;
+        const uint32_t rows[2] = {y0, J->H - y0 < run ? J->H - y0 : run};
+        memcpy(t, proto, J->elem);
+        memcpy(t + J->row_at, rows, sizeof rows);
+    }
+    return 0;
+}
+
+static void lbl_job_free(lbl_job *J)
+{
+    free(J->tasks);
+    free(J->TX.buf);
+    free(J->TX.ax);
+    free(J->TY.buf);
+    free(J->TY.ax);
+}
+
 DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
                                             const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n,
                                             uint32_t flags, const debig_png_label_desc *desc)
@@ -1133,112 +1244,39 @@ DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const 
         for (uint32_t k = 0; k < 256; k++)
             if (desc->lut[k] < 0 || desc->lut[k] > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)) return DEBIG_PNG_BAD_ARG;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
-    const uint64_t slot = (uint64_t)H * W * es;
+    /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0};
 
-    uint32_t *pre = (uint32_t *)calloc(n, sizeof(uint32_t));
-    uint64_t *offs = (uint64_t *)calloc(n, sizeof(uint64_t)), *caps = (uint64_t *)calloc(n, sizeof(uint64_t));
-    debig_png_box *box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
-    debig_png_info *inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
-    debig_png_label_task *tasks = NULL;
-    lbl_tables TX = {NULL, 0, 0, NULL, 0, 0, W}, TY = {NULL, 0, 0, NULL, 0, 0, H};
-    int rc = 2;
-    if (!pre || !offs || !caps || !box || !inf) goto done;
-    /* ---- IHDR: E_LABEL, then the box; the image's place in the context's arena */
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        spec_file f0;
-        memset(&f0, 0, sizeof f0);
-        const uint32_t st = spec_walk(inputs[i], input_sizes[i], &f0, 1);
-        spec_free(&f0);
-        offs[i] = total;
-        const uint64_t iw = f0.info.width, ih = f0.info.height;
-        if (iw == 0) continue; /* no valid IHDR: the walk's status stands */
-        const uint32_t ct = f0.info.color_type, d = f0.info.bit_depth;
-        if ((ct != 0 && ct != 3) || (d == 16 && (desc->dtype == DEBIG_PNG_L_U8 || desc->lut))) {
-            pre[i] = DEBIG_PNG_E_LABEL;
-            continue;
-        }
-        debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
-        if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
-        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih) {
-            pre[i] = DEBIG_PNG_E_BOX;
-            continue;
-        }
-        box[i] = b;
-        if (st != DEBIG_PNG_OK) continue;
-        const uint64_t sz = fmt_size(iw, ih, DEBIG_PNG_FMT_GRAY | (d == 16 ? DEBIG_PNG_FMT_16 : DEBIG_PNG_FMT_8));
-        if (sz > RSZ_MAX_IMAGE_BYTES) continue; /* caps[i] stays 0: E_OUTPUT */
-        caps[i] = sz;
-        total += debig_align16(sz) + 16;
-    }
-    {
-        /* one element per pixel, as wide as the file's samples: the size rules of GRAY at the file's own depth */
-        const spec_target tg = {NULL, NULL, offs, total + 64, pre, 1};
-        if ((rc = spec_decode_core(inputs, input_sizes, &tg, caps, status, inf, n, flags,
-                                   DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, DEBIG_PNG_LAYOUT_HWC)))
-            goto done;
-    }
-    if (infos) memcpy(infos, inf, (size_t)n * sizeof(debig_png_info));
-    /* ---- the row runs of every decoded image */
-    const uint32_t run = W >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / W;
-    uint64_t n_tasks = 0;
-    uint32_t cap_tasks = 0;
+    stage S = {NULL, NULL, NULL, NULL, NULL};
+    dev_table tab[3] = {{desc->lut, 1024, 0}, {NULL, 0, 0}, {NULL, 0, 0}}; /* the LUT (or its room), the X tables, the Y tables */
+    lbl_job J = {NULL, 0, 0, W, H, sizeof(debig_png_label_task), offsetof(debig_png_label_task, row0),
+                 {NULL, 0, 0, NULL, 0, 0, W}, {NULL, 0, 0, NULL, 0, 0, H}, &tab[1], &tab[2]};
+    int rc;
+    if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags)) || (rc = lbl_axes(&J, &S, status, n)))
+        goto done;
+    dev_tables_place(tab, 3);
     for (uint32_t i = 0; i < n; i++) {
         if (status[i] != DEBIG_PNG_OK) continue;
-        const uint64_t ox = lbl_axis_get(&TX, box[i].w), oy = lbl_axis_get(&TY, box[i].h);
-        if (ox == UINT64_MAX || oy == UINT64_MAX) { rc = 2; goto done; }
-        const uint32_t sb = inf[i].bit_depth == 16 ? 2u : 1u;
-        for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu) { rc = 2; goto done; }
-            if (!grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof(debig_png_label_task))) { rc = 2; goto done; }
-            debig_png_label_task *t = &tasks[n_tasks++];
-            memset(t, 0, sizeof *t);
-            t->src_off = offs[i] + ((uint64_t)box[i].y * inf[i].width + box[i].x) * sb;
-            t->out_off = (uint64_t)i * slot;
-            t->sx_off = ox; /* (the vertical tables follow the horizontal ones, the LUT comes first: fixed up below) */
-            t->sy_off = oy;
-            t->src_pitch = inf[i].width;
-            t->out_w = W;
-            t->out_h = H;
-            t->row0 = y0;
-            t->rows = H - y0 < run ? H - y0 : run;
-            t->src_bytes = (uint8_t)sb;
-            t->dtype = (uint8_t)desc->dtype;
-        }
+        debig_png_label_task p;
+        memset(&p, 0, sizeof p);
+        p.src_pitch = S.inf[i].width;
+        p.out_w = W;
+        p.out_h = H;
+        p.src_bytes = S.inf[i].bit_depth == 16 ? 2u : 1u;
+        p.dtype = (uint8_t)desc->dtype;
+        if ((rc = lbl_runs(&J, &S, i, p.src_bytes, (uint64_t)H * W * es, &p))) goto done;
     }
-    rc = 0;
-    if (n_tasks == 0) goto done;
-    {
-        const uint64_t lut_bytes = 1024, tx_bytes = TX.len * sizeof(uint32_t), ty_bytes = TY.len * sizeof(uint32_t);
-        for (uint64_t k = 0; k < n_tasks; k++) {
-            tasks[k].sx_off += lut_bytes;
-            tasks[k].sy_off += lut_bytes + tx_bytes;
-        }
-        debig_ctx *c = debig_ctx_get(0);
-        if (!c) { rc = 1; goto done; }
-        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_label_task))) ||
-            (rc = debig_devbuf_reserve(&c->rsz_weights, lut_bytes + tx_bytes + ty_bytes)) ||
-            (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, tasks, n_tasks * sizeof(debig_png_label_task), NULL)) ||
-            (desc->lut && (rc = debig_hip_memcpy_h2d(c->rsz_weights.ptr, desc->lut, lut_bytes, NULL))) ||
-            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + lut_bytes, TX.buf, tx_bytes, NULL)) ||
-            (rc = debig_hip_memcpy_h2d((uint8_t *)c->rsz_weights.ptr + lut_bytes + tx_bytes, TY.buf, ty_bytes, NULL)) ||
-            (rc = debig_hip_png_label_gather_batch(c->rsz_src.ptr, d_out, (const debig_png_label_task *)c->rsz_tasks.ptr,
-                                                   c->rsz_weights.ptr, desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL,
-                                                   (uint32_t)n_tasks, NULL)) ||
-            (rc = debig_hip_stream_sync(NULL)))
-            goto done;
-    }
+    if (J.n_tasks == 0) goto done;
+    debig_ctx *c = dev_upload(J.tasks, J.n_tasks, J.elem, tab, 3, &rc);
+    if (!c) goto done;
+    if ((rc = debig_hip_png_label_gather_batch(c->rsz_src.ptr, d_out, (const debig_png_label_task *)c->rsz_tasks.ptr,
+                                               c->rsz_weights.ptr, desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL,
+                                               (uint32_t)J.n_tasks, NULL)))
+        goto done;
+    rc = debig_hip_stream_sync(NULL);
 done:
-    free(pre);
-    free(offs);
-    free(caps);
-    free(box);
-    free(inf);
-    free(tasks);
-    free(TX.buf);
-    free(TX.ax);
-    free(TY.buf);
-    free(TY.ax);
+    stage_free(&S);
+    lbl_job_free(&J);
     return rc;
 }
 
@@ -1291,17 +1329,16 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
     if (!map_mode && (desc->dtype < DEBIG_PNG_L_I32 || desc->n_maps != 0)) return DEBIG_PNG_BAD_ARG;
     if (map_mode && ((desc->n_maps != 1 && desc->n_maps != n) || !desc->maps)) return DEBIG_PNG_BAD_ARG;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
-    const uint64_t slot = (uint64_t)H * W * es;
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0}; /* E_LABEL: a 16-bit file */
 
     uint32_t *mtab = NULL;          /* the maps' tables, one behind the other */
     uint64_t *moff = NULL;          /* table k: at moff[k] bytes, mslots[k] slots */
-    uint32_t *mslots = NULL, *pre = NULL, *cnt = NULL;
-    uint64_t *offs = NULL, *caps = NULL;
-    debig_png_box *box = NULL;
-    debig_png_info *inf = NULL;
-    debig_png_color_label_task *tasks = NULL;
-    lbl_tables TX = {NULL, 0, 0, NULL, 0, 0, W}, TY = {NULL, 0, 0, NULL, 0, 0, H};
-    uint64_t map_bytes = 0;
+    uint32_t *mslots = NULL, *cnt = NULL;
+    stage S = {NULL, NULL, NULL, NULL, NULL};
+    /* the maps' tables (first: map_off needs no base), the X tables, the Y tables, the counters (16-byte aligned) */
+    dev_table tab[4] = {{NULL, 0, 0}, {NULL, 0, 0}, {NULL, 0, 0}, {NULL, (uint64_t)n * sizeof(uint32_t), 0}};
+    lbl_job J = {NULL, 0, 0, W, H, sizeof(debig_png_color_label_task), offsetof(debig_png_color_label_task, row0),
+                 {NULL, 0, 0, NULL, 0, 0, W}, {NULL, 0, 0, NULL, 0, 0, H}, &tab[1], &tab[2]};
     int rc = 2;
     if (map_mode) {
         const int64_t top = desc->dtype == DEBIG_PNG_L_U8 ? 255 : desc->dtype == DEBIG_PNG_L_U16 ? 65535 : INT32_MAX;
@@ -1320,129 +1357,54 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
         mslots = (uint32_t *)calloc(n_maps, sizeof(uint32_t));
         if (!mtab || !moff || !mslots) goto done;
         for (uint32_t k = 0; k < n_maps; k++) {
-            moff[k] = map_bytes;
-            mslots[k] = debig_png_color_map_table(&desc->maps[k], mtab + map_bytes / 4u, DEBIG_PNG_CMAP_MAX_SLOTS);
+            moff[k] = tab[0].bytes;
+            mslots[k] = debig_png_color_map_table(&desc->maps[k], mtab + tab[0].bytes / 4u, DEBIG_PNG_CMAP_MAX_SLOTS);
             if (mslots[k] == 0) { rc = DEBIG_PNG_BAD_ARG; goto done; } /* a key above 0xFFFFFF, or two equal keys */
-            map_bytes += (uint64_t)mslots[k] * 8u;
+            tab[0].bytes += (uint64_t)mslots[k] * 8u;
         }
+        tab[0].src = mtab;
     }
-    pre = (uint32_t *)calloc(n, sizeof(uint32_t));
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
-    offs = (uint64_t *)calloc(n, sizeof(uint64_t));
-    caps = (uint64_t *)calloc(n, sizeof(uint64_t));
-    box = (debig_png_box *)calloc(n, sizeof(debig_png_box));
-    inf = (debig_png_info *)calloc(n, sizeof(debig_png_info));
-    if (!pre || !cnt || !offs || !caps || !box || !inf) goto done;
-    /* ---- IHDR: E_LABEL (16-bit), then the box; the image's place in the context's arena */
-    const uint32_t fmt = DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8;
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        spec_file f0;
-        memset(&f0, 0, sizeof f0);
-        const uint32_t st = spec_walk(inputs[i], input_sizes[i], &f0, 1);
-        spec_free(&f0);
-        offs[i] = total;
-        const uint64_t iw = f0.info.width, ih = f0.info.height;
-        if (iw == 0) continue; /* no valid IHDR: the walk's status stands */
-        if (f0.info.bit_depth == 16) {
-            pre[i] = DEBIG_PNG_E_LABEL;
-            continue;
-        }
-        debig_png_box b = {0, 0, (uint32_t)iw, (uint32_t)ih};
-        if (boxes && (boxes[i].w || boxes[i].h)) b = boxes[i];
-        if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih) {
-            pre[i] = DEBIG_PNG_E_BOX;
-            continue;
-        }
-        box[i] = b;
-        if (st != DEBIG_PNG_OK) continue;
-        const uint64_t sz = fmt_size(iw, ih, fmt);
-        if (sz > RSZ_MAX_IMAGE_BYTES) continue; /* caps[i] stays 0: E_OUTPUT */
-        caps[i] = sz;
-        total += debig_align16(sz) + 16;
-    }
-    {
-        const spec_target tg = {NULL, NULL, offs, total + 64, pre, 0};
-        if ((rc = spec_decode_core(inputs, input_sizes, &tg, caps, status, inf, n, flags, fmt, DEBIG_PNG_LAYOUT_HWC))) goto done;
-    }
-    if (infos) memcpy(infos, inf, (size_t)n * sizeof(debig_png_info));
+    if (!cnt) goto done;
+    if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
-    /* ---- the row runs of every decoded image */
-    const uint32_t run = W >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / W;
-    uint64_t n_tasks = 0;
-    uint32_t cap_tasks = 0;
-    rc = 2;
+    if ((rc = lbl_axes(&J, &S, status, n))) goto done;
+    dev_tables_place(tab, 4);
     for (uint32_t i = 0; i < n; i++) {
         if (status[i] != DEBIG_PNG_OK) continue;
-        const uint64_t ox = lbl_axis_get(&TX, box[i].w), oy = lbl_axis_get(&TY, box[i].h);
-        if (ox == UINT64_MAX || oy == UINT64_MAX) goto done;
         const uint32_t mk = n_maps == 1 ? 0u : i;
-        for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu) goto done;
-            if (!grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof(debig_png_color_label_task))) goto done;
-            debig_png_color_label_task *t = &tasks[n_tasks++];
-            memset(t, 0, sizeof *t);
-            t->src_off = offs[i] + ((uint64_t)box[i].y * inf[i].width + box[i].x) * 3u;
-            t->out_off = (uint64_t)i * slot;
-            t->sx_off = ox; /* (the maps' tables come first, then the horizontal, then the vertical tables: fixed up below) */
-            t->sy_off = oy;
-            t->src_pitch = inf[i].width;
-            t->out_w = W;
-            t->out_h = H;
-            t->row0 = y0;
-            t->rows = H - y0 < run ? H - y0 : run;
-            t->dtype = (uint8_t)desc->dtype;
-            t->mode = (uint8_t)desc->mode;
-            t->image = i;
-            if (map_mode) {
-                t->map_off = moff[mk];
-                t->map_slots = mslots[mk];
-                t->missing = desc->missing;
-            }
+        debig_png_color_label_task p;
+        memset(&p, 0, sizeof p);
+        p.src_pitch = S.inf[i].width;
+        p.out_w = W;
+        p.out_h = H;
+        p.dtype = (uint8_t)desc->dtype;
+        p.mode = (uint8_t)desc->mode;
+        p.image = i;
+        if (map_mode) {
+            p.map_off = tab[0].off + moff[mk];
+            p.map_slots = mslots[mk];
+            p.missing = desc->missing;
         }
+        if ((rc = lbl_runs(&J, &S, i, 3u, (uint64_t)H * W * es, &p))) goto done;
     }
-    rc = 0;
-    if (n_tasks == 0) goto done;
-    {
-        const uint64_t tx_bytes = TX.len * sizeof(uint32_t), ty_bytes = TY.len * sizeof(uint32_t);
-        const uint64_t cnt_off = map_bytes + tx_bytes + ty_bytes, cnt_bytes = (uint64_t)n * sizeof(uint32_t); /* (16-byte aligned) */
-        for (uint64_t k = 0; k < n_tasks; k++) {
-            tasks[k].sx_off += map_bytes;
-            tasks[k].sy_off += map_bytes + tx_bytes;
-        }
-        debig_ctx *c = debig_ctx_get(0);
-        if (!c) { rc = 1; goto done; }
-        if ((rc = debig_devbuf_reserve(&c->rsz_tasks, n_tasks * sizeof(debig_png_color_label_task))) ||
-            (rc = debig_devbuf_reserve(&c->rsz_weights, cnt_off + cnt_bytes)))
-            goto done;
-        uint8_t *d_tab = (uint8_t *)c->rsz_weights.ptr;
-        uint32_t *d_cnt = map_mode ? (uint32_t *)(d_tab + cnt_off) : NULL;
-        if ((rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, tasks, n_tasks * sizeof(debig_png_color_label_task), NULL)) ||
-            (map_bytes && (rc = debig_hip_memcpy_h2d(d_tab, mtab, map_bytes, NULL))) ||
-            (rc = debig_hip_memcpy_h2d(d_tab + map_bytes, TX.buf, tx_bytes, NULL)) ||
-            (rc = debig_hip_memcpy_h2d(d_tab + map_bytes + tx_bytes, TY.buf, ty_bytes, NULL)) ||
-            (d_cnt && (rc = debig_hip_memset(d_cnt, 0, cnt_bytes, NULL))) ||
-            (rc = debig_hip_png_color_label_batch(c->rsz_src.ptr, d_out, (const debig_png_color_label_task *)c->rsz_tasks.ptr, d_tab,
-                                                  d_cnt, (uint32_t)n_tasks, NULL)) ||
-            (d_cnt && (rc = debig_hip_memcpy_d2h(cnt, d_cnt, cnt_bytes, NULL))) ||
-            (rc = debig_hip_stream_sync(NULL)))
-            goto done;
-        if (unmatched && map_mode) memcpy(unmatched, cnt, (size_t)n * sizeof(uint32_t));
-    }
+    if (J.n_tasks == 0) goto done;
+    debig_ctx *c = dev_upload(J.tasks, J.n_tasks, J.elem, tab, 4, &rc);
+    if (!c) goto done;
+    uint32_t *d_cnt = map_mode ? (uint32_t *)((uint8_t *)c->rsz_weights.ptr + tab[3].off) : NULL;
+    if ((d_cnt && (rc = debig_hip_memset(d_cnt, 0, tab[3].bytes, NULL))) ||
+        (rc = debig_hip_png_color_label_batch(c->rsz_src.ptr, d_out, (const debig_png_color_label_task *)c->rsz_tasks.ptr,
+                                              c->rsz_weights.ptr, d_cnt, (uint32_t)J.n_tasks, NULL)) ||
+        (d_cnt && (rc = debig_hip_memcpy_d2h(cnt, d_cnt, tab[3].bytes, NULL))) ||
+        (rc = debig_hip_stream_sync(NULL)))
+        goto done;
+    if (unmatched && map_mode) memcpy(unmatched, cnt, (size_t)n * sizeof(uint32_t));
 done:
     free(mtab);
     free(moff);
     free(mslots);
-    free(pre);
     free(cnt);
-    free(offs);
-    free(caps);
-    free(box);
-    free(inf);
-    free(tasks);
-    free(TX.buf);
-    free(TX.ax);
-    free(TY.buf);
-    free(TY.ax);
+    stage_free(&S);
+    lbl_job_free(&J);
     return rc;
 }
