@@ -211,7 +211,8 @@ def gunzip_batch(datas, out_caps):
 
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
-              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box", 15: "label"}
+              8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box", 15: "label",
+              16: "warp"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -531,9 +532,107 @@ def png_filter_desc(filter="bilinear"):
     return PngFilterDesc(filter=PNG_FILTERS[filter])
 
 
+class PngWarp(C.Structure):  # include/decode_png.h: debig_png_warp
+    _fields_ = [("m", C.c_double * 6)]
+
+
+class PngWarpDesc(C.Structure):  # include/decode_png.h: debig_png_warp_desc
+    _fields_ = [("filter", C.c_uint32), ("border_mode", C.c_uint32), ("border", C.c_uint16 * 4), ("alpha_mode", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PngLabelWarpDesc(C.Structure):  # include/decode_png.h: debig_png_label_warp_desc
+    _fields_ = [("border_mode", C.c_uint32), ("border_label", C.c_int32)]
+
+
+PNG_BORDERS = {"constant": 0, "clamp": 1}  # include/decode_png.h: DEBIG_PNG_BORDER_*
+PNG_WARP_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def png_warp_matrix(src_wh, out_size, angle=0.0, scale=1.0, shear=(0, 0), translate=(0, 0), hflip=False, vflip=False):
+    """the INVERSE 2 x 3 matrix (a tuple of two rows of three floats) that png_decode_batch_tensor(..., warp=) and
+    png_decode_batch_labels(..., warp=) take, for a source (crop) of src_wh = (w, h) pixels and an output of out_size = (H, W),
+    built about the two centres (no GPU needed).  Seen from the source to the output, the operations compose in this order:
+      1. the flips (hflip: left <-> right, vflip: top <-> bottom);
+      2. scale: a number or (sx, sy), > 1 enlarges;
+      3. shear = (x, y) in degrees: x' = x + tan(x) y, y' = tan(y) x + y;
+      4. the rotation by `angle` degrees, counter-clockwise as the image is seen (what PIL's and torchvision's rotate mean);
+         multiples of 90 are exact;
+      5. translate = (tx, ty) in OUTPUT pixels, to the right and down;
+    and the source centre (w / 2, h / 2) lands on the output centre (W / 2, H / 2) before the translation.  With no other argument
+    png_warp_matrix((w, h), (h, w)) is the identity; hflip, vflip and angle = 90 / 180 / 270 with the matching out_size give
+    numpy.fliplr / flipud / rot90(k = 1, 2, 3) of the decode exactly."""
+    import math
+
+    w, h = (float(v) for v in src_wh)
+    H, W = (float(v) for v in out_size)
+    sx, sy = (float(v) for v in (scale if hasattr(scale, "__len__") else (scale, scale)))
+    if sx == 0.0 or sy == 0.0:
+        raise ValueError("scale must not be 0")
+    a = float(angle) % 360.0
+    if a % 90.0 == 0.0:
+        c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(a // 90.0)]
+    else:
+        c, s = math.cos(math.radians(a)), math.sin(math.radians(a))
+    tx_, ty_ = (math.tan(math.radians(float(v))) if float(v) != 0.0 else 0.0 for v in shear)
+    det = 1.0 - tx_ * ty_
+    if abs(det) < 1e-12:  # (tan(45 degrees) is not exactly 1 in float64)
+        raise ValueError("the shear is singular")
+    # the inverse chain, output -> source: rotation^-1, shear^-1, scale^-1, flips
+    m = ((c, -s), (s, c))
+    sh = ((1.0 / det, -tx_ / det), (-ty_ / det, 1.0 / det))
+    m = tuple(tuple(sh[r][0] * m[0][k] + sh[r][1] * m[1][k] for k in range(2)) for r in range(2))
+    fx, fy = (-1.0 if hflip else 1.0), (-1.0 if vflip else 1.0)
+    m = (tuple(fx * v / sx for v in m[0]), tuple(fy * v / sy for v in m[1]))
+    ox, oy = W / 2.0 + float(translate[0]), H / 2.0 + float(translate[1])
+    rows = ((m[0][0], m[0][1], w / 2.0 - (m[0][0] * ox + m[0][1] * oy)),
+            (m[1][0], m[1][1], h / 2.0 - (m[1][0] * ox + m[1][1] * oy)))
+    return tuple(tuple(v + 0.0 for v in r) for r in rows)  # (+ 0.0: no negative zeros)
+
+
+def _png_warps(warp, n):
+    """warp: a sequence of n entries, each None (the identity) or a 2 x 3 matrix -> (PngWarp * n)"""
+    if len(warp) != n:
+        raise ValueError("warp needs one entry (a 2 x 3 matrix, or None) per file")
+    ws = (PngWarp * n)()
+    for i, m in enumerate(warp):
+        v = PNG_WARP_IDENTITY if m is None else [float(x) for x in np.asarray(m, dtype=np.float64).reshape(-1)]
+        if len(v) != 6:
+            raise ValueError(f"warp[{i}] must be a 2 x 3 matrix")
+        ws[i].m[:] = v
+    return ws
+
+
+def png_warp_desc(filter="bilinear", border="constant", border_value=None, mode="rgb", depth=8, alpha="straight"):
+    """the debig_png_warp_desc of png_decode_batch_tensor's warp arguments (no GPU needed).  filter: "bilinear" | "nearest";
+    border: "constant" (a tap outside the crop is border_value: per channel on the [0, 1] scale, a number for every channel,
+    None: 0, stored as round(x * (2^depth - 1))) or "clamp" (the edge pixels repeat)."""
+    if filter not in ("bilinear", "nearest"):
+        raise ValueError(f"a warp goes with filter 'bilinear' or 'nearest', not {filter!r}")
+    if alpha != "straight":
+        raise ValueError(f"a warp goes with alpha='straight' only, not {alpha!r}")
+    if border not in PNG_BORDERS:
+        raise ValueError(f"border must be one of {sorted(PNG_BORDERS)}, not {border!r}")
+    if depth not in (8, 16):
+        raise ValueError("a warp needs a concrete depth (8 or 16)")
+    ch = {"rgba": 4, "rgb": 3, "gray": 1, "gray_alpha": 2}[mode]
+    d = PngWarpDesc(filter=PNG_FILTERS[filter], border_mode=PNG_BORDERS[border])
+    if border_value is not None:
+        if border != "constant":
+            raise ValueError("border_value needs border='constant'")
+        bv = [float(x) for x in (border_value if hasattr(border_value, "__len__") else [border_value] * ch)]
+        if len(bv) != ch:
+            raise ValueError(f"border_value needs {ch} values for mode {mode!r}, not {len(bv)}")
+        if not all(0.0 <= x <= 1.0 for x in bv):  # (a NaN fails every comparison)
+            raise ValueError(f"border_value values must lie in [0, 1], not {bv!r}")
+        for k, x in enumerate(bv):
+            d.border[k] = int(round(x * ((1 << depth) - 1)))
+    return d
+
+
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
                             antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
-                            background=None, filter="bilinear"):
+                            background=None, warp=None, border="constant", border_value=None, filter="bilinear"):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
     (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
@@ -552,12 +651,28 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     antialias=True) mean, in Q14 integer weights with signed sums and clamps to [0, 1] of full scale; a crop more than 32
     times the output on an axis is E_BOX) or "nearest" (the source sample at the output pixel's centre, torch's
     "nearest-exact"; antialias is ignored) -- debig_png_decode_batch_tensor_filter, see png_filter_desc.  Every alpha mode
-    goes with every filter."""
+    goes with every filter.
+    warp: None (everything above, unchanged), or one entry per file: None (the identity) or the INVERSE 2 x 3 matrix that
+    takes the centre of output pixel (X, Y) to a position inside the crop (png_warp_matrix makes one from flips, an angle, a
+    scale, a shear and a translation) -- debig_png_decode_batch_tensor_warp: the resize is replaced by the affine map, in
+    integer arithmetic, filter "bilinear" or "nearest", alpha "straight"; `antialias` is not applied under a warp.  border:
+    what a tap outside the crop is: "constant" (border_value, per channel on the [0, 1] scale, default 0) or "clamp" (the edge
+    pixels).  A matrix with a non-finite or too large entry: status 16 ("warp").  (Pass warp, border and border_value by
+    name: `filter` stays the last parameter, as its callers and tests know it.)"""
     import torch
 
+    wd = None
+    if warp is not None:
+        wd = png_warp_desc(filter, border, border_value, mode, depth, alpha)
+        if background is not None:
+            raise ValueError("background needs alpha='over'")
+        antialias = False
+    elif border != "constant" or border_value is not None:
+        raise ValueError("border / border_value need warp")
     d, ch, es = png_tensor_desc(size, mode, depth, dtype, layout, mean, std, antialias)
     ad = png_alpha_desc(alpha, background, mode, depth)
     fd = png_filter_desc(filter)
+    ws = _png_warps(warp, len(datas)) if warp is not None else None
     L = _png_spec_lib()
     L.debig_png_decode_batch_tensor.restype = C.c_int
     L.debig_png_decode_batch_tensor.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
@@ -573,7 +688,12 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
     out = _png_dense_out(shape, tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if fd is not None:
+    if wd is not None:
+        L.debig_png_decode_batch_tensor_warp.restype = C.c_int
+        L.debig_png_decode_batch_tensor_warp.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_tensor_warp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos, n,
+                                                  PNG_FORCE_GENERAL if force_general else 0, C.byref(d), C.byref(wd))
+    elif fd is not None:
         L.debig_png_decode_batch_tensor_filter.restype = C.c_int
         L.debig_png_decode_batch_tensor_filter.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         rc = L.debig_png_decode_batch_tensor_filter(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n,
@@ -621,7 +741,25 @@ def png_label_desc(size, dtype="int64", lut=None):
     return d, 1 << PNG_LABEL_DTYPES[dtype]
 
 
-def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fill=None, device="cuda:0"):
+def png_label_warp_desc(border="constant", border_label=None, dtype="int64"):
+    """the debig_png_label_warp_desc of png_decode_batch_labels' warp arguments (no GPU needed).  border_label: the element of
+    a pick outside the crop under border="constant" (the ignore index; None: 0); it must fit dtype."""
+    if border not in PNG_BORDERS:
+        raise ValueError(f"border must be one of {sorted(PNG_BORDERS)}, not {border!r}")
+    if dtype not in PNG_LABEL_DTYPES:
+        raise ValueError(f"dtype must be one of {sorted(PNG_LABEL_DTYPES)}, not {dtype!r}")
+    if border_label is not None and border != "constant":
+        raise ValueError("border_label needs border='constant'")
+    v = 0 if border_label is None else int(border_label)
+    top = {"uint8": 255, "uint16": 65535}.get(dtype, 2 ** 31 - 1)
+    low = 0 if dtype in ("uint8", "uint16") else -2 ** 31
+    if not low <= v <= top:
+        raise ValueError(f"border_label must lie in [{low}, {top}] for dtype {dtype!r}, not {v}")
+    return PngLabelWarpDesc(border_mode=PNG_BORDERS[border], border_label=v)
+
+
+def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fill=None, device="cuda:0", warp=None,
+                            border="constant", border_label=None):
     """bytes of N label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_labels) -> (statuses, tensor, infos).  The label of a pixel is its palette index (colour type 3)
     or its raw grey sample (colour type 0, 1 to 16 bits): nothing is scaled, PLTE colours and tRNS are ignored.  size =
@@ -630,10 +768,21 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     element is lut[label] (an id -> train-id remap; 16-bit files take none).  dtype: "uint8" | "uint16" | "int32" | "int64";
     uint16 comes as torch.int16 bits where torch has no uint16.  Colour types 2, 4 and 6, a 16-bit file with dtype "uint8" or
     with a lut: status 15 ("label").  The slot of a file whose status is not 0 is left as allocated, or holds `fill` when that
-    is given.  Same device rule as png_decode_batch_device."""
+    is given.  Same device rule as png_decode_batch_device.
+    warp: None (everything above, unchanged), or one entry per file: None (the identity) or the INVERSE 2 x 3 matrix of
+    png_decode_batch_tensor(warp=) -- debig_png_decode_batch_labels_warp: the pick is the one of that call's filter="nearest"
+    under the same matrix, so an image and its mask stay aligned.  border: "constant" (a pick outside the crop stores
+    border_label as it is, not through the lut: the ignore index; default 0) or "clamp".  A matrix with a non-finite or too
+    large entry: status 16 ("warp")."""
     import torch
 
+    wd = None
+    if warp is not None:
+        wd = png_label_warp_desc(border, border_label, dtype)
+    elif border != "constant" or border_label is not None:
+        raise ValueError("border / border_label need warp")
     d, es = png_label_desc(size, dtype, lut)
+    ws = _png_warps(warp, len(datas)) if warp is not None else None
     L = _png_spec_lib()
     L.debig_png_decode_batch_labels.restype = C.c_int
     L.debig_png_decode_batch_labels.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
@@ -643,7 +792,13 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     tdt = {"uint8": torch.uint8, "uint16": getattr(torch, "uint16", torch.int16), "int32": torch.int32, "int64": torch.int64}[dtype]
     out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    rc = L.debig_png_decode_batch_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n, 0, C.byref(d))
+    if wd is not None:
+        L.debig_png_decode_batch_labels_warp.restype = C.c_int
+        L.debig_png_decode_batch_labels_warp.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_labels_warp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos, n, 0,
+                                                  C.byref(d), C.byref(wd))
+    else:
+        rc = L.debig_png_decode_batch_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, n, 0, C.byref(d))
     if rc == PNG_BAD_ARG:
         raise ValueError(f"debig_png_decode_batch_labels rejected its arguments ({rc})")
     N.check(rc, "debig_png_decode_batch_labels")

@@ -866,6 +866,7 @@ typedef struct stage_rule {
     uint32_t index_only;   /* != 0: colour types 2, 4 and 6 are E_LABEL */
     uint32_t no16;         /* != 0: a 16-bit file is E_LABEL */
     uint64_t max_w, max_h; /* max_w != 0: a crop wider / taller than this is E_BOX (the antialiased resize) */
+    const uint8_t *warp_bad; /* != NULL: file i with warp_bad[i] != 0 is E_WARP (the warp calls) */
 } stage_rule;
 
 /* per file: the status decided from IHDR (0: none), the image's place and size in the arena, the resolved box, the walk's info */
@@ -885,7 +886,7 @@ static void stage_free(stage *S)
     free(S->inf);
 }
 
-/* IHDR -> E_LABEL, then E_BOX, then the walk's own error, then the size cap; the decode of what is left into the arena.
+/* IHDR -> E_LABEL, then E_BOX, then E_WARP, then the walk's own error, then the size cap; the decode of what is left into the arena.
  * -> 0 (status and infos written; S filled, the caller's to stage_free either way) or the call's return value */
 static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inputs, const uint64_t *input_sizes,
                         const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags)
@@ -915,6 +916,10 @@ static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inp
         if (b.w == 0 || b.h == 0 || (uint64_t)b.x + b.w > iw || (uint64_t)b.y + b.h > ih ||
             (R->max_w && (b.w > R->max_w || b.h > R->max_h))) {
             S->pre[i] = DEBIG_PNG_E_BOX;
+            continue;
+        }
+        if (R->warp_bad && R->warp_bad[i]) {
+            S->pre[i] = DEBIG_PNG_E_WARP;
             continue;
         }
         S->box[i] = b;
@@ -986,7 +991,7 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     /* the largest antialiased scale (decode_png.h); NEAREST ignores the flag */
     const uint64_t max_scale = filter == DEBIG_PNG_FILTER_BICUBIC ? 32u : 64u;
     const int aa_box = aa && filter != DEBIG_PNG_FILTER_NEAREST;
-    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H};
+    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H, NULL};
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     uint8_t *tasks = NULL;
@@ -1230,12 +1235,9 @@ static void lbl_job_free(lbl_job *J)
     free(J->TY.ax);
 }
 
-DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                            const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n,
-                                            uint32_t flags, const debig_png_label_desc *desc)
+/* the argument checks of debig_png_decode_batch_labels (n > 0): 0 or DEBIG_PNG_BAD_ARG */
+static int label_args_check(const void *d_out, const debig_png_label_desc *desc)
 {
-    /* the arguments on their own, before any file is looked at */
-    if (n == 0) return 0;
     if (!desc || !d_out || ((uintptr_t)d_out & 15u)) return DEBIG_PNG_BAD_ARG;
     if (desc->out_w == 0 || desc->out_w > 16384u || desc->out_h == 0 || desc->out_h > 16384u || desc->dtype > DEBIG_PNG_L_I64 ||
         desc->reserved != 0)
@@ -1243,9 +1245,20 @@ DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const 
     if (desc->lut && desc->dtype <= DEBIG_PNG_L_U16)
         for (uint32_t k = 0; k < 256; k++)
             if (desc->lut[k] < 0 || desc->lut[k] > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)) return DEBIG_PNG_BAD_ARG;
+    return 0;
+}
+
+DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                            const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                            uint32_t flags, const debig_png_label_desc *desc)
+{
+    /* the arguments on their own, before any file is looked at */
+    if (n == 0) return 0;
+    const int bad = label_args_check(d_out, desc);
+    if (bad) return bad;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, NULL};
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     dev_table tab[3] = {{desc->lut, 1024, 0}, {NULL, 0, 0}, {NULL, 0, 0}}; /* the LUT (or its room), the X tables, the Y tables */
@@ -1329,7 +1342,7 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
     if (!map_mode && (desc->dtype < DEBIG_PNG_L_I32 || desc->n_maps != 0)) return DEBIG_PNG_BAD_ARG;
     if (map_mode && ((desc->n_maps != 1 && desc->n_maps != n) || !desc->maps)) return DEBIG_PNG_BAD_ARG;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL}; /* E_LABEL: a 16-bit file */
 
     uint32_t *mtab = NULL;          /* the maps' tables, one behind the other */
     uint64_t *moff = NULL;          /* table k: at moff[k] bytes, mslots[k] slots */
@@ -1406,5 +1419,187 @@ done:
     free(cnt);
     stage_free(&S);
     lbl_job_free(&J);
+    return rc;
+}
+
+/* ---- the affine warp of the tensor and the label decode (decode_png.h) ------------------------------------------------------ */
+
+#define WARP_TASK_PIXELS 4096u /* output pixels of one warp task (a run of whole rows; one row when it is wider): 16 per lane */
+
+DEBIG_API int debig_png_warp_quantise(const double M[6], int64_t m[6])
+{
+    for (uint32_t k = 0; k < 6; k++) {
+        uint64_t u;
+        memcpy(&u, &M[k], 8);
+        if ((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull) return 0; /* infinity or NaN */
+        const double lim = k == 2 || k == 5 ? 16777216.0 : 32768.0, a = M[k] < 0 ? -M[k] : M[k];
+        if (a > lim) return 0;
+        /* llround: the product is exact (a power of two) and below 2^41, so is x - trunc(x); halves go away from zero */
+        const double x = M[k] * 65536.0;
+        int64_t q = (int64_t)x;
+        const double d = x - (double)q;
+        if (d >= 0.5) q++;
+        else if (d <= -0.5) q--;
+        m[k] = q;
+    }
+    return 1;
+}
+
+/* the files' matrices quantised (6 int64 each) and their E_WARP flags; -> 0 or 2 */
+static int warp_prepare(const debig_png_warp *warps, uint32_t n, int64_t **m, uint8_t **bad)
+{
+    *m = (int64_t *)calloc((size_t)n * 6u, sizeof(int64_t));
+    *bad = (uint8_t *)calloc(n, 1);
+    if (!*m || !*bad) return 2;
+    for (uint32_t i = 0; i < n; i++) (*bad)[i] = !debig_png_warp_quantise(warps[i].m, *m + 6u * (size_t)i);
+    return 0;
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                 const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                 debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                 const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
+{
+    /* every check of debig_png_decode_batch_tensor first and unchanged, then the warp's; all before any file is looked at */
+    if (n == 0) return 0;
+    const int badarg = tensor_args_check(d_out, desc);
+    if (badarg) return badarg;
+    if (!warps || !wd || (wd->filter != DEBIG_PNG_FILTER_BILINEAR && wd->filter != DEBIG_PNG_FILTER_NEAREST) ||
+        wd->border_mode > DEBIG_PNG_BORDER_CLAMP || wd->alpha_mode != DEBIG_PNG_ALPHA_STRAIGHT || wd->reserved != 0 ||
+        desc->resize_flags != 0)
+        return DEBIG_PNG_BAD_ARG;
+    const uint32_t fmt = desc->out_format, ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u, sb = bits / 8u;
+    if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT)
+        for (uint32_t k = 0; k < ch; k++)
+            if (wd->border[k] > (1u << bits) - 1u) return DEBIG_PNG_BAD_ARG;
+    const uint32_t W = desc->out_w, H = desc->out_h;
+    const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? sb : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
+    const uint64_t slot = (uint64_t)H * W * ch * es;
+    const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
+
+    stage S = {NULL, NULL, NULL, NULL, NULL};
+    int64_t *m = NULL;
+    uint8_t *wbad = NULL;
+    debig_png_warp_task *tasks = NULL;
+    uint64_t n_tasks = 0;
+    uint32_t cap_tasks = 0;
+    int rc;
+    if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
+    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad}; /* no crop-size cap */
+    if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
+    rc = 2;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status[i] != DEBIG_PNG_OK) continue;
+        debig_png_warp_task p;
+        memset(&p, 0, sizeof p);
+        p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * ch * sb;
+        p.out_off = (uint64_t)i * slot;
+        memcpy(p.m, m + 6u * (size_t)i, sizeof p.m);
+        p.src_pitch = S.inf[i].width * ch;
+        p.crop_w = S.box[i].w;
+        p.crop_h = S.box[i].h;
+        p.out_w = W;
+        p.out_h = H;
+        p.out_sx = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? 1u : ch;
+        p.out_sy = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? W : W * ch;
+        p.out_sc = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? H * W : 1u;
+        p.channels = (uint8_t)ch;
+        p.bits = (uint8_t)bits;
+        p.dtype = (uint8_t)desc->dtype;
+        p.filter = (uint8_t)wd->filter;
+        p.border_mode = (uint8_t)wd->border_mode;
+        for (uint32_t k = 0; k < 4; k++) {
+            p.border[k] = k < ch ? wd->border[k] : 0;
+            p.a[k] = (float)((double)desc->scale[k] / ((double)((1u << bits) - 1u) * (double)(1u << (30u - bits))));
+            p.b[k] = desc->bias[k];
+        }
+        for (uint32_t y0 = 0; y0 < H; y0 += run) {
+            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof p)) goto done;
+            p.row0 = y0;
+            p.rows = H - y0 < run ? H - y0 : run;
+            tasks[n_tasks++] = p;
+        }
+    }
+    rc = 0;
+    if (n_tasks == 0) goto done;
+    const dev_table none = {NULL, 0, 0}; /* the warp has no tables: the six int64 travel in the task */
+    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, &none, 1, &rc);
+    if (!c) goto done;
+    if ((rc = debig_hip_png_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_warp_task *)c->rsz_tasks.ptr, (uint32_t)n_tasks, NULL)))
+        goto done;
+    rc = debig_hip_stream_sync(NULL);
+done:
+    stage_free(&S);
+    free(m);
+    free(wbad);
+    free(tasks);
+    return rc;
+}
+
+DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                 const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                 debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                 const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
+{
+    /* every check of debig_png_decode_batch_labels first and unchanged, then the warp's; all before any file is looked at */
+    if (n == 0) return 0;
+    const int badarg = label_args_check(d_out, desc);
+    if (badarg) return badarg;
+    if (!warps || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) return DEBIG_PNG_BAD_ARG;
+    if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
+        (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
+        return DEBIG_PNG_BAD_ARG;
+    const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
+    const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
+
+    stage S = {NULL, NULL, NULL, NULL, NULL};
+    int64_t *m = NULL;
+    uint8_t *wbad = NULL;
+    debig_png_label_warp_task *tasks = NULL;
+    uint64_t n_tasks = 0;
+    uint32_t cap_tasks = 0;
+    int rc;
+    if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
+    /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad};
+    if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
+    rc = 2;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status[i] != DEBIG_PNG_OK) continue;
+        debig_png_label_warp_task p;
+        memset(&p, 0, sizeof p);
+        p.src_bytes = S.inf[i].bit_depth == 16 ? 2u : 1u;
+        p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * p.src_bytes;
+        p.out_off = (uint64_t)i * H * W * es;
+        memcpy(p.m, m + 6u * (size_t)i, sizeof p.m);
+        p.src_pitch = S.inf[i].width;
+        p.crop_w = S.box[i].w;
+        p.crop_h = S.box[i].h;
+        p.out_w = W;
+        p.out_h = H;
+        p.border_label = wd->border_label;
+        p.dtype = (uint8_t)desc->dtype;
+        p.border_mode = (uint8_t)wd->border_mode;
+        for (uint32_t y0 = 0; y0 < H; y0 += run) {
+            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof p)) goto done;
+            p.row0 = y0;
+            p.rows = H - y0 < run ? H - y0 : run;
+            tasks[n_tasks++] = p;
+        }
+    }
+    rc = 0;
+    if (n_tasks == 0) goto done;
+    const dev_table lut = {desc->lut, 1024, 0}; /* the LUT (or its room) */
+    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, &lut, 1, &rc);
+    if (!c) goto done;
+    if ((rc = debig_hip_png_label_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_warp_task *)c->rsz_tasks.ptr,
+                                             desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL, (uint32_t)n_tasks, NULL)))
+        goto done;
+    rc = debig_hip_stream_sync(NULL);
+done:
+    stage_free(&S);
+    free(m);
+    free(wbad);
+    free(tasks);
     return rc;
 }

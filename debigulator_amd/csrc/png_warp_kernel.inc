@@ -1,0 +1,190 @@
+// png_warp_kernel.inc -- crop + affine warp (flips, quarter turns, rotation, scale, shear) + normalise of decoded PNG pixels into
+// one dense tensor, and the same warp of raw labels into one dense integer tensor
+// (include/decode_png.h: debig_png_decode_batch_tensor_warp, debig_png_decode_batch_labels_warp; include/debig_hip.h:
+// debig_hip_png_warp_batch, debig_hip_png_label_warp_batch).
+//
+// The arithmetic is fixed by decode_png.h: the inverse map as six int64 in Q16, the source position of an output pixel's
+// centre in Q17 (U, V: int64, below 2^48 in magnitude), floor shifts for the pick, Q14 weights from the low 17 bits, the
+// horizontal pass rounded to 16 bits, the vertical pass into 30 bits, then the ONE conversion of the resize kernels
+// (rsz_cubic_store).  An affine map is not separable, so nothing of the two-pass LDS scheme of png_resize_kernel.inc carries
+// over: this is a gather.
+//
+// One TASK is a run of output rows of one image; one workgroup of 256 lanes per task:
+//   - an ITEM is one output pixel; the lanes run along X, then on into the next row of the run, so narrow tensors keep every
+//     lane busy and a wavefront's stores are adjacent pixels of a row (CHW: adjacent elements of each plane row; HWC: elements
+//     `channels` apart, the channel loop fills the gaps within the same cache lines);
+//   - a lane computes U and V of its pixel from the task's six int64, then per channel loads its 1 (nearest) or 4 (bilinear)
+//     taps straight from the arena.  The source footprint of a row run is a thin parallelogram of the crop; neighbouring lanes
+//     read neighbouring or identical samples, and the second tap row of one output row is the first of a later one: the
+//     re-reads are L1 / L2 hits.  (An LDS-staged footprint was not built: profiles/png_warp.txt has the measurement of this
+//     version against the two-pass torch route.)
+//   - every tap index is clamped into the crop BEFORE it addresses memory, whatever the border mode; under CONSTANT the
+//     loaded value is then replaced by the border sample by a select.  No lane reads outside the crop, and no branch diverges
+//     on the position;
+//   - a[] / b[] / border[] are read through tg, the task in global memory, where a run-time channel index costs nothing
+//     (into the by-value struct it would go through scratch).
+// The label kernel has the same tasks and the same U, V; its 256-entry LUT is staged in LDS once per workgroup, as in
+// png_label_kernel.inc.  A border pick stores border_label as it is (it does not pass through the LUT).
+// A task that breaks a bound is skipped (never indexed out of range).  No atomics, no scratch, nothing shared between
+// workgroups; plain vector stores only.
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_resize_kernel.inc and png_label_kernel.inc
+// in front of it.
+
+#define WARP_THREADS 256u
+#define WARP_FILTER_BILINEAR 0u // decode_png.h: DEBIG_PNG_FILTER_BILINEAR
+#define WARP_FILTER_NEAREST 2u  // decode_png.h: DEBIG_PNG_FILTER_NEAREST
+#define WARP_BORDER_CLAMP 1u    // decode_png.h: DEBIG_PNG_BORDER_CLAMP (0: _CONSTANT)
+
+// the matrix limits of decode_png.h on the quantised entries: they keep |U|, |V| below 2^48
+DEV_INLINE bool warp_matrix_ok(int64_t m00, int64_t m01, int64_t m02, int64_t m10, int64_t m11, int64_t m12)
+{
+    const int64_t lin = (int64_t)1 << 31, tr = (int64_t)1 << 40;
+    return m00 >= -lin && m00 <= lin && m01 >= -lin && m01 <= lin && m10 >= -lin && m10 <= lin && m11 >= -lin && m11 <= lin &&
+           m02 >= -tr && m02 <= tr && m12 >= -tr && m12 <= tr;
+}
+
+// the sizes every warp task shares
+DEV_INLINE bool warp_sizes_ok(uint32_t out_w, uint32_t out_h, uint32_t row0, uint32_t rows, uint32_t crop_w, uint32_t crop_h)
+{
+    return out_w != 0u && out_w <= 16384u && out_h <= 16384u && rows != 0u && row0 < out_h && rows <= out_h - row0 &&
+           crop_w != 0u && crop_w <= 0x7fffffffu && crop_h != 0u && crop_h <= 0x7fffffffu;
+}
+
+// an index clamped into [0, cl - 1]; *inside: whether it lay there (int64 comparisons, before anything is narrowed)
+DEV_INLINE uint32_t warp_clamp(int64_t j, uint32_t cl, bool *inside)
+{
+    *inside = j >= 0 && j < (int64_t)cl;
+    return (uint32_t)(j < 0 ? 0 : j >= (int64_t)cl ? (int64_t)cl - 1 : j);
+}
+
+// the rows of one task at source precision P
+template <uint32_t P>
+DEV_INLINE void warp_rows(const debig_png_warp_task &t, const debig_png_warp_task *__restrict__ tg, const uint8_t *__restrict__ src,
+                          uint8_t *__restrict__ out, uint32_t tid)
+{
+    typedef typename RszSample<P>::sample_t sample_t;
+    const sample_t *s = reinterpret_cast<const sample_t *>(src + t.src_off);
+    uint8_t *o = out + t.out_off;
+    const uint32_t ch = t.channels, n = t.rows * t.out_w;
+    const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
+    uint32_t r = tid / t.out_w, X = tid - r * t.out_w;
+    const uint32_t dr = WARP_THREADS / t.out_w, dx = WARP_THREADS - dr * t.out_w;
+    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
+        const uint32_t Y = t.row0 + r;
+        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
+        const int64_t U = t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], V = t.m[3] * cx + t.m[4] * cy + 2 * t.m[5];
+        const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
+        if (nearest) {
+            bool inx, iny;
+            const uint32_t jx = warp_clamp(U >> 17, t.crop_w, &inx), jy = warp_clamp(V >> 17, t.crop_h, &iny);
+            const bool keep = clamp || (inx && iny);
+            const uint64_t at = (uint64_t)jy * t.src_pitch + (uint64_t)jx * ch;
+            for (uint32_t c = 0; c < ch; c++) {
+                uint32_t v = s[at + c];
+                if (!keep) v = tg->border[c];
+                rsz_cubic_store(t.dtype, P, tg->a[c], tg->b[c], o, el + (uint64_t)c * t.out_sc, v << (30u - P));
+            }
+        } else {
+            const int64_t tu = U - 65536, tv = V - 65536;
+            const int64_t ix = tu >> 17, iy = tv >> 17;
+            const uint32_t w1x = ((uint32_t)(tu & 0x1FFFF) + 4u) >> 3, w0x = 16384u - w1x;
+            const uint32_t w1y = ((uint32_t)(tv & 0x1FFFF) + 4u) >> 3, w0y = 16384u - w1y;
+            bool ix0, ix1, iy0, iy1;
+            const uint32_t x0 = warp_clamp(ix, t.crop_w, &ix0), x1 = warp_clamp(ix + 1, t.crop_w, &ix1);
+            const uint32_t y0 = warp_clamp(iy, t.crop_h, &iy0), y1 = warp_clamp(iy + 1, t.crop_h, &iy1);
+            const bool k00 = clamp || (ix0 && iy0), k01 = clamp || (ix1 && iy0), k10 = clamp || (ix0 && iy1), k11 = clamp || (ix1 && iy1);
+            const uint64_t r0 = (uint64_t)y0 * t.src_pitch, r1 = (uint64_t)y1 * t.src_pitch;
+            const uint64_t c0 = (uint64_t)x0 * ch, c1 = (uint64_t)x1 * ch;
+            for (uint32_t c = 0; c < ch; c++) {
+                const uint32_t bd = tg->border[c];
+                uint32_t s00 = s[r0 + c0 + c], s01 = s[r0 + c1 + c], s10 = s[r1 + c0 + c], s11 = s[r1 + c1 + c];
+                if (!k00) s00 = bd;
+                if (!k01) s01 = bd;
+                if (!k10) s10 = bd;
+                if (!k11) s11 = bd;
+                const uint32_t h0 = (w0x * s00 + w1x * s01 + (1u << (P - 3u))) >> (P - 2u);
+                const uint32_t h1 = (w0x * s10 + w1x * s11 + (1u << (P - 3u))) >> (P - 2u);
+                rsz_cubic_store(t.dtype, P, tg->a[c], tg->b[c], o, el + (uint64_t)c * t.out_sc, w0y * h0 + w1y * h1);
+            }
+        }
+        r += dr;
+        X += dx;
+        if (X >= t.out_w) { X -= t.out_w; r++; }
+    }
+}
+
+__global__ void __launch_bounds__(WARP_THREADS)
+debig_png_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, const debig_png_warp_task *__restrict__ tasks,
+                      uint32_t n_tasks)
+{
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
+        const debig_png_warp_task t = tasks[ti];
+        // (uniform over the workgroup: every lane skips, or none)
+        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || t.channels == 0u || t.channels > 4u ||
+            (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.filter != WARP_FILTER_BILINEAR && t.filter != WARP_FILTER_NEAREST) ||
+            t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
+            (t.src_off & ((uint32_t)t.bits / 8u - 1u)))
+            continue;
+        if (t.bits == 8u) warp_rows<8u>(t, &tasks[ti], src, out, tid);
+        else warp_rows<16u>(t, &tasks[ti], src, out, tid);
+    }
+}
+
+// ---- the same warp of raw labels: nearest only, the picks of the image kernel's NEAREST filter ---------------------------------
+
+// the rows of one task: elements of ES bytes, source labels of SB bytes
+template <uint32_t ES, uint32_t SB>
+DEV_INLINE void warp_label_rows(const int32_t *lut, const debig_png_label_warp_task &t, const uint8_t *__restrict__ src,
+                                uint8_t *__restrict__ out, uint32_t tid)
+{
+    const uint8_t *s0 = src + t.src_off;
+    const uint32_t n = t.rows * t.out_w;
+    const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
+    uint32_t r = tid / t.out_w, X = tid - r * t.out_w;
+    const uint32_t dr = WARP_THREADS / t.out_w, dx = WARP_THREADS - dr * t.out_w;
+    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
+        const uint32_t Y = t.row0 + r;
+        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
+        const int64_t U = t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], V = t.m[3] * cx + t.m[4] * cy + 2 * t.m[5];
+        bool inx, iny;
+        const uint32_t jx = warp_clamp(U >> 17, t.crop_w, &inx), jy = warp_clamp(V >> 17, t.crop_h, &iny);
+        const uint64_t at = (uint64_t)jy * t.src_pitch + jx;
+        uint32_t v = SB == 1u ? (uint32_t)s0[at] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[at];
+        if (lut) v = (uint32_t)lut[v & 255u];
+        if (!clamp && !(inx && iny)) v = (uint32_t)t.border_label;
+        lbl_store1<ES>(out + t.out_off + ((uint64_t)Y * t.out_w + X) * ES, v);
+        r += dr;
+        X += dx;
+        if (X >= t.out_w) { X -= t.out_w; r++; }
+    }
+}
+
+__global__ void __launch_bounds__(WARP_THREADS)
+debig_png_label_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                            const debig_png_label_warp_task *__restrict__ tasks, const int32_t *__restrict__ lut, uint32_t n_tasks)
+{
+    __shared__ int32_t lds_lut[256];
+    const uint32_t tid = threadIdx.x;
+    if (lut) lds_lut[tid & 255u] = lut[tid & 255u];
+    __syncthreads();
+    const int32_t *L = lut ? lds_lut : nullptr;
+    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
+        const debig_png_label_warp_task t = tasks[ti];
+        // (uniform over the workgroup: every lane skips, or none)
+        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || (t.src_bytes != 1u && t.src_bytes != 2u) ||
+            t.dtype > 3u || (t.dtype == 0u && t.src_bytes == 2u) || (lut && t.src_bytes == 2u) || t.border_mode > WARP_BORDER_CLAMP ||
+            !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || (t.src_off & (t.src_bytes - 1u)))
+            continue;
+        if (t.src_bytes == 1u) {
+            if (t.dtype == 0u) warp_label_rows<1u, 1u>(L, t, src, out, tid);
+            else if (t.dtype == 1u) warp_label_rows<2u, 1u>(L, t, src, out, tid);
+            else if (t.dtype == 2u) warp_label_rows<4u, 1u>(L, t, src, out, tid);
+            else warp_label_rows<8u, 1u>(L, t, src, out, tid);
+        } else {
+            if (t.dtype == 1u) warp_label_rows<2u, 2u>(L, t, src, out, tid);
+            else if (t.dtype == 2u) warp_label_rows<4u, 2u>(L, t, src, out, tid);
+            else warp_label_rows<8u, 2u>(L, t, src, out, tid);
+        }
+    }
+}

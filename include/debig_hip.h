@@ -518,6 +518,61 @@ typedef struct debig_png_color_label_task {
 int debig_hip_png_color_label_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_task *d_tasks,
                                     const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream);
 
+/* Crop + affine warp + normalise of decoded pixels (csrc/png_warp_kernel.inc, behind debig_png_decode_batch_tensor_warp in
+ * decode_png.h, which has the rule).  One task: the output rows [row0, row0 + rows) of one image, one workgroup of 256 lanes, one
+ * lane per output pixel.  m[] is the image's inverse map as debig_png_warp_quantise gives it (Q16; |m[0]|, |m[1]|, |m[3]|,
+ * |m[4]| <= 2^31, |m[2]|, |m[5]| <= 2^40); the pixels are gathered straight from the arena, every tap index clamped into the
+ * crop before it addresses memory.  A task that breaks a bound -- the sizes (out_w, out_h 1 .. 16384, row0 + rows <= out_h,
+ * crop_w, crop_h 1 .. 2^31 - 1), channels outside 1 .. 4, bits other than 8 / 16, an unknown dtype, filter or border mode, a
+ * matrix entry beyond its limit, a src_off that is not aligned to the sample size -- is skipped. */
+typedef struct debig_png_warp_task {
+    uint64_t src_off;       /* sample (0, 0) of the CROP, in bytes rel. to d_src_arena (aligned to the sample size)         */
+    uint64_t out_off;       /* the image's slot, in bytes rel. to d_out (aligned to the element size)                       */
+    int64_t m[6];           /* the inverse map, row major, Q16                                                               */
+    uint32_t src_pitch;     /* samples from one source row to the next (image width * channels)                              */
+    uint32_t crop_w, crop_h; /* the crop in pixels: taps outside [0, crop_w) x [0, crop_h) are border                        */
+    uint32_t out_w, out_h;  /* 1 .. 16384                                                                                    */
+    uint32_t row0, rows;    /* row0 + rows <= out_h                                                                          */
+    uint32_t out_sx, out_sy, out_sc; /* output strides of x, y and the channel, in ELEMENTS (HWC: C, W*C, 1; CHW: 1, W, H*W) */
+    uint8_t channels;       /* 1..4, interleaved in the source                                                               */
+    uint8_t bits;           /* P: 8 (uint8 samples) or 16 (uint16, little-endian)                                            */
+    uint8_t dtype;          /* decode_png.h DEBIG_PNG_T_*                                                                    */
+    uint8_t filter;         /* decode_png.h DEBIG_PNG_FILTER_BILINEAR or _NEAREST                                            */
+    uint8_t border_mode;    /* decode_png.h DEBIG_PNG_BORDER_CONSTANT or _CLAMP                                              */
+    uint8_t reserved[3];
+    uint16_t border[4];     /* CONSTANT: the border sample per channel at precision P, 0 .. 2^P - 1                          */
+    float a[4], b[4];       /* float dtypes: element = (float)v * a[c] + b[c], two rounded operations (decode_png.h)         */
+} debig_png_warp_task;
+/* Warp n_tasks row runs (device pointers, asynchronous on hip_stream).  Nothing but the tasks' own output elements is written. */
+int debig_hip_png_warp_batch(const void *d_src_arena, void *d_out, const debig_png_warp_task *d_tasks, uint32_t n_tasks,
+                             void *hip_stream);
+
+/* The same warp of raw labels (debig_png_label_warp_kernel, behind debig_png_decode_batch_labels_warp in decode_png.h): nearest
+ * only, the pick of the image task's NEAREST filter under the same m[].  The source is one byte or one little-endian uint16 per
+ * pixel; the element is the label, through the call's LUT when it has one, or border_label AS IT IS where the pick leaves the
+ * crop under CONSTANT; stored as `dtype`.  A task that breaks a bound -- the sizes and matrix limits above, src_bytes other than
+ * 1 / 2, an unknown dtype or border mode, a dtype of one byte or a LUT with two-byte labels, a src_off that is not aligned to
+ * src_bytes -- is skipped. */
+typedef struct debig_png_label_warp_task {
+    uint64_t src_off;        /* label (0, 0) of the CROP, in bytes rel. to d_src_arena (aligned to src_bytes)                 */
+    uint64_t out_off;        /* the image's slot, in bytes rel. to d_out (aligned to the element size)                        */
+    int64_t m[6];            /* the inverse map, row major, Q16                                                               */
+    uint32_t src_pitch;      /* labels from one source row to the next (the image's width)                                    */
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;   /* 1 .. 16384                                                                                    */
+    uint32_t row0, rows;     /* row0 + rows <= out_h                                                                          */
+    int32_t border_label;    /* CONSTANT: the element of a pick outside the crop (inside the dtype's range)                   */
+    uint8_t src_bytes;       /* 1, or 2 (little-endian uint16)                                                                */
+    uint8_t dtype;           /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                       */
+    uint8_t border_mode;     /* decode_png.h DEBIG_PNG_BORDER_CONSTANT or _CLAMP                                              */
+    uint8_t reserved;
+    uint32_t reserved2;
+} debig_png_label_warp_task;
+/* n_tasks row runs (device pointers, asynchronous on hip_stream).  d_lut: 256 int32 in device memory, staged in LDS once per
+ * workgroup, or NULL.  Nothing but the tasks' own output elements is written. */
+int debig_hip_png_label_warp_batch(const void *d_src_arena, void *d_out, const debig_png_label_warp_task *d_tasks,
+                                   const int32_t *d_lut, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

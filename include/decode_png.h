@@ -235,8 +235,9 @@ int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *inp
  * (64-bit sums), or antialias with cl > 64 L on either axis (that bounds the taps at 129 and keeps the corrected weight
  * positive).  E_OUTPUT: the decoded image is larger than 2^31 bytes.  A file with any non-zero status leaves its slot
  * untouched; nothing outside d_out[0 .. n * slot) is written.
- * Not provided: flips, colour jitter, animated PNGs, inputs already on the device, an asynchronous variant; other filters than
- * bilinear are debig_png_decode_batch_tensor_filter's (below). */
+ * Not provided: colour jitter, animated PNGs, inputs already on the device, an asynchronous variant; other filters than
+ * bilinear are debig_png_decode_batch_tensor_filter's, flips, quarter turns and every other affine map are
+ * debig_png_decode_batch_tensor_warp's (both below). */
 typedef struct debig_png_box { uint32_t x, y, w, h; } debig_png_box; /* w == 0 && h == 0: the whole image */
 enum { DEBIG_PNG_T_UINT = 0, DEBIG_PNG_T_F32 = 1, DEBIG_PNG_T_F16 = 2, DEBIG_PNG_T_BF16 = 3 };
 #define DEBIG_PNG_RESIZE_ANTIALIAS 1u
@@ -332,8 +333,8 @@ int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, const uint
  * Checked before any file is looked at, with status unwritten: every check of debig_png_decode_batch_tensor_alpha first and
  * unchanged; then DEBIG_PNG_BAD_ARG for an unknown filter or reserved != 0.  Per image: statuses, their order, the untouched
  * slot of a failed file and infos are those of debig_png_decode_batch_tensor_alpha, with the E_BOX scale rule of the filter.
- * Not provided: Lanczos and other kernels, the a = -3/4 variant, border replication, flips, colour jitter, animated PNGs,
- * inputs already on the device, an asynchronous variant. */
+ * Not provided: Lanczos and other kernels, the a = -3/4 variant, border replication, colour jitter, animated PNGs,
+ * inputs already on the device, an asynchronous variant.  (Flips and affine maps: debig_png_decode_batch_tensor_warp below.) */
 enum { DEBIG_PNG_FILTER_BILINEAR = 0, DEBIG_PNG_FILTER_BICUBIC = 1, DEBIG_PNG_FILTER_NEAREST = 2 };
 typedef struct debig_png_filter_desc { uint32_t filter; uint32_t reserved; /* 0 */ } debig_png_filter_desc;
 int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -374,8 +375,8 @@ uint32_t debig_png_resize_weights_filter(uint32_t filter, uint32_t cl, uint32_t 
  * found on the GPU; E_OUTPUT: the raw labels are larger than 2^31 bytes).  A file with a non-zero status leaves its slot
  * untouched; nothing outside d_out[0 .. n * slot) is written.
  * Not provided: label output to host buffers or at each file's own size, LUTs for 16-bit sources, boundary / ignore-ring
- * generation, flips, animated PNGs, inputs already on the device, an asynchronous variant.  (Colour -> class lookup for
- * RGB-coded masks: debig_png_decode_batch_color_labels below.) */
+ * generation, animated PNGs, inputs already on the device, an asynchronous variant.  (Colour -> class lookup for
+ * RGB-coded masks: debig_png_decode_batch_color_labels below; flips and affine maps: debig_png_decode_batch_labels_warp.) */
 #define DEBIG_PNG_E_LABEL 15 /* not a label file for this call (rules above) */
 enum { DEBIG_PNG_L_U8 = 0, DEBIG_PNG_L_U16 = 1, DEBIG_PNG_L_I32 = 2, DEBIG_PNG_L_I64 = 3 };
 typedef struct debig_png_label_desc {
@@ -420,8 +421,8 @@ int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *
  * statuses of debig_png_decode_batch_fmt in their order (E_PALETTE; E_OUTPUT: more than 2^31 decoded RGB8 bytes).  A file with
  * a non-zero status leaves its slot untouched; nothing outside d_out[0 .. n * slot) is written.
  * Not provided: arithmetic decodings other than PACK (e.g. ADE20K's R / 10 * 256 + G), maps above DEBIG_PNG_CMAP_MAX entries,
- * 16-bit sources, nearest-colour matching for unmatched pixels, host-buffer output, flips, animated PNGs, inputs already on the
- * device, an asynchronous variant. */
+ * 16-bit sources, nearest-colour matching for unmatched pixels, host-buffer output, flips and affine maps (the warp calls below
+ * cover images and raw labels only), animated PNGs, inputs already on the device, an asynchronous variant. */
 #define DEBIG_PNG_CMAP_MAX 2048u
 enum { DEBIG_PNG_CL_PACK = 0, DEBIG_PNG_CL_MAP = 1 };
 typedef struct debig_png_color_map {      /* host memory, read before the call returns */
@@ -449,6 +450,73 @@ int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, const uint
  * nothing written for a map the call refuses (map NULL, n > DEBIG_PNG_CMAP_MAX, n > 0 with a NULL array, a key above
  * 0xFFFFFF, two equal keys) or when cap_slots is too small (4096 always suffices). */
 uint32_t debig_png_color_map_table(const debig_png_color_map *map, uint32_t *table, uint32_t cap_slots);
+
+/* ---- affine warp: flips, quarter turns, rotation, scale and shear in the tensor and label decodes ---------------------------------
+ * debig_png_decode_batch_tensor_warp and debig_png_decode_batch_labels_warp are debig_png_decode_batch_tensor and
+ * debig_png_decode_batch_labels with the resize replaced by an affine map, one per file: warps[i].m is the INVERSE map M
+ * (2 x 3, row major).  The continuous source position of output pixel (X, Y) is
+ *     (u, v) = M . (X + 1/2, Y + 1/2, 1)
+ * in pixel units of the CROP (boxes[i], or the whole image), where source pixel j covers [j, j + 1).  Singular matrices are
+ * legal: the map is only ever applied in this direction.
+ * The host quantises once: m_k = llround(M_k * 65536) as int64 (debig_png_warp_quantise).  A file whose matrix has a non-finite
+ * entry, |M00|, |M01|, |M10| or |M11| above 32768, or |M02| or |M12| above 2^24 gets DEBIG_PNG_E_WARP; it is decided when IHDR
+ * has been read, ranks behind E_LABEL and E_BOX and, like them, ahead of whatever is found later in the file.
+ * All position arithmetic is int64, in Q17:
+ *     U = m00 (2X + 1) + m01 (2Y + 1) + 2 m02,    V = m10 (2X + 1) + m11 (2Y + 1) + 2 m12.
+ * With |m00|, |m01| <= 2^31, 2X + 1, 2Y + 1 < 2^15 and |m02| <= 2^40: |U|, |V| <= 2 * 2^31 * (2^15 - 1) + 2^41 < 2^48.
+ *   - DEBIG_PNG_FILTER_NEAREST: the pick is (jx, jy) = (U >> 17, V >> 17), the shift arithmetic (floor); v30 = s << (30 - P).
+ *   - DEBIG_PNG_FILTER_BILINEAR, per axis: t = U - 65536, i0 = t >> 17, f = t & 0x1FFFF, w1 = (f + 4) >> 3 (Q14, 0 .. 16384),
+ *     w0 = 16384 - w1; the taps are i0 and i0 + 1.  Horizontal first, precision handling exactly as in the resize:
+ *     h = w0x s(i0x) + w1x s(i0x + 1);  Hq = (h + (1 << (P - 3))) >> (P - 2);  v = w0y Hq(row i0y) + w1y Hq(row i0y + 1)  (< 2^30).
+ *   - then the ONE conversion of debig_png_decode_batch_tensor, unchanged: UINT, F32 with a separately rounded multiply and
+ *     add, F16, BF16; scale / bias as there.
+ *   - border_mode DEBIG_PNG_BORDER_CONSTANT: a tap whose x or y lies outside [0, cl) is border[c], an integer sample at
+ *     precision P per source channel (for NEAREST: an outside pick is the border); DEBIG_PNG_BORDER_CLAMP: tap indices are
+ *     clamped to [0, cl - 1].  All comparisons happen in int64 before anything is narrowed.
+ * Consequences: the identity matrix with out == crop gives the cropped decode exactly in UINT (f = 0: the second tap weighs 0);
+ * an integer translation gives the shifted decode, with border where it leaves the crop; the flip matrices
+ * ((-1, 0, cw), (0, 1, 0)) and ((1, 0, 0), (0, -1, chh)) and the quarter-turn matrices ((0, -1, cw), (1, 0, 0)),
+ * ((-1, 0, cw), (0, -1, chh)), ((0, 1, 0), (-1, 0, chh)) -- numpy.rot90 with k = 1, 2, 3, into an output of chh x cw pixels
+ * (w x h) for k = 1 and 3 -- give numpy.flip / numpy.rot90 of the decode exactly, for both filters (U and V are odd multiples
+ * of 65536 there: f = 0 again).
+ * Labels: nearest only, with the same jx, jy -- an image warped with filter NEAREST and its label map warped with the same
+ * matrix pick the same source pixels.  An outside pick under CONSTANT stores border_label as it is (the ignore index: it does
+ * not pass through the lut); CLAMP as above.  lut, dtypes and the E_LABEL rules are those of debig_png_decode_batch_labels.
+ * Both calls decode as the calls they extend (the same arena, no crop-size cap), then ONE launch warps all images
+ * (debig_hip_png_warp_batch / debig_hip_png_label_warp_batch: a gather, one lane per output pixel).
+ * Checked first, before any file is looked at (status unwritten): every check of the call that is extended, unchanged; then
+ * DEBIG_PNG_BAD_ARG for warps or the warp descriptor NULL, a filter other than BILINEAR / NEAREST (BICUBIC included), an
+ * unknown border_mode, alpha_mode other than DEBIG_PNG_ALPHA_STRAIGHT, reserved != 0, the antialias flag in desc->resize_flags,
+ * a used border[c] above 2^P - 1 under CONSTANT, a border_label outside the dtype's range under CONSTANT (U8: 0 .. 255,
+ * U16: 0 .. 65535).  Per image: statuses, their order, infos and the untouched slot of a failed file are those of the call
+ * that is extended, with E_WARP as above.
+ * Not provided: antialiasing under a shrinking warp (shrink with the resize calls, or accept aliasing), bicubic, the OVER and
+ * PREMULTIPLIED alpha modes together with a warp (alpha is warped like a colour channel, as in debig_png_decode_batch_tensor),
+ * perspective maps, colour-coded label maps (debig_png_decode_batch_color_labels stays as it is), colour jitter. */
+#define DEBIG_PNG_E_WARP 16 /* the warp matrix (rules above) */
+enum { DEBIG_PNG_BORDER_CONSTANT = 0, DEBIG_PNG_BORDER_CLAMP = 1 };
+typedef struct debig_png_warp { double m[6]; } debig_png_warp; /* the inverse map, row major: (m00 m01 m02) (m10 m11 m12) */
+typedef struct debig_png_warp_desc {
+    uint32_t filter;        /* DEBIG_PNG_FILTER_BILINEAR or DEBIG_PNG_FILTER_NEAREST */
+    uint32_t border_mode;   /* DEBIG_PNG_BORDER_* */
+    uint16_t border[4];     /* CONSTANT: one integer sample per source channel at precision P, 0 .. 2^P - 1 */
+    uint32_t alpha_mode;    /* DEBIG_PNG_ALPHA_STRAIGHT (0): the other modes are not provided with a warp */
+    uint32_t reserved;      /* 0 */
+} debig_png_warp_desc;
+typedef struct debig_png_label_warp_desc {
+    uint32_t border_mode;   /* DEBIG_PNG_BORDER_* */
+    int32_t border_label;   /* CONSTANT: the element of a pick outside the crop */
+} debig_png_label_warp_desc;
+/* Host only: m[k] = llround(M[k] * 65536) -> 1, or 0 (m unspecified) on the E_WARP conditions above. */
+int debig_png_warp_quantise(const double M[6], int64_t m[6]);
+int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                       const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps, uint32_t *status,
+                                       debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                       const debig_png_tensor_desc *desc, const debig_png_warp_desc *warp_desc);
+int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                       const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps, uint32_t *status,
+                                       debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                       const debig_png_label_desc *desc, const debig_png_label_warp_desc *warp_desc);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

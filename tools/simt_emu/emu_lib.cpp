@@ -19,6 +19,7 @@
 #include "../../debigulator_amd/csrc/png_resize_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_label_kernel.inc"
+#include "../../debigulator_amd/csrc/png_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -391,5 +392,22 @@ extern "C" int emu_png_color_label_batch(const void *src_arena, void *out, const
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_color_label_kernel, grid, CLBL_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
                       (const uint8_t *)tables, unmatched, n);
+    return 0;
+}
+
+/* crop + affine warp + normalise (png_warp_kernel.inc) as debig_hip_png_warp_batch launches it (grid as above) */
+extern "C" int emu_png_warp_batch(const void *src_arena, void *out, const debig_png_warp_task *tasks, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_warp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks, n);
+    return 0;
+}
+
+/* ... and the same warp of raw labels, as debig_hip_png_label_warp_batch launches it (lut: 256 int32 or NULL) */
+extern "C" int emu_png_label_warp_batch(const void *src_arena, void *out, const debig_png_label_warp_task *tasks, const int32_t *lut,
+                                        uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_warp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks, lut, n);
     return 0;
 }
