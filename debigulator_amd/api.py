@@ -879,7 +879,8 @@ def png_color_label_desc(size, colors=None, missing=-1, dtype="int64", n=None):
     return d, 1 << PNG_LABEL_DTYPES[dtype]
 
 
-def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="int64", boxes=None, fill=None, device="cuda:0"):
+def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="int64", boxes=None, fill=None, device="cuda:0",
+                                  warp=None, border="constant", border_label=None):
     """bytes of N colour-coded label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_color_labels) -> (statuses, tensor, infos, unmatched).  The colour of a pixel is what
     png_decode_batch(mode="rgb") gives for it (palette files through PLTE, grey replicated, alpha and tRNS dropped), packed as
@@ -888,11 +889,22 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     colours --: the element is the colour's value, or `missing`; a list of N of those gives every file its own map (COCO
     panoptic's per-image segment id -> category tables, with keys packed as the segment ids are).  unmatched[i]: how many
     elements of image i took `missing`.  size, boxes, fill, dtype, the device rule and the grid are those of
-    png_decode_batch_labels; 16-bit files have status 15 ("label")."""
+    png_decode_batch_labels; 16-bit files have status 15 ("label").
+    warp: None (everything above, unchanged), or one entry per file: None (the identity) or the INVERSE 2 x 3 matrix of
+    png_decode_batch_tensor(warp=) -- debig_png_decode_batch_color_labels_warp: the pick is the one of that call's
+    filter="nearest" and of png_decode_batch_labels(warp=) under the same matrix, so an image and its colour mask stay aligned.
+    border: "constant" (a pick outside the crop stores border_label as it is, not through the map, and is never counted in
+    unmatched: the ignore index; default 0) or "clamp".  A matrix with a non-finite or too large entry: status 16 ("warp")."""
     import torch
 
+    wd = None
+    if warp is not None:
+        wd = png_label_warp_desc(border, border_label, dtype)
+    elif border != "constant" or border_label is not None:
+        raise ValueError("border / border_label need warp")
     n = len(datas)
     d, es = png_color_label_desc(size, colors, missing, dtype, n)
+    ws = _png_warps(warp, n) if warp is not None else None
     L = _png_spec_lib()
     L.debig_png_decode_batch_color_labels.restype = C.c_int
     L.debig_png_decode_batch_color_labels.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p]
@@ -902,8 +914,14 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
     unmatched = (C.c_uint32 * n)()
-    rc = L.debig_png_decode_batch_color_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, unmatched, n, 0,
-                                               C.byref(d))
+    if wd is not None:
+        L.debig_png_decode_batch_color_labels_warp.restype = C.c_int
+        L.debig_png_decode_batch_color_labels_warp.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_color_labels_warp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos,
+                                                        unmatched, n, 0, C.byref(d), C.byref(wd))
+    else:
+        rc = L.debig_png_decode_batch_color_labels(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, status, infos, unmatched,
+                                                   n, 0, C.byref(d))
     if rc == PNG_BAD_ARG:
         raise ValueError(f"debig_png_decode_batch_color_labels rejected its arguments ({rc})")
     N.check(rc, "debig_png_decode_batch_color_labels")

@@ -1327,13 +1327,25 @@ DEBIG_API uint32_t debig_png_color_map_table(const debig_png_color_map *map, uin
     return slots;
 }
 
-DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                                  const debig_png_box *boxes, uint32_t *status, debig_png_info *infos,
-                                                  uint32_t *unmatched, uint32_t n, uint32_t flags,
-                                                  const debig_png_color_label_desc *desc)
+/* the maps of one call as the device takes them: the tables one behind the other, table k at off[k] bytes with slots[k] slots */
+typedef struct clbl_maps {
+    uint32_t *tab;
+    uint64_t *off, bytes;
+    uint32_t *slots;
+} clbl_maps;
+
+static void clbl_maps_free(clbl_maps *M)
 {
-    /* the arguments on their own, before any file is looked at: the label call's, then the mode's and the maps' */
-    if (n == 0) return 0;
+    free(M->tab);
+    free(M->off);
+    free(M->slots);
+}
+
+/* the argument checks of debig_png_decode_batch_color_labels (n > 0) on their own, before any file is looked at: the label
+ * call's, then the mode's and the maps'; in MAP mode the tables are made on the way (two equal keys show up there).
+ * -> 0 (*M filled, the caller's to clbl_maps_free either way), DEBIG_PNG_BAD_ARG or 2 */
+static int clbl_args_check(const void *d_out, const debig_png_color_label_desc *desc, uint32_t n, clbl_maps *M)
+{
     if (!desc || !d_out || ((uintptr_t)d_out & 15u)) return DEBIG_PNG_BAD_ARG;
     if (desc->out_w == 0 || desc->out_w > 16384u || desc->out_h == 0 || desc->out_h > 16384u || desc->dtype > DEBIG_PNG_L_I64 ||
         desc->reserved != 0 || desc->mode > DEBIG_PNG_CL_MAP)
@@ -1341,42 +1353,55 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
     const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
     if (!map_mode && (desc->dtype < DEBIG_PNG_L_I32 || desc->n_maps != 0)) return DEBIG_PNG_BAD_ARG;
     if (map_mode && ((desc->n_maps != 1 && desc->n_maps != n) || !desc->maps)) return DEBIG_PNG_BAD_ARG;
-    const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL}; /* E_LABEL: a 16-bit file */
+    if (!map_mode) return 0;
+    const uint32_t n_maps = desc->n_maps;
+    const int64_t top = desc->dtype == DEBIG_PNG_L_U8 ? 255 : desc->dtype == DEBIG_PNG_L_U16 ? 65535 : INT32_MAX;
+    const int64_t low = desc->dtype <= DEBIG_PNG_L_U16 ? 0 : INT32_MIN;
+    if (desc->missing < low || desc->missing > top) return DEBIG_PNG_BAD_ARG;
+    uint64_t total_slots = 0;
+    for (uint32_t k = 0; k < n_maps; k++) {
+        const debig_png_color_map *m = &desc->maps[k];
+        if (m->n > DEBIG_PNG_CMAP_MAX || (m->n && (!m->keys || !m->values))) return DEBIG_PNG_BAD_ARG;
+        for (uint32_t j = 0; j < m->n; j++)
+            if (m->values[j] < low || m->values[j] > top) return DEBIG_PNG_BAD_ARG;
+        total_slots += cmap_slots(m->n);
+    }
+    M->tab = (uint32_t *)malloc((size_t)total_slots * 8u);
+    M->off = (uint64_t *)calloc(n_maps, sizeof(uint64_t));
+    M->slots = (uint32_t *)calloc(n_maps, sizeof(uint32_t));
+    if (!M->tab || !M->off || !M->slots) return 2;
+    for (uint32_t k = 0; k < n_maps; k++) {
+        M->off[k] = M->bytes;
+        M->slots[k] = debig_png_color_map_table(&desc->maps[k], M->tab + M->bytes / 4u, DEBIG_PNG_CMAP_MAX_SLOTS);
+        if (M->slots[k] == 0) return DEBIG_PNG_BAD_ARG; /* a key above 0xFFFFFF, or two equal keys */
+        M->bytes += (uint64_t)M->slots[k] * 8u;
+    }
+    return 0;
+}
 
-    uint32_t *mtab = NULL;          /* the maps' tables, one behind the other */
-    uint64_t *moff = NULL;          /* table k: at moff[k] bytes, mslots[k] slots */
-    uint32_t *mslots = NULL, *cnt = NULL;
+DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                  const debig_png_box *boxes, uint32_t *status, debig_png_info *infos,
+                                                  uint32_t *unmatched, uint32_t n, uint32_t flags,
+                                                  const debig_png_color_label_desc *desc)
+{
+    if (n == 0) return 0;
+    clbl_maps M = {NULL, NULL, 0, NULL};
+    uint32_t *cnt = NULL;
     stage S = {NULL, NULL, NULL, NULL, NULL};
     /* the maps' tables (first: map_off needs no base), the X tables, the Y tables, the counters (16-byte aligned) */
     dev_table tab[4] = {{NULL, 0, 0}, {NULL, 0, 0}, {NULL, 0, 0}, {NULL, (uint64_t)n * sizeof(uint32_t), 0}};
-    lbl_job J = {NULL, 0, 0, W, H, sizeof(debig_png_color_label_task), offsetof(debig_png_color_label_task, row0),
-                 {NULL, 0, 0, NULL, 0, 0, W}, {NULL, 0, 0, NULL, 0, 0, H}, &tab[1], &tab[2]};
-    int rc = 2;
-    if (map_mode) {
-        const int64_t top = desc->dtype == DEBIG_PNG_L_U8 ? 255 : desc->dtype == DEBIG_PNG_L_U16 ? 65535 : INT32_MAX;
-        const int64_t low = desc->dtype <= DEBIG_PNG_L_U16 ? 0 : INT32_MIN;
-        if (desc->missing < low || desc->missing > top) return DEBIG_PNG_BAD_ARG;
-        uint64_t total_slots = 0;
-        for (uint32_t k = 0; k < n_maps; k++) {
-            const debig_png_color_map *m = &desc->maps[k];
-            if (m->n > DEBIG_PNG_CMAP_MAX || (m->n && (!m->keys || !m->values))) return DEBIG_PNG_BAD_ARG;
-            for (uint32_t j = 0; j < m->n; j++)
-                if (m->values[j] < low || m->values[j] > top) return DEBIG_PNG_BAD_ARG;
-            total_slots += cmap_slots(m->n);
-        }
-        mtab = (uint32_t *)malloc((size_t)total_slots * 8u);
-        moff = (uint64_t *)calloc(n_maps, sizeof(uint64_t));
-        mslots = (uint32_t *)calloc(n_maps, sizeof(uint32_t));
-        if (!mtab || !moff || !mslots) goto done;
-        for (uint32_t k = 0; k < n_maps; k++) {
-            moff[k] = tab[0].bytes;
-            mslots[k] = debig_png_color_map_table(&desc->maps[k], mtab + tab[0].bytes / 4u, DEBIG_PNG_CMAP_MAX_SLOTS);
-            if (mslots[k] == 0) { rc = DEBIG_PNG_BAD_ARG; goto done; } /* a key above 0xFFFFFF, or two equal keys */
-            tab[0].bytes += (uint64_t)mslots[k] * 8u;
-        }
-        tab[0].src = mtab;
-    }
+    lbl_job J = {NULL, 0, 0, 0, 0, sizeof(debig_png_color_label_task), offsetof(debig_png_color_label_task, row0),
+                 {NULL, 0, 0, NULL, 0, 0, 0}, {NULL, 0, 0, NULL, 0, 0, 0}, &tab[1], &tab[2]};
+    int rc;
+    if ((rc = clbl_args_check(d_out, desc, n, &M))) goto done;
+    const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
+    const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL}; /* E_LABEL: a 16-bit file */
+    J.W = J.TX.L = W;
+    J.H = J.TY.L = H;
+    tab[0].src = M.tab;
+    tab[0].bytes = M.bytes;
+    rc = 2;
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
     if (!cnt) goto done;
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
@@ -1395,8 +1420,8 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
         p.mode = (uint8_t)desc->mode;
         p.image = i;
         if (map_mode) {
-            p.map_off = tab[0].off + moff[mk];
-            p.map_slots = mslots[mk];
+            p.map_off = tab[0].off + M.off[mk];
+            p.map_slots = M.slots[mk];
             p.missing = desc->missing;
         }
         if ((rc = lbl_runs(&J, &S, i, 3u, (uint64_t)H * W * es, &p))) goto done;
@@ -1413,9 +1438,7 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
         goto done;
     if (unmatched && map_mode) memcpy(unmatched, cnt, (size_t)n * sizeof(uint32_t));
 done:
-    free(mtab);
-    free(moff);
-    free(mslots);
+    clbl_maps_free(&M);
     free(cnt);
     stage_free(&S);
     lbl_job_free(&J);
@@ -1597,6 +1620,95 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
         goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
+    stage_free(&S);
+    free(m);
+    free(wbad);
+    free(tasks);
+    return rc;
+}
+
+DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                       const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                       debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
+                                                       const debig_png_color_label_desc *desc,
+                                                       const debig_png_label_warp_desc *wd)
+{
+    /* every check of debig_png_decode_batch_color_labels first and unchanged, then the warp's; all before any file is looked at */
+    if (n == 0) return 0;
+    clbl_maps M = {NULL, NULL, 0, NULL};
+    uint32_t *cnt = NULL;
+    stage S = {NULL, NULL, NULL, NULL, NULL};
+    int64_t *m = NULL;
+    uint8_t *wbad = NULL;
+    debig_png_color_label_warp_task *tasks = NULL;
+    uint64_t n_tasks = 0;
+    uint32_t cap_tasks = 0;
+    int rc;
+    if ((rc = clbl_args_check(d_out, desc, n, &M))) goto done;
+    rc = DEBIG_PNG_BAD_ARG;
+    if (!warps || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) goto done;
+    if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
+        (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
+        goto done;
+    const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
+    const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
+    const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
+    /* the maps' tables (first: map_off needs no base), the counters (16-byte aligned: a table is a multiple of 16 bytes) */
+    dev_table tab[2] = {{M.tab, M.bytes, 0}, {NULL, (uint64_t)n * sizeof(uint32_t), 0}};
+    rc = 2;
+    cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
+    if (!cnt) goto done;
+    if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad}; /* E_LABEL: a 16-bit file */
+    if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
+    if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
+    dev_tables_place(tab, 2);
+    rc = 2;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status[i] != DEBIG_PNG_OK) continue;
+        const uint32_t mk = n_maps == 1 ? 0u : i;
+        debig_png_color_label_warp_task p;
+        memset(&p, 0, sizeof p);
+        p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * 3u;
+        p.out_off = (uint64_t)i * H * W * es;
+        memcpy(p.m, m + 6u * (size_t)i, sizeof p.m);
+        p.src_pitch = S.inf[i].width;
+        p.crop_w = S.box[i].w;
+        p.crop_h = S.box[i].h;
+        p.out_w = W;
+        p.out_h = H;
+        p.border_label = wd->border_label;
+        p.dtype = (uint8_t)desc->dtype;
+        p.mode = (uint8_t)desc->mode;
+        p.border_mode = (uint8_t)wd->border_mode;
+        p.image = i;
+        if (map_mode) {
+            p.map_off = tab[0].off + M.off[mk];
+            p.map_slots = M.slots[mk];
+            p.missing = desc->missing;
+        }
+        for (uint32_t y0 = 0; y0 < H; y0 += run) {
+            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof p)) goto done;
+            p.row0 = y0;
+            p.rows = H - y0 < run ? H - y0 : run;
+            tasks[n_tasks++] = p;
+        }
+    }
+    rc = 0;
+    if (n_tasks == 0) goto done;
+    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, tab, 2, &rc);
+    if (!c) goto done;
+    uint32_t *d_cnt = map_mode ? (uint32_t *)((uint8_t *)c->rsz_weights.ptr + tab[1].off) : NULL;
+    if ((d_cnt && (rc = debig_hip_memset(d_cnt, 0, tab[1].bytes, NULL))) ||
+        (rc = debig_hip_png_color_label_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_color_label_warp_task *)c->rsz_tasks.ptr,
+                                                   c->rsz_weights.ptr, d_cnt, (uint32_t)n_tasks, NULL)) ||
+        (d_cnt && (rc = debig_hip_memcpy_d2h(cnt, d_cnt, tab[1].bytes, NULL))) ||
+        (rc = debig_hip_stream_sync(NULL)))
+        goto done;
+    if (unmatched && map_mode) memcpy(unmatched, cnt, (size_t)n * sizeof(uint32_t));
+done:
+    clbl_maps_free(&M);
+    free(cnt);
     stage_free(&S);
     free(m);
     free(wbad);

@@ -573,6 +573,39 @@ typedef struct debig_png_label_warp_task {
 int debig_hip_png_label_warp_batch(const void *d_src_arena, void *d_out, const debig_png_label_warp_task *d_tasks,
                                    const int32_t *d_lut, uint32_t n_tasks, void *hip_stream);
 
+/* The same warp of colour-coded masks (debig_png_color_label_warp_kernel in csrc/png_color_label_warp_kernel.inc, behind
+ * debig_png_decode_batch_color_labels_warp in decode_png.h): tasks, workgroups, m[] and the pick are those of the label warp
+ * above; the source, the key, the two modes, THE TABLE and the counters are those of debig_png_color_label_task, unchanged.
+ * The picked pixel is three bytes at src_off + (jy * src_pitch + jx) * 3, both indices clamped into the crop first; an element
+ * whose pick leaves the crop under CONSTANT is border_label AS IT IS: it does not pass through the table and is never counted
+ * in d_unmatched[image], even where border_label == missing.  A clamped pick goes through the table and is counted like any
+ * other.  A task that breaks a bound -- the sizes and matrix limits of the warp tasks, an unknown dtype, mode or border mode,
+ * PACK with a dtype of one or two bytes, MAP with a slot count that is no power of two, below 2 or above
+ * DEBIG_PNG_CMAP_MAX_SLOTS, with a map_off that is no multiple of 16 or without d_unmatched -- is skipped. */
+typedef struct debig_png_color_label_warp_task {
+    uint64_t src_off;        /* pixel (0, 0) of the CROP, in bytes rel. to d_src_arena (any alignment)                        */
+    uint64_t out_off;        /* the image's slot, in bytes rel. to d_out (aligned to the element size)                        */
+    uint64_t map_off;        /* MAP: the image's table, in bytes rel. to d_tables (16-byte aligned)                           */
+    int64_t m[6];            /* the inverse map, row major, Q16                                                               */
+    uint32_t src_pitch;      /* pixels from one source row to the next (the image's width)                                    */
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;   /* 1 .. 16384                                                                                    */
+    uint32_t row0, rows;     /* row0 + rows <= out_h                                                                          */
+    int32_t border_label;    /* CONSTANT: the element of a pick outside the crop (inside the dtype's range)                   */
+    uint32_t map_slots;      /* MAP: slots of the table                                                                       */
+    int32_t missing;         /* MAP: the element of a colour that is not in the table                                         */
+    uint32_t image;          /* MAP: the image's counter in d_unmatched                                                       */
+    uint8_t dtype;           /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                       */
+    uint8_t mode;            /* decode_png.h DEBIG_PNG_CL_*                                                                   */
+    uint8_t border_mode;     /* decode_png.h DEBIG_PNG_BORDER_CONSTANT or _CLAMP                                              */
+    uint8_t reserved;
+} debig_png_color_label_warp_task;
+/* n_tasks row runs (device pointers, asynchronous on hip_stream).  d_tables holds the tasks' tables; d_unmatched: one uint32
+ * per image, zeroed by the caller; one atomic add per wavefront and task; may be NULL when every task is PACK.  Nothing but
+ * the tasks' own output elements and counters is written. */
+int debig_hip_png_color_label_warp_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_warp_task *d_tasks,
+                                         const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

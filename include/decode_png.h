@@ -421,8 +421,8 @@ int debig_png_decode_batch_labels(const uint8_t *const *inputs, const uint64_t *
  * statuses of debig_png_decode_batch_fmt in their order (E_PALETTE; E_OUTPUT: more than 2^31 decoded RGB8 bytes).  A file with
  * a non-zero status leaves its slot untouched; nothing outside d_out[0 .. n * slot) is written.
  * Not provided: arithmetic decodings other than PACK (e.g. ADE20K's R / 10 * 256 + G), maps above DEBIG_PNG_CMAP_MAX entries,
- * 16-bit sources, nearest-colour matching for unmatched pixels, host-buffer output, flips and affine maps (the warp calls below
- * cover images and raw labels only), animated PNGs, inputs already on the device, an asynchronous variant. */
+ * 16-bit sources, nearest-colour matching for unmatched pixels, host-buffer output, animated PNGs, inputs already on the
+ * device, an asynchronous variant.  (Flips and affine maps: debig_png_decode_batch_color_labels_warp below.) */
 #define DEBIG_PNG_CMAP_MAX 2048u
 enum { DEBIG_PNG_CL_PACK = 0, DEBIG_PNG_CL_MAP = 1 };
 typedef struct debig_png_color_map {      /* host memory, read before the call returns */
@@ -452,8 +452,9 @@ int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, const uint
 uint32_t debig_png_color_map_table(const debig_png_color_map *map, uint32_t *table, uint32_t cap_slots);
 
 /* ---- affine warp: flips, quarter turns, rotation, scale and shear in the tensor and label decodes ---------------------------------
- * debig_png_decode_batch_tensor_warp and debig_png_decode_batch_labels_warp are debig_png_decode_batch_tensor and
- * debig_png_decode_batch_labels with the resize replaced by an affine map, one per file: warps[i].m is the INVERSE map M
+ * debig_png_decode_batch_tensor_warp, debig_png_decode_batch_labels_warp and debig_png_decode_batch_color_labels_warp are
+ * debig_png_decode_batch_tensor, debig_png_decode_batch_labels and debig_png_decode_batch_color_labels with the resize (the
+ * nearest grid) replaced by an affine map, one per file: warps[i].m is the INVERSE map M
  * (2 x 3, row major).  The continuous source position of output pixel (X, Y) is
  *     (u, v) = M . (X + 1/2, Y + 1/2, 1)
  * in pixel units of the CROP (boxes[i], or the whole image), where source pixel j covers [j, j + 1).  Singular matrices are
@@ -482,17 +483,25 @@ uint32_t debig_png_color_map_table(const debig_png_color_map *map, uint32_t *tab
  * Labels: nearest only, with the same jx, jy -- an image warped with filter NEAREST and its label map warped with the same
  * matrix pick the same source pixels.  An outside pick under CONSTANT stores border_label as it is (the ignore index: it does
  * not pass through the lut); CLAMP as above.  lut, dtypes and the E_LABEL rules are those of debig_png_decode_batch_labels.
- * Both calls decode as the calls they extend (the same arena, no crop-size cap), then ONE launch warps all images
- * (debig_hip_png_warp_batch / debig_hip_png_label_warp_batch: a gather, one lane per output pixel).
+ * Colour-coded labels: the same jx, jy again, so the colour-label call, the raw-label call and the image's NEAREST filter pick
+ * the same source pixel for every output element under one matrix.  Decode, colour and key = R | G << 8 | B << 16 are those of
+ * debig_png_decode_batch_color_labels.  Inside the crop, or anywhere under CLAMP, the element is the PACK or MAP value of the
+ * picked pixel as in that call; an outside pick under CONSTANT stores border_label as it is (it does not pass through the map).
+ * unmatched[i] is the exact number of output elements of image i that took `missing`: a border element under CONSTANT is never
+ * counted, even when border_label == missing; a clamped pick goes through the map and is counted like any other; 0 in PACK
+ * mode and for a file with a non-zero status.  E_LABEL is that call's (a 16-bit file).
+ * All three calls decode as the calls they extend (the same arena, no crop-size cap), then ONE launch warps all images
+ * (debig_hip_png_warp_batch / debig_hip_png_label_warp_batch / debig_hip_png_color_label_warp_batch: a gather, one lane per
+ * output pixel).
  * Checked first, before any file is looked at (status unwritten): every check of the call that is extended, unchanged; then
  * DEBIG_PNG_BAD_ARG for warps or the warp descriptor NULL, a filter other than BILINEAR / NEAREST (BICUBIC included), an
  * unknown border_mode, alpha_mode other than DEBIG_PNG_ALPHA_STRAIGHT, reserved != 0, the antialias flag in desc->resize_flags,
  * a used border[c] above 2^P - 1 under CONSTANT, a border_label outside the dtype's range under CONSTANT (U8: 0 .. 255,
- * U16: 0 .. 65535).  Per image: statuses, their order, infos and the untouched slot of a failed file are those of the call
+ * U16: 0 .. 65535; under CLAMP border_label is not read).  The colour-label warp leaves unmatched unwritten as well.  Per image: statuses, their order, infos and the untouched slot of a failed file are those of the call
  * that is extended, with E_WARP as above.
  * Not provided: antialiasing under a shrinking warp (shrink with the resize calls, or accept aliasing), bicubic, the OVER and
  * PREMULTIPLIED alpha modes together with a warp (alpha is warped like a colour channel, as in debig_png_decode_batch_tensor),
- * perspective maps, colour-coded label maps (debig_png_decode_batch_color_labels stays as it is), colour jitter. */
+ * perspective maps, colour jitter. */
 #define DEBIG_PNG_E_WARP 16 /* the warp matrix (rules above) */
 enum { DEBIG_PNG_BORDER_CONSTANT = 0, DEBIG_PNG_BORDER_CLAMP = 1 };
 typedef struct debig_png_warp { double m[6]; } debig_png_warp; /* the inverse map, row major: (m00 m01 m02) (m10 m11 m12) */
@@ -517,6 +526,10 @@ int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint6
                                        const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps, uint32_t *status,
                                        debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
                                        const debig_png_label_desc *desc, const debig_png_label_warp_desc *warp_desc);
+int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+        const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps, uint32_t *status,
+        debig_png_info *infos /* may be NULL */, uint32_t *unmatched /* may be NULL */, uint32_t n, uint32_t flags,
+        const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *warp_desc);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

@@ -20,6 +20,7 @@
 #include "../../debigulator_amd/csrc/png_label_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_label_kernel.inc"
 #include "../../debigulator_amd/csrc/png_warp_kernel.inc"
+#include "../../debigulator_amd/csrc/png_color_label_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -409,5 +410,16 @@ extern "C" int emu_png_label_warp_batch(const void *src_arena, void *out, const 
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_label_warp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks, lut, n);
+    return 0;
+}
+
+/* ... and of colour-coded masks (png_color_label_warp_kernel.inc), as debig_hip_png_color_label_warp_batch launches it
+ * (unmatched: one zeroed uint32 per image, or NULL) */
+extern "C" int emu_png_color_label_warp_batch(const void *src_arena, void *out, const debig_png_color_label_warp_task *tasks,
+                                              const void *tables, uint32_t *unmatched, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_color_label_warp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)tables, unmatched, n);
     return 0;
 }
