@@ -212,7 +212,7 @@ def gunzip_batch(datas, out_caps):
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
               8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box", 15: "label",
-              16: "warp"}
+              16: "warp", 17: "color"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -630,9 +630,60 @@ def png_warp_desc(filter="bilinear", border="constant", border_value=None, mode=
     return d
 
 
+class PngColor(C.Structure):  # include/decode_png.h: debig_png_color
+    _fields_ = [("m", C.c_double * 12)]
+
+
+PNG_LUMA = (6968 / 32768, 23434 / 32768, 2366 / 32768)  # include/decode_png.h: the grey weights of the RGB -> GRAY conversion
+
+
+def png_color_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, center=0.5, luma=PNG_LUMA):
+    """the 3 x 4 colour matrix (numpy float64: row c is (m_c0 m_c1 m_c2 | m_c3), out_c = m_c0 R + m_c1 G + m_c2 B + m_c3 on the
+    [0, 1] scale) that png_decode_batch_tensor(..., color=) takes (no GPU needed).  The operations compose in this fixed order:
+      1. brightness b: x -> b x;
+      2. contrast c about `center`: x -> c x + (1 - c) center (the same fixed centre for every image, not the image's mean);
+      3. saturation s: x -> s x + (1 - s) (luma . x) (1, 1, 1); luma: the grey weights (the default: the header's);
+      4. hue, in degrees: the rotation about the grey axis (1, 1, 1),
+         cos h I + (1 - cos h) / 3 J + sin h / sqrt(3) [[0, -1, 1], [1, 0, -1], [-1, 1, 0]]  (J: all ones).
+    The defaults give the identity exactly; saturation=0 gives three rows equal to luma; hue=120 and hue=240 are the cyclic
+    channel permutations (exact once quantised).  There is no clamp between the operations: the call clamps once, at the end."""
+    import math
+
+    b, c, s_, ce = float(brightness), float(contrast), float(saturation), float(center)
+    lw = [float(v) for v in luma]
+    if len(lw) != 3:
+        raise ValueError("luma needs three weights")
+    h = float(hue) % 360.0
+    if h % 90.0 == 0.0:  # (cos and sin of a quarter turn are not exact in float64)
+        ch_, sh_ = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(h // 90.0)]
+    else:
+        ch_, sh_ = math.cos(math.radians(h)), math.sin(math.radians(h))
+    eye = np.eye(3)
+    S = s_ * eye + (1.0 - s_) * np.outer(np.ones(3), np.asarray(lw, np.float64))
+    Hm = ch_ * eye + ((1.0 - ch_) / 3.0) * np.ones((3, 3)) + (sh_ / math.sqrt(3.0)) * np.array([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]])
+    HS = Hm @ S
+    M = np.empty((3, 4), np.float64)
+    M[:, :3] = HS * (c * b)
+    M[:, 3] = HS @ np.full(3, (1.0 - c) * ce)
+    return M + 0.0  # (+ 0.0: no negative zeros)
+
+
+def _png_colors(color, n):
+    """color: one 3 x 4 matrix for the batch, or an (n, 3, 4) array / a sequence of n matrices -> (PngColor * n)"""
+    a = np.asarray(color, dtype=np.float64)
+    if a.shape == (3, 4):
+        a = np.broadcast_to(a, (n, 3, 4))
+    if a.shape != (n, 3, 4):
+        raise ValueError(f"color must be one 3 x 4 matrix or an ({n}, 3, 4) array, not shape {a.shape}")
+    cs = (PngColor * n)()
+    for i in range(n):
+        cs[i].m[:] = [float(x) for x in a[i].reshape(-1)]
+    return cs
+
+
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
                             antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
-                            background=None, warp=None, border="constant", border_value=None, filter="bilinear"):
+                            background=None, warp=None, border="constant", border_value=None, color=None, filter="bilinear"):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
     (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
@@ -658,9 +709,22 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     integer arithmetic, filter "bilinear" or "nearest", alpha "straight"; `antialias` is not applied under a warp.  border:
     what a tap outside the crop is: "constant" (border_value, per channel on the [0, 1] scale, default 0) or "clamp" (the edge
     pixels).  A matrix with a non-finite or too large entry: status 16 ("warp").  (Pass warp, border and border_value by
-    name: `filter` stays the last parameter, as its callers and tests know it.)"""
+    name: `filter` stays the last parameter, as its callers and tests know it; `color` below likewise goes by name.)
+    color: None (everything above, unchanged), or one 3 x 4 colour matrix for the batch or an (N, 3, 4) array, one per file
+    (png_color_matrix makes one from brightness, contrast, saturation and hue): out_c = m_c0 R + m_c1 G + m_c2 B + m_c3 on the
+    [0, 1] scale, applied in integers between the filter and the conversion, clamped once, before mean / std --
+    debig_png_decode_batch_tensor_color, or debig_png_decode_batch_tensor_warp_color together with warp.  It goes with mode "rgb"
+    or "rgba" (alpha is not mixed), filter "bilinear" or "nearest" and alpha "straight".  A matrix with a non-finite entry or
+    one above 16 in magnitude: status 17 ("color")."""
     import torch
 
+    if color is not None:
+        if filter == "bicubic":
+            raise ValueError("color goes with filter 'bilinear' or 'nearest', not 'bicubic'")
+        if alpha != "straight":
+            raise ValueError(f"color goes with alpha='straight' only, not {alpha!r}")
+        if mode not in ("rgb", "rgba"):
+            raise ValueError(f"color needs mode 'rgb' or 'rgba', not {mode!r}")
     wd = None
     if warp is not None:
         wd = png_warp_desc(filter, border, border_value, mode, depth, alpha)
@@ -673,6 +737,7 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     ad = png_alpha_desc(alpha, background, mode, depth)
     fd = png_filter_desc(filter)
     ws = _png_warps(warp, len(datas)) if warp is not None else None
+    cs = _png_colors(color, len(datas)) if color is not None else None
     L = _png_spec_lib()
     L.debig_png_decode_batch_tensor.restype = C.c_int
     L.debig_png_decode_batch_tensor.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p]
@@ -688,7 +753,18 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
     out = _png_dense_out(shape, tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if wd is not None:
+    if cs is not None and wd is not None:
+        L.debig_png_decode_batch_tensor_warp_color.restype = C.c_int
+        L.debig_png_decode_batch_tensor_warp_color.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_tensor_warp_color(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, cs, status, infos, n,
+                                                        PNG_FORCE_GENERAL if force_general else 0, C.byref(d), C.byref(wd))
+    elif cs is not None:
+        L.debig_png_decode_batch_tensor_color.restype = C.c_int
+        L.debig_png_decode_batch_tensor_color.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_tensor_color(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, cs, status, infos, n,
+                                                   PNG_FORCE_GENERAL if force_general else 0, C.byref(d),
+                                                   C.byref(fd) if fd is not None else None)
+    elif wd is not None:
         L.debig_png_decode_batch_tensor_warp.restype = C.c_int
         L.debig_png_decode_batch_tensor_warp.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         rc = L.debig_png_decode_batch_tensor_warp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos, n,

@@ -20,6 +20,7 @@
 #include "png_color_label_kernel.inc"
 #include "png_warp_kernel.inc"
 #include "png_color_label_warp_kernel.inc"
+#include "png_color_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -857,6 +858,29 @@ int debig_hip_png_color_label_warp_batch(const void *d_src_arena, void *d_out, c
     const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
     hipLaunchKernelGGL(debig_png_color_label_warp_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched, n_tasks);
+    return (int)hipGetLastError();
+}
+
+// the resize and the warp with a colour matrix per image (png_color_kernel.inc): the tasks and grid rules of the kernels they extend
+int debig_hip_png_resize_color_batch(const void *d_src_arena, void *d_out, const debig_png_resize_color_task *d_tasks,
+                                     const void *d_weights, uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_resize_color_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
+    return (int)hipGetLastError();
+}
+
+int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const debig_png_warp_color_task *d_tasks,
+                                   const void *d_weights, uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_warp_color_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
     return (int)hipGetLastError();
 }
 

@@ -867,6 +867,7 @@ typedef struct stage_rule {
     uint32_t no16;         /* != 0: a 16-bit file is E_LABEL */
     uint64_t max_w, max_h; /* max_w != 0: a crop wider / taller than this is E_BOX (the antialiased resize) */
     const uint8_t *warp_bad; /* != NULL: file i with warp_bad[i] != 0 is E_WARP (the warp calls) */
+    const uint8_t *color_bad; /* != NULL: file i with color_bad[i] != 0 is E_COLOR (the colour-matrix calls) */
 } stage_rule;
 
 /* per file: the status decided from IHDR (0: none), the image's place and size in the arena, the resolved box, the walk's info */
@@ -886,7 +887,7 @@ static void stage_free(stage *S)
     free(S->inf);
 }
 
-/* IHDR -> E_LABEL, then E_BOX, then E_WARP, then the walk's own error, then the size cap; the decode of what is left into the arena.
+/* IHDR -> E_LABEL, then E_BOX, then E_WARP, then E_COLOR, then the walk's own error, then the size cap; the decode of what is left into the arena.
  * -> 0 (status and infos written; S filled, the caller's to stage_free either way) or the call's return value */
 static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inputs, const uint64_t *input_sizes,
                         const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags)
@@ -920,6 +921,10 @@ static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inp
         }
         if (R->warp_bad && R->warp_bad[i]) {
             S->pre[i] = DEBIG_PNG_E_WARP;
+            continue;
+        }
+        if (R->color_bad && R->color_bad[i]) {
+            S->pre[i] = DEBIG_PNG_E_COLOR;
             continue;
         }
         S->box[i] = b;
@@ -966,14 +971,58 @@ static debig_ctx *dev_upload(const void *tasks, uint64_t n_tasks, size_t elem, c
     return c;
 }
 
+/* ---- the per-image colour matrix of the tensor decodes (decode_png.h) --------------------------------------------------------- */
+
+_Static_assert(offsetof(debig_png_resize_color_task, reserved2) == RSZ_TASK_FIELDS && sizeof(debig_png_resize_color_task) == 120 &&
+                   offsetof(debig_png_resize_color_task, b) == offsetof(debig_png_resize_task, b) && sizeof(debig_png_color_rec) == 64,
+               "debig_png_resize_color_task starts with the fields of debig_png_resize_task");
+
+/* llround of a finite x below 2^62 in magnitude: x - trunc(x) is exact; halves go away from zero */
+static int64_t color_llround(double x)
+{
+    int64_t q = (int64_t)x;
+    const double d = x - (double)q;
+    if (d >= 0.5) q++;
+    else if (d <= -0.5) q--;
+    return q;
+}
+
+DEBIG_API int debig_png_color_quantise(const double M[12], uint32_t bits, int32_t k[9], int64_t o[3])
+{
+    if (bits != 8u && bits != 16u) return 0;
+    for (uint32_t j = 0; j < 12; j++) {
+        uint64_t u;
+        memcpy(&u, &M[j], 8);
+        if ((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull) return 0; /* infinity or NaN */
+        if ((M[j] < 0 ? -M[j] : M[j]) > 16.0) return 0;
+    }
+    const double vmax = (double)(((1u << bits) - 1u) << (30u - bits));
+    for (uint32_t c = 0; c < 3; c++) {
+        for (uint32_t j = 0; j < 3; j++) k[3 * c + j] = (int32_t)color_llround(M[4 * c + j] * 65536.0); /* (exact product) */
+        o[c] = color_llround(M[4 * c + 3] * vmax); /* (the product as float64 rounds it, below 2^34) */
+    }
+    return 1;
+}
+
+/* the files' matrices as device records and their E_COLOR flags; -> 0 or 2 */
+static int color_prepare(const debig_png_color *colors, uint32_t n, uint32_t bits, debig_png_color_rec **rec, uint8_t **bad)
+{
+    *rec = (debig_png_color_rec *)calloc(n, sizeof(debig_png_color_rec));
+    *bad = (uint8_t *)calloc(n, 1);
+    if (!*rec || !*bad) return 2;
+    for (uint32_t i = 0; i < n; i++) (*bad)[i] = !debig_png_color_quantise(colors[i].m, bits, (*rec)[i].k, (*rec)[i].o);
+    return 0;
+}
+
 /* debig_png_decode_batch_tensor (amode == DEBIG_PNG_ALPHA_STRAIGHT: bg unused), debig_png_decode_batch_tensor_alpha and
  * debig_png_decode_batch_tensor_filter behind their argument checks.  With alpha the pixels are decoded WITH their alpha (dfmt:
  * 4 or 2 channels) and the tiles go to the alpha kernel, which writes the channels of desc->out_format.  The filter picks the
  * weight rule and the E_BOX scale; BICUBIC tiles, of every alpha mode, go to the signed kernel (debig_hip_png_resize_cubic_batch),
- * NEAREST ones to the kernels of BILINEAR. */
+ * NEAREST ones to the kernels of BILINEAR.  colors != NULL (debig_png_decode_batch_tensor_color: STRAIGHT, not BICUBIC, 3 or 4
+ * channels): the tiles carry the offset of their image's record, which travels as a third table, and go to the colour kernel. */
 static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
                        uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
-                       uint32_t amode, const uint16_t *bg, uint32_t filter)
+                       uint32_t amode, const uint16_t *bg, uint32_t filter, const debig_png_color *colors)
 {
     /* fmt: the format decoded into the arena (ch channels); oc: the channels of the tensor */
     uint32_t fmt = desc->out_format;
@@ -987,23 +1036,25 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     /* the plain kernel's task, or the alpha kernel's and the signed kernel's of one layout: the plain one (channels: the
      * source's) + mode, channel counts, background */
     const int plain = amode == DEBIG_PNG_ALPHA_STRAIGHT && filter != DEBIG_PNG_FILTER_BICUBIC;
-    const size_t elem = plain ? sizeof(debig_png_resize_task) : sizeof(debig_png_resize_alpha_task);
+    const size_t elem = colors ? sizeof(debig_png_resize_color_task) : plain ? sizeof(debig_png_resize_task) : sizeof(debig_png_resize_alpha_task);
     /* the largest antialiased scale (decode_png.h); NEAREST ignores the flag */
     const uint64_t max_scale = filter == DEBIG_PNG_FILTER_BICUBIC ? 32u : 64u;
     const int aa_box = aa && filter != DEBIG_PNG_FILTER_NEAREST;
-    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H, NULL};
-
     stage S = {NULL, NULL, NULL, NULL, NULL};
-    uint8_t *tasks = NULL;
+    uint8_t *tasks = NULL, *cbad = NULL;
+    debig_png_color_rec *crec = NULL;
     rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa, filter}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa, filter};
     int rc;
+    if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
+    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H, NULL, cbad};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     /* ---- the axis tables of every decoded image, then their places behind one another */
     rc = 2;
     for (uint32_t i = 0; i < n; i++)
         if (status[i] == DEBIG_PNG_OK && (rsz_axis_get(&TX, S.box[i].w) < 0 || rsz_axis_get(&TY, S.box[i].h) < 0)) goto done;
-    dev_table tab[2] = {{TX.buf, TX.len, 0}, {TY.buf, TY.len, 0}};
-    dev_tables_place(tab, 2);
+    dev_table tab[3] = {{TX.buf, TX.len, 0}, {TY.buf, TY.len, 0}, {crec, colors ? (uint64_t)n * sizeof *crec : 0, 0}};
+    const uint32_t n_tab = colors ? 3u : 2u;
+    dev_tables_place(tab, n_tab); /* (the axis tables are multiples of 8 bytes long: the records are 8-byte aligned) */
     /* ---- the tiles of every decoded image */
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
@@ -1050,7 +1101,14 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
             for (uint32_t x0 = 0; x0 < W; x0 += tw) {
                 if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
                 debig_png_resize_task *t = (debig_png_resize_task *)(tasks + n_tasks++ * elem);
-                memcpy(t, &proto, elem);
+                if (colors) { /* the plain task's fields, then the record's place */
+                    debig_png_resize_color_task *ct = (debig_png_resize_color_task *)t;
+                    memset(ct, 0, sizeof *ct);
+                    memcpy(ct, &proto, RSZ_TASK_FIELDS);
+                    ct->color_off = tab[2].off + (uint64_t)i * sizeof *crec;
+                } else {
+                    memcpy(t, &proto, elem);
+                }
                 t->tile_x = x0;
                 t->tile_y = y0;
                 t->tile_w = W - x0 < tw ? W - x0 : tw;
@@ -1063,10 +1121,12 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     }
     rc = 0;
     if (n_tasks == 0) goto done;
-    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, 2, &rc);
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
     if (!c) goto done;
     const void *d_tasks = c->rsz_tasks.ptr;
-    if ((rc = filter == DEBIG_PNG_FILTER_BICUBIC
+    if ((rc = colors ? debig_hip_png_resize_color_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_color_task *)d_tasks,
+                                                        c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
+              : filter == DEBIG_PNG_FILTER_BICUBIC
                   ? debig_hip_png_resize_cubic_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_cubic_task *)d_tasks,
                                                      c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
               : plain ? debig_hip_png_resize_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_task *)d_tasks,
@@ -1078,6 +1138,8 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
 done:
     stage_free(&S);
     free(tasks);
+    free(crec);
+    free(cbad);
     free(TX.buf);
     free(TX.ax);
     free(TY.buf);
@@ -1093,7 +1155,7 @@ DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const 
     if (n == 0) return 0;
     const int bad = tensor_args_check(d_out, desc);
     if (bad) return bad;
-    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL, DEBIG_PNG_FILTER_BILINEAR);
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL, DEBIG_PNG_FILTER_BILINEAR, NULL);
 }
 
 /* the checks of debig_png_decode_batch_tensor_alpha (n > 0): those of debig_png_decode_batch_tensor first and unchanged, then
@@ -1128,7 +1190,7 @@ DEBIG_API int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, 
     const int bad = tensor_alpha_check(d_out, desc, alpha, &amode);
     if (bad) return bad;
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
-                       DEBIG_PNG_FILTER_BILINEAR);
+                       DEBIG_PNG_FILTER_BILINEAR, NULL);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -1143,7 +1205,28 @@ DEBIG_API int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs,
     if (bad) return bad;
     if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
-                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR);
+                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, NULL);
+}
+
+/* the colour matrix goes with three colour channels: RGB or RGBA */
+static int color_layout_ok(uint32_t out_format)
+{
+    return (out_format & 15u) == DEBIG_PNG_FMT_RGB || (out_format & 15u) == DEBIG_PNG_FMT_RGBA;
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                  const debig_png_box *boxes, const debig_png_color *colors, uint32_t *status,
+                                                  debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                  const debig_png_tensor_desc *desc, const debig_png_filter_desc *filter)
+{
+    /* every check of debig_png_decode_batch_tensor first and unchanged, then the filter's, then the matrix call's own */
+    if (n == 0) return 0;
+    const int bad = tensor_args_check(d_out, desc);
+    if (bad) return bad;
+    if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
+    if (!colors || !color_layout_ok(desc->out_format) || (filter && filter->filter == DEBIG_PNG_FILTER_BICUBIC)) return DEBIG_PNG_BAD_ARG;
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL,
+                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors);
 }
 
 /* ---- debig_png_decode_batch_labels: palette indices / raw grey samples -> one dense integer class-map tensor (decode_png.h) - */
@@ -1258,7 +1341,7 @@ DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const 
     if (bad) return bad;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, NULL};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, NULL, NULL};
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     dev_table tab[3] = {{desc->lut, 1024, 0}, {NULL, 0, 0}, {NULL, 0, 0}}; /* the LUT (or its room), the X tables, the Y tables */
@@ -1396,7 +1479,7 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
     if ((rc = clbl_args_check(d_out, desc, n, &M))) goto done;
     const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL, NULL}; /* E_LABEL: a 16-bit file */
     J.W = J.TX.L = W;
     J.H = J.TY.L = H;
     tab[0].src = M.tab;
@@ -1478,23 +1561,38 @@ static int warp_prepare(const debig_png_warp *warps, uint32_t n, int64_t **m, ui
     return 0;
 }
 
-DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                                 const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
-                                                 debig_png_info *infos, uint32_t n, uint32_t flags,
-                                                 const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
+_Static_assert(offsetof(debig_png_warp_color_task, color_off) == sizeof(debig_png_warp_task) &&
+                   offsetof(debig_png_warp_color_task, b) == offsetof(debig_png_warp_task, b) &&
+                   offsetof(debig_png_warp_color_task, border) == offsetof(debig_png_warp_task, border) &&
+                   sizeof(debig_png_warp_color_task) == 160,
+               "debig_png_warp_color_task starts with debig_png_warp_task, field for field");
+
+/* the checks of debig_png_decode_batch_tensor_warp (n > 0): those of debig_png_decode_batch_tensor first and unchanged, then the
+ * warp's; all before any file is looked at -> 0 or the call's return value */
+static int tensor_warp_check(const void *d_out, const debig_png_warp *warps, const debig_png_tensor_desc *desc,
+                             const debig_png_warp_desc *wd)
 {
-    /* every check of debig_png_decode_batch_tensor first and unchanged, then the warp's; all before any file is looked at */
-    if (n == 0) return 0;
     const int badarg = tensor_args_check(d_out, desc);
     if (badarg) return badarg;
     if (!warps || !wd || (wd->filter != DEBIG_PNG_FILTER_BILINEAR && wd->filter != DEBIG_PNG_FILTER_NEAREST) ||
         wd->border_mode > DEBIG_PNG_BORDER_CLAMP || wd->alpha_mode != DEBIG_PNG_ALPHA_STRAIGHT || wd->reserved != 0 ||
         desc->resize_flags != 0)
         return DEBIG_PNG_BAD_ARG;
-    const uint32_t fmt = desc->out_format, ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u, sb = bits / 8u;
+    const uint32_t fmt = desc->out_format, ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u;
     if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT)
         for (uint32_t k = 0; k < ch; k++)
             if (wd->border[k] > (1u << bits) - 1u) return DEBIG_PNG_BAD_ARG;
+    return 0;
+}
+
+/* debig_png_decode_batch_tensor_warp (colors == NULL) and debig_png_decode_batch_tensor_warp_color behind their argument checks.
+ * With colors the tasks are debig_png_warp_color_task -- the warp task and the place of the image's record, which travels as the
+ * launch's one table -- and go to the colour kernel. */
+static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
+                            const debig_png_warp *warps, const debig_png_color *colors, uint32_t *status, debig_png_info *infos,
+                            uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
+{
+    const uint32_t fmt = desc->out_format, ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u, sb = bits / 8u;
     const uint32_t W = desc->out_w, H = desc->out_h;
     const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? sb : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
     const uint64_t slot = (uint64_t)H * W * ch * es;
@@ -1502,19 +1600,22 @@ DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, c
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     int64_t *m = NULL;
-    uint8_t *wbad = NULL;
-    debig_png_warp_task *tasks = NULL;
+    uint8_t *wbad = NULL, *cbad = NULL, *tasks = NULL;
+    debig_png_color_rec *crec = NULL;
+    const size_t elem = colors ? sizeof(debig_png_warp_color_task) : sizeof(debig_png_warp_task);
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     int rc;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
-    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad}; /* no crop-size cap */
+    if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
+    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad}; /* no crop-size cap */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     rc = 2;
     for (uint32_t i = 0; i < n; i++) {
         if (status[i] != DEBIG_PNG_OK) continue;
-        debig_png_warp_task p;
+        debig_png_warp_color_task p; /* (the plain task: its first elem bytes) */
         memset(&p, 0, sizeof p);
+        p.color_off = (uint64_t)i * sizeof *crec;
         p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * ch * sb;
         p.out_off = (uint64_t)i * slot;
         memcpy(p.m, m + 6u * (size_t)i, sizeof p.m);
@@ -1537,26 +1638,56 @@ DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, c
             p.b[k] = desc->bias[k];
         }
         for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof p)) goto done;
+            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
             p.rows = H - y0 < run ? H - y0 : run;
-            tasks[n_tasks++] = p;
+            memcpy(tasks + n_tasks++ * elem, &p, elem);
         }
     }
     rc = 0;
     if (n_tasks == 0) goto done;
-    const dev_table none = {NULL, 0, 0}; /* the warp has no tables: the six int64 travel in the task */
-    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, &none, 1, &rc);
+    /* the plain warp has no tables (the six int64 travel in the task); with colours the records are the one table, at offset 0 */
+    const dev_table tab = {crec, colors ? (uint64_t)n * sizeof *crec : 0, 0};
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, &tab, 1, &rc);
     if (!c) goto done;
-    if ((rc = debig_hip_png_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_warp_task *)c->rsz_tasks.ptr, (uint32_t)n_tasks, NULL)))
+    if ((rc = colors ? debig_hip_png_warp_color_batch(c->rsz_src.ptr, d_out, (const debig_png_warp_color_task *)c->rsz_tasks.ptr,
+                                                      c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
+                     : debig_hip_png_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_warp_task *)c->rsz_tasks.ptr, (uint32_t)n_tasks, NULL)))
         goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
     stage_free(&S);
     free(m);
     free(wbad);
+    free(crec);
+    free(cbad);
     free(tasks);
     return rc;
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                 const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                 debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                 const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
+{
+    if (n == 0) return 0;
+    const int badarg = tensor_warp_check(d_out, warps, desc, wd);
+    if (badarg) return badarg;
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, n, flags, desc, wd);
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                       const debig_png_box *boxes, const debig_png_warp *warps,
+                                                       const debig_png_color *colors, uint32_t *status, debig_png_info *infos,
+                                                       uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                                                       const debig_png_warp_desc *wd)
+{
+    /* every check of debig_png_decode_batch_tensor_warp first and unchanged, then the matrix call's own */
+    if (n == 0) return 0;
+    const int badarg = tensor_warp_check(d_out, warps, desc, wd);
+    if (badarg) return badarg;
+    if (!colors || !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -1584,7 +1715,7 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
     int rc;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     rc = 2;
     for (uint32_t i = 0; i < n; i++) {
@@ -1659,7 +1790,7 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
     if (!cnt) goto done;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL}; /* E_LABEL: a 16-bit file */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
     dev_tables_place(tab, 2);

@@ -606,6 +606,58 @@ typedef struct debig_png_color_label_warp_task {
 int debig_hip_png_color_label_warp_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_warp_task *d_tasks,
                                          const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream);
 
+/* ---- the per-image colour matrix of the tensor decodes (csrc/png_color_kernel.inc, behind debig_png_decode_batch_tensor_color and
+ * debig_png_decode_batch_tensor_warp_color in decode_png.h, which has the rule).  One RECORD per image, 64 bytes, 8-byte aligned in
+ * d_weights: the matrix as debig_png_color_quantise gives it -- k[3 c + j] = llround(m_cj * 65536), |k| <= 2^20; o[c] =
+ * llround(m_c3 * Vmax), |o| <= 16 Vmax, Vmax = (2^P - 1) << (30 - P).  It is uniform over a task, so it arrives by scalar loads and
+ * the tasks stay small.  A task whose record breaks a limit, or whose color_off is not a multiple of 8, is skipped. */
+typedef struct debig_png_color_rec {
+    int64_t o[3];
+    int32_t k[9];           /* row major: output channel c takes k[3 c .. 3 c + 2]                                           */
+    uint32_t reserved;
+} debig_png_color_rec;
+
+/* Resize + colour matrix + normalise (debig_png_resize_color_kernel): the tile, the axis tables, the bounds and pass 1 are those of
+ * debig_png_resize_task, whose fields come first with the same meaning; channels is 3 (RGB) or 4 (RGBA: the fourth channel is
+ * not mixed).  Pass 2 takes an output PIXEL per lane: it sums the channels down the Hq rows, mixes the three colours, converts
+ * and stores.  A task that breaks a bound of debig_png_resize_task, or with other channels, bits other than 8 / 16 or an unknown
+ * dtype, is skipped. */
+typedef struct debig_png_resize_color_task {
+    uint64_t src_off, out_off, wx_off, wy_off;
+    uint32_t src_pitch;
+    uint32_t tile_x, tile_y, tile_w, tile_h;
+    uint32_t src_y0, src_rows;
+    uint32_t out_sx, out_sy, out_sc;
+    uint8_t channels;       /* 3 or 4                                                                                         */
+    uint8_t bits, dtype, reserved;
+    float a[4], b[4];
+    uint32_t reserved2;
+    uint64_t color_off;     /* the image's debig_png_color_rec, in bytes rel. to d_weights (8-byte aligned)                   */
+} debig_png_resize_color_task;
+int debig_hip_png_resize_color_batch(const void *d_src_arena, void *d_out, const debig_png_resize_color_task *d_tasks,
+                                     const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
+/* Warp + colour matrix + normalise (debig_png_warp_color_kernel): debig_png_warp_task, field for field, and the image's record.
+ * Picks, border rule and clamps are the warp kernel's; a CONSTANT border sample is mixed like any other.  d_weights holds the
+ * records (nothing else is read from it). */
+typedef struct debig_png_warp_color_task {
+    uint64_t src_off, out_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    uint32_t out_sx, out_sy, out_sc;
+    uint8_t channels;       /* 3 or 4                                                                                         */
+    uint8_t bits, dtype, filter, border_mode;
+    uint8_t reserved[3];
+    uint16_t border[4];
+    float a[4], b[4];
+    uint64_t color_off;     /* the image's debig_png_color_rec, in bytes rel. to d_weights (8-byte aligned)                   */
+} debig_png_warp_color_task;
+int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const debig_png_warp_color_task *d_tasks,
+                                   const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

@@ -235,9 +235,10 @@ int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *inp
  * (64-bit sums), or antialias with cl > 64 L on either axis (that bounds the taps at 129 and keeps the corrected weight
  * positive).  E_OUTPUT: the decoded image is larger than 2^31 bytes.  A file with any non-zero status leaves its slot
  * untouched; nothing outside d_out[0 .. n * slot) is written.
- * Not provided: colour jitter, animated PNGs, inputs already on the device, an asynchronous variant; other filters than
+ * Not provided: animated PNGs, inputs already on the device, an asynchronous variant; other filters than
  * bilinear are debig_png_decode_batch_tensor_filter's, flips, quarter turns and every other affine map are
- * debig_png_decode_batch_tensor_warp's (both below). */
+ * debig_png_decode_batch_tensor_warp's, colour jitter (one colour matrix per file) is debig_png_decode_batch_tensor_color's
+ * (all below). */
 typedef struct debig_png_box { uint32_t x, y, w, h; } debig_png_box; /* w == 0 && h == 0: the whole image */
 enum { DEBIG_PNG_T_UINT = 0, DEBIG_PNG_T_F32 = 1, DEBIG_PNG_T_F16 = 2, DEBIG_PNG_T_BF16 = 3 };
 #define DEBIG_PNG_RESIZE_ANTIALIAS 1u
@@ -333,8 +334,9 @@ int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, const uint
  * Checked before any file is looked at, with status unwritten: every check of debig_png_decode_batch_tensor_alpha first and
  * unchanged; then DEBIG_PNG_BAD_ARG for an unknown filter or reserved != 0.  Per image: statuses, their order, the untouched
  * slot of a failed file and infos are those of debig_png_decode_batch_tensor_alpha, with the E_BOX scale rule of the filter.
- * Not provided: Lanczos and other kernels, the a = -3/4 variant, border replication, colour jitter, animated PNGs,
- * inputs already on the device, an asynchronous variant.  (Flips and affine maps: debig_png_decode_batch_tensor_warp below.) */
+ * Not provided: Lanczos and other kernels, the a = -3/4 variant, border replication, animated PNGs,
+ * inputs already on the device, an asynchronous variant.  (Flips and affine maps: debig_png_decode_batch_tensor_warp below;
+ * colour jitter: debig_png_decode_batch_tensor_color below, for BILINEAR and NEAREST.) */
 enum { DEBIG_PNG_FILTER_BILINEAR = 0, DEBIG_PNG_FILTER_BICUBIC = 1, DEBIG_PNG_FILTER_NEAREST = 2 };
 typedef struct debig_png_filter_desc { uint32_t filter; uint32_t reserved; /* 0 */ } debig_png_filter_desc;
 int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -501,7 +503,7 @@ uint32_t debig_png_color_map_table(const debig_png_color_map *map, uint32_t *tab
  * that is extended, with E_WARP as above.
  * Not provided: antialiasing under a shrinking warp (shrink with the resize calls, or accept aliasing), bicubic, the OVER and
  * PREMULTIPLIED alpha modes together with a warp (alpha is warped like a colour channel, as in debig_png_decode_batch_tensor),
- * perspective maps, colour jitter. */
+ * perspective maps.  (Colour jitter under a warp: debig_png_decode_batch_tensor_warp_color below.) */
 #define DEBIG_PNG_E_WARP 16 /* the warp matrix (rules above) */
 enum { DEBIG_PNG_BORDER_CONSTANT = 0, DEBIG_PNG_BORDER_CLAMP = 1 };
 typedef struct debig_png_warp { double m[6]; } debig_png_warp; /* the inverse map, row major: (m00 m01 m02) (m10 m11 m12) */
@@ -530,6 +532,57 @@ int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inputs, const
         const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps, uint32_t *status,
         debig_png_info *infos /* may be NULL */, uint32_t *unmatched /* may be NULL */, uint32_t n, uint32_t flags,
         const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *warp_desc);
+
+/* ---- colour jitter: one 3 x 4 colour matrix per file in the tensor decodes ------------------------------------------------------
+ * Brightness, contrast, saturation, hue, random grey, channel order and the negative are all one affine map of a pixel's three
+ * colours.  debig_png_decode_batch_tensor_color and debig_png_decode_batch_tensor_warp_color are debig_png_decode_batch_tensor
+ * (with a filter: BILINEAR, antialiased or not, or NEAREST) and debig_png_decode_batch_tensor_warp with such a map applied between
+ * the filter and the ONE conversion, inside the same launch (debig_hip_png_resize_color_batch / debig_hip_png_warp_color_batch), so
+ * that scale / bias still normalise the jittered sample.  colors[i].m is the matrix of file i, row major: row c is
+ * (m_c0 m_c1 m_c2 | m_c3) and
+ *     out_c = m_c0 R + m_c1 G + m_c2 B + m_c3,    samples in [0, 1] of full scale.
+ * The host quantises once (debig_png_color_quantise; M = 2^P - 1, Vmax = M << (30 - P)):
+ *     k_cj = llround(m_cj * 65536)  (int32, |k| <= 2^20),    o_c = llround(m_c3 * Vmax)  (int64; the product as float64 rounds it),
+ * halves away from zero.  A file whose matrix has a non-finite entry or an entry above 16 in magnitude gets DEBIG_PNG_E_COLOR; it
+ * is decided when IHDR has been read, ranks behind E_BOX and E_WARP and, like them, ahead of whatever is found later in the file.
+ * The map is applied to the three colour values v_j the filter passes deliver -- the sample times 2^(30 - P), 0 .. Vmax -- in
+ * 64-bit integers:
+ *     acc_c = k_c0 v_0 + k_c1 v_1 + k_c2 v_2        (|acc_c| <= 3 * 2^20 * 2^30 < 2^52)
+ *     v'_c  = clamp(((acc_c + 32768) >> 16) + o_c, 0, Vmax)        (the shift arithmetic: floor)
+ * and v'_c takes the place of v_c in the ONE conversion of debig_png_decode_batch_tensor, unchanged: UINT, F32 with a separately
+ * rounded multiply and add, F16, BF16.  The fourth channel of RGBA (alpha) is not mixed: it passes through untouched.  There is ONE
+ * clamp, after the whole matrix.  torchvision's ColorJitter applies its operations one after the other and clamps to [0, 1] after
+ * each; a matrix that composes them (brightness 1.5, then contrast 0.5) keeps the values that an intermediate clamp would have cut
+ * off, so the two differ wherever an intermediate result leaves [0, 1].  That is on purpose: no information is lost between steps.
+ * Consequences (all bit for bit, in every dtype):
+ *   - the identity matrix gives the call without a matrix: ((v << 16) + 32768) >> 16 == v;
+ *   - a permutation matrix gives that call with its colour channels permuted (scale / bias stay with the OUTPUT channel);
+ *   - a zero matrix with an offset gives the constant clamp(o_c, 0, Vmax);
+ *   - the negative (-I, offsets 1) gives v'_c = Vmax - v_c exactly: where the filter is exact (out == crop, or NEAREST) the UINT
+ *     element is M - s.
+ * Under a warp a CONSTANT border sample is mixed like any other sample.
+ * Checked first, before any file is looked at (status unwritten): every check of the call that is extended, unchanged -- those
+ * of debig_png_decode_batch_tensor, then an unknown filter or filter->reserved != 0; those of debig_png_decode_batch_tensor_warp
+ * (its alpha_mode check included) --; then DEBIG_PNG_BAD_ARG for colors NULL, an out_format whose layout is not RGB or RGBA, and
+ * DEBIG_PNG_FILTER_BICUBIC.  debig_png_decode_batch_tensor_color has no alpha descriptor: alpha is STRAIGHT.  Per image: statuses,
+ * their order, infos and the untouched slot of a failed file are those of the call that is extended, with E_COLOR as above.
+ * Not provided: bicubic, the OVER and PREMULTIPLIED alpha modes together with a matrix, grey outputs, intermediate clamps
+ * between the operations a matrix composes, hue as a rotation in HSV (torchvision's; here it is a rotation about the grey axis,
+ * as in DALI), contrast about the image's own mean (it needs a reduction over the image first). */
+#define DEBIG_PNG_E_COLOR 17 /* the colour matrix (rules above) */
+typedef struct debig_png_color { double m[12]; } debig_png_color; /* row major: (m00 m01 m02 | m03) (m10 ..) (m20 ..) */
+/* Host only: k[3 c + j] = llround(M[4 c + j] * 65536), o[c] = llround(M[4 c + 3] * Vmax) at precision bits (8 or 16) -> 1, or 0
+ * (k, o unspecified) on the E_COLOR conditions above or for other bits. */
+int debig_png_color_quantise(const double M[12], uint32_t bits, int32_t k[9], int64_t o[3]);
+int debig_png_decode_batch_tensor_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                        const debig_png_box *boxes /* may be NULL */, const debig_png_color *colors, uint32_t *status,
+                                        debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                        const debig_png_tensor_desc *desc, const debig_png_filter_desc *filter /* may be NULL */);
+int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                             const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps,
+                                             const debig_png_color *colors, uint32_t *status, debig_png_info *infos /* may be NULL */,
+                                             uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                                             const debig_png_warp_desc *warp_desc);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

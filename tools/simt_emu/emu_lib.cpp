@@ -21,6 +21,7 @@
 #include "../../debigulator_amd/csrc/png_color_label_kernel.inc"
 #include "../../debigulator_amd/csrc/png_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_label_warp_kernel.inc"
+#include "../../debigulator_amd/csrc/png_color_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -421,5 +422,25 @@ extern "C" int emu_png_color_label_warp_batch(const void *src_arena, void *out, 
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_color_label_warp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
                       (const uint8_t *)tables, unmatched, n);
+    return 0;
+}
+
+/* the resize and the warp with a colour matrix per image (png_color_kernel.inc), as debig_hip_png_resize_color_batch and
+ * debig_hip_png_warp_color_batch launch them (weights: the axis tables and the records; grid as above) */
+extern "C" int emu_png_resize_color_batch(const void *src_arena, void *out, const debig_png_resize_color_task *tasks,
+                                          const void *weights, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_resize_color_kernel, grid, RSZ_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)weights, n);
+    return 0;
+}
+
+extern "C" int emu_png_warp_color_batch(const void *src_arena, void *out, const debig_png_warp_color_task *tasks, const void *weights,
+                                        uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_warp_color_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)weights, n);
     return 0;
 }
