@@ -561,6 +561,9 @@ DEV_INLINE uint32_t wave_max_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn
 
 // Restates unpack_huffman (src/inflate.c:565-706) + huffman_to_hashmap (:494-557):
 //   * a length >= n fails the stream (Q6)
+//   * strict (streams with DEBIG_STREAM_NO_REF_GATES only): an over-subscribed set of lengths (Kraft sum above 1) fails the
+//     stream as well.  The reference only asserts there, and without this every kernel would resolve the overlapping codes
+//     by its own table layout: the same stream would end differently at different widths.  Wave-uniform like Q6.
 //   * canonical codes for every non-zero length
 //   * probe range [qmin,qmax] from the reference's if / else-if update in symbol order (Q7):
 //     qmin = smallest non-zero length; qmax = the largest length among the symbols that are
@@ -569,7 +572,7 @@ DEV_INLINE uint32_t wave_max_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn
 // symbol inside its length class come from ballots, offsets from a 15-step prefix sum, the
 // direct table is filled in parallel.  `lens` points into LDS, n <= 320.
 // Returns 0 on the Q6 failure (wave-uniform).
-template <class LDS> DEV_INLINE int build_code(LDS &S, int c, const uint8_t *lens, uint32_t n)
+template <class LDS> DEV_INLINE int build_code(LDS &S, int c, const uint8_t *lens, uint32_t n, const int strict = 0)
 {
     constexpr int NW = LDS::NW;
     (void)NW;
@@ -609,6 +612,12 @@ DEV_UNROLL
         running_min = wm < running_min ? wm : running_min;
     }
     if (__any(bad)) return 0;
+    if (strict) { /* DEBIG_STREAM_NO_REF_GATES (plain RFC 1951): an over-subscribed set fails the stream, at every width alike */
+        uint32_t kraft = 0;
+DEV_UNROLL
+        for (int L = 1; L < 16; L++) kraft += run[L] << (15 - L);
+        if (kraft > (1u << 15)) return 0;
+    }
     // canonical first codes / offsets (uniform: every lane computes the same 15 steps)
     {
         uint32_t code = 0, off = 0, prev = 0;
@@ -1777,7 +1786,7 @@ debig_inflate_kernel(const uint8_t *__restrict__ in_arena, uint8_t *__restrict__
                     __syncthreads();
                     if (lane < 19) S.cl_len[lane] = S.lens[lane];
                     tables = 2;
-                    if (!build_code(S, CODE_CL, S.lens, 19)) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
+                    if (!build_code(S, CODE_CL, S.lens, 19, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES))) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
                     if (need_p2 && lane < 19) { /* table image for the aliasing replay */
                         uint32_t l = S.cl_len[lane];
                         uint32_t used = l != 0, code = 1234543u;
@@ -1795,8 +1804,8 @@ debig_inflate_kernel(const uint8_t *__restrict__ in_arena, uint8_t *__restrict__
                     const int bad = decode_code_lengths(S, hb, org, total);
                     if (bad) { status = DEBIG_E_NO_CODE; break; }
                     __syncthreads();
-                    if (!build_code(S, CODE_LIT, S.lens, hlit)) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
-                    if (!build_code(S, CODE_DIST, S.lens + hlit, hdist)) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
+                    if (!build_code(S, CODE_LIT, S.lens, hlit, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES))) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
+                    if (!build_code(S, CODE_DIST, S.lens + hlit, hdist, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES))) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
                 }
                 if (need_p2) {
                     // decode_png aliasing replay (SURVEY.md Appendix C): the reference's first

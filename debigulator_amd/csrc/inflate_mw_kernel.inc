@@ -155,7 +155,7 @@ debig_inflate_mw_kernel(const uint8_t *__restrict__ in_arena, uint8_t *__restric
                     if (tid < 19) S.cl_len[tid] = S.lens[tid];
                     tables = 2;
                     if (wave == 0) {
-                        int ok = build_code(S, CODE_CL, S.lens, 19);
+                        int ok = build_code(S, CODE_CL, S.lens, 19, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES));
                         if (ok && need_p2 && lane < 19) {
                             uint32_t l = S.cl_len[lane];
                             uint32_t used = l != 0, code = 1234543u;
@@ -177,8 +177,8 @@ debig_inflate_mw_kernel(const uint8_t *__restrict__ in_arena, uint8_t *__restric
                     if (bad) { status = DEBIG_E_NO_CODE; break; }
                     __syncthreads();
                     if (wave == 0) {
-                        int ok = build_code(S, CODE_LIT, S.lens, hlit);
-                        if (ok) ok = build_code(S, CODE_DIST, S.lens + hlit, hdist);
+                        int ok = build_code(S, CODE_LIT, S.lens, hlit, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES));
+                        if (ok) ok = build_code(S, CODE_DIST, S.lens + hlit, hdist, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES));
                         if (lane == 0) X.build_ok = (uint32_t)ok;
                     }
                     __syncthreads();

@@ -639,7 +639,7 @@ DEV_INLINE void scan_body(ScanLds &S, const uint8_t *__restrict__ in_arena, uint
                 wave_local_sync();
                 if (lane < 19) S.cl_len[lane] = S.lens[lane];
                 tables = 2;
-                if (!build_code(S, CODE_CL, S.lens, 19)) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
+                if (!build_code(S, CODE_CL, S.lens, 19, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES))) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
                 if (need_p2 && lane < 19) {
                     uint32_t l = S.cl_len[lane];
                     uint32_t used = l != 0, code = 1234543u;
@@ -656,8 +656,8 @@ DEV_INLINE void scan_body(ScanLds &S, const uint8_t *__restrict__ in_arena, uint
                 const int bad = decode_code_lengths(S, hb, org, total);
                 if (bad) { status = DEBIG_E_NO_CODE; break; }
                 wave_local_sync();
-                if (!build_code(S, CODE_LIT, S.lens, hlit)) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
-                if (!build_code(S, CODE_DIST, S.lens + hlit, hdist)) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
+                if (!build_code(S, CODE_LIT, S.lens, hlit, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES))) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
+                if (!build_code(S, CODE_DIST, S.lens + hlit, hdist, (int)(st.flags & DEBIG_STREAM_NO_REF_GATES))) { status = DEBIG_E_BAD_CODE_LENGTHS; break; }
             }
             if (need_p2) {
                 // the table image the reference writes over [p2_s0, outpos): applied by the LZ77

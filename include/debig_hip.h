@@ -50,7 +50,11 @@ typedef struct debig_stream {
 /* debig_stream.flags.  NO_REF_GATES: skip the reference's argument gates
  * (recipient_size < compressed_input_size, compressed_input_size < 5; quirk Q1) -- for
  * callers outside the reference's API whose input span is not "one stream", e.g. a gzip
- * member followed by further members (debig_gunzip_batch). */
+ * member followed by further members (debig_gunzip_batch).  Such a span is plain RFC 1951 to its
+ * caller, so one more of the reference's liberties ends with the gates: an over-subscribed set of
+ * code lengths (Kraft sum above 1; the reference only asserts) fails the stream with
+ * DEBIG_E_BAD_CODE_LENGTHS, in every kernel alike -- left alone, each kernel would resolve the
+ * overlapping codes by its own table layout and the result would depend on the batch size. */
 #define DEBIG_STREAM_NO_REF_GATES 1u
 /* A HINT for the host layers' choice of path, ignored by the kernels: the stream holds filtered image rows (a PNG IDAT
  * payload).  Such data is short matches a few bytes back, chained a dozen deep: a wavefront resolves it at the latency

@@ -86,13 +86,28 @@ int debig_png_probe(const uint8_t *compressed_input, const uint64_t compressed_i
  *     h_p * (1 + ceil(w_p * channels * depth / 8))): output past it -> E_DATA_LONG, short of it -> E_DATA_SHORT, any
  *     other inflate failure -> E_INFLATE.  The Adler-32 trailer (at ceil(in_end_bits / 8)) is verified on the GPU;
  *     missing or wrong -> E_ADLER.  Bytes after the trailer are ignored;
- *     (The inflate is the library's shared one: a block of the reserved type 3 is skipped there, as by the
- *     reference, so such a stream ends in E_DATA_SHORT or E_ADLER rather than E_INFLATE.)
+ *     (The inflate is the library's shared one, more lenient than zlib in two places:
+ *       - a block of the reserved type 3 is skipped, as by the reference, so such a stream ends in E_DATA_SHORT or E_ADLER
+ *         rather than E_INFLATE;
+ *       - input that runs out is an end, not an error: no symbol starts in the last byte of the span, so a stream that is
+ *         cut short -- or whose last block lost its BFINAL bit, so that decoding runs on into the trailer -- ends in
+ *         E_DATA_SHORT (the scanlines are incomplete) or E_ADLER (they are complete, the trailer is missing or is not
+ *         where decoding stopped), not in E_INFLATE.  A cut inside a block header can still be E_INFLATE: the missing
+ *         bits read as zeros and may give LEN != ~NLEN or an unusable code-length set.
+ *       An over-subscribed set of code lengths (more codes of some length than the shorter ones leave room for), which the
+ *       reference only asserts on, is NOT among these liberties: it is E_INFLATE, whatever kernel the batch size selects.
+ *      Neither ever yields DEBIG_PNG_OK for scanlines the Adler-32 trailer does not vouch for, and neither yields a
+ *      status of an earlier stage.)
  *   - pixels: a filter type > 4 -> E_FILTER; 16-bit samples reduce to their high byte; 1/2/4-bit grey scales by
  *     255/85/17; sub-byte samples are packed MSB first, every row starts on a byte boundary; grey -> (g, g, g, a).
  *     Adam7 passes (x0, y0, dx, dy) = (0,0,8,8) (4,0,8,8) (0,4,4,8) (2,0,4,4) (0,2,2,4) (1,0,2,2) (0,1,1,2).
  * Statuses are decided in this order: the chunk walk (in file order), missing PLTE / IDAT / IEND, zlib header, E_OUTPUT,
  * CRC, inflate, Adler-32, filter types, palette indices.  On error outs[i] is unspecified; other files are not affected.
+ * One resource limit stands beside that promise: the device arenas of a call are sized from every file that passes the host
+ * rules (its scanline size and out_bytes, as IHDR claims them), before any CRC is looked at.  A file whose IHDR claims a huge
+ * image fails alone with E_OUTPUT when out_caps[i] is smaller than 4wh; when the caller offers a buffer that large and the
+ * device cannot hold the arenas, the CALL returns a device error (out of memory) and no file is decoded.  Callers of untrusted
+ * files bound the out_caps they are willing to offer (debig_png_info_get gives the claimed size without any allocation).
  * Routing: non-interlaced 8-bit colour type 6, and 2 without a tRNS key, go through the tuned de-filter kernels of
  * debig_decode_png_batch (spec output); everything else through the general kernel (debig_hip_png_spec_defilter_batch).
  * DEBIG_PNG_FORCE_GENERAL sends every file through the general kernel (tests, measurements).

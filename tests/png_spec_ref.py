@@ -5,6 +5,7 @@ numpy + the stdlib's zlib only:
                     combination, with stored / fixed / dynamic DEFLATE blocks;
   * decode(data) -- a straightforward reference decoder of the rules debig_png_decode_batch documents:
                     -> (status, rgba (h, w, 4) uint8 or None, info dict).
+  * pixels(raw, ...) -- the de-filter and conversion steps of decode on their own (tests/png_damage.py);
   * scanlines(...) / tasks_for(...) -- the scanline stream and the Adam7 pass geometry (emulator tests).
 """
 import struct
@@ -369,6 +370,14 @@ def decode(data, out_cap=None):
     tail = d.unused_data
     if len(tail) < 4 or struct.unpack(">I", tail[:4])[0] != zlib.adler32(raw) & 0xFFFFFFFF:
         return E_ADLER, None, inf
+    st, out = pixels(raw, inf, pal, key)
+    return st, out, inf
+
+
+def pixels(raw, inf, pal, key):
+    """the scanline stream (exactly scanline_size bytes) -> (OK, rgba (h, w, 4)) or (E_FILTER / E_PALETTE, None): the
+    last two steps of decode (a filter error anywhere outranks a palette error)"""
+    w, h, ct, depth, il = inf["width"], inf["height"], inf["color_type"], inf["bit_depth"], inf["interlace"]
     out = np.zeros((h, w, 4), dtype=np.uint8)
     pos = 0
     parts = []
@@ -376,14 +385,14 @@ def decode(data, out_cap=None):
         rb = row_bytes(wp, ct, depth)
         rows, bad, pos = _unfilter(raw, pos, wp, hp, rb, bpp_f(ct, depth))
         if bad is not None:
-            return E_FILTER, None, inf
+            return E_FILTER, None
         parts.append((x0, y0, dx, dy, _samples(rows, wp, ct, depth)))
     for x0, y0, dx, dy, s in parts:
         rgba, bad = _to_rgba(s, ct, depth, key, pal)
         if bad:
-            return E_PALETTE, None, inf
+            return E_PALETTE, None
         out[y0::dy, x0::dx] = rgba
-    return OK, out, inf
+    return OK, out
 
 
 def full_palette(pal_rgb, trns=b""):
