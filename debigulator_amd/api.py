@@ -212,7 +212,7 @@ def gunzip_batch(datas, out_caps):
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
               8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box", 15: "label",
-              16: "warp", 17: "color"}
+              16: "warp", 17: "color", 18: "tone"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -681,9 +681,70 @@ def _png_colors(color, n):
     return cs
 
 
+class PngTone(C.Structure):  # include/decode_png.h: debig_png_tone
+    _fields_ = [("op", C.c_uint32), ("param", C.c_uint32)]
+
+
+PNG_TONE_OPS = {"none": 0, "autocontrast": 1, "equalize": 2, "posterize": 3, "solarize": 4, "table": 5}  # DEBIG_PNG_TONE_*
+
+
+def png_tone_table(op, param=0, hist=None):
+    """the 256-entry table (numpy uint8) of one colour channel for the tone operation `op` ("autocontrast", "equalize",
+    "posterize", "solarize", or its number) with `param` (bits to keep; threshold), from the channel's histogram `hist` (256
+    counts below 2^32; ignored by "posterize" and "solarize") -- include/decode_png.h: debig_png_tone_table, the host's own
+    statement of what the device builds (no GPU needed).  None on the conditions of status 18 ("tone")."""
+    code = PNG_TONE_OPS.get(op, op) if isinstance(op, str) else int(op)
+    if isinstance(op, str) and op not in PNG_TONE_OPS:
+        raise ValueError(f"op must be one of {sorted(PNG_TONE_OPS)}, not {op!r}")
+    if not 0 <= int(param) < 1 << 32 or not 0 <= code < 1 << 32:
+        return None
+    h = None
+    if hist is not None:
+        h = np.ascontiguousarray(hist, dtype=np.uint32)
+        if h.shape != (256,):
+            raise ValueError("hist must hold 256 counts")
+    L = _png_spec_lib()
+    L.debig_png_tone_table.restype = C.c_int
+    L.debig_png_tone_table.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lut = np.zeros(256, np.uint8)
+    ok = L.debig_png_tone_table(code, int(param), h.ctypes.data if h is not None else None, lut.ctypes.data)
+    return lut if ok else None
+
+
+def _png_tones(tone, n):
+    """tone: a sequence of n entries, each None, "autocontrast", "equalize", ("posterize", bits), ("solarize", threshold) or
+    ("table", 256 uint8) -> ((PngTone * n), the distinct tables one behind the other (numpy uint8) or None, their number)"""
+    if len(tone) != n:
+        raise ValueError(f"tone must have one entry per file ({n}), not {len(tone)}")
+    ts = (PngTone * n)()
+    tabs, index = [], {}
+    for i, e in enumerate(tone):
+        if e is None:
+            continue
+        name, arg = (e, 0) if isinstance(e, str) else (e[0], e[1]) if len(e) == 2 else (None, None)
+        if name not in PNG_TONE_OPS or name == "none" or (isinstance(e, str) and name in ("posterize", "solarize", "table")):
+            raise ValueError(f"tone[{i}]: None, 'autocontrast', 'equalize', ('posterize', bits), ('solarize', threshold) or "
+                             f"('table', 256 uint8), not {e!r}")
+        ts[i].op = PNG_TONE_OPS[name]
+        if name == "table":
+            t = np.asarray(arg)
+            if t.shape != (256,) or t.dtype.kind not in "iu" or t.min() < 0 or t.max() > 255:
+                raise ValueError(f"tone[{i}]: a table is 256 integers in 0 .. 255")
+            key = t.astype(np.uint8).tobytes()
+            if key not in index:
+                index[key] = len(tabs)
+                tabs.append(key)
+            ts[i].param = index[key]
+        else:
+            a = int(arg)
+            ts[i].param = a if 0 <= a < 1 << 32 else 0xFFFFFFFF  # (out of range either way: status 18)
+    return ts, (np.frombuffer(b"".join(tabs), np.uint8).copy() if tabs else None), len(tabs)
+
+
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
                             antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
-                            background=None, warp=None, border="constant", border_value=None, color=None, filter="bilinear"):
+                            background=None, warp=None, border="constant", border_value=None, color=None, tone=None,
+                            filter="bilinear"):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
     (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
@@ -715,8 +776,21 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     [0, 1] scale, applied in integers between the filter and the conversion, clamped once, before mean / std --
     debig_png_decode_batch_tensor_color, or debig_png_decode_batch_tensor_warp_color together with warp.  It goes with mode "rgb"
     or "rgba" (alpha is not mixed), filter "bilinear" or "nearest" and alpha "straight".  A matrix with a non-finite entry or
-    one above 16 in magnitude: status 17 ("color")."""
+    one above 16 in magnitude: status 17 ("color").
+    tone: None (everything above, unchanged), or one entry per file: None, "autocontrast", "equalize", ("posterize", bits 1 .. 8),
+    ("solarize", threshold 0 .. 256) or ("table", 256 uint8) -- debig_png_decode_batch_tensor_tone: the file's image goes
+    through everything above to 8-bit samples, then every colour channel (not alpha) through a 256-entry table -- Pillow's
+    ImageOps.equalize exactly, autocontrast with cutoff 0 in exact integers, posterize, solarize, or the caller's --, then
+    through the conversion with mean / std.  The histograms of "autocontrast" and "equalize" are taken on the device.  A file
+    whose entry is None gets, bit for bit, what the call without `tone` gives it.  It goes with depth 8 and alpha "straight" or
+    "over"; bits or a threshold out of range: status 18 ("tone").  (By name, like `color`.)"""
     import torch
+
+    if tone is not None:
+        if depth != 8:
+            raise ValueError("tone needs depth 8")
+        if alpha == "premultiplied":
+            raise ValueError("tone goes with alpha 'straight' or 'over', not 'premultiplied'")
 
     if color is not None:
         if filter == "bicubic":
@@ -753,7 +827,19 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
     out = _png_dense_out(shape, tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if cs is not None and wd is not None:
+    if tone is not None:
+        ts, tabs, n_tabs = _png_tones(tone, n)
+        L.debig_png_decode_batch_tensor_tone.restype = C.c_int
+        L.debig_png_decode_batch_tensor_tone.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + \
+            [C.c_void_p] * 4
+        plain = wd is None and cs is None
+        rc = L.debig_png_decode_batch_tensor_tone(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, cs, ts,
+                                                  tabs.ctypes.data if tabs is not None else None, n_tabs, status, infos, n,
+                                                  PNG_FORCE_GENERAL if force_general else 0, C.byref(d),
+                                                  C.byref(ad) if plain and ad is not None else None,
+                                                  C.byref(fd) if wd is None and fd is not None else None,
+                                                  C.byref(wd) if wd is not None else None)
+    elif cs is not None and wd is not None:
         L.debig_png_decode_batch_tensor_warp_color.restype = C.c_int
         L.debig_png_decode_batch_tensor_warp_color.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         rc = L.debig_png_decode_batch_tensor_warp_color(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, cs, status, infos, n,

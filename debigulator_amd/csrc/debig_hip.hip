@@ -21,6 +21,7 @@
 #include "png_warp_kernel.inc"
 #include "png_color_label_warp_kernel.inc"
 #include "png_color_kernel.inc"
+#include "png_tone_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -881,6 +882,29 @@ int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const d
     const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
     hipLaunchKernelGGL(debig_png_warp_color_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
+    return (int)hipGetLastError();
+}
+
+// the tone curves of the tensor decode (png_tone_kernel.inc): one workgroup per pixel run, as many workgroups as tasks
+int debig_hip_png_tone_hist_batch(const void *d_src, uint32_t *d_hist, const debig_png_tone_task *d_tasks, uint32_t n_tasks,
+                                  void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_tone_hist_kernel, dim3(grid), dim3(TONE_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src, d_hist, d_tasks, n_tasks);
+    return (int)hipGetLastError();
+}
+
+int debig_hip_png_tone_apply_batch(const void *d_src, void *d_out, const debig_png_tone_task *d_tasks, const uint32_t *d_hist,
+                                   const void *d_tables, uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_tone_apply_kernel, dim3(grid), dim3(TONE_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks, d_hist, (const uint8_t *)d_tables, n_tasks);
     return (int)hipGetLastError();
 }
 

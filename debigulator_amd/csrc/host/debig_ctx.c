@@ -52,6 +52,9 @@ void debig_ctx_release_ptr(debig_ctx *c)
     buf_free(&c->rsz_src);
     buf_free(&c->rsz_tasks);
     buf_free(&c->rsz_weights);
+    buf_free(&c->tone_px);
+    buf_free(&c->tone_tasks);
+    buf_free(&c->tone_hist);
     buf_free(&c->ws);
     buf_free(&c->dense);
     buf_free(&c->dense_list);

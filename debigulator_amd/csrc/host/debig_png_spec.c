@@ -868,6 +868,7 @@ typedef struct stage_rule {
     uint64_t max_w, max_h; /* max_w != 0: a crop wider / taller than this is E_BOX (the antialiased resize) */
     const uint8_t *warp_bad; /* != NULL: file i with warp_bad[i] != 0 is E_WARP (the warp calls) */
     const uint8_t *color_bad; /* != NULL: file i with color_bad[i] != 0 is E_COLOR (the colour-matrix calls) */
+    const uint8_t *tone_bad; /* != NULL: file i with tone_bad[i] != 0 is E_TONE (the tone call) */
 } stage_rule;
 
 /* per file: the status decided from IHDR (0: none), the image's place and size in the arena, the resolved box, the walk's info */
@@ -887,7 +888,7 @@ static void stage_free(stage *S)
     free(S->inf);
 }
 
-/* IHDR -> E_LABEL, then E_BOX, then E_WARP, then E_COLOR, then the walk's own error, then the size cap; the decode of what is left into the arena.
+/* IHDR -> E_LABEL, then E_BOX, then E_WARP, then E_COLOR, then E_TONE, then the walk's own error, then the size cap; the decode of what is left into the arena.
  * -> 0 (status and infos written; S filled, the caller's to stage_free either way) or the call's return value */
 static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inputs, const uint64_t *input_sizes,
                         const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags)
@@ -925,6 +926,10 @@ static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inp
         }
         if (R->color_bad && R->color_bad[i]) {
             S->pre[i] = DEBIG_PNG_E_COLOR;
+            continue;
+        }
+        if (R->tone_bad && R->tone_bad[i]) {
+            S->pre[i] = DEBIG_PNG_E_TONE;
             continue;
         }
         S->box[i] = b;
@@ -1014,15 +1019,216 @@ static int color_prepare(const debig_png_color *colors, uint32_t n, uint32_t bit
     return 0;
 }
 
+/* ---- the tone curves of the tensor decode (decode_png.h: debig_png_decode_batch_tensor_tone) -------------------------------- */
+
+_Static_assert(sizeof(debig_png_tone_task) == 96, "debig_png_tone_task: 96 bytes, no padding");
+
+/* the E_TONE rule of one file */
+static int tone_param_ok(uint32_t op, uint32_t param, uint32_t n_tables)
+{
+    switch (op) {
+    case DEBIG_PNG_TONE_NONE:
+    case DEBIG_PNG_TONE_AUTOCONTRAST:
+    case DEBIG_PNG_TONE_EQUALIZE: return param == 0;
+    case DEBIG_PNG_TONE_POSTERIZE: return param >= 1 && param <= 8;
+    case DEBIG_PNG_TONE_SOLARIZE: return param <= 256;
+    case DEBIG_PNG_TONE_TABLE: return param < n_tables;
+    default: return 0;
+    }
+}
+
+DEBIG_API int debig_png_tone_table(uint32_t op, uint32_t param, const uint32_t hist[256], uint8_t lut[256])
+{
+    if (op == DEBIG_PNG_TONE_NONE || op == DEBIG_PNG_TONE_TABLE || !tone_param_ok(op, param, 0)) return 0;
+    if (op == DEBIG_PNG_TONE_POSTERIZE) {
+        for (uint32_t i = 0; i < 256; i++) lut[i] = (uint8_t)(i & ~((1u << (8u - param)) - 1u));
+        return 1;
+    }
+    if (op == DEBIG_PNG_TONE_SOLARIZE) {
+        for (uint32_t i = 0; i < 256; i++) lut[i] = (uint8_t)(i < param ? i : 255u - i);
+        return 1;
+    }
+    if (!hist) return 0;
+    uint32_t lo = 0, hi = 0, nz = 0;
+    uint64_t total = 0; /* (the device's counts fit 32 bits; any 256 uint32 fit 40) */
+    for (uint32_t i = 0; i < 256; i++) {
+        if (!hist[i]) continue;
+        if (!nz++) lo = i;
+        hi = i;
+        total += hist[i];
+    }
+    for (uint32_t i = 0; i < 256; i++) lut[i] = (uint8_t)i;
+    if (nz < 2) return 1;
+    if (op == DEBIG_PNG_TONE_AUTOCONTRAST) {
+        for (uint32_t i = 0; i < 256; i++) {
+            const uint32_t v = i < lo ? 0 : (i - lo) * 255u / (hi - lo);
+            lut[i] = (uint8_t)(v < 255u ? v : 255u);
+        }
+        return 1;
+    }
+    const uint64_t step = (total - hist[hi]) / 255u;
+    if (step == 0) return 1;
+    uint64_t acc = step / 2u;
+    for (uint32_t i = 0; i < 256; i++) {
+        const uint64_t v = acc / step;
+        lut[i] = (uint8_t)(v < 255u ? v : 255u);
+        acc += hist[i];
+    }
+    return 1;
+}
+
+/* what the tone call adds to a tensor core: per file its E_TONE flag and, once the statuses are known, the place of a decoded
+ * file whose op is not NONE among the 8-bit intermediates (UINT32_MAX: none) */
+typedef struct tone_plan {
+    const debig_png_tone *tones;
+    const uint8_t *tables;
+    uint32_t n_tables;
+    uint32_t oc;         /* the channels of the tensor */
+    uint8_t *bad;
+    uint32_t *place;
+    uint8_t *lut;        /* 16 bytes of slack, then 256 bytes per tone file: the fixed and the caller's tables */
+    debig_png_tone_task *tasks;
+    uint32_t n_tone;
+    uint64_t img;        /* bytes of one intermediate, a multiple of 16 */
+} tone_plan;
+
+static void tone_free(tone_plan *tp)
+{
+    if (!tp) return;
+    free(tp->bad);
+    free(tp->place);
+    free(tp->lut);
+    free(tp->tasks);
+}
+
+/* the E_TONE flags; -> 0 or 2 */
+static int tone_prepare(tone_plan *tp, uint32_t n)
+{
+    if (!tp) return 0;
+    tp->bad = (uint8_t *)calloc(n, 1);
+    tp->place = (uint32_t *)malloc((size_t)n * sizeof(uint32_t));
+    if (!tp->bad || !tp->place) return 2;
+    for (uint32_t i = 0; i < n; i++) {
+        tp->bad[i] = !tone_param_ok(tp->tones[i].op, tp->tones[i].param, tp->n_tables);
+        tp->place[i] = UINT32_MAX;
+    }
+    return 0;
+}
+
+/* after the decode: the places of the tone files, and room for their tables; -> 0 or 2 */
+static int tone_place(tone_plan *tp, const uint32_t *status, uint32_t n, uint32_t W, uint32_t H)
+{
+    if (!tp) return 0;
+    tp->img = debig_align16((uint64_t)W * H * tp->oc);
+    for (uint32_t i = 0; i < n; i++)
+        if (status[i] == DEBIG_PNG_OK && tp->tones[i].op != DEBIG_PNG_TONE_NONE) tp->place[i] = tp->n_tone++;
+    tp->lut = (uint8_t *)calloc((size_t)tp->n_tone * 256u + 16u, 1);
+    return tp->lut ? 0 : 2;
+}
+
+static int tone_is(const tone_plan *tp, uint32_t i) { return tp && tp->place[i] != UINT32_MAX; }
+
+/* the tables at their place: the table lands at table_off in the weights buffer, its first 256 bytes at the next multiple of
+ * 16 -> that offset */
+static uint64_t tone_fill(tone_plan *tp, uint32_t n, uint64_t table_off)
+{
+    const uint64_t pad = (16u - (table_off & 15u)) & 15u;
+    for (uint32_t i = 0; i < n; i++) {
+        if (tp->place[i] == UINT32_MAX) continue;
+        uint8_t *l = tp->lut + pad + (size_t)tp->place[i] * 256u;
+        const debig_png_tone o = tp->tones[i];
+        if (o.op == DEBIG_PNG_TONE_TABLE) memcpy(l, tp->tables + (size_t)o.param * 256u, 256);
+        else if (o.op == DEBIG_PNG_TONE_POSTERIZE || o.op == DEBIG_PNG_TONE_SOLARIZE) (void)debig_png_tone_table(o.op, o.param, NULL, l);
+    }
+    return table_off + pad;
+}
+
+/* the first stage has been launched: the pixel runs of every tone file (those with a histogram first), the cleared histograms,
+ * the histogram kernel over the first and the apply kernel over all of them, on the same stream.  lut_off: where tone_fill put
+ * the tables in c->rsz_weights.  -> 0 or the call's return value */
+static int tone_run(tone_plan *tp, debig_ctx *c, void *d_out, uint32_t n, const debig_png_tensor_desc *desc, uint64_t lut_off)
+{
+    if (!tp || tp->n_tone == 0) return 0;
+    const uint32_t W = desc->out_w, H = desc->out_h, oc = tp->oc, cc = oc & 1u ? oc : oc - 1u, px = W * H;
+    const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? 1u : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
+    const uint64_t slot = (uint64_t)px * oc * es;
+    const uint64_t per = (px + DEBIG_PNG_TONE_RUN - 1u) / DEBIG_PNG_TONE_RUN, n_tasks = per * tp->n_tone;
+    if (n_tasks > 0x7fffffffu) return 2;
+    tp->tasks = (debig_png_tone_task *)calloc((size_t)n_tasks, sizeof(debig_png_tone_task));
+    if (!tp->tasks) return 2;
+    uint64_t at = 0, n_hist_tasks = 0;
+    uint32_t n_hist = 0;
+    for (uint32_t pass = 0; pass < 2; pass++) {
+        for (uint32_t i = 0; i < n; i++) {
+            if (tp->place[i] == UINT32_MAX) continue;
+            const uint32_t op = tp->tones[i].op;
+            const uint32_t hist = op == DEBIG_PNG_TONE_AUTOCONTRAST || op == DEBIG_PNG_TONE_EQUALIZE;
+            if (hist == pass) continue;
+            debig_png_tone_task p;
+            memset(&p, 0, sizeof p);
+            p.src_off = (uint64_t)tp->place[i] * tp->img;
+            p.out_off = (uint64_t)i * slot;
+            p.hist_off = hist ? (uint64_t)n_hist++ * cc * 1024u : 0;
+            p.lut_off = lut_off + (uint64_t)tp->place[i] * 256u;
+            p.out_w = W;
+            p.out_h = H;
+            p.out_sx = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? 1u : oc;
+            p.out_sy = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? W : W * oc;
+            p.out_sc = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? H * W : 1u;
+            p.channels = (uint8_t)oc;
+            p.colour_channels = (uint8_t)cc;
+            p.dtype = (uint8_t)desc->dtype;
+            p.op = (uint8_t)op;
+            for (uint32_t k = 0; k < 4; k++) {
+                p.a[k] = (float)((double)desc->scale[k] / (255.0 * (double)(1u << 22)));
+                p.b[k] = desc->bias[k];
+            }
+            for (uint32_t p0 = 0; p0 < px; p0 += DEBIG_PNG_TONE_RUN) {
+                p.pix0 = p0;
+                p.pix_n = px - p0 < DEBIG_PNG_TONE_RUN ? px - p0 : DEBIG_PNG_TONE_RUN;
+                tp->tasks[at++] = p;
+            }
+        }
+        if (pass == 0) n_hist_tasks = at;
+    }
+    int rc;
+    if ((rc = debig_devbuf_reserve(&c->tone_tasks, n_tasks * sizeof(debig_png_tone_task))) ||
+        (rc = debig_devbuf_reserve(&c->tone_hist, (uint64_t)n_hist * cc * 1024u + 16u)) ||
+        (rc = debig_hip_memcpy_h2d(c->tone_tasks.ptr, tp->tasks, n_tasks * sizeof(debig_png_tone_task), NULL)) ||
+        (n_hist && (rc = debig_hip_memset(c->tone_hist.ptr, 0, (uint64_t)n_hist * cc * 1024u, NULL))) ||
+        (rc = debig_hip_png_tone_hist_batch(c->tone_px.ptr, (uint32_t *)c->tone_hist.ptr, (const debig_png_tone_task *)c->tone_tasks.ptr,
+                                            (uint32_t)n_hist_tasks, NULL)))
+        return rc;
+    return debig_hip_png_tone_apply_batch(c->tone_px.ptr, d_out, (const debig_png_tone_task *)c->tone_tasks.ptr,
+                                          (const uint32_t *)c->tone_hist.ptr, c->rsz_weights.ptr, (uint32_t)n_tasks, NULL);
+}
+
 /* debig_png_decode_batch_tensor (amode == DEBIG_PNG_ALPHA_STRAIGHT: bg unused), debig_png_decode_batch_tensor_alpha and
  * debig_png_decode_batch_tensor_filter behind their argument checks.  With alpha the pixels are decoded WITH their alpha (dfmt:
  * 4 or 2 channels) and the tiles go to the alpha kernel, which writes the channels of desc->out_format.  The filter picks the
  * weight rule and the E_BOX scale; BICUBIC tiles, of every alpha mode, go to the signed kernel (debig_hip_png_resize_cubic_batch),
  * NEAREST ones to the kernels of BILINEAR.  colors != NULL (debig_png_decode_batch_tensor_color: STRAIGHT, not BICUBIC, 3 or 4
- * channels): the tiles carry the offset of their image's record, which travels as a third table, and go to the colour kernel. */
+ * channels): the tiles carry the offset of their image's record, which travels as a third table, and go to the colour kernel.
+ * tp != NULL (debig_png_decode_batch_tensor_tone): the tiles of a file with a tone operation are UINT8 HWC tiles into the
+ * context's tone arena; they come behind all others, and the kernel is launched once per target over its range of the one task
+ * array; tone_run does the rest. */
+/* one range of the uploaded tiles through the kernel of the call */
+static int tensor_launch(const debig_ctx *c, void *out, const uint8_t *d_tasks, uint64_t cnt, int colors, uint32_t filter, int plain)
+{
+    return colors ? debig_hip_png_resize_color_batch(c->rsz_src.ptr, out, (const debig_png_resize_color_task *)d_tasks,
+                                                     c->rsz_weights.ptr, (uint32_t)cnt, NULL)
+           : filter == DEBIG_PNG_FILTER_BICUBIC
+               ? debig_hip_png_resize_cubic_batch(c->rsz_src.ptr, out, (const debig_png_resize_cubic_task *)d_tasks,
+                                                  c->rsz_weights.ptr, (uint32_t)cnt, NULL)
+           : plain ? debig_hip_png_resize_batch(c->rsz_src.ptr, out, (const debig_png_resize_task *)d_tasks, c->rsz_weights.ptr,
+                                                (uint32_t)cnt, NULL)
+                   : debig_hip_png_resize_alpha_batch(c->rsz_src.ptr, out, (const debig_png_resize_alpha_task *)d_tasks,
+                                                      c->rsz_weights.ptr, (uint32_t)cnt, NULL);
+}
+
 static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
                        uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
-                       uint32_t amode, const uint16_t *bg, uint32_t filter, const debig_png_color *colors)
+                       uint32_t amode, const uint16_t *bg, uint32_t filter, const debig_png_color *colors, tone_plan *tp)
 {
     /* fmt: the format decoded into the arena (ch channels); oc: the channels of the tensor */
     uint32_t fmt = desc->out_format;
@@ -1046,20 +1252,26 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     rsz_tables TX = {NULL, 0, 0, NULL, 0, 0, W, aa, filter}, TY = {NULL, 0, 0, NULL, 0, 0, H, aa, filter};
     int rc;
     if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
-    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H, NULL, cbad};
+    if ((rc = tone_prepare(tp, n))) goto done;
+    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H, NULL, cbad, tp ? tp->bad : NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
+    if ((rc = tone_place(tp, status, n, W, H))) goto done;
     /* ---- the axis tables of every decoded image, then their places behind one another */
     rc = 2;
     for (uint32_t i = 0; i < n; i++)
         if (status[i] == DEBIG_PNG_OK && (rsz_axis_get(&TX, S.box[i].w) < 0 || rsz_axis_get(&TY, S.box[i].h) < 0)) goto done;
-    dev_table tab[3] = {{TX.buf, TX.len, 0}, {TY.buf, TY.len, 0}, {crec, colors ? (uint64_t)n * sizeof *crec : 0, 0}};
-    const uint32_t n_tab = colors ? 3u : 2u;
+    dev_table tab[4] = {{TX.buf, TX.len, 0}, {TY.buf, TY.len, 0}, {crec, colors ? (uint64_t)n * sizeof *crec : 0, 0},
+                        {tp ? tp->lut : NULL, tp ? (uint64_t)tp->n_tone * 256u + 16u : 0, 0}};
+    const uint32_t n_tab = tp ? 4u : colors ? 3u : 2u;
     dev_tables_place(tab, n_tab); /* (the axis tables are multiples of 8 bytes long: the records are 8-byte aligned) */
-    /* ---- the tiles of every decoded image */
-    uint64_t n_tasks = 0;
+    const uint64_t lut_off = tp ? tone_fill(tp, n, tab[3].off) : 0;
+    /* ---- the tiles of every decoded image; with tp those of the tone files last, n_direct tiles in front of them */
+    uint64_t n_tasks = 0, n_direct = 0;
     uint32_t cap_tasks = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (status[i] != DEBIG_PNG_OK) continue;
+    for (uint64_t q = 0; q < (tp ? 2u : 1u) * (uint64_t)n; q++) { /* (with tp: every file twice, the tone files the second time) */
+        const uint32_t pass = q >= n, i = (uint32_t)(pass ? q - n : q);
+        if (q == n) n_direct = n_tasks;
+        if (status[i] != DEBIG_PNG_OK || tone_is(tp, i) != (int)pass) continue;
         const rsz_axis *ax = &TX.ax[rsz_axis_get(&TX, S.box[i].w)], *ay = &TY.ax[rsz_axis_get(&TY, S.box[i].h)];
         const uint32_t mtx = ax->max_taps, mty = ay->max_taps;
         const uint32_t *ey = (const uint32_t *)(TY.buf + ay->off) + 2;
@@ -1082,6 +1294,13 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
         for (uint32_t k = 0; k < 4; k++) {
             proto.a[k] = (float)((double)desc->scale[k] / ((double)((1u << bits) - 1u) * (double)(1u << (30u - bits))));
             proto.b[k] = desc->bias[k];
+        }
+        if (pass) { /* the 8-bit HWC intermediate */
+            proto.out_off = (uint64_t)tp->place[i] * tp->img;
+            proto.out_sx = oc;
+            proto.out_sy = W * oc;
+            proto.out_sc = 1u;
+            proto.dtype = DEBIG_PNG_T_UINT;
         }
         proto.mode = amode;
         proto.src_channels = (uint8_t)ch;
@@ -1119,24 +1338,22 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
             y0 += th;
         }
     }
+    if (!tp) n_direct = n_tasks;
     rc = 0;
     if (n_tasks == 0) goto done;
     debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
     if (!c) goto done;
-    const void *d_tasks = c->rsz_tasks.ptr;
-    if ((rc = colors ? debig_hip_png_resize_color_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_color_task *)d_tasks,
-                                                        c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
-              : filter == DEBIG_PNG_FILTER_BICUBIC
-                  ? debig_hip_png_resize_cubic_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_cubic_task *)d_tasks,
-                                                     c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
-              : plain ? debig_hip_png_resize_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_task *)d_tasks,
-                                                   c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
-                      : debig_hip_png_resize_alpha_batch(c->rsz_src.ptr, d_out, (const debig_png_resize_alpha_task *)d_tasks,
-                                                         c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)))
+    const uint8_t *d_tasks = (const uint8_t *)c->rsz_tasks.ptr;
+    if (n_tasks > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, (uint64_t)tp->n_tone * tp->img))) goto done;
+    if ((n_direct && (rc = tensor_launch(c, d_out, d_tasks, n_direct, colors != NULL, filter, plain))) ||
+        (n_tasks > n_direct &&
+         (rc = tensor_launch(c, c->tone_px.ptr, d_tasks + n_direct * elem, n_tasks - n_direct, colors != NULL, filter, plain))) ||
+        (rc = tone_run(tp, c, d_out, n, desc, lut_off)))
         goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
     stage_free(&S);
+    tone_free(tp);
     free(tasks);
     free(crec);
     free(cbad);
@@ -1155,7 +1372,7 @@ DEBIG_API int debig_png_decode_batch_tensor(const uint8_t *const *inputs, const 
     if (n == 0) return 0;
     const int bad = tensor_args_check(d_out, desc);
     if (bad) return bad;
-    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL, DEBIG_PNG_FILTER_BILINEAR, NULL);
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL, DEBIG_PNG_FILTER_BILINEAR, NULL, NULL);
 }
 
 /* the checks of debig_png_decode_batch_tensor_alpha (n > 0): those of debig_png_decode_batch_tensor first and unchanged, then
@@ -1190,7 +1407,7 @@ DEBIG_API int debig_png_decode_batch_tensor_alpha(const uint8_t *const *inputs, 
     const int bad = tensor_alpha_check(d_out, desc, alpha, &amode);
     if (bad) return bad;
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
-                       DEBIG_PNG_FILTER_BILINEAR, NULL);
+                       DEBIG_PNG_FILTER_BILINEAR, NULL, NULL);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -1205,7 +1422,7 @@ DEBIG_API int debig_png_decode_batch_tensor_filter(const uint8_t *const *inputs,
     if (bad) return bad;
     if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
-                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, NULL);
+                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, NULL, NULL);
 }
 
 /* the colour matrix goes with three colour channels: RGB or RGBA */
@@ -1226,7 +1443,7 @@ DEBIG_API int debig_png_decode_batch_tensor_color(const uint8_t *const *inputs, 
     if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
     if (!colors || !color_layout_ok(desc->out_format) || (filter && filter->filter == DEBIG_PNG_FILTER_BICUBIC)) return DEBIG_PNG_BAD_ARG;
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, DEBIG_PNG_ALPHA_STRAIGHT, NULL,
-                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors);
+                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors, NULL);
 }
 
 /* ---- debig_png_decode_batch_labels: palette indices / raw grey samples -> one dense integer class-map tensor (decode_png.h) - */
@@ -1341,7 +1558,7 @@ DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const 
     if (bad) return bad;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, NULL, NULL};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, NULL, NULL, NULL};
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     dev_table tab[3] = {{desc->lut, 1024, 0}, {NULL, 0, 0}, {NULL, 0, 0}}; /* the LUT (or its room), the X tables, the Y tables */
@@ -1479,7 +1696,7 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
     if ((rc = clbl_args_check(d_out, desc, n, &M))) goto done;
     const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL, NULL}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
     J.W = J.TX.L = W;
     J.H = J.TY.L = H;
     tab[0].src = M.tab;
@@ -1587,10 +1804,12 @@ static int tensor_warp_check(const void *d_out, const debig_png_warp *warps, con
 
 /* debig_png_decode_batch_tensor_warp (colors == NULL) and debig_png_decode_batch_tensor_warp_color behind their argument checks.
  * With colors the tasks are debig_png_warp_color_task -- the warp task and the place of the image's record, which travels as the
- * launch's one table -- and go to the colour kernel. */
+ * launch's one table -- and go to the colour kernel.  tp != NULL (debig_png_decode_batch_tensor_tone): as in tensor_core, the
+ * tasks of the tone files come last, write UINT8 HWC into the tone arena through a launch of their own, and tone_run follows. */
 static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
                             const debig_png_warp *warps, const debig_png_color *colors, uint32_t *status, debig_png_info *infos,
-                            uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
+                            uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd,
+                            tone_plan *tp)
 {
     const uint32_t fmt = desc->out_format, ch = fmt_channels(fmt), bits = fmt & DEBIG_PNG_FMT_16 ? 16u : 8u, sb = bits / 8u;
     const uint32_t W = desc->out_w, H = desc->out_h;
@@ -1608,11 +1827,22 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     int rc;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
     if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
-    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad}; /* no crop-size cap */
+    if ((rc = tone_prepare(tp, n))) goto done;
+    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad, tp ? tp->bad : NULL}; /* no crop-size cap */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
+    if ((rc = tone_place(tp, status, n, W, H))) goto done;
+    /* the plain warp has no tables (the six int64 travel in the task); with colours the records are the first table, at offset 0;
+     * the tone call's tables follow */
+    dev_table tab[2] = {{crec, colors ? (uint64_t)n * sizeof *crec : 0, 0}, {tp ? tp->lut : NULL, tp ? (uint64_t)tp->n_tone * 256u + 16u : 0, 0}};
+    const uint32_t n_tab = tp ? 2u : 1u;
+    dev_tables_place(tab, n_tab);
+    const uint64_t lut_off = tp ? tone_fill(tp, n, tab[1].off) : 0;
+    uint64_t n_direct = 0; /* with tp: the tasks in front of those of the tone files */
     rc = 2;
-    for (uint32_t i = 0; i < n; i++) {
-        if (status[i] != DEBIG_PNG_OK) continue;
+    for (uint64_t q = 0; q < (tp ? 2u : 1u) * (uint64_t)n; q++) { /* (with tp: every file twice, the tone files the second time) */
+        const uint32_t pass = q >= n, i = (uint32_t)(pass ? q - n : q);
+        if (q == n) n_direct = n_tasks;
+        if (status[i] != DEBIG_PNG_OK || tone_is(tp, i) != (int)pass) continue;
         debig_png_warp_color_task p; /* (the plain task: its first elem bytes) */
         memset(&p, 0, sizeof p);
         p.color_off = (uint64_t)i * sizeof *crec;
@@ -1637,6 +1867,13 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
             p.a[k] = (float)((double)desc->scale[k] / ((double)((1u << bits) - 1u) * (double)(1u << (30u - bits))));
             p.b[k] = desc->bias[k];
         }
+        if (pass) { /* the 8-bit HWC intermediate */
+            p.out_off = (uint64_t)tp->place[i] * tp->img;
+            p.out_sx = ch;
+            p.out_sy = W * ch;
+            p.out_sc = 1u;
+            p.dtype = DEBIG_PNG_T_UINT;
+        }
         for (uint32_t y0 = 0; y0 < H; y0 += run) {
             if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
@@ -1644,19 +1881,27 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
             memcpy(tasks + n_tasks++ * elem, &p, elem);
         }
     }
+    if (!tp) n_direct = n_tasks;
     rc = 0;
     if (n_tasks == 0) goto done;
-    /* the plain warp has no tables (the six int64 travel in the task); with colours the records are the one table, at offset 0 */
-    const dev_table tab = {crec, colors ? (uint64_t)n * sizeof *crec : 0, 0};
-    debig_ctx *c = dev_upload(tasks, n_tasks, elem, &tab, 1, &rc);
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
     if (!c) goto done;
-    if ((rc = colors ? debig_hip_png_warp_color_batch(c->rsz_src.ptr, d_out, (const debig_png_warp_color_task *)c->rsz_tasks.ptr,
-                                                      c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
-                     : debig_hip_png_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_warp_task *)c->rsz_tasks.ptr, (uint32_t)n_tasks, NULL)))
-        goto done;
+    if (n_tasks > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, (uint64_t)tp->n_tone * tp->img))) goto done;
+    for (uint32_t part = 0; part < 2; part++) { /* the caller's tensor, then the tone arena */
+        const uint8_t *d_tasks = (const uint8_t *)c->rsz_tasks.ptr + (part ? n_direct * elem : 0);
+        const uint64_t cnt = part ? n_tasks - n_direct : n_direct;
+        void *out = part ? c->tone_px.ptr : d_out;
+        if (cnt == 0) continue;
+        if ((rc = colors ? debig_hip_png_warp_color_batch(c->rsz_src.ptr, out, (const debig_png_warp_color_task *)d_tasks,
+                                                          c->rsz_weights.ptr, (uint32_t)cnt, NULL)
+                         : debig_hip_png_warp_batch(c->rsz_src.ptr, out, (const debig_png_warp_task *)d_tasks, (uint32_t)cnt, NULL)))
+            goto done;
+    }
+    if ((rc = tone_run(tp, c, d_out, n, desc, lut_off))) goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
     stage_free(&S);
+    tone_free(tp);
     free(m);
     free(wbad);
     free(crec);
@@ -1673,7 +1918,7 @@ DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, c
     if (n == 0) return 0;
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, n, flags, desc, wd);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, n, flags, desc, wd, NULL);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -1687,7 +1932,45 @@ DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inp
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
     if (!colors || !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd, NULL);
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                 const debig_png_box *boxes, const debig_png_warp *warps,
+                                                 const debig_png_color *colors, const debig_png_tone *tones, const uint8_t *tables,
+                                                 uint32_t n_tables, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                                 uint32_t flags, const debig_png_tensor_desc *desc,
+                                                 const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter,
+                                                 const debig_png_warp_desc *wd)
+{
+    /* every check of the call that is extended first, unchanged and in its order; then the tone call's own */
+    if (n == 0) return 0;
+    uint32_t amode = DEBIG_PNG_ALPHA_STRAIGHT;
+    if (warps || wd) {
+        const int badarg = tensor_warp_check(d_out, warps, desc, wd);
+        if (badarg) return badarg;
+        if ((colors && !color_layout_ok(desc->out_format)) || alpha || filter) return DEBIG_PNG_BAD_ARG;
+    } else if (colors) {
+        const int badarg = tensor_args_check(d_out, desc);
+        if (badarg) return badarg;
+        if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
+        if (!color_layout_ok(desc->out_format) || (filter && filter->filter == DEBIG_PNG_FILTER_BICUBIC) || alpha) return DEBIG_PNG_BAD_ARG;
+    } else {
+        const int badarg = tensor_alpha_check(d_out, desc, alpha, &amode);
+        if (badarg) return badarg;
+        if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
+    }
+    if (!tones || (desc->out_format & DEBIG_PNG_FMT_16) || amode == DEBIG_PNG_ALPHA_PREMULTIPLIED || (!tables && n_tables > 0))
+        return DEBIG_PNG_BAD_ARG;
+    tone_plan tp;
+    memset(&tp, 0, sizeof tp);
+    tp.tones = tones;
+    tp.tables = tables;
+    tp.n_tables = n_tables;
+    tp.oc = fmt_channels(desc->out_format);
+    if (warps) return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd, &tp);
+    return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
+                       filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors, &tp);
 }
 
 DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -1715,7 +1998,7 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
     int rc;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL, NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     rc = 2;
     for (uint32_t i = 0; i < n; i++) {
@@ -1790,7 +2073,7 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
     if (!cnt) goto done;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL, NULL}; /* E_LABEL: a 16-bit file */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
     dev_tables_place(tab, 2);

@@ -662,6 +662,38 @@ typedef struct debig_png_warp_color_task {
 int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const debig_png_warp_color_task *d_tasks,
                                    const void *d_weights, uint32_t n_tasks, void *hip_stream);
 
+/* ---- tone curves of the tensor decodes (csrc/png_tone_kernel.inc, behind debig_png_decode_batch_tensor_tone in decode_png.h,
+ * which has the rule).  The first stage writes every tone file as UINT8 HWC into an arena; one TASK of both kernels is a run of
+ * pix_n pixels of one such image, row major from pixel pix0, for one workgroup of 256 lanes.  The histogram kernel takes the tasks
+ * of AUTOCONTRAST / EQUALIZE files and adds the counts of the run's colour samples to the image's colour_channels x 256 uint32 at
+ * hist_off in d_hist (cleared by the caller before the launch).  The apply kernel takes the tasks of every tone file: it builds
+ * the image's tables from that histogram (AUTOCONTRAST, EQUALIZE: d_hist may be NULL when no task needs it) or copies the 256
+ * bytes at lut_off in d_tables (every other op: one table for every colour channel), maps the run's colour samples, passes alpha
+ * through and stores a[c] * (float)(entry << 22) + b[c] as dtype at out_off + (X out_sx + Y out_sy + c out_sc) elements.
+ * A task is skipped when out_w or out_h is 0 or above 16384, pix_n is 0 or above DEBIG_PNG_TONE_MAX_RUN, the run leaves the image,
+ * channels is not 1..4, colour_channels is not channels (1, 3) or channels - 1 (2, 4), dtype is above 3, op is not 1..5, hist_off
+ * or lut_off is not a multiple of 16, or src_off is not a multiple of a 2- or 4-byte pixel; the histogram kernel also skips the
+ * tasks of other ops. */
+#define DEBIG_PNG_TONE_RUN 4096u      /* pixels of a task as the host cuts them (the warp kernels' unit)                       */
+#define DEBIG_PNG_TONE_MAX_RUN 65536u
+typedef struct debig_png_tone_task {
+    uint64_t src_off;       /* the image's first pixel, in bytes rel. to d_src                                                 */
+    uint64_t out_off;       /* the image's slot, in bytes rel. to d_out                                                        */
+    uint64_t hist_off;      /* the image's histograms, in bytes rel. to d_hist                                                 */
+    uint64_t lut_off;       /* the image's 256-byte table, in bytes rel. to d_tables                                           */
+    uint32_t pix0, pix_n;
+    uint32_t out_w, out_h;
+    uint32_t out_sx, out_sy, out_sc; /* in elements                                                                            */
+    uint8_t channels, colour_channels;
+    uint8_t dtype;          /* DEBIG_PNG_T_*                                                                                   */
+    uint8_t op;             /* DEBIG_PNG_TONE_* (never NONE)                                                                   */
+    float a[4], b[4];
+} debig_png_tone_task;
+int debig_hip_png_tone_hist_batch(const void *d_src, uint32_t *d_hist, const debig_png_tone_task *d_tasks, uint32_t n_tasks,
+                                  void *hip_stream);
+int debig_hip_png_tone_apply_batch(const void *d_src, void *d_out, const debig_png_tone_task *d_tasks, const uint32_t *d_hist,
+                                   const void *d_tables, uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

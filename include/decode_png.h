@@ -252,8 +252,8 @@ int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *inp
  * untouched; nothing outside d_out[0 .. n * slot) is written.
  * Not provided: animated PNGs, inputs already on the device, an asynchronous variant; other filters than
  * bilinear are debig_png_decode_batch_tensor_filter's, flips, quarter turns and every other affine map are
- * debig_png_decode_batch_tensor_warp's, colour jitter (one colour matrix per file) is debig_png_decode_batch_tensor_color's
- * (all below). */
+ * debig_png_decode_batch_tensor_warp's, colour jitter (one colour matrix per file) is debig_png_decode_batch_tensor_color's,
+ * autocontrast, equalize, posterize and solarize are debig_png_decode_batch_tensor_tone's (all below). */
 typedef struct debig_png_box { uint32_t x, y, w, h; } debig_png_box; /* w == 0 && h == 0: the whole image */
 enum { DEBIG_PNG_T_UINT = 0, DEBIG_PNG_T_F32 = 1, DEBIG_PNG_T_F16 = 2, DEBIG_PNG_T_BF16 = 3 };
 #define DEBIG_PNG_RESIZE_ANTIALIAS 1u
@@ -583,7 +583,8 @@ int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inputs, const
  * their order, infos and the untouched slot of a failed file are those of the call that is extended, with E_COLOR as above.
  * Not provided: bicubic, the OVER and PREMULTIPLIED alpha modes together with a matrix, grey outputs, intermediate clamps
  * between the operations a matrix composes, hue as a rotation in HSV (torchvision's; here it is a rotation about the grey axis,
- * as in DALI), contrast about the image's own mean (it needs a reduction over the image first). */
+ * as in DALI), contrast about the image's own mean.  (Operations that reduce over the image first -- autocontrast, equalize --
+ * and the table operations posterize and solarize: debig_png_decode_batch_tensor_tone below.) */
 #define DEBIG_PNG_E_COLOR 17 /* the colour matrix (rules above) */
 typedef struct debig_png_color { double m[12]; } debig_png_color; /* row major: (m00 m01 m02 | m03) (m10 ..) (m20 ..) */
 /* Host only: k[3 c + j] = llround(M[4 c + j] * 65536), o[c] = llround(M[4 c + 3] * Vmax) at precision bits (8 or 16) -> 1, or 0
@@ -598,6 +599,75 @@ int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inputs, const
                                              const debig_png_color *colors, uint32_t *status, debig_png_info *infos /* may be NULL */,
                                              uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
                                              const debig_png_warp_desc *warp_desc);
+
+/* ---- tone curves: autocontrast, equalize, posterize, solarize and caller's tables in the tensor decodes --------------------------
+ * The operation lists of RandAugment, AutoAugment and TrivialAugment are the geometric and colour-matrix operations above plus
+ * four per-channel look-up tables of 256 entries on the 8-bit image; two of them are computed from the image's own histogram.
+ * debig_png_decode_batch_tensor_tone is the tensor call that its optional arguments select --
+ *     warps == NULL, colors == NULL: debig_png_decode_batch_tensor_filter (boxes, alpha, filter as there);
+ *     colors only:                   debig_png_decode_batch_tensor_color  (filter as there; alpha must be NULL);
+ *     warps only:                    debig_png_decode_batch_tensor_warp   (warp_desc as there; alpha and filter must be NULL);
+ *     both:                          debig_png_decode_batch_tensor_warp_color
+ * -- with one tone operation per file, tones[i] = {op, param}:
+ *     DEBIG_PNG_TONE_NONE          param 0          nothing: the file's slot is, bit for bit, what the extended call writes
+ *     DEBIG_PNG_TONE_AUTOCONTRAST  param 0          stretch every colour channel's occupied range to 0 .. 255
+ *     DEBIG_PNG_TONE_EQUALIZE      param 0          equalise every colour channel's histogram
+ *     DEBIG_PNG_TONE_POSTERIZE     bits, 1 .. 8     keep the high `bits` bits
+ *     DEBIG_PNG_TONE_SOLARIZE      threshold, 0 .. 256   invert the samples at or above the threshold
+ *     DEBIG_PNG_TONE_TABLE         index < n_tables the caller's table `tables + 256 * param` (host memory, read before the call
+ *                                                   returns), one table for every colour channel
+ * Any other op or param gives the file DEBIG_PNG_E_TONE; it is decided when IHDR has been read, ranks behind E_BOX, E_WARP and
+ * E_COLOR and, like them, ahead of whatever is found later in the file.
+ * Where it acts: on the 8-bit result of everything the extended call does -- crop, filter or warp, colour matrix, and the
+ * DEBIG_PNG_T_UINT conversion, which gives a sample s in 0 .. 255 per element.  This rounding to 8 bits between the geometric /
+ * colour step and the tone step is on purpose: it is what a Pillow pipeline does and it makes the histograms well defined.  The
+ * table is applied per colour channel; the last channel of RGBA / GRAY_ALPHA tensors is alpha, is not counted in any histogram
+ * and passes through unchanged.  The ONE conversion of debig_png_decode_batch_tensor is then applied to
+ *     v = LUT_c[s] << 22        (the sample times 2^(30 - P) at P = 8):
+ * UINT gives LUT_c[s]; F32 is (float)v * A_c + B_c with a separately rounded multiply and add; F16 / BF16 as there.  A file whose
+ * op is NONE does not go through the 8-bit intermediate at all.
+ * The tables (debig_png_tone_table).  h_c[0 .. 255] is the count of the sample values of colour channel c over ALL out_h x out_w
+ * elements of the file's image, elements that a CONSTANT warp border produced included (counts fit 32 bits: out_w, out_h <= 16384).
+ *   EQUALIZE (Pillow's ImageOps.equalize, exactly): nz = the non-zero bins in order, S = sum(nz) - nz[last], step = S div 255.
+ *       Fewer than 2 non-zero bins, or step == 0: the identity.  Otherwise n_0 = step div 2, n_(i+1) = n_i + h[i],
+ *       lut[i] = min(n_i div step, 255)  (the min is what Pillow's point() does with entries above 255; they occur: a 20 x 20
+ *       noise image has step 1 and entries up to 400).
+ *   AUTOCONTRAST (cutoff 0): lo / hi = the lowest / highest non-empty bin; hi <= lo: the identity.  Otherwise
+ *       lut[i] = 0 for i < lo,  clamp(((i - lo) * 255) div (hi - lo), 0, 255) for i >= lo:
+ *       exact integer arithmetic, so lo -> 0 and hi -> 255 always.  Pillow's ImageOps.autocontrast evaluates
+ *       int(i * (255.0 / (hi - lo)) - lo * (255.0 / (hi - lo))) in doubles, which lands one BELOW at some points where
+ *       (i - lo) * 255 is an exact multiple of hi - lo (lo = 0, hi = 25, i = 25 gives 254): 12,094 of the 8,355,840 entries over all
+ *       (lo, hi, i) differ, every one at such a point and by exactly 1.  That is on purpose: the brightest sample reaches 255.
+ *   POSTERIZE: lut[i] = i & ~(2^(8 - bits) - 1).    SOLARIZE: lut[i] = i < threshold ? i : 255 - i.    TABLE: the caller's bytes.
+ * The device builds the EQUALIZE / AUTOCONTRAST tables from a histogram it takes itself (debig_hip_png_tone_hist_batch, then
+ * debig_hip_png_tone_apply_batch; integer adds, so the histogram is exact whatever the order); they equal debig_png_tone_table's.
+ * Checked first, before any file is looked at (status unwritten): every check of the call that is extended, unchanged and in its
+ * order (see the list above for the arguments that must then be NULL; warp_desc must be given exactly when warps is: all
+ * DEBIG_PNG_BAD_ARG); then DEBIG_PNG_BAD_ARG for tones NULL, a 16-bit out_format, alpha mode PREMULTIPLIED (a tone curve on
+ * premultiplied colour means nothing; OVER and STRAIGHT are fine) and tables NULL with n_tables > 0.  Per image: statuses, their
+ * order, infos and the untouched slot of a failed file are those of the call that is extended, with E_TONE as above.
+ * Not provided: 16-bit tensors, autocontrast's cutoff / ignore / preserve_tone, one caller's table per channel, torchvision's
+ * contrast about the image's mean, tone curves in the decode calls that do not write a tensor. */
+#define DEBIG_PNG_E_TONE 18 /* the tone operation (rules above) */
+#define DEBIG_PNG_TONE_NONE 0u
+#define DEBIG_PNG_TONE_AUTOCONTRAST 1u
+#define DEBIG_PNG_TONE_EQUALIZE 2u
+#define DEBIG_PNG_TONE_POSTERIZE 3u
+#define DEBIG_PNG_TONE_SOLARIZE 4u
+#define DEBIG_PNG_TONE_TABLE 5u
+typedef struct debig_png_tone { uint32_t op; uint32_t param; } debig_png_tone;
+/* Host only: the table of one channel for op / param from its histogram (ignored by POSTERIZE and SOLARIZE; may then be NULL) -> 1,
+ * or 0 (lut unspecified) on the E_TONE conditions above and for NONE and TABLE, which have no table of their own. */
+int debig_png_tone_table(uint32_t op, uint32_t param, const uint32_t hist[256], uint8_t lut[256]);
+int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                       const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps /* may be NULL */,
+                                       const debig_png_color *colors /* may be NULL */, const debig_png_tone *tones,
+                                       const uint8_t *tables /* n_tables x 256 bytes; may be NULL when n_tables == 0 */,
+                                       uint32_t n_tables, uint32_t *status, debig_png_info *infos /* may be NULL */, uint32_t n,
+                                       uint32_t flags, const debig_png_tensor_desc *desc,
+                                       const debig_png_alpha_desc *alpha /* may be NULL */,
+                                       const debig_png_filter_desc *filter /* may be NULL */,
+                                       const debig_png_warp_desc *warp_desc /* exactly when warps is given */);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

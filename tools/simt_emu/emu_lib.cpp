@@ -22,6 +22,7 @@
 #include "../../debigulator_amd/csrc/png_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_label_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_kernel.inc"
+#include "../../debigulator_amd/csrc/png_tone_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -442,5 +443,23 @@ extern "C" int emu_png_warp_color_batch(const void *src_arena, void *out, const 
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_warp_color_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
                       (const uint8_t *)weights, n);
+    return 0;
+}
+
+/* the tone curves of the tensor decode (png_tone_kernel.inc), as debig_hip_png_tone_hist_batch and debig_hip_png_tone_apply_batch
+ * launch them (grid as above) */
+extern "C" int emu_png_tone_hist_batch(const void *src, uint32_t *hist, const debig_png_tone_task *tasks, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_tone_hist_kernel, grid, TONE_THREADS, (const uint8_t *)src, hist, tasks, n);
+    return 0;
+}
+
+extern "C" int emu_png_tone_apply_batch(const void *src, void *out, const debig_png_tone_task *tasks, const uint32_t *hist,
+                                        const void *tables, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_tone_apply_kernel, grid, TONE_THREADS, (const uint8_t *)src, (uint8_t *)out, tasks, hist,
+                      (const uint8_t *)tables, n);
     return 0;
 }
