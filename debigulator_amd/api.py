@@ -212,7 +212,7 @@ def gunzip_batch(datas, out_caps):
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
               8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box", 15: "label",
-              16: "warp", 17: "color", 18: "tone"}
+              16: "warp", 17: "color", 18: "tone", 19: "blur"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -741,9 +741,49 @@ def _png_tones(tone, n):
     return ts, (np.frombuffer(b"".join(tabs), np.uint8).copy() if tabs else None), len(tabs)
 
 
+class PngBlur(C.Structure):  # include/decode_png.h: debig_png_blur
+    _fields_ = [("op", C.c_uint32), ("ksize", C.c_uint32), ("value", C.c_double)]
+
+
+PNG_BLUR_OPS = {"none": 0, "gaussian": 1, "sharpness": 2}  # DEBIG_PNG_BLUR_*
+
+
+def png_blur_weights(ksize, sigma):
+    """the ksize Q14 taps (numpy int16; symmetric, not negative, their sum 16384) of the Gaussian blur with `sigma` --
+    include/decode_png.h: debig_png_blur_weights, the host's own statement of what the device convolves with (no GPU needed).
+    None on the conditions of status 19 ("blur"): ksize even or outside 3 .. 63, sigma not finite, not above 0 or above 1000."""
+    k = int(ksize)
+    if not 0 <= k < 1 << 32:
+        return None
+    L = _png_spec_lib()
+    L.debig_png_blur_weights.restype = C.c_int
+    L.debig_png_blur_weights.argtypes = [C.c_uint32, C.c_double, C.c_void_p]
+    q = np.zeros(63, np.int16)
+    return q[:k].copy() if L.debig_png_blur_weights(k, float(sigma), q.ctypes.data) else None
+
+
+def _png_blurs(blur, n):
+    """blur: a sequence of n entries, each None, ("gaussian", ksize, sigma) or ("sharpness", factor) -> (PngBlur * n)"""
+    if len(blur) != n:
+        raise ValueError(f"blur must have one entry per file ({n}), not {len(blur)}")
+    bs = (PngBlur * n)()
+    for i, e in enumerate(blur):
+        if e is None:
+            continue
+        ok = isinstance(e, (tuple, list)) and len(e) >= 1 and ((e[0] == "gaussian" and len(e) == 3) or (e[0] == "sharpness" and len(e) == 2))
+        if not ok:
+            raise ValueError(f"blur[{i}]: None, ('gaussian', ksize, sigma) or ('sharpness', factor), not {e!r}")
+        bs[i].op = PNG_BLUR_OPS[e[0]]
+        if e[0] == "gaussian":
+            k = int(e[1])
+            bs[i].ksize = k if 0 <= k < 1 << 32 and k == e[1] else 0  # (out of range either way: status 19)
+        bs[i].value = float(e[-1])
+    return bs
+
+
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
                             antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
-                            background=None, warp=None, border="constant", border_value=None, color=None, tone=None,
+                            background=None, warp=None, border="constant", border_value=None, color=None, tone=None, blur=None,
                             filter="bilinear"):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
@@ -783,7 +823,15 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     ImageOps.equalize exactly, autocontrast with cutoff 0 in exact integers, posterize, solarize, or the caller's --, then
     through the conversion with mean / std.  The histograms of "autocontrast" and "equalize" are taken on the device.  A file
     whose entry is None gets, bit for bit, what the call without `tone` gives it.  It goes with depth 8 and alpha "straight" or
-    "over"; bits or a threshold out of range: status 18 ("tone").  (By name, like `color`.)"""
+    "over"; bits or a threshold out of range: status 18 ("tone").  (By name, like `color`.)
+    blur: None (everything above, unchanged), or one entry per file: None, ("gaussian", ksize, sigma) -- ksize odd, 3 .. 63,
+    0 < sigma <= 1000: torchvision's GaussianBlur with reflected borders, on every channel, alpha included -- or
+    ("sharpness", factor) -- |factor| <= 16: Pillow's ImageEnhance.Sharpness, the blend of the colour channels with their 3 x 3
+    SMOOTH; 1 is the identity, 0 is SMOOTH -- debig_png_decode_batch_tensor_blur: the file's image goes through everything above,
+    `tone` included, to 8-bit samples, then through the filter in integers (Q14 taps, see png_blur_weights), then ONCE through the
+    conversion with mean / std, so float outputs keep the precision below an 8-bit step.  A file whose entry is None gets, bit
+    for bit, what the call without `blur` gives it.  It goes with depth 8 and alpha "straight" or "over"; a bad ksize, sigma or
+    factor: status 19 ("blur").  (By name, like `tone`.)"""
     import torch
 
     if tone is not None:
@@ -791,6 +839,11 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
             raise ValueError("tone needs depth 8")
         if alpha == "premultiplied":
             raise ValueError("tone goes with alpha 'straight' or 'over', not 'premultiplied'")
+    if blur is not None:
+        if depth != 8:
+            raise ValueError("blur needs depth 8")
+        if alpha == "premultiplied":
+            raise ValueError("blur goes with alpha 'straight' or 'over', not 'premultiplied'")
 
     if color is not None:
         if filter == "bicubic":
@@ -827,7 +880,20 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
     out = _png_dense_out(shape, tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if tone is not None:
+    if blur is not None:
+        bs = _png_blurs(blur, n)
+        ts, tabs, n_tabs = _png_tones(tone, n) if tone is not None else (None, None, 0)
+        L.debig_png_decode_batch_tensor_blur.restype = C.c_int
+        L.debig_png_decode_batch_tensor_blur.argtypes = [C.c_void_p] * 8 + [C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + \
+            [C.c_void_p] * 4
+        plain = wd is None and cs is None
+        rc = L.debig_png_decode_batch_tensor_blur(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, cs, ts,
+                                                  tabs.ctypes.data if tabs is not None else None, n_tabs, bs, status, infos, n,
+                                                  PNG_FORCE_GENERAL if force_general else 0, C.byref(d),
+                                                  C.byref(ad) if plain and ad is not None else None,
+                                                  C.byref(fd) if wd is None and fd is not None else None,
+                                                  C.byref(wd) if wd is not None else None)
+    elif tone is not None:
         ts, tabs, n_tabs = _png_tones(tone, n)
         L.debig_png_decode_batch_tensor_tone.restype = C.c_int
         L.debig_png_decode_batch_tensor_tone.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + \

@@ -22,6 +22,7 @@
 #include "png_color_label_warp_kernel.inc"
 #include "png_color_kernel.inc"
 #include "png_tone_kernel.inc"
+#include "png_blur_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -905,6 +906,18 @@ int debig_hip_png_tone_apply_batch(const void *d_src, void *d_out, const debig_p
     const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
     hipLaunchKernelGGL(debig_png_tone_apply_kernel, dim3(grid), dim3(TONE_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks, d_hist, (const uint8_t *)d_tables, n_tasks);
+    return (int)hipGetLastError();
+}
+
+// Gaussian blur and sharpness of the tensor decode (png_blur_kernel.inc): one workgroup per output tile, as many workgroups as tasks
+int debig_hip_png_blur_batch(const void *d_src, void *d_out, const debig_png_blur_task *d_tasks, const void *d_tables,
+                             uint32_t n_tasks, void *hip_stream)
+{
+    if (n_tasks == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    hipLaunchKernelGGL(debig_png_blur_kernel, dim3(grid), dim3(BLUR_THREADS), 0, (hipStream_t)hip_stream,
+                       (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, n_tasks);
     return (int)hipGetLastError();
 }
 

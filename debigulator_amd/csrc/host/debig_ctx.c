@@ -55,6 +55,7 @@ void debig_ctx_release_ptr(debig_ctx *c)
     buf_free(&c->tone_px);
     buf_free(&c->tone_tasks);
     buf_free(&c->tone_hist);
+    buf_free(&c->blur_tasks);
     buf_free(&c->ws);
     buf_free(&c->dense);
     buf_free(&c->dense_list);

@@ -15,6 +15,7 @@
  * kernel (debig_hip_png_spec_defilter_batch: every colour type, depth, Adam7 pass, tRNS) for the rest of RGBA8, and
  * its output-format twin (debig_hip_png_spec_defilter_fmt_batch) for every image whose resolved format is not RGBA8.
  */
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "decode_png.h"
@@ -869,6 +870,7 @@ typedef struct stage_rule {
     const uint8_t *warp_bad; /* != NULL: file i with warp_bad[i] != 0 is E_WARP (the warp calls) */
     const uint8_t *color_bad; /* != NULL: file i with color_bad[i] != 0 is E_COLOR (the colour-matrix calls) */
     const uint8_t *tone_bad; /* != NULL: file i with tone_bad[i] != 0 is E_TONE (the tone call) */
+    const uint8_t *blur_bad; /* != NULL: file i with blur_bad[i] != 0 is E_BLUR (the blur call) */
 } stage_rule;
 
 /* per file: the status decided from IHDR (0: none), the image's place and size in the arena, the resolved box, the walk's info */
@@ -888,7 +890,7 @@ static void stage_free(stage *S)
     free(S->inf);
 }
 
-/* IHDR -> E_LABEL, then E_BOX, then E_WARP, then E_COLOR, then E_TONE, then the walk's own error, then the size cap; the decode of what is left into the arena.
+/* IHDR -> E_LABEL, then E_BOX, then E_WARP, then E_COLOR, then E_TONE, then E_BLUR, then the walk's own error, then the size cap; the decode of what is left into the arena.
  * -> 0 (status and infos written; S filled, the caller's to stage_free either way) or the call's return value */
 static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inputs, const uint64_t *input_sizes,
                         const debig_png_box *boxes, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags)
@@ -930,6 +932,10 @@ static int stage_decode(stage *S, const stage_rule *R, const uint8_t *const *inp
         }
         if (R->tone_bad && R->tone_bad[i]) {
             S->pre[i] = DEBIG_PNG_E_TONE;
+            continue;
+        }
+        if (R->blur_bad && R->blur_bad[i]) {
+            S->pre[i] = DEBIG_PNG_E_BLUR;
             continue;
         }
         S->box[i] = b;
@@ -1077,18 +1083,63 @@ DEBIG_API int debig_png_tone_table(uint32_t op, uint32_t param, const uint32_t h
     return 1;
 }
 
-/* what the tone call adds to a tensor core: per file its E_TONE flag and, once the statuses are known, the place of a decoded
- * file whose op is not NONE among the 8-bit intermediates (UINT32_MAX: none) */
+/* ---- Gaussian blur and sharpness of the tensor decode (decode_png.h: debig_png_decode_batch_tensor_blur) ---------------------- */
+
+_Static_assert(sizeof(debig_png_blur_task) == 104, "debig_png_blur_task: 104 bytes, no padding");
+
+/* the E_BLUR rule of one file */
+static int blur_param_ok(const debig_png_blur *b)
+{
+    uint64_t u;
+    memcpy(&u, &b->value, 8);
+    const int finite = (u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; /* neither infinity nor NaN */
+    switch (b->op) {
+    case DEBIG_PNG_BLUR_NONE: return 1;
+    case DEBIG_PNG_BLUR_GAUSSIAN:
+        return (b->ksize & 1u) && b->ksize >= 3u && b->ksize <= 63u && finite && b->value > 0.0 && b->value <= 1000.0;
+    case DEBIG_PNG_BLUR_SHARPNESS: return finite && b->value >= -16.0 && b->value <= 16.0;
+    default: return 0;
+    }
+}
+
+DEBIG_API int debig_png_blur_weights(uint32_t ksize, double sigma, int16_t q[63])
+{
+    const debig_png_blur b = {DEBIG_PNG_BLUR_GAUSSIAN, ksize, sigma};
+    if (!blur_param_ok(&b)) return 0;
+    const int32_t r = (int32_t)(ksize / 2u);
+    double w[63], sum = 0.0;
+    for (int32_t j = -r; j <= r; j++) {
+        const double t = (double)j / sigma;
+        sum += w[j + r] = exp(-0.5 * (t * t));
+    }
+    int32_t total = 0;
+    memset(q, 0, 63 * sizeof(int16_t));
+    for (uint32_t j = 0; j < ksize; j++) {
+        q[j] = (int16_t)(w[j] / sum * 16384.0 + 0.5); /* (non-negative: the cast is the floor) */
+        total += q[j];
+    }
+    q[r] = (int16_t)(q[r] + (16384 - total)); /* (the deficit is below 32 in magnitude, the centre weight is at least 16384 / 63) */
+    return 1;
+}
+
+/* what the tone and blur calls add to a tensor core: per file its E_TONE and E_BLUR flags and, once the statuses are known, the
+ * place of a decoded file that has a tone or a blur operation among the 8-bit intermediates (UINT32_MAX: none), and the place
+ * of a file that has both among the second intermediates, which lie behind the first in the same arena */
+#define POST_TONE_REC 256u /* a file's bytes among the uploaded tables: its tone table ...                                    */
+#define POST_BLUR_REC 384u /* ... and, in the blur call, its 63 int16 weights and a zero behind it                            */
 typedef struct tone_plan {
-    const debig_png_tone *tones;
+    const debig_png_tone *tones; /* NULL (the blur call only): no file has a tone operation */
     const uint8_t *tables;
     uint32_t n_tables;
+    const debig_png_blur *blurs; /* NULL: the tone call */
     uint32_t oc;         /* the channels of the tensor */
-    uint8_t *bad;
-    uint32_t *place;
-    uint8_t *lut;        /* 16 bytes of slack, then 256 bytes per tone file: the fixed and the caller's tables */
+    uint8_t *bad, *blur_bad;
+    uint32_t *place, *place2;
+    uint8_t *lut;        /* 16 bytes of slack, then rec bytes per placed file */
+    uint32_t rec;
     debig_png_tone_task *tasks;
-    uint32_t n_tone;
+    debig_png_blur_task *btasks;
+    uint32_t n_tone, n_both;
     uint64_t img;        /* bytes of one intermediate, a multiple of 16 */
 } tone_plan;
 
@@ -1096,85 +1147,192 @@ static void tone_free(tone_plan *tp)
 {
     if (!tp) return;
     free(tp->bad);
+    free(tp->blur_bad);
     free(tp->place);
+    free(tp->place2);
     free(tp->lut);
     free(tp->tasks);
+    free(tp->btasks);
 }
 
-/* the E_TONE flags; -> 0 or 2 */
+static uint32_t tone_op(const tone_plan *tp, uint32_t i) { return tp->tones ? tp->tones[i].op : DEBIG_PNG_TONE_NONE; }
+static uint32_t blur_op(const tone_plan *tp, uint32_t i) { return tp->blurs ? tp->blurs[i].op : DEBIG_PNG_BLUR_NONE; }
+
+/* the E_TONE and E_BLUR flags; -> 0 or 2 */
 static int tone_prepare(tone_plan *tp, uint32_t n)
 {
     if (!tp) return 0;
     tp->bad = (uint8_t *)calloc(n, 1);
+    tp->blur_bad = tp->blurs ? (uint8_t *)calloc(n, 1) : NULL;
     tp->place = (uint32_t *)malloc((size_t)n * sizeof(uint32_t));
-    if (!tp->bad || !tp->place) return 2;
+    tp->place2 = (uint32_t *)malloc((size_t)n * sizeof(uint32_t));
+    if (!tp->bad || !tp->place || !tp->place2 || (tp->blurs && !tp->blur_bad)) return 2;
     for (uint32_t i = 0; i < n; i++) {
-        tp->bad[i] = !tone_param_ok(tp->tones[i].op, tp->tones[i].param, tp->n_tables);
-        tp->place[i] = UINT32_MAX;
+        if (tp->tones) tp->bad[i] = !tone_param_ok(tp->tones[i].op, tp->tones[i].param, tp->n_tables);
+        if (tp->blurs) tp->blur_bad[i] = !blur_param_ok(&tp->blurs[i]);
+        tp->place[i] = tp->place2[i] = UINT32_MAX;
     }
     return 0;
 }
 
-/* after the decode: the places of the tone files, and room for their tables; -> 0 or 2 */
+/* after the decode: the places of the files with an operation, and room for their tables; -> 0 or 2 */
 static int tone_place(tone_plan *tp, const uint32_t *status, uint32_t n, uint32_t W, uint32_t H)
 {
     if (!tp) return 0;
     tp->img = debig_align16((uint64_t)W * H * tp->oc);
-    for (uint32_t i = 0; i < n; i++)
-        if (status[i] == DEBIG_PNG_OK && tp->tones[i].op != DEBIG_PNG_TONE_NONE) tp->place[i] = tp->n_tone++;
-    tp->lut = (uint8_t *)calloc((size_t)tp->n_tone * 256u + 16u, 1);
+    tp->rec = tp->blurs ? POST_BLUR_REC : POST_TONE_REC;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status[i] != DEBIG_PNG_OK) continue;
+        const int t = tone_op(tp, i) != DEBIG_PNG_TONE_NONE, b = blur_op(tp, i) != DEBIG_PNG_BLUR_NONE;
+        if (t || b) tp->place[i] = tp->n_tone++;
+        if (t && b) tp->place2[i] = tp->n_both++;
+    }
+    tp->lut = (uint8_t *)calloc((size_t)tp->n_tone * tp->rec + 16u, 1);
     return tp->lut ? 0 : 2;
 }
 
 static int tone_is(const tone_plan *tp, uint32_t i) { return tp && tp->place[i] != UINT32_MAX; }
+static uint64_t tone_table_bytes(const tone_plan *tp) { return tp ? (uint64_t)tp->n_tone * tp->rec + 16u : 0; }
+static uint64_t tone_arena_bytes(const tone_plan *tp) { return ((uint64_t)tp->n_tone + tp->n_both) * tp->img; }
 
-/* the tables at their place: the table lands at table_off in the weights buffer, its first 256 bytes at the next multiple of
+/* the tables at their place: the table lands at table_off in the weights buffer, its first record at the next multiple of
  * 16 -> that offset */
 static uint64_t tone_fill(tone_plan *tp, uint32_t n, uint64_t table_off)
 {
     const uint64_t pad = (16u - (table_off & 15u)) & 15u;
     for (uint32_t i = 0; i < n; i++) {
         if (tp->place[i] == UINT32_MAX) continue;
-        uint8_t *l = tp->lut + pad + (size_t)tp->place[i] * 256u;
-        const debig_png_tone o = tp->tones[i];
-        if (o.op == DEBIG_PNG_TONE_TABLE) memcpy(l, tp->tables + (size_t)o.param * 256u, 256);
-        else if (o.op == DEBIG_PNG_TONE_POSTERIZE || o.op == DEBIG_PNG_TONE_SOLARIZE) (void)debig_png_tone_table(o.op, o.param, NULL, l);
+        uint8_t *l = tp->lut + pad + (size_t)tp->place[i] * tp->rec;
+        if (tp->tones) {
+            const debig_png_tone o = tp->tones[i];
+            if (o.op == DEBIG_PNG_TONE_TABLE) memcpy(l, tp->tables + (size_t)o.param * 256u, 256);
+            else if (o.op == DEBIG_PNG_TONE_POSTERIZE || o.op == DEBIG_PNG_TONE_SOLARIZE) (void)debig_png_tone_table(o.op, o.param, NULL, l);
+        }
+        if (blur_op(tp, i) == DEBIG_PNG_BLUR_GAUSSIAN) {
+            int16_t q[64] = {0};
+            (void)debig_png_blur_weights(tp->blurs[i].ksize, tp->blurs[i].value, q);
+            memcpy(l + POST_TONE_REC, q, sizeof q);
+        }
     }
     return table_off + pad;
 }
 
-/* the first stage has been launched: the pixel runs of every tone file (those with a histogram first), the cleared histograms,
- * the histogram kernel over the first and the apply kernel over all of them, on the same stream.  lut_off: where tone_fill put
- * the tables in c->rsz_weights.  -> 0 or the call's return value */
+/* the first stage has been launched: the pixel runs of every file with a tone operation -- first those whose result is the
+ * caller's, then those that a blur follows, which write UINT8 HWC into the second intermediates; in either group those with a
+ * histogram first --, the cleared histograms, the histogram kernel over the front of either group and the apply kernel over
+ * either group, on the same stream.  lut_off: where tone_fill put the tables in c->rsz_weights.  -> 0 or the call's return value */
 static int tone_run(tone_plan *tp, debig_ctx *c, void *d_out, uint32_t n, const debig_png_tensor_desc *desc, uint64_t lut_off)
 {
-    if (!tp || tp->n_tone == 0) return 0;
+    if (!tp || !tp->tones || tp->n_tone == 0) return 0;
     const uint32_t W = desc->out_w, H = desc->out_h, oc = tp->oc, cc = oc & 1u ? oc : oc - 1u, px = W * H;
     const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? 1u : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
     const uint64_t slot = (uint64_t)px * oc * es;
-    const uint64_t per = (px + DEBIG_PNG_TONE_RUN - 1u) / DEBIG_PNG_TONE_RUN, n_tasks = per * tp->n_tone;
+    uint64_t n_files = 0;
+    for (uint32_t i = 0; i < n; i++) n_files += tp->place[i] != UINT32_MAX && tone_op(tp, i) != DEBIG_PNG_TONE_NONE;
+    const uint64_t per = (px + DEBIG_PNG_TONE_RUN - 1u) / DEBIG_PNG_TONE_RUN, n_tasks = per * n_files;
+    if (n_tasks == 0) return 0;
     if (n_tasks > 0x7fffffffu) return 2;
     tp->tasks = (debig_png_tone_task *)calloc((size_t)n_tasks, sizeof(debig_png_tone_task));
     if (!tp->tasks) return 2;
-    uint64_t at = 0, n_hist_tasks = 0;
+    uint64_t at = 0, first[2] = {0, 0}, cnt[2] = {0, 0}, n_hist_tasks[2] = {0, 0};
     uint32_t n_hist = 0;
-    for (uint32_t pass = 0; pass < 2; pass++) {
+    for (uint32_t part = 0; part < 2; part++) {
+        first[part] = at;
+        for (uint32_t pass = 0; pass < 2; pass++) {
+            for (uint32_t i = 0; i < n; i++) {
+                const uint32_t op = tone_op(tp, i);
+                if (tp->place[i] == UINT32_MAX || op == DEBIG_PNG_TONE_NONE || (tp->place2[i] != UINT32_MAX) != part) continue;
+                const uint32_t hist = op == DEBIG_PNG_TONE_AUTOCONTRAST || op == DEBIG_PNG_TONE_EQUALIZE;
+                if (hist == pass) continue;
+                const int chw = !part && desc->out_layout == DEBIG_PNG_LAYOUT_CHW;
+                debig_png_tone_task p;
+                memset(&p, 0, sizeof p);
+                p.src_off = (uint64_t)tp->place[i] * tp->img;
+                p.out_off = part ? ((uint64_t)tp->n_tone + tp->place2[i]) * tp->img : (uint64_t)i * slot;
+                p.hist_off = hist ? (uint64_t)n_hist++ * cc * 1024u : 0;
+                p.lut_off = lut_off + (uint64_t)tp->place[i] * tp->rec;
+                p.out_w = W;
+                p.out_h = H;
+                p.out_sx = chw ? 1u : oc;
+                p.out_sy = chw ? W : W * oc;
+                p.out_sc = chw ? H * W : 1u;
+                p.channels = (uint8_t)oc;
+                p.colour_channels = (uint8_t)cc;
+                p.dtype = (uint8_t)(part ? DEBIG_PNG_T_UINT : desc->dtype);
+                p.op = (uint8_t)op;
+                for (uint32_t k = 0; k < 4; k++) {
+                    p.a[k] = (float)((double)desc->scale[k] / (255.0 * (double)(1u << 22)));
+                    p.b[k] = desc->bias[k];
+                }
+                for (uint32_t p0 = 0; p0 < px; p0 += DEBIG_PNG_TONE_RUN) {
+                    p.pix0 = p0;
+                    p.pix_n = px - p0 < DEBIG_PNG_TONE_RUN ? px - p0 : DEBIG_PNG_TONE_RUN;
+                    tp->tasks[at++] = p;
+                }
+            }
+            if (pass == 0) n_hist_tasks[part] = at - first[part];
+        }
+        cnt[part] = at - first[part];
+    }
+    int rc;
+    if ((rc = debig_devbuf_reserve(&c->tone_tasks, n_tasks * sizeof(debig_png_tone_task))) ||
+        (rc = debig_devbuf_reserve(&c->tone_hist, (uint64_t)n_hist * cc * 1024u + 16u)) ||
+        (rc = debig_hip_memcpy_h2d(c->tone_tasks.ptr, tp->tasks, n_tasks * sizeof(debig_png_tone_task), NULL)) ||
+        (n_hist && (rc = debig_hip_memset(c->tone_hist.ptr, 0, (uint64_t)n_hist * cc * 1024u, NULL))))
+        return rc;
+    const debig_png_tone_task *d_tasks = (const debig_png_tone_task *)c->tone_tasks.ptr;
+    for (uint32_t part = 0; part < 2; part++)
+        if (n_hist_tasks[part] &&
+            (rc = debig_hip_png_tone_hist_batch(c->tone_px.ptr, (uint32_t *)c->tone_hist.ptr, d_tasks + first[part],
+                                                (uint32_t)n_hist_tasks[part], NULL)))
+            return rc;
+    for (uint32_t part = 0; part < 2; part++) /* (the tone call has no second part: its launches are what they were) */
+        if (cnt[part] &&
+            (rc = debig_hip_png_tone_apply_batch(c->tone_px.ptr, part ? c->tone_px.ptr : d_out, d_tasks + first[part],
+                                                 (const uint32_t *)c->tone_hist.ptr, c->rsz_weights.ptr, (uint32_t)cnt[part], NULL)))
+            return rc;
+    return 0;
+}
+
+/* behind tone_run: the tiles of every file with a blur operation, from its first intermediate or, where a tone operation came
+ * in between, from its second, through the blur kernel into the caller's tensor, on the same stream.  -> 0 or the call's return
+ * value */
+static int blur_run(tone_plan *tp, debig_ctx *c, void *d_out, uint32_t n, const debig_png_tensor_desc *desc, uint64_t lut_off)
+{
+    if (!tp || !tp->blurs || tp->n_tone == 0) return 0;
+    const uint32_t W = desc->out_w, H = desc->out_h, oc = tp->oc, cc = oc & 1u ? oc : oc - 1u;
+    const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? 1u : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
+    const uint64_t slot = (uint64_t)W * H * oc * es;
+    uint64_t n_tasks = 0, at = 0;
+    for (uint32_t fill = 0; fill < 2; fill++) { /* count, then write */
+        if (fill) {
+            if (n_tasks == 0) return 0;
+            if (n_tasks > 0x7fffffffu) return 2;
+            tp->btasks = (debig_png_blur_task *)calloc((size_t)n_tasks, sizeof(debig_png_blur_task));
+            if (!tp->btasks) return 2;
+        }
         for (uint32_t i = 0; i < n; i++) {
-            if (tp->place[i] == UINT32_MAX) continue;
-            const uint32_t op = tp->tones[i].op;
-            const uint32_t hist = op == DEBIG_PNG_TONE_AUTOCONTRAST || op == DEBIG_PNG_TONE_EQUALIZE;
-            if (hist == pass) continue;
-            debig_png_tone_task p;
+            const uint32_t op = blur_op(tp, i);
+            if (tp->place[i] == UINT32_MAX || op == DEBIG_PNG_BLUR_NONE) continue;
+            const uint32_t r = op == DEBIG_PNG_BLUR_GAUSSIAN ? tp->blurs[i].ksize / 2u : 1u;
+            const uint32_t tw = DEBIG_PNG_BLUR_TILE, th = DEBIG_PNG_BLUR_TILE; /* (fits the two LDS caps at every radius) */
+            if (!fill) {
+                n_tasks += (uint64_t)((W + tw - 1u) / tw) * ((H + th - 1u) / th);
+                continue;
+            }
+            const int chw = desc->out_layout == DEBIG_PNG_LAYOUT_CHW;
+            debig_png_blur_task p;
             memset(&p, 0, sizeof p);
-            p.src_off = (uint64_t)tp->place[i] * tp->img;
+            p.src_off = (tp->place2[i] != UINT32_MAX ? (uint64_t)tp->n_tone + tp->place2[i] : (uint64_t)tp->place[i]) * tp->img;
             p.out_off = (uint64_t)i * slot;
-            p.hist_off = hist ? (uint64_t)n_hist++ * cc * 1024u : 0;
-            p.lut_off = lut_off + (uint64_t)tp->place[i] * 256u;
-            p.out_w = W;
-            p.out_h = H;
-            p.out_sx = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? 1u : oc;
-            p.out_sy = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? W : W * oc;
-            p.out_sc = desc->out_layout == DEBIG_PNG_LAYOUT_CHW ? H * W : 1u;
+            p.table_off = lut_off + (uint64_t)tp->place[i] * tp->rec + POST_TONE_REC;
+            p.k = op == DEBIG_PNG_BLUR_SHARPNESS ? (int32_t)color_llround(tp->blurs[i].value * 65536.0) : 0; /* (exact product) */
+            p.radius = r;
+            p.w = W;
+            p.h = H;
+            p.out_sx = chw ? 1u : oc;
+            p.out_sy = chw ? W : W * oc;
+            p.out_sc = chw ? H * W : 1u;
             p.channels = (uint8_t)oc;
             p.colour_channels = (uint8_t)cc;
             p.dtype = (uint8_t)desc->dtype;
@@ -1183,24 +1341,23 @@ static int tone_run(tone_plan *tp, debig_ctx *c, void *d_out, uint32_t n, const 
                 p.a[k] = (float)((double)desc->scale[k] / (255.0 * (double)(1u << 22)));
                 p.b[k] = desc->bias[k];
             }
-            for (uint32_t p0 = 0; p0 < px; p0 += DEBIG_PNG_TONE_RUN) {
-                p.pix0 = p0;
-                p.pix_n = px - p0 < DEBIG_PNG_TONE_RUN ? px - p0 : DEBIG_PNG_TONE_RUN;
-                tp->tasks[at++] = p;
+            for (uint32_t y0 = 0; y0 < H; y0 += th) {
+                for (uint32_t x0 = 0; x0 < W; x0 += tw) {
+                    p.x0 = x0;
+                    p.y0 = y0;
+                    p.tile_w = W - x0 < tw ? W - x0 : tw;
+                    p.tile_h = H - y0 < th ? H - y0 : th;
+                    tp->btasks[at++] = p;
+                }
             }
         }
-        if (pass == 0) n_hist_tasks = at;
     }
     int rc;
-    if ((rc = debig_devbuf_reserve(&c->tone_tasks, n_tasks * sizeof(debig_png_tone_task))) ||
-        (rc = debig_devbuf_reserve(&c->tone_hist, (uint64_t)n_hist * cc * 1024u + 16u)) ||
-        (rc = debig_hip_memcpy_h2d(c->tone_tasks.ptr, tp->tasks, n_tasks * sizeof(debig_png_tone_task), NULL)) ||
-        (n_hist && (rc = debig_hip_memset(c->tone_hist.ptr, 0, (uint64_t)n_hist * cc * 1024u, NULL))) ||
-        (rc = debig_hip_png_tone_hist_batch(c->tone_px.ptr, (uint32_t *)c->tone_hist.ptr, (const debig_png_tone_task *)c->tone_tasks.ptr,
-                                            (uint32_t)n_hist_tasks, NULL)))
+    if ((rc = debig_devbuf_reserve(&c->blur_tasks, n_tasks * sizeof(debig_png_blur_task))) ||
+        (rc = debig_hip_memcpy_h2d(c->blur_tasks.ptr, tp->btasks, n_tasks * sizeof(debig_png_blur_task), NULL)))
         return rc;
-    return debig_hip_png_tone_apply_batch(c->tone_px.ptr, d_out, (const debig_png_tone_task *)c->tone_tasks.ptr,
-                                          (const uint32_t *)c->tone_hist.ptr, c->rsz_weights.ptr, (uint32_t)n_tasks, NULL);
+    return debig_hip_png_blur_batch(c->tone_px.ptr, d_out, (const debig_png_blur_task *)c->blur_tasks.ptr, c->rsz_weights.ptr,
+                                    (uint32_t)n_tasks, NULL);
 }
 
 /* debig_png_decode_batch_tensor (amode == DEBIG_PNG_ALPHA_STRAIGHT: bg unused), debig_png_decode_batch_tensor_alpha and
@@ -1209,9 +1366,9 @@ static int tone_run(tone_plan *tp, debig_ctx *c, void *d_out, uint32_t n, const 
  * weight rule and the E_BOX scale; BICUBIC tiles, of every alpha mode, go to the signed kernel (debig_hip_png_resize_cubic_batch),
  * NEAREST ones to the kernels of BILINEAR.  colors != NULL (debig_png_decode_batch_tensor_color: STRAIGHT, not BICUBIC, 3 or 4
  * channels): the tiles carry the offset of their image's record, which travels as a third table, and go to the colour kernel.
- * tp != NULL (debig_png_decode_batch_tensor_tone): the tiles of a file with a tone operation are UINT8 HWC tiles into the
- * context's tone arena; they come behind all others, and the kernel is launched once per target over its range of the one task
- * array; tone_run does the rest. */
+ * tp != NULL (debig_png_decode_batch_tensor_tone, debig_png_decode_batch_tensor_blur): the tiles of a file with a tone or a blur
+ * operation are UINT8 HWC tiles into the context's tone arena; they come behind all others, and the kernel is launched once per
+ * target over its range of the one task array; tone_run and blur_run do the rest. */
 /* one range of the uploaded tiles through the kernel of the call */
 static int tensor_launch(const debig_ctx *c, void *out, const uint8_t *d_tasks, uint64_t cnt, int colors, uint32_t filter, int plain)
 {
@@ -1253,7 +1410,7 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     int rc;
     if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
     if ((rc = tone_prepare(tp, n))) goto done;
-    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H, NULL, cbad, tp ? tp->bad : NULL};
+    const stage_rule rule = {fmt, 0, 0, 0, aa_box ? max_scale * W : 0, max_scale * H, NULL, cbad, tp ? tp->bad : NULL, tp ? tp->blur_bad : NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if ((rc = tone_place(tp, status, n, W, H))) goto done;
     /* ---- the axis tables of every decoded image, then their places behind one another */
@@ -1261,7 +1418,7 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     for (uint32_t i = 0; i < n; i++)
         if (status[i] == DEBIG_PNG_OK && (rsz_axis_get(&TX, S.box[i].w) < 0 || rsz_axis_get(&TY, S.box[i].h) < 0)) goto done;
     dev_table tab[4] = {{TX.buf, TX.len, 0}, {TY.buf, TY.len, 0}, {crec, colors ? (uint64_t)n * sizeof *crec : 0, 0},
-                        {tp ? tp->lut : NULL, tp ? (uint64_t)tp->n_tone * 256u + 16u : 0, 0}};
+                        {tp ? tp->lut : NULL, tone_table_bytes(tp), 0}};
     const uint32_t n_tab = tp ? 4u : colors ? 3u : 2u;
     dev_tables_place(tab, n_tab); /* (the axis tables are multiples of 8 bytes long: the records are 8-byte aligned) */
     const uint64_t lut_off = tp ? tone_fill(tp, n, tab[3].off) : 0;
@@ -1344,11 +1501,11 @@ static int tensor_core(const uint8_t *const *inputs, const uint64_t *input_sizes
     debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
     if (!c) goto done;
     const uint8_t *d_tasks = (const uint8_t *)c->rsz_tasks.ptr;
-    if (n_tasks > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, (uint64_t)tp->n_tone * tp->img))) goto done;
+    if (n_tasks > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, tone_arena_bytes(tp)))) goto done;
     if ((n_direct && (rc = tensor_launch(c, d_out, d_tasks, n_direct, colors != NULL, filter, plain))) ||
         (n_tasks > n_direct &&
          (rc = tensor_launch(c, c->tone_px.ptr, d_tasks + n_direct * elem, n_tasks - n_direct, colors != NULL, filter, plain))) ||
-        (rc = tone_run(tp, c, d_out, n, desc, lut_off)))
+        (rc = tone_run(tp, c, d_out, n, desc, lut_off)) || (rc = blur_run(tp, c, d_out, n, desc, lut_off)))
         goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
@@ -1558,7 +1715,7 @@ DEBIG_API int debig_png_decode_batch_labels(const uint8_t *const *inputs, const 
     if (bad) return bad;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, NULL, NULL, NULL};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, NULL, NULL, NULL, NULL};
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     dev_table tab[3] = {{desc->lut, 1024, 0}, {NULL, 0, 0}, {NULL, 0, 0}}; /* the LUT (or its room), the X tables, the Y tables */
@@ -1696,7 +1853,7 @@ DEBIG_API int debig_png_decode_batch_color_labels(const uint8_t *const *inputs, 
     if ((rc = clbl_args_check(d_out, desc, n, &M))) goto done;
     const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, NULL, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
     J.W = J.TX.L = W;
     J.H = J.TY.L = H;
     tab[0].src = M.tab;
@@ -1804,8 +1961,9 @@ static int tensor_warp_check(const void *d_out, const debig_png_warp *warps, con
 
 /* debig_png_decode_batch_tensor_warp (colors == NULL) and debig_png_decode_batch_tensor_warp_color behind their argument checks.
  * With colors the tasks are debig_png_warp_color_task -- the warp task and the place of the image's record, which travels as the
- * launch's one table -- and go to the colour kernel.  tp != NULL (debig_png_decode_batch_tensor_tone): as in tensor_core, the
- * tasks of the tone files come last, write UINT8 HWC into the tone arena through a launch of their own, and tone_run follows. */
+ * launch's one table -- and go to the colour kernel.  tp != NULL (debig_png_decode_batch_tensor_tone, _blur): as in tensor_core, the
+ * tasks of the tone and blur files come last, write UINT8 HWC into the tone arena through a launch of their own, and tone_run and
+ * blur_run follow. */
 static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
                             const debig_png_warp *warps, const debig_png_color *colors, uint32_t *status, debig_png_info *infos,
                             uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd,
@@ -1828,12 +1986,12 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
     if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
     if ((rc = tone_prepare(tp, n))) goto done;
-    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad, tp ? tp->bad : NULL}; /* no crop-size cap */
+    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad, tp ? tp->bad : NULL, tp ? tp->blur_bad : NULL}; /* no crop-size cap */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if ((rc = tone_place(tp, status, n, W, H))) goto done;
     /* the plain warp has no tables (the six int64 travel in the task); with colours the records are the first table, at offset 0;
      * the tone call's tables follow */
-    dev_table tab[2] = {{crec, colors ? (uint64_t)n * sizeof *crec : 0, 0}, {tp ? tp->lut : NULL, tp ? (uint64_t)tp->n_tone * 256u + 16u : 0, 0}};
+    dev_table tab[2] = {{crec, colors ? (uint64_t)n * sizeof *crec : 0, 0}, {tp ? tp->lut : NULL, tone_table_bytes(tp), 0}};
     const uint32_t n_tab = tp ? 2u : 1u;
     dev_tables_place(tab, n_tab);
     const uint64_t lut_off = tp ? tone_fill(tp, n, tab[1].off) : 0;
@@ -1886,7 +2044,7 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     if (n_tasks == 0) goto done;
     debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
     if (!c) goto done;
-    if (n_tasks > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, (uint64_t)tp->n_tone * tp->img))) goto done;
+    if (n_tasks > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, tone_arena_bytes(tp)))) goto done;
     for (uint32_t part = 0; part < 2; part++) { /* the caller's tensor, then the tone arena */
         const uint8_t *d_tasks = (const uint8_t *)c->rsz_tasks.ptr + (part ? n_direct * elem : 0);
         const uint64_t cnt = part ? n_tasks - n_direct : n_direct;
@@ -1897,7 +2055,7 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
                          : debig_hip_png_warp_batch(c->rsz_src.ptr, out, (const debig_png_warp_task *)d_tasks, (uint32_t)cnt, NULL)))
             goto done;
     }
-    if ((rc = tone_run(tp, c, d_out, n, desc, lut_off))) goto done;
+    if ((rc = tone_run(tp, c, d_out, n, desc, lut_off)) || (rc = blur_run(tp, c, d_out, n, desc, lut_off))) goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
     stage_free(&S);
@@ -1935,15 +2093,14 @@ DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inp
     return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd, NULL);
 }
 
-DEBIG_API int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                                 const debig_png_box *boxes, const debig_png_warp *warps,
-                                                 const debig_png_color *colors, const debig_png_tone *tones, const uint8_t *tables,
-                                                 uint32_t n_tables, uint32_t *status, debig_png_info *infos, uint32_t n,
-                                                 uint32_t flags, const debig_png_tensor_desc *desc,
-                                                 const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter,
-                                                 const debig_png_warp_desc *wd)
+/* debig_png_decode_batch_tensor_tone (blurs == NULL, blur_call == 0) and debig_png_decode_batch_tensor_blur */
+static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
+                            const debig_png_warp *warps, const debig_png_color *colors, const debig_png_tone *tones,
+                            const uint8_t *tables, uint32_t n_tables, const debig_png_blur *blurs, int blur_call, uint32_t *status,
+                            debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                            const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
 {
-    /* every check of the call that is extended first, unchanged and in its order; then the tone call's own */
+    /* every check of the call that is extended first, unchanged and in its order; then the call's own */
     if (n == 0) return 0;
     uint32_t amode = DEBIG_PNG_ALPHA_STRAIGHT;
     if (warps || wd) {
@@ -1960,17 +2117,43 @@ DEBIG_API int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, c
         if (badarg) return badarg;
         if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
     }
-    if (!tones || (desc->out_format & DEBIG_PNG_FMT_16) || amode == DEBIG_PNG_ALPHA_PREMULTIPLIED || (!tables && n_tables > 0))
+    if ((blur_call ? !blurs : !tones) || (desc->out_format & DEBIG_PNG_FMT_16) || amode == DEBIG_PNG_ALPHA_PREMULTIPLIED ||
+        (!tables && n_tables > 0))
         return DEBIG_PNG_BAD_ARG;
     tone_plan tp;
     memset(&tp, 0, sizeof tp);
     tp.tones = tones;
     tp.tables = tables;
     tp.n_tables = n_tables;
+    tp.blurs = blurs;
     tp.oc = fmt_channels(desc->out_format);
     if (warps) return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd, &tp);
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
                        filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors, &tp);
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                 const debig_png_box *boxes, const debig_png_warp *warps,
+                                                 const debig_png_color *colors, const debig_png_tone *tones, const uint8_t *tables,
+                                                 uint32_t n_tables, uint32_t *status, debig_png_info *infos, uint32_t n,
+                                                 uint32_t flags, const debig_png_tensor_desc *desc,
+                                                 const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter,
+                                                 const debig_png_warp_desc *wd)
+{
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, colors, tones, tables, n_tables, NULL, 0, status, infos, n, flags,
+                            desc, alpha, filter, wd);
+}
+
+DEBIG_API int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                 const debig_png_box *boxes, const debig_png_warp *warps,
+                                                 const debig_png_color *colors, const debig_png_tone *tones, const uint8_t *tables,
+                                                 uint32_t n_tables, const debig_png_blur *blurs, uint32_t *status,
+                                                 debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                 const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha,
+                                                 const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
+{
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, colors, tones, tables, n_tables, blurs, 1, status, infos, n, flags,
+                            desc, alpha, filter, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -1998,7 +2181,7 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
     int rc;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL, NULL};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL, NULL, NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     rc = 2;
     for (uint32_t i = 0; i < n; i++) {
@@ -2073,7 +2256,7 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
     if (!cnt) goto done;
     if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL, NULL}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
     dev_tables_place(tab, 2);

@@ -694,6 +694,40 @@ int debig_hip_png_tone_hist_batch(const void *d_src, uint32_t *d_hist, const deb
 int debig_hip_png_tone_apply_batch(const void *d_src, void *d_out, const debig_png_tone_task *d_tasks, const uint32_t *d_hist,
                                    const void *d_tables, uint32_t n_tasks, void *hip_stream);
 
+/* ---- Gaussian blur and sharpness of the tensor decodes (csrc/png_blur_kernel.inc, behind debig_png_decode_batch_tensor_blur in
+ * decode_png.h, which has the rule).  The stages in front (a resize or warp kernel, then the tone apply kernel where the file has
+ * a tone operation too) have written every blur file as UINT8 HWC into an arena; one TASK is a tile of tile_w x tile_h output
+ * pixels at (x0, y0) of one such image of w x h pixels, for one workgroup of 256 lanes.  The workgroup brings the tile and a halo
+ * of `radius` pixels on every side (indices folded by the mirror rule) into LDS as bytes, runs the horizontal pass into a 16-bit
+ * LDS plane and the vertical pass out of it (GAUSSIAN: the 63 int16 weights at table_off in d_tables, of which 2 radius + 1 are
+ * used), or takes the 3 x 3 SMOOTH and the blend with K = k from the byte tile (SHARPNESS), and stores
+ * a[c] * (float)v + b[c] as dtype at out_off + (X out_sx + Y out_sy + c out_sc) elements.
+ * A task is skipped whole when w or h is 0 or above 16384, the tile is empty, wider or taller than DEBIG_PNG_BLUR_MAX_TILE or
+ * leaves the image, channels is not 1..4, colour_channels is not channels (1, 3) or channels - 1 (2, 4), dtype is above 3, op is
+ * not 1..2, radius is not 1..31 (GAUSSIAN) or not 1 (SHARPNESS), |k| is above 16 * 65536, (tile_h + 2 radius) x (tile_w + 2 radius)
+ * x channels is above DEBIG_PNG_BLUR_PX_CAP, (tile_h + 2 radius) x tile_w x channels is above DEBIG_PNG_BLUR_H16_CAP (GAUSSIAN),
+ * table_off is not a multiple of 16, or src_off is not a multiple of a 2- or 4-byte pixel. */
+#define DEBIG_PNG_BLUR_TILE 32u       /* the tile edge at which every radius and channel count fits                            */
+#define DEBIG_PNG_BLUR_MAX_TILE 64u
+#define DEBIG_PNG_BLUR_PX_CAP 35840u  /* bytes of the tile with its halo: (32 + 62)^2 x 4 = 35,344                             */
+#define DEBIG_PNG_BLUR_H16_CAP 12288u /* halfwords of the horizontal pass: (32 + 62) x 32 x 4 = 12,032                         */
+typedef struct debig_png_blur_task {
+    uint64_t src_off;       /* the image's first pixel, in bytes rel. to d_src                                                 */
+    uint64_t out_off;       /* the image's slot, in bytes rel. to d_out                                                        */
+    uint64_t table_off;     /* GAUSSIAN: the file's 63 int16 weights, in bytes rel. to d_tables                                */
+    int32_t k;              /* SHARPNESS: llround(factor * 65536)                                                              */
+    uint32_t radius;        /* GAUSSIAN: ksize / 2; SHARPNESS: 1                                                               */
+    uint32_t w, h;          /* the image                                                                                       */
+    uint32_t x0, y0, tile_w, tile_h;
+    uint32_t out_sx, out_sy, out_sc; /* in elements                                                                            */
+    uint8_t channels, colour_channels;
+    uint8_t dtype;          /* DEBIG_PNG_T_*                                                                                   */
+    uint8_t op;             /* DEBIG_PNG_BLUR_* (never NONE)                                                                   */
+    float a[4], b[4];
+} debig_png_blur_task;
+int debig_hip_png_blur_batch(const void *d_src, void *d_out, const debig_png_blur_task *d_tasks, const void *d_tables,
+                             uint32_t n_tasks, void *hip_stream);
+
 /* A byte span of a device arena. */
 typedef struct debig_span {
     uint64_t off;

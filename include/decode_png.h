@@ -253,7 +253,8 @@ int debig_png_decode_batch_dev(const uint8_t *const *inputs, const uint64_t *inp
  * Not provided: animated PNGs, inputs already on the device, an asynchronous variant; other filters than
  * bilinear are debig_png_decode_batch_tensor_filter's, flips, quarter turns and every other affine map are
  * debig_png_decode_batch_tensor_warp's, colour jitter (one colour matrix per file) is debig_png_decode_batch_tensor_color's,
- * autocontrast, equalize, posterize and solarize are debig_png_decode_batch_tensor_tone's (all below). */
+ * autocontrast, equalize, posterize and solarize are debig_png_decode_batch_tensor_tone's, Gaussian blur and sharpness are
+ * debig_png_decode_batch_tensor_blur's (all below). */
 typedef struct debig_png_box { uint32_t x, y, w, h; } debig_png_box; /* w == 0 && h == 0: the whole image */
 enum { DEBIG_PNG_T_UINT = 0, DEBIG_PNG_T_F32 = 1, DEBIG_PNG_T_F16 = 2, DEBIG_PNG_T_BF16 = 3 };
 #define DEBIG_PNG_RESIZE_ANTIALIAS 1u
@@ -666,6 +667,63 @@ int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, const uint6
                                        uint32_t n_tables, uint32_t *status, debig_png_info *infos /* may be NULL */, uint32_t n,
                                        uint32_t flags, const debig_png_tensor_desc *desc,
                                        const debig_png_alpha_desc *alpha /* may be NULL */,
+                                       const debig_png_filter_desc *filter /* may be NULL */,
+                                       const debig_png_warp_desc *warp_desc /* exactly when warps is given */);
+
+/* ---- Gaussian blur and sharpness in the tensor decodes ---------------------------------------------------------------------------
+ * The two neighbourhood filters of the augmentation lists: Sharpness (RandAugment, AutoAugment: Pillow's ImageEnhance.Sharpness)
+ * and the Gaussian blur of SimCLR / BYOL / DINO / MoCo-v3 (torchvision's GaussianBlur; after colour jitter, before normalisation).
+ * debig_png_decode_batch_tensor_blur is debig_png_decode_batch_tensor_tone -- the tensor call that warps, colors, alpha, filter
+ * and warp_desc select, with its tone operations; here tones may be NULL (no file has one; tables may then be NULL too) -- with
+ * one more operation per file, blurs[i] = {op, ksize, value}:
+ *     DEBIG_PNG_BLUR_NONE       ksize, value ignored             nothing: the file's slot is, bit for bit, what the tone call (or,
+ *                                                                with tones NULL, the extended call) writes
+ *     DEBIG_PNG_BLUR_GAUSSIAN   ksize odd, 3 .. 63; value = sigma, finite, 0 < sigma <= 1000
+ *     DEBIG_PNG_BLUR_SHARPNESS  value = factor, finite, |factor| <= 16; ksize ignored
+ * Any other op, ksize or value gives the file DEBIG_PNG_E_BLUR; it is decided when IHDR has been read, ranks behind E_BOX, E_WARP,
+ * E_COLOR and E_TONE and, like them, ahead of whatever is found later in the file.
+ * Where it acts: on the 8-bit samples p that everything in front gives -- crop, filter or warp, colour matrix, the
+ * DEBIG_PNG_T_UINT conversion and the file's tone table --, of the whole out_h x out_w image.  It produces v, the sample in Q22
+ * (the sample times 2^22, at most 255 << 22), to which the ONE conversion of debig_png_decode_batch_tensor is applied as in the
+ * tone call: UINT gives (v + 2^21) >> 22; F32 is (float)v * A_c + B_c with a separately rounded multiply and add; F16 / BF16 as
+ * there.  Float outputs therefore keep the precision below one 8-bit step; UINT rounds once.
+ * GAUSSIAN, on every channel, alpha included (as torchvision's GaussianBlur treats a 4-channel tensor), r = ksize div 2:
+ *   weights (debig_png_blur_weights): w_j = exp(-(j / sigma)^2 / 2) for j = -r .. r in doubles, divided by their sum;
+ *       q_j = floor(w_j * 16384 + 1/2); then 16384 - sum(q) is added to the centre tap q_0.  The taps are symmetric, not
+ *       negative, and sum to exactly 16384;
+ *   borders: mirrored without repeating the edge sample (torchvision's "reflect", scipy's "mirror"), made total by folding with
+ *       period 2 (n - 1): fold(i) = m if m < n else 2 (n - 1) - m, with m = i mod 2 (n - 1) (not negative); n == 1: always 0.  A
+ *       radius larger than the image is therefore defined;
+ *   horizontal: h = sum_j q_j * p[y][fold(x + j)],  h16 = (h + 32) >> 6            (at most 65280: 16 bits);
+ *   vertical:   v = sum_j q_j * h16[fold(y + j)][x]                               (at most 65280 << 14 = 255 << 22).
+ *   v / 2^22 is within 0.05 of an 8-bit step of the mirrored separable convolution in doubles on the images tested (0.0233
+ *   measured on noise, 0.0406 on blocks of 0 and 255; tests/test_png_blur_cpu.py).
+ * SHARPNESS, on the colour channels only; the last channel of RGBA / GRAY_ALPHA tensors passes through (v = p << 22), as in Pillow:
+ *   s = (2 * sum_9 k * p + 13) div 26 with k = (1 1 1; 1 5 1; 1 1 1) for 1 <= x <= out_w - 2 and 1 <= y <= out_h - 2, and s = p on
+ *       the one-pixel border ring (everywhere when out_w < 3 or out_h < 3): Pillow's ImageFilter.SMOOTH exactly (13 is odd: no ties);
+ *   K = llround(factor * 65536),  v = clamp((s << 22) + K * (p - s) * 64, 0, 255 << 22) in 64-bit integers.
+ *   Factor 1 is the identity and factor 0 is SMOOTH, both exactly; the UINT result is within 1 of ImageEnhance.Sharpness, which
+ *   truncates a float blend where this rule rounds.
+ * Checked first, before any file is looked at (status unwritten): every check of the tone call, unchanged and in its order, except
+ * that tones may be NULL; DEBIG_PNG_BAD_ARG for blurs NULL.  Like a tone operation, a blur operation goes with 8-bit out_formats
+ * and alpha modes STRAIGHT and OVER.  Per image: statuses, their order, infos and the untouched slot of a failed file are those
+ * of the tone call, with E_BLUR as above.
+ * Not provided: 16-bit tensors, other sigmas per axis, other border rules, kernels above 63 taps, unsharp masking with a radius. */
+#define DEBIG_PNG_E_BLUR 19 /* the blur operation (rules above) */
+#define DEBIG_PNG_BLUR_NONE 0u
+#define DEBIG_PNG_BLUR_GAUSSIAN 1u
+#define DEBIG_PNG_BLUR_SHARPNESS 2u
+typedef struct debig_png_blur { uint32_t op; uint32_t ksize; double value; } debig_png_blur;
+/* Host only: the ksize Q14 taps of GAUSSIAN in q[0 .. ksize), zeros behind them -> 1, or 0 (q unspecified) on the E_BLUR
+ * conditions above. */
+int debig_png_blur_weights(uint32_t ksize, double sigma, int16_t q[63]);
+int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                       const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps /* may be NULL */,
+                                       const debig_png_color *colors /* may be NULL */, const debig_png_tone *tones /* may be NULL */,
+                                       const uint8_t *tables /* n_tables x 256 bytes; may be NULL when n_tables == 0 */,
+                                       uint32_t n_tables, const debig_png_blur *blurs, uint32_t *status,
+                                       debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                       const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha /* may be NULL */,
                                        const debig_png_filter_desc *filter /* may be NULL */,
                                        const debig_png_warp_desc *warp_desc /* exactly when warps is given */);
 

@@ -23,6 +23,7 @@
 #include "../../debigulator_amd/csrc/png_color_label_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_kernel.inc"
 #include "../../debigulator_amd/csrc/png_tone_kernel.inc"
+#include "../../debigulator_amd/csrc/png_blur_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
@@ -461,5 +462,14 @@ extern "C" int emu_png_tone_apply_batch(const void *src, void *out, const debig_
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_tone_apply_kernel, grid, TONE_THREADS, (const uint8_t *)src, (uint8_t *)out, tasks, hist,
                       (const uint8_t *)tables, n);
+    return 0;
+}
+
+/* Gaussian blur and sharpness of the tensor decode (png_blur_kernel.inc), as debig_hip_png_blur_batch launches it (grid as above) */
+extern "C" int emu_png_blur_batch(const void *src, void *out, const debig_png_blur_task *tasks, const void *tables, uint32_t n,
+                                  uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_blur_kernel, grid, BLUR_THREADS, (const uint8_t *)src, (uint8_t *)out, tasks, (const uint8_t *)tables, n);
     return 0;
 }
