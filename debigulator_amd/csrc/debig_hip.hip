@@ -260,6 +260,15 @@ static uint32_t pipe_big_tile_streams()
     return cap[dev];
 }
 
+// DEBIG_NO_HANDBACK (include/debig_hip.h): the launch of debig_inflate_kernel / debig_inflate_mw_kernel behind a
+// throughput route is left out, so a stream the route handed back stays DEBIG_E_RETRY.  Read at every call, as
+// DEBIG_CHUNK_BYTES is: tests switch it between two launches of one process.
+static bool no_handback()
+{
+    const char *e = getenv("DEBIG_NO_HANDBACK");
+    return e && *e && !(e[0] == '0' && e[1] == 0);
+}
+
 // one group of at most SPLIT_GROUP streams: plan, scan, lz, and debig_inflate_kernel for what the
 // pair handed back.  Returns 0, a hipError_t, or -1 when the workspace is too small to try.
 // what = 1: carve the workspace only (debig_split_plan_kernel), 2: scan + lz + hand-back over a
@@ -299,8 +308,9 @@ static int launch_split_group(hipStream_t s, const void *d_in, void *d_out, cons
     else
         hipLaunchKernelGGL(debig_scanlz_kernel, dim3(n), dim3(64), 0, s, (const uint8_t *)d_in, (uint8_t *)d_out, d_streams, n,
                            tabs->scan, slots, recs, rows, d_results);
-    hipLaunchKernelGGL(debig_inflate_kernel, dim3(n), dim3(64), 0, s, (const uint8_t *)d_in, (uint8_t *)d_out, d_streams,
-                       d_results, n, tabs->one, DEBIG_CLASS_RETRY);
+    if (!no_handback())
+        hipLaunchKernelGGL(debig_inflate_kernel, dim3(n), dim3(64), 0, s, (const uint8_t *)d_in, (uint8_t *)d_out, d_streams,
+                           d_results, n, tabs->one, DEBIG_CLASS_RETRY);
     return (int)hipGetLastError();
 }
 
@@ -351,6 +361,7 @@ static int launch_chunked(hipStream_t s, const void *d_in, void *d_out, const de
     hipLaunchKernelGGL(debig_ck_window_kernel, dim3(n), dim3(CK_WIN_THREADS), 0, s, (const uint8_t *)out, d_streams, n, ws, mt);
     hipLaunchKernelGGL(debig_ck_translate_kernel, dim3(mt * CK_TR_PARTS), dim3(CK_TR_THREADS), 0, s, out, d_streams, n, ws, mt);
     hipLaunchKernelGGL(debig_ck_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint8_t *)ws, d_results);
+    if (no_handback()) return (int)hipGetLastError();
     return launch_inflate(retry_w, DEBIG_CLASS_RETRY, s, d_in, d_out, d_streams, d_results, n, tabs);
 }
 
@@ -413,14 +424,22 @@ uint64_t debig_hip_inflate_workspace_bytes_io(uint64_t total_in_bytes, uint64_t 
     const uint32_t group = n < SPLIT_GROUP ? n : SPLIT_GROUP;
     const uint64_t out_term = total_out_cap / 64u < 4u * total_in_bytes ? total_out_cap / 64u : 4u * total_in_bytes;
     const uint64_t per_group = n ? (out_term + n - 1) / n * group : 0;
-    return debig_hip_inflate_workspace_bytes(total_in_bytes, n) + align_up(per_group * 12u, 4096);
+    // ... and what the weight adds for SHORT streams (in_len < PLAN_SHORT_IN_BYTES: min(out_cap / 16, PLAN_SHORT_UNITS) each).
+    // Only the sums are known here, so every stream is allowed for: at most 51 KiB per stream, 3/4 of total_out_cap
+    const uint64_t short_all = total_out_cap / 16u < (uint64_t)PLAN_SHORT_UNITS * n ? total_out_cap / 16u : (uint64_t)PLAN_SHORT_UNITS * n;
+    const uint64_t short_group = n ? (short_all + n - 1) / n * group : 0;
+    return debig_hip_inflate_workspace_bytes(total_in_bytes, n) + align_up(per_group * 12u, 4096) + align_up(short_group * 12u, 4096);
 }
 
 uint64_t debig_hip_inflate_chunked_workspace_bytes(uint64_t total_in_bytes, uint64_t total_out_bytes, uint32_t n)
 {
     // tables + tokens (about 9 x the compressed bytes) + two planes of the output + per chunk task
     // (32 KiB of input at the smallest chunk size) a window, two synthetic histories and token slack
-    const uint64_t tasks = total_in_bytes / CK_MIN_CHUNK + n;
+    // (DEBIG_CHUNK_BYTES cuts smaller tasks: the estimate follows it, with the plan kernel's floor of 1 KiB)
+    uint32_t chunk = chunk_bytes_override();
+    if (chunk == 0) chunk = CK_MIN_CHUNK;
+    if (chunk < 1024u) chunk = 1024u;
+    const uint64_t tasks = total_in_bytes / chunk + n;
     return align_up((uint64_t)n * 4224u + tasks * (128u + 24576u + 98304u) + total_in_bytes * 10u + total_out_bytes * 2u +
                         (total_out_bytes >> 6) + (1u << 20), 4096);
 }
@@ -456,6 +475,7 @@ int debig_hip_inflate_batch_ws(const void *d_in, void *d_out, const debig_stream
             if (rc == 0 && frc) return frc;
         }
         if (rc >= 0) return rc;
+        if (no_handback()) return (int)hipErrorInvalidValue; /* the whole batch would go to the workgroup-per-stream kernels */
         d_workspace = nullptr;
         waves_per_stream = n <= 256u ? 8u : n <= 512u ? 4u : n <= 1024u ? 2u : 1u; /* no usable workspace */
     }
@@ -477,6 +497,7 @@ int debig_hip_inflate_batch_ws(const void *d_in, void *d_out, const debig_stream
             if (rc == 0 && frc) return frc;
         }
         if (rc >= 0) return rc;
+        if (no_handback()) return (int)hipErrorInvalidValue; /* the whole batch would go to the one-kernel path */
         waves_per_stream = 1; /* no usable workspace: the one-kernel path */
     }
     if (!mixed) return launch_inflate(waves_per_stream, DEBIG_CLASS_ALL, s, d_in, d_out, d_streams, d_results, n, ft);

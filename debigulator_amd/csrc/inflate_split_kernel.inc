@@ -25,7 +25,7 @@
 // debig_inflate_kernel (the two share every helper); streams that do not fit their share of the
 // token workspace are handed to debig_inflate_kernel (DEBIG_CLASS_RETRY).
 
-#define DEBIG_E_RETRY 11u /* internal: not decoded by the split path, debig_inflate_kernel takes it */
+/* DEBIG_E_RETRY (include/debig_hip.h): not decoded by the split path, debig_inflate_kernel takes it */
 #define DEBIG_CLASS_RETRY 3u
 
 // ---- workspace (one allocation, carved by debig_split_plan_kernel in proportion to in_len)
@@ -200,10 +200,24 @@ struct PlanStreamWeight {
     // 4 MB, a block every few hundred bytes) has a window -- info rows, at least one unit row -- per block, many times what
     // its input length suggests; with shares by input length alone such streams went to the one-kernel path (config 3:
     // 69 instead of 39 ms).  Capped by the input, so that a caller's generous recipient_size cannot starve the others.
+    // A SHORT stream of one- and two-bit codes (a run of one byte: 60 KB from 50 bytes) is the other end of the same matter:
+    // one or two lanes decode all of it, and the symbols of a window's busiest lane take a token ROW each -- about
+    // out_cap / 258 rows, up to the 272 two-bit symbols of a 68-byte lane segment, whatever the input length says (4 in_len is
+    // a few hundred units there).  A unit is worth 12 bytes = 1 / 22.8 row (debig_hip_inflate_workspace_bytes_io), so below
+    // PLAN_SHORT_IN_BYTES of input the recipient counts as out_cap / 16, at most PLAN_SHORT_UNITS: with the 2048 of every
+    // stream that is 92 + out_cap / 364 rows up to 64 KiB of recipient and 281 rows beyond.  From PLAN_SHORT_IN_BYTES on
+    // in_len + 4 in_len + 2048 is that much by itself.
+#define PLAN_SHORT_IN_BYTES 1024u
+#define PLAN_SHORT_UNITS 4352u
     DEV_MEMBER_INLINE uint64_t operator()(uint32_t i) const
     {
-        const uint64_t il = streams[i].in_len, oc = streams[i].out_cap >> 6;
-        return il + (oc < 4u * il ? oc : 4u * il) + 2048u;
+        const uint64_t il = streams[i].in_len, cap = streams[i].out_cap, oc = cap >> 6;
+        uint64_t t = oc < 4u * il ? oc : 4u * il;
+        if (il < PLAN_SHORT_IN_BYTES) {
+            const uint64_t s = (cap >> 4) < PLAN_SHORT_UNITS ? (cap >> 4) : PLAN_SHORT_UNITS;
+            t = t > s ? t : s;
+        }
+        return il + t + 2048u;
     }
 };
 __global__ void __launch_bounds__(1024)

@@ -79,8 +79,12 @@ enum {
     DEBIG_E_DIST_TOO_FAR = 7,         /* distance beyond start of output (inflate.c:1843)       */
     DEBIG_E_OUTPUT_FULL = 8,          /* output would exceed recipient_size (ref: overflow/assert) */
     DEBIG_E_LITLEN_286_287 = 9,       /* symbols 286/287 (ref: reads past its table)            */
-    DEBIG_E_INTERNAL = 10             /* a kernel-internal guard tripped (bounded wait exhausted); never
+    DEBIG_E_INTERNAL = 10,            /* a kernel-internal guard tripped (bounded wait exhausted); never
                                          expected -- the stream is reported failed, not silently wrong */
+    DEBIG_E_RETRY = 11                /* a throughput route (DEBIG_WAVES_SPLIT, _SPLIT_QUEUED, _STRAND, _STRAND_PIPE,
+                                         _CHUNKED) handed the stream back.  Visible only under DEBIG_NO_HANDBACK (below):
+                                         otherwise the workgroup-per-stream kernel launched behind the route in the same
+                                         call has replaced it with the stream's own status */
 };
 
 typedef struct debig_result {
@@ -185,6 +189,17 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  *              blocks, a block longer than the workspace share, a failing stream, any doubt)
  *              are decoded by the one-kernel path in the same call.  Never picked by 0. */
 #define DEBIG_WAVES_CHUNKED 0x20u
+/* DEBIG_NO_HANDBACK (environment variable, read at every call; tests and measurements): set to anything but the empty
+ * string or "0", the five routes above that hand streams back -- DEBIG_WAVES_SPLIT, _SPLIT_QUEUED, _STRAND,
+ * _STRAND_PIPE and _CHUNKED, in debig_hip_inflate_batch / _ex / _ws and debig_hip_inflate_planned_ws / _ex -- do NOT
+ * launch the workgroup-per-stream kernel behind themselves.  A stream the route handed back then keeps what the route
+ * wrote: good = 0, status = DEBIG_E_RETRY, final_set = 0 (DEBIG_WAVES_STRAND_PIPE, whose LZ77 wavefront replays behind the
+ * scan and has come some way when the scan gives up: final_set and final_size as that wavefront left them, they mean
+ * nothing); its output bytes are unspecified.  Every other stream is the
+ * route's own work, which is what the switch is for: without it nothing in the results says which kernel produced the
+ * bytes.  Where a call would send the WHOLE batch to the workgroup-per-stream kernels because the workspace is missing
+ * or too small to try, it returns hipErrorInvalidValue under the switch and launches nothing.  (The fused PNG kernel has
+ * its own switch, DEBIG_FUSED_FLAGS & 2.) */
 int debig_hip_inflate_batch_ex(const void *d_in, void *d_out, const debig_stream *d_streams,
                                debig_result *d_results, uint32_t n, uint32_t waves_per_stream,
                                void *hip_stream);
@@ -211,7 +226,14 @@ uint64_t debig_hip_inflate_workspace_bytes(uint64_t total_in_bytes, uint32_t n);
 /* The same for a caller that also knows the recipients: total_out_cap = the sum of out_cap.  Highly compressible
  * streams (flat image areas: 30 KB for 4 MB, codes of one or two bits) write many more token units per compressed byte
  * than 12 x allows for; the plan step gives every stream a share by in_len + min(out_cap / 64, 4 in_len) + 2 KiB, and
- * this size adds the second term (at most 3/16 of total_out_cap), so that such streams are not handed back. */
+ * this size adds the second term (at most 3/16 of total_out_cap), so that such streams are not handed back.
+ * The other end of the same matter is a SHORT stream of such codes (a run of one byte: 60 KB from 50 bytes of input): one
+ * lane decodes all of it, and DEBIG_WAVES_SPLIT / _SPLIT_QUEUED keep a 256-byte token row per symbol of a window's busiest
+ * lane.  Below 1 KiB of input the plan step therefore counts the recipient as min(out_cap / 16, 4352), and this size allows
+ * every stream for it (it sees sums only): at most 3/4 of total_out_cap and 51 KiB per stream on top.  What this does NOT
+ * cover: symbols of one or two bits that produce ONE byte each (a run coded as literals, Z_HUFFMAN_ONLY: 545 rows for 4 KB
+ * of input) -- those are handed back.  tests/test_emu_handback.py and tests/test_gpu_handback.py hold the routes to this
+ * under DEBIG_NO_HANDBACK. */
 uint64_t debig_hip_inflate_workspace_bytes_io(uint64_t total_in_bytes, uint64_t total_out_cap, uint32_t n);
 /* workspace that lets DEBIG_WAVES_CHUNKED take every stream of a batch: total_out_bytes = the sum
  * of the recipients (out_cap), which should be close to the decoded sizes */

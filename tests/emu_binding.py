@@ -54,13 +54,16 @@ STRAND_PIPE_BIG = 0x113  # (test code only) the same with the 12 KB LZ77 tile th
 last_split_retried = 0  # streams the pair handed to the one-kernel path in the last SPLIT call
 
 
-def layout_batch(raws, caps, in_misalign=0, out_misalign=0, p2=None, flags=0):
-    """Pack streams into arenas.  Returns (in_arena, out_arena, streams[], results[])."""
+def layout_batch(raws, caps, in_misalign=0, out_misalign=0, p2=None, flags=0, align=16):
+    """Pack streams into arenas.  Returns (in_arena, out_arena, streams[], results[]).
+    align > 16: every stream and every recipient starts in_misalign / out_misalign bytes behind a multiple of `align`
+    (debigulator_amd.batch.pack_streams with in_align = out_align = align lays a batch out the same way)."""
     n = len(raws)
+    up = (lambda x: (x + align - 1) // align * align) if align > 16 else (lambda x: x)
     streams = (DebigStream * n)()
     results = (DebigResult * n)()
-    in_off = 64 + in_misalign
-    out_off = 64 + out_misalign
+    in_off = up(64) + in_misalign
+    out_off = up(64) + out_misalign
     offs = []
     for i, (r, cap) in enumerate(zip(raws, caps)):
         streams[i].in_off = in_off
@@ -75,6 +78,8 @@ def layout_batch(raws, caps, in_misalign=0, out_misalign=0, p2=None, flags=0):
         offs.append((in_off, out_off))
         in_off += (len(r) + 63 + 16) // 16 * 16 + in_misalign
         out_off += (cap + 1024 + 15) // 16 * 16 + out_misalign
+        if align > 16:
+            in_off, out_off = up(in_off) + in_misalign, up(out_off) + out_misalign
     in_arena = np.zeros(in_off + 64, dtype=np.uint8)
     out_arena = np.full(out_off + 64, 0xA5, dtype=np.uint8)
     for (io, _), r in zip(offs, raws):
@@ -84,12 +89,29 @@ def layout_batch(raws, caps, in_misalign=0, out_misalign=0, p2=None, flags=0):
     return in_arena, out_arena, streams, results, offs
 
 
-def emu_inflate(L, raws, caps, grid=0, nw=1, classes=None, ws_bytes=None, chunk_bytes=4096, retry_width=1, **kw):
+def emu_inflate(L, raws, caps, grid=0, nw=1, classes=None, ws_bytes=None, chunk_bytes=4096, retry_width=1, no_handback=False,
+                **kw):
     """nw = 1: debig_inflate_kernel; nw = 2 / 4: debig_inflate_mw_kernel<nw> (one stream per
     workgroup of nw wavefronts).  classes = [(nw, cls), ...]: one launch per entry, each
-    restricted to a stream class (1 small, 2 large), like the shim's mixed-width mode."""
+    restricted to a stream class (1 small, 2 large), like the shim's mixed-width mode.
+    no_handback: DEBIG_NO_HANDBACK for this call (the split and chunked routes leave what they hand back as
+    status 11, good 0, final_set 0)."""
     global last_split_retried
     in_arena, out_arena, streams, results, offs = layout_batch(raws, caps, **kw)
+    if no_handback:
+        os.environ["DEBIG_NO_HANDBACK"] = "1"
+    try:
+        return _emu_inflate(L, raws, in_arena, out_arena, streams, results, offs, grid, nw, classes, ws_bytes,
+                            chunk_bytes, retry_width)
+    finally:
+        if no_handback:
+            os.environ.pop("DEBIG_NO_HANDBACK", None)
+
+
+def _emu_inflate(L, raws, in_arena, out_arena, streams, results, offs, grid, nw, classes, ws_bytes, chunk_bytes,
+                 retry_width):
+    global last_split_retried
+    caps = [s.out_cap for s in streams]
     if classes is not None:
         rc = 0
         for w, cls in classes:

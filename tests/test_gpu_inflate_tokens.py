@@ -10,6 +10,7 @@ import os
 
 import pytest
 
+import handback_corpus as hc
 import token_fuzz as tf
 from debigulator_amd.batch import DeviceBatch
 from test_gpu_inflate import WIDTHS, _check
@@ -52,6 +53,18 @@ def test_chunked_path_small_tasks_far_matches_across_tasks(oracle, gpu_device, m
     monkeypatch.setenv("DEBIG_CHUNK_BYTES", chunk)
     _run(oracle, gpu_device, _family(oracle, "F5") + _family(oracle, "F8"), widths=(0x20,),
          in_skew=int(chunk) % 7, out_skew=3)
+    # ... and the chunk tasks themselves did it: under DEBIG_NO_HANDBACK (include/debig_hip.h) the kernel behind them is not
+    # launched, a stream handed back stays DEBIG_E_RETRY and every other one is held to the oracle once more
+    monkeypatch.setenv("DEBIG_NO_HANDBACK", "1")
+    for fam, cap in (("F5", 1), ("F8", 30)):
+        items = [hc.Item(c.name, c.raw, c.cap) for c in _family(oracle, fam)]
+        b = DeviceBatch.from_streams([i.raw for i in items], [i.cap for i in items], device=gpu_device,
+                                     in_skew=int(chunk) % 7, out_skew=3)
+        b.launch(waves_per_stream=0x20)
+        names = hc.handed_back(items, hc.expectations(oracle.inflate, items),
+                               hc.device_rows(items, b.streams_host, b.results(), b.outputs_host()), fam)
+        assert len(names) <= cap, (fam, sorted(names))
+    monkeypatch.delenv("DEBIG_NO_HANDBACK", raising=False)
     monkeypatch.delenv("DEBIG_CHUNK_BYTES", raising=False)
 
 

@@ -26,6 +26,13 @@
 #include "../../debigulator_amd/csrc/png_blur_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
+/* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
+static bool emu_no_handback()
+{
+    const char *e = getenv("DEBIG_NO_HANDBACK");
+    return e && *e && !(e[0] == '0' && e[1] == 0);
+}
+
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
 extern "C" int emu_inflate_batch_cls(const void *in, void *out, const debig_stream *streams,
                                      debig_result *results, uint32_t n, uint32_t grid, uint32_t nw, uint32_t cls);
@@ -139,7 +146,8 @@ extern "C" int emu_inflate_split_batch(const void *in, void *out, const debig_st
     uint32_t retried = 0;
     for (uint32_t i = 0; i < n; i++) retried += results[i].status == DEBIG_E_RETRY;
     if (n_retried) *n_retried = retried;
-    EMU_LAUNCH(debig_inflate_kernel, n, 64, (const uint8_t *)in, (uint8_t *)out, streams, results, n, ft, DEBIG_CLASS_RETRY);
+    if (!emu_no_handback())
+        EMU_LAUNCH(debig_inflate_kernel, n, 64, (const uint8_t *)in, (uint8_t *)out, streams, results, n, ft, DEBIG_CLASS_RETRY);
     free(ws);
     return 0;
 }
@@ -197,7 +205,8 @@ extern "C" int emu_inflate_chunked_batch(const void *in, void *out, const debig_
             }
         }
     }
-    if (retry_width > 1) {
+    if (emu_no_handback()) { /* what was handed back stays DEBIG_E_RETRY */
+    } else if (retry_width > 1) {
         static uint32_t *ftm = nullptr;
         if (!ftm) {
             ftm = (uint32_t *)calloc(1, sizeof(decltype(WaveLdsT<2>::t)));
