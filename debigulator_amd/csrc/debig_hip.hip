@@ -269,6 +269,18 @@ static bool no_handback()
     return e && *e && !(e[0] == '0' && e[1] == 0);
 }
 
+// workgroups of a tensor-stage launch (the APNG compositing, the resize / warp / label / tone / blur launchers below): one per
+// task up to 2^20, the kernels loop over the rest.  DEBIG_STAGE_GRID (include/debig_hip.h; tests: read at every call) lowers it.
+static uint32_t stage_grid(uint32_t n_tasks)
+{
+    const uint32_t cap = 1u << 20;
+    const uint32_t grid = n_tasks < cap ? n_tasks : cap;
+    const char *e = getenv("DEBIG_STAGE_GRID");
+    const unsigned long forced = e && *e ? strtoul(e, nullptr, 0) : 0ul;
+    if (forced == 0) return grid;
+    return forced < grid ? (uint32_t)forced : grid;
+}
+
 // one group of at most SPLIT_GROUP streams: plan, scan, lz, and debig_inflate_kernel for what the
 // pair handed back.  Returns 0, a hipError_t, or -1 when the workspace is too small to try.
 // what = 1: carve the workspace only (debig_split_plan_kernel), 2: scan + lz + hand-back over a
@@ -779,7 +791,7 @@ int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_apng_composite_kernel, dim3(grid), dim3(APNG_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_frames_arena, (uint8_t *)d_out_arena, d_tasks, n_tasks);
     return (int)hipGetLastError();
@@ -791,7 +803,7 @@ int debig_hip_png_resize_batch(const void *d_src_arena, void *d_out, const debig
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_resize_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
     return (int)hipGetLastError();
@@ -803,7 +815,7 @@ int debig_hip_png_resize_alpha_batch(const void *d_src_arena, void *d_out, const
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_resize_alpha_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
     return (int)hipGetLastError();
@@ -815,7 +827,7 @@ int debig_hip_png_resize_cubic_batch(const void *d_src_arena, void *d_out, const
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_resize_cubic_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
     return (int)hipGetLastError();
@@ -828,7 +840,7 @@ int debig_hip_png_label_gather_batch(const void *d_src_arena, void *d_out, const
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_label_gather_kernel, dim3(grid), dim3(LBL_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_lut, n_tasks);
     return (int)hipGetLastError();
@@ -841,7 +853,7 @@ int debig_hip_png_color_label_batch(const void *d_src_arena, void *d_out, const 
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_color_label_kernel, dim3(grid), dim3(CLBL_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched, n_tasks);
     return (int)hipGetLastError();
@@ -854,7 +866,7 @@ int debig_hip_png_warp_batch(const void *d_src_arena, void *d_out, const debig_p
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_warp_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, n_tasks);
     return (int)hipGetLastError();
@@ -866,7 +878,7 @@ int debig_hip_png_label_warp_batch(const void *d_src_arena, void *d_out, const d
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_label_warp_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, d_lut, n_tasks);
     return (int)hipGetLastError();
@@ -878,7 +890,7 @@ int debig_hip_png_color_label_warp_batch(const void *d_src_arena, void *d_out, c
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_color_label_warp_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched, n_tasks);
     return (int)hipGetLastError();
@@ -890,7 +902,7 @@ int debig_hip_png_resize_color_batch(const void *d_src_arena, void *d_out, const
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_resize_color_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
     return (int)hipGetLastError();
@@ -901,7 +913,7 @@ int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const d
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_warp_color_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
     return (int)hipGetLastError();
@@ -913,7 +925,7 @@ int debig_hip_png_tone_hist_batch(const void *d_src, uint32_t *d_hist, const deb
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_tone_hist_kernel, dim3(grid), dim3(TONE_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src, d_hist, d_tasks, n_tasks);
     return (int)hipGetLastError();
@@ -924,7 +936,7 @@ int debig_hip_png_tone_apply_batch(const void *d_src, void *d_out, const debig_p
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_tone_apply_kernel, dim3(grid), dim3(TONE_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks, d_hist, (const uint8_t *)d_tables, n_tasks);
     return (int)hipGetLastError();
@@ -936,7 +948,7 @@ int debig_hip_png_blur_batch(const void *d_src, void *d_out, const debig_png_blu
 {
     if (n_tasks == 0) return 0;
     DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = n_tasks < (1u << 20) ? n_tasks : (1u << 20);
+    const uint32_t grid = stage_grid(n_tasks);
     hipLaunchKernelGGL(debig_png_blur_kernel, dim3(grid), dim3(BLUR_THREADS), 0, (hipStream_t)hip_stream,
                        (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, n_tasks);
     return (int)hipGetLastError();

@@ -200,6 +200,12 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * bytes.  Where a call would send the WHOLE batch to the workgroup-per-stream kernels because the workspace is missing
  * or too small to try, it returns hipErrorInvalidValue under the switch and launches nothing.  (The fused PNG kernel has
  * its own switch, DEBIG_FUSED_FLAGS & 2.) */
+/* DEBIG_STAGE_GRID (environment variable, read at every call; tests): the launchers below whose kernels loop over their
+ * tasks -- debig_hip_apng_composite_batch, debig_hip_png_resize_batch / _resize_alpha / _resize_cubic / _resize_color,
+ * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _tone_hist / _tone_apply and _blur --
+ * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
+ * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
+ * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
 int debig_hip_inflate_batch_ex(const void *d_in, void *d_out, const debig_stream *d_streams,
                                debig_result *d_results, uint32_t n, uint32_t waves_per_stream,
                                void *hip_stream);

@@ -13,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import apng_ref as A  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 
 class FrameDesc(C.Structure):  # include/debig_hip.h: debig_apng_frame_desc
@@ -93,7 +94,7 @@ def run(files, out_misalign=None, task_px=TASK_PX, grid=0, frame_misalign=4):
     C.memmove(a.ctypes.data, ft, C.sizeof(ft))
     out = np.full(out_total + 64, FILL, dtype=np.uint8)
     TT = (Task * len(tasks))(*tasks)
-    assert _emu().emu_apng_composite_batch(a.ctypes.data, out.ctypes.data, TT, len(tasks), grid) == 0
+    assert launch("apng_composite", a, out, TT, len(tasks), grid, emu=_emu) == 0
     untouched = np.ones(len(out), dtype=bool)
     res = []
     for (W, H, frames), (off, size) in zip(files, outs):

@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import png_blur_ref as B  # noqa: E402
 import png_resize_ref as Z  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 FILL, GAP = 0xEE, 4096
 SCALE, BIAS = (1 / 0.229, 1 / 0.224, 1 / 0.225, 3.0), (-0.485 / 0.229, -0.456 / 0.224, -0.406 / 0.225, 0.25)
@@ -117,7 +118,7 @@ def run(files, size, dtype, layout, tile=(TILE, TILE), grid=0, spoil=None):
     arr = (BlurTask * n)(*tasks)
     ta = np.frombuffer(bytes(tables), np.uint8).copy() if tables else np.zeros(16, np.uint8)
     out = np.full(GAP + len(files) * slot + GAP, FILL, np.uint8)
-    assert _emu().emu_png_blur_batch(a.ctypes.data, out.ctypes.data, arr, ta.ctypes.data, n, grid) == 0
+    assert launch("png_blur", a, out, arr, ta, n, grid, emu=_emu) == 0
     assert (out[:GAP] == FILL).all() and (out[GAP + len(files) * slot:] == FILL).all(), "the sentinel around the tensor was written"
     npdt = {0: np.uint8, 1: np.float32, 2: np.float16, 3: np.uint16}[code]
     shape = (len(files), ch, H, W) if layout == "chw" else (len(files), H, W, ch)

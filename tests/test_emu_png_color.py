@@ -20,6 +20,7 @@ import png_filter_ref as FR  # noqa: E402
 import png_resize_ref as Z  # noqa: E402
 import png_warp_ref as WR  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from debigulator_amd.api import png_color_matrix, png_warp_matrix  # noqa: E402
@@ -156,7 +157,7 @@ def run_resize(srcs, mats, size, dtype, layout, filt, aa=True, tile_h=64, grid=0
     wa = np.frombuffer(bytes(weights), np.uint8).copy()
     out = np.full(GAP + len(srcs) * slot + GAP, FILL, np.uint8)
     n = len(tasks)
-    assert _emu().emu_png_resize_color_batch(a.ctypes.data, out.ctypes.data, (ResizeColorTask * n)(*tasks), wa.ctypes.data, n, grid) == 0
+    assert launch("png_resize_color", a, out, (ResizeColorTask * n)(*tasks), wa, n, grid, emu=_emu) == 0
     return _view(out, len(srcs), size, ch, P, code, layout), n
 
 
@@ -186,7 +187,7 @@ def run_warp(srcs, mats, warps, size, dtype, layout, filt, mode, border=(0, 0, 0
     wa = np.frombuffer(_records(mats, P), np.uint8).copy()
     out = np.full(GAP + len(srcs) * slot + GAP, FILL, np.uint8)
     n = len(tasks)
-    assert _emu().emu_png_warp_color_batch(a.ctypes.data, out.ctypes.data, (WarpColorTask * n)(*tasks), wa.ctypes.data, n, grid) == 0
+    assert launch("png_warp_color", a, out, (WarpColorTask * n)(*tasks), wa, n, grid, emu=_emu) == 0
     return _view(out, len(srcs), size, ch, P, code, layout), n
 
 

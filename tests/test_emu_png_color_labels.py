@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import png_color_label_ref as CR  # noqa: E402
 import png_label_ref as LR  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 FILL = 0xEE
 PACK, MAP = 0, 1
@@ -92,8 +93,8 @@ def run_gather(srcs, jobs, size, dtype, maps=None, missing=-1, run=None, grid=0)
     out = _aligned(4096 + len(jobs) * slot + 4096, FILL)
     cnt = np.zeros(len(jobs) + 2, dtype=np.uint32)
     cnt[0] = cnt[-1] = 0xDEAD
-    assert _emu().emu_png_color_label_batch(a.ctypes.data, out.ctypes.data + 4096, (ColorLabelTask * n)(*tasks), tb.ctypes.data,
-                                            cnt.ctypes.data + 4 if maps is not None else None, n, grid) == 0
+    assert launch("png_color_label", a, out[4096:], (ColorLabelTask * n)(*tasks), tb, cnt[1:] if maps is not None else None, n, grid,
+                  emu=_emu) == 0
     assert (out[:4096] == FILL).all() and (out[4096 + len(jobs) * slot:] == FILL).all(), "the sentinel around the tensor was written"
     assert cnt[0] == 0xDEAD and cnt[-1] == 0xDEAD
     return out[4096: 4096 + len(jobs) * slot].view(CR.DTYPES[dtype]).reshape(len(jobs), H, W), cnt[1:-1].tolist()
@@ -274,7 +275,7 @@ def test_probing_terminates_on_a_table_without_an_empty_slot():
     cnt = np.zeros(1, dtype=np.uint32)
     t = ColorLabelTask(src_off=1, out_off=0, sx_off=16, sy_off=32, map_off=0, src_pitch=4, out_w=4, out_h=1, row0=0, rows=1, map_slots=2,
                        missing=-3, image=0, dtype=2, mode=MAP)
-    assert _emu().emu_png_color_label_batch(a.ctypes.data, out.ctypes.data, (ColorLabelTask * 1)(t), tb.ctypes.data, cnt.ctypes.data, 1, 0) == 0
+    assert launch("png_color_label", a, out, (ColorLabelTask * 1)(t), tb, cnt, 1, 0, emu=_emu) == 0
     assert out.view(np.int32).tolist() == [10, 20, -3, -3] and cnt[0] == 2
 
 

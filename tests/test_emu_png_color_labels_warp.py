@@ -22,6 +22,7 @@ import png_color_label_ref as CR  # noqa: E402
 import png_color_label_warp_ref as CW  # noqa: E402
 import test_emu_png_warp as EW  # noqa: E402  (the matrices of the label warp's tests)
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from debigulator_amd.api import png_warp_matrix  # noqa: E402
@@ -101,8 +102,8 @@ def run_warp(srcs, jobs, size, dtype, maps=None, missing=-1, mode=CONSTANT, bord
     out = _aligned(4096 + len(jobs) * slot + 4096, FILL)
     cnt = np.zeros(len(jobs) + 2, dtype=np.uint32)
     cnt[0] = cnt[-1] = 0xDEAD
-    assert _emu().emu_png_color_label_warp_batch(a.ctypes.data, out.ctypes.data + 4096, (ColorLabelWarpTask * n)(*tasks),
-                                                 tb.ctypes.data, cnt.ctypes.data + 4 if maps is not None else None, n, grid) == 0
+    assert launch("png_color_label_warp", a, out[4096:], (ColorLabelWarpTask * n)(*tasks), tb, cnt[1:] if maps is not None else None, n, grid,
+                  emu=_emu) == 0
     assert (out[:4096] == FILL).all() and (out[4096 + len(jobs) * slot:] == FILL).all(), "the sentinel around the tensor was written"
     assert cnt[0] == 0xDEAD and cnt[-1] == 0xDEAD
     return out[4096: 4096 + len(jobs) * slot].view(CR.DTYPES[dtype]).reshape(len(jobs), H, W), cnt[1:-1].tolist()
@@ -320,8 +321,7 @@ def test_probing_terminates_on_a_table_without_an_empty_slot():
     cnt = np.zeros(1, dtype=np.uint32)
     t = _task(EW.q((1, 0, 0, 0, 1, 0)), src_off=1, out_off=0, map_off=0, src_pitch=4, crop_w=4, crop_h=1, out_w=6, out_h=1, row0=0,
               rows=1, border_label=-3, map_slots=2, missing=-3, image=0, dtype=2, mode=MAP, border_mode=CONSTANT)
-    assert _emu().emu_png_color_label_warp_batch(a.ctypes.data, out.ctypes.data, (ColorLabelWarpTask * 1)(t), tb.ctypes.data,
-                                                 cnt.ctypes.data, 1, 0) == 0
+    assert launch("png_color_label_warp", a, out, (ColorLabelWarpTask * 1)(t), tb, cnt, 1, 0, emu=_emu) == 0
     assert out.view(np.int32).tolist() == [10, 20, -3, -3, -3, -3] and cnt[0] == 2  # two misses, two border elements
 
 

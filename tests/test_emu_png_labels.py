@@ -17,6 +17,7 @@ import png_label_ref as LR  # noqa: E402
 import png_spec_ref as R  # noqa: E402
 import test_emu_png_spec as T  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 FILL = 0xEE
 LABEL_FORMATS = [(0, 1), (0, 2), (0, 4), (0, 8), (0, 16), (3, 1), (3, 2), (3, 4), (3, 8)]
@@ -203,7 +204,7 @@ def run_gather(srcs, jobs, size, dtype, lut=None, run=None, grid=0):
     slot = H * W * es
     out = _aligned(4096 + len(jobs) * slot + 4096, FILL)
     lt = (C.c_int32 * 256)(*[int(v) for v in lut]) if lut is not None else None
-    assert _emu().emu_png_label_gather_batch(a.ctypes.data, out.ctypes.data + 4096, (LabelTask * n)(*tasks), tb.ctypes.data, lt, n, grid) == 0
+    assert launch("png_label_gather", a, out[4096:], (LabelTask * n)(*tasks), tb, lt, n, grid, emu=_emu) == 0
     assert (out[:4096] == FILL).all() and (out[4096 + len(jobs) * slot:] == FILL).all(), "the sentinel around the tensor was written"
     return out[4096: 4096 + len(jobs) * slot].view(LR.DTYPES[dtype]).reshape(len(jobs), H, W)
 

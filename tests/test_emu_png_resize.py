@@ -13,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import png_resize_ref as Z  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 
 class Task(C.Structure):  # include/debig_hip.h: debig_png_resize_task
@@ -111,7 +112,7 @@ def run(images, size, dtype, layout, aa, tile=(TILE_W, 64), grid=0, scale=(1, 1,
     wa = np.frombuffer(bytes(weights), np.uint8).copy()
     out = np.full(gap + n * slot + gap, FILL, np.uint8)
     TT = (Task * len(tasks))(*tasks)
-    assert _emu().emu_png_resize_batch(sa.ctypes.data, out.ctypes.data, TT, wa.ctypes.data, len(tasks), grid) == 0
+    assert launch("png_resize", sa, out, TT, wa, len(tasks), grid, emu=_emu) == 0
     assert (out[:gap] == FILL).all() and (out[gap + n * slot:] == FILL).all(), "bytes outside the tensor were written"
     np_dt = {Z.T_UINT: np.uint8 if P == 8 else np.uint16, Z.T_F32: np.float32, Z.T_F16: np.float16, Z.T_BF16: np.uint16}[dtype]
     return out[gap: gap + n * slot].view(np_dt).reshape((n, Cn, H, W) if layout == "chw" else (n, H, W, Cn))

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import png_alpha_ref as A  # noqa: E402
 import png_resize_ref as Z  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 from test_emu_png_resize import ES, FILL, HQ_CAP, SCALE, BIAS, TILE_W, WX_CAP, Task, axis_table  # noqa: E402
 
 
@@ -98,7 +99,7 @@ def run(images, size, mode, dtype, layout, aa, bg=(0, 0, 0), tile=(TILE_W, 64), 
     wa = np.frombuffer(bytes(weights), np.uint8).copy()
     out = np.full(gap + n * slot + gap, FILL, np.uint8)
     TT = (AlphaTask * len(tasks))(*tasks)
-    assert _emu().emu_png_resize_alpha_batch(sa.ctypes.data, out.ctypes.data, TT, wa.ctypes.data, len(tasks), grid) == 0
+    assert launch("png_resize_alpha", sa, out, TT, wa, len(tasks), grid, emu=_emu) == 0
     assert (out[:gap] == FILL).all() and (out[gap + n * slot:] == FILL).all(), "bytes outside the tensor were written"
     np_dt = {Z.T_UINT: np.uint8 if P == 8 else np.uint16, Z.T_F32: np.float32, Z.T_F16: np.float16, Z.T_BF16: np.uint16}[dtype]
     return out[gap: gap + n * slot].view(np_dt).reshape((n, oc, H, W) if layout == "chw" else (n, H, W, oc))

@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import png_resize_ref as Z  # noqa: E402
 import png_tone_ref as T  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 FILL, GAP = 0xEE, 4096
 SCALE, BIAS = (1 / 0.229, 1 / 0.224, 1 / 0.225, 3.0), (-0.485 / 0.229, -0.456 / 0.224, -0.406 / 0.225, 0.25)
@@ -106,9 +107,8 @@ def run(files, size, dtype, layout, run_len=RUN, grid=0, spoil=None):
     hist = np.zeros((len(hist_files), cc, 256), np.uint32)
     la = np.frombuffer(bytes(luts), np.uint8).copy()
     out = np.full(GAP + len(files) * slot + GAP, FILL, np.uint8)
-    L = _emu()
-    assert L.emu_png_tone_hist_batch(a.ctypes.data, hist.ctypes.data, arr, n_hist_tasks, grid) == 0
-    assert L.emu_png_tone_apply_batch(a.ctypes.data, out.ctypes.data, arr, hist.ctypes.data, la.ctypes.data, n, grid) == 0
+    assert launch("png_tone_hist", a, hist, arr, n_hist_tasks, grid, emu=_emu) == 0
+    assert launch("png_tone_apply", a, out, arr, hist, la, n, grid, emu=_emu) == 0
     assert (out[:GAP] == FILL).all() and (out[GAP + len(files) * slot:] == FILL).all(), "the sentinel around the tensor was written"
     npdt = {0: np.uint8, 1: np.float32, 2: np.float16, 3: np.uint16}[code]
     shape = (len(files), ch, H, W) if layout == "chw" else (len(files), H, W, ch)

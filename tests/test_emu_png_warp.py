@@ -21,6 +21,7 @@ import png_label_ref as LR  # noqa: E402
 import png_resize_ref as Z  # noqa: E402
 import png_warp_ref as WR  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from debigulator_amd.api import png_warp_matrix  # noqa: E402
@@ -108,7 +109,7 @@ def run_warp(srcs, jobs, size, dtype="uint", layout="hwc", filt=WR.BILINEAR, mod
             tasks.append(t)
     n = len(tasks)
     out = _aligned(4096 + len(jobs) * slot + 4096, FILL)
-    assert _emu().emu_png_warp_batch(a.ctypes.data, out.ctypes.data + 4096, (WarpTask * n)(*tasks), n, grid) == 0
+    assert launch("png_warp", a, out[4096:], (WarpTask * n)(*tasks), n, grid, emu=_emu) == 0
     assert (out[:4096] == FILL).all() and (out[4096 + len(jobs) * slot:] == FILL).all(), "the sentinel around the tensor was written"
     npdt = {0: np.uint8 if P == 8 else np.uint16, 1: np.float32, 2: np.float16, 3: np.uint16}[code]
     shape = (len(jobs), ch, H, W) if layout == "chw" else (len(jobs), H, W, ch)
@@ -136,7 +137,7 @@ def run_label_warp(srcs, jobs, size, dtype, mode=WR.CONSTANT, border_label=0, lu
     slot = H * W * es
     out = _aligned(4096 + len(jobs) * slot + 4096, FILL)
     lt = (C.c_int32 * 256)(*[int(v) for v in lut]) if lut is not None else None
-    assert _emu().emu_png_label_warp_batch(a.ctypes.data, out.ctypes.data + 4096, (LabelWarpTask * n)(*tasks), lt, n, grid) == 0
+    assert launch("png_label_warp", a, out[4096:], (LabelWarpTask * n)(*tasks), lt, n, grid, emu=_emu) == 0
     assert (out[:4096] == FILL).all() and (out[4096 + len(jobs) * slot:] == FILL).all(), "the sentinel around the tensor was written"
     return out[4096: 4096 + len(jobs) * slot].view(LR.DTYPES[dtype]).reshape(len(jobs), H, W)
 
