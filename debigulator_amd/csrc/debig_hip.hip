@@ -15,6 +15,7 @@
 #include "png_fused_kernel.inc"
 #include "png_spec_kernel.inc"
 #include "apng_kernel.inc"
+#include "png_stage_common.inc"
 #include "png_resize_kernel.inc"
 #include "png_label_kernel.inc"
 #include "png_color_label_kernel.inc"
@@ -743,94 +744,87 @@ int debig_hip_png_defilter_batch(const void *d_streams_arena, void *d_rgba_arena
     return (int)hipGetLastError();
 }
 
+} // extern "C"
+
+// one launch of a task kernel: `grid` workgroups of `threads` lanes on the stream's device; an empty batch launches nothing
+template <class... Params, class... Args>
+static int launch_tasks(void (*kernel)(Params...), uint32_t grid, uint32_t threads, void *hip_stream, Args... args)
+{
+    if (grid == 0) return 0;
+    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, (hipStream_t)hip_stream, args...);
+    return (int)hipGetLastError();
+}
+
+// ... of a tensor-stage kernel: the grid is capped (stage_grid), the kernel loops over its n_tasks, its last argument
+template <class... Params, class... Args>
+static int launch_stage(void (*kernel)(Params...), uint32_t threads, uint32_t n_tasks, void *hip_stream, Args... args)
+{
+    return launch_tasks(kernel, stage_grid(n_tasks), threads, hip_stream, args..., n_tasks);
+}
+
+extern "C" {
+
 // the general de-filter (png_spec_kernel.inc): one workgroup of PNG_SPEC_NWD wavefronts per (image, pass) task
 int debig_hip_png_spec_defilter_batch(void *d_arena, void *d_rgba_arena, const debig_png_spec_task *d_tasks,
                                       debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
 {
-    if (n == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    hipLaunchKernelGGL(debig_png_spec_defilter_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
-                       (uint8_t *)d_arena, (uint8_t *)d_rgba_arena, d_tasks, d_results, n);
-    return (int)hipGetLastError();
+    return launch_tasks(debig_png_spec_defilter_kernel, n, 64 * PNG_SPEC_NWD, hip_stream, (uint8_t *)d_arena, (uint8_t *)d_rgba_arena,
+                        d_tasks, d_results, n);
 }
 
 int debig_hip_png_spec_defilter_fmt_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
                                           debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
 {
-    if (n == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    hipLaunchKernelGGL(debig_png_spec_defilter_fmt_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
-                       (uint8_t *)d_arena, (uint8_t *)d_out_arena, d_tasks, d_results, n);
-    return (int)hipGetLastError();
+    return launch_tasks(debig_png_spec_defilter_fmt_kernel, n, 64 * PNG_SPEC_NWD, hip_stream, (uint8_t *)d_arena,
+                        (uint8_t *)d_out_arena, d_tasks, d_results, n);
 }
 
 int debig_hip_png_spec_defilter_planar_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
                                              debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
 {
-    if (n == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    hipLaunchKernelGGL(debig_png_spec_defilter_planar_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
-                       (uint8_t *)d_arena, (uint8_t *)d_out_arena, d_tasks, d_results, n);
-    return (int)hipGetLastError();
+    return launch_tasks(debig_png_spec_defilter_planar_kernel, n, 64 * PNG_SPEC_NWD, hip_stream, (uint8_t *)d_arena,
+                        (uint8_t *)d_out_arena, d_tasks, d_results, n);
 }
 
 // ... and to raw labels (palette indices, grey samples as stored): colour types 3 and 0 only
 int debig_hip_png_spec_defilter_index_batch(void *d_arena, void *d_out_arena, const debig_png_spec_task *d_tasks,
                                             debig_png_spec_result *d_results, uint32_t n, void *hip_stream)
 {
-    if (n == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    hipLaunchKernelGGL(debig_png_spec_defilter_index_kernel, dim3(n), dim3(64 * PNG_SPEC_NWD), 0, (hipStream_t)hip_stream,
-                       (uint8_t *)d_arena, (uint8_t *)d_out_arena, d_tasks, d_results, n);
-    return (int)hipGetLastError();
+    return launch_tasks(debig_png_spec_defilter_index_kernel, n, 64 * PNG_SPEC_NWD, hip_stream, (uint8_t *)d_arena,
+                        (uint8_t *)d_out_arena, d_tasks, d_results, n);
 }
 
 // APNG compositing (apng_kernel.inc): one workgroup of 256 lanes per canvas slice; the grid is capped, the kernel loops
 int debig_hip_apng_composite_batch(const void *d_frames_arena, void *d_out_arena, const debig_apng_task *d_tasks,
                                    uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_apng_composite_kernel, dim3(grid), dim3(APNG_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_frames_arena, (uint8_t *)d_out_arena, d_tasks, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_apng_composite_kernel, APNG_THREADS, n_tasks, hip_stream, (const uint8_t *)d_frames_arena,
+                        (uint8_t *)d_out_arena, d_tasks);
 }
 
 // resize + normalise (png_resize_kernel.inc): one workgroup of 256 lanes per output tile; the grid is capped, the kernel loops
 int debig_hip_png_resize_batch(const void *d_src_arena, void *d_out, const debig_png_resize_task *d_tasks,
                                const void *d_weights, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_resize_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_resize_kernel, RSZ_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena, (uint8_t *)d_out,
+                        d_tasks, (const uint8_t *)d_weights);
 }
 
 // ... and its twin with alpha (premultiply, filter, composite or keep premultiplied): the same grid rule
 int debig_hip_png_resize_alpha_batch(const void *d_src_arena, void *d_out, const debig_png_resize_alpha_task *d_tasks,
                                      const void *d_weights, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_resize_alpha_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_resize_alpha_kernel, RSZ_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights);
 }
 
 // ... and the signed filter (bicubic: weights of either sign), straight or with alpha: the same grid rule
 int debig_hip_png_resize_cubic_batch(const void *d_src_arena, void *d_out, const debig_png_resize_cubic_task *d_tasks,
                                      const void *d_weights, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_resize_cubic_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_resize_cubic_kernel, RSZ_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights);
 }
 
 // crop + nearest pick + remap + widening of raw labels (png_label_kernel.inc): one workgroup of 256 lanes per run of output
@@ -838,12 +832,8 @@ int debig_hip_png_resize_cubic_batch(const void *d_src_arena, void *d_out, const
 int debig_hip_png_label_gather_batch(const void *d_src_arena, void *d_out, const debig_png_label_task *d_tasks,
                                      const void *d_tables, const int32_t *d_lut, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_label_gather_kernel, dim3(grid), dim3(LBL_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_lut, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_label_gather_kernel, LBL_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_lut);
 }
 
 // crop + nearest pick + colour pack + colour -> class lookup + widening of RGB8 masks (png_color_label_kernel.inc): one
@@ -851,12 +841,8 @@ int debig_hip_png_label_gather_batch(const void *d_src_arena, void *d_out, const
 int debig_hip_png_color_label_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_task *d_tasks,
                                     const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_color_label_kernel, dim3(grid), dim3(CLBL_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_color_label_kernel, CLBL_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched);
 }
 
 // crop + affine warp + normalise (png_warp_kernel.inc): one workgroup of 256 lanes per run of output rows, one lane per
@@ -864,94 +850,61 @@ int debig_hip_png_color_label_batch(const void *d_src_arena, void *d_out, const 
 int debig_hip_png_warp_batch(const void *d_src_arena, void *d_out, const debig_png_warp_task *d_tasks, uint32_t n_tasks,
                              void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_warp_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_warp_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena, (uint8_t *)d_out,
+                        d_tasks);
 }
 
 // ... and the same warp of raw labels (nearest pick, remap, widening)
 int debig_hip_png_label_warp_batch(const void *d_src_arena, void *d_out, const debig_png_label_warp_task *d_tasks,
                                    const int32_t *d_lut, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_label_warp_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, d_lut, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_label_warp_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, d_lut);
 }
 
 // ... and of colour-coded masks (png_color_label_warp_kernel.inc): the same tasks, the lookup table of the colour-label gather
 int debig_hip_png_color_label_warp_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_warp_task *d_tasks,
                                          const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_color_label_warp_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_color_label_warp_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched);
 }
 
 // the resize and the warp with a colour matrix per image (png_color_kernel.inc): the tasks and grid rules of the kernels they extend
 int debig_hip_png_resize_color_batch(const void *d_src_arena, void *d_out, const debig_png_resize_color_task *d_tasks,
                                      const void *d_weights, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_resize_color_kernel, dim3(grid), dim3(RSZ_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_resize_color_kernel, RSZ_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights);
 }
 
 int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const debig_png_warp_color_task *d_tasks,
                                    const void *d_weights, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_warp_color_kernel, dim3(grid), dim3(WARP_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src_arena, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_warp_color_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights);
 }
 
 // the tone curves of the tensor decode (png_tone_kernel.inc): one workgroup per pixel run, as many workgroups as tasks
 int debig_hip_png_tone_hist_batch(const void *d_src, uint32_t *d_hist, const debig_png_tone_task *d_tasks, uint32_t n_tasks,
                                   void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_tone_hist_kernel, dim3(grid), dim3(TONE_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src, d_hist, d_tasks, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_tone_hist_kernel, TONE_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src, d_hist, d_tasks);
 }
 
 int debig_hip_png_tone_apply_batch(const void *d_src, void *d_out, const debig_png_tone_task *d_tasks, const uint32_t *d_hist,
                                    const void *d_tables, uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_tone_apply_kernel, dim3(grid), dim3(TONE_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks, d_hist, (const uint8_t *)d_tables, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_tone_apply_kernel, TONE_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src, (uint8_t *)d_out,
+                        d_tasks, d_hist, (const uint8_t *)d_tables);
 }
 
 // Gaussian blur and sharpness of the tensor decode (png_blur_kernel.inc): one workgroup per output tile, as many workgroups as tasks
 int debig_hip_png_blur_batch(const void *d_src, void *d_out, const debig_png_blur_task *d_tasks, const void *d_tables,
                              uint32_t n_tasks, void *hip_stream)
 {
-    if (n_tasks == 0) return 0;
-    DeviceGuard launch_guard(launch_device((hipStream_t)hip_stream));
-    const uint32_t grid = stage_grid(n_tasks);
-    hipLaunchKernelGGL(debig_png_blur_kernel, dim3(grid), dim3(BLUR_THREADS), 0, (hipStream_t)hip_stream,
-                       (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, n_tasks);
-    return (int)hipGetLastError();
+    return launch_stage(debig_png_blur_kernel, BLUR_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks,
+                        (const uint8_t *)d_tables);
 }
 
 // inflate -> de-filter in one kernel (png_fused_kernel.inc).  Per group of at most SPLIT_GROUP

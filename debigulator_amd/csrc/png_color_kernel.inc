@@ -12,15 +12,17 @@
 // color_off and read once per task at a uniform address (scalar loads); it is passed on by value and indexed by unrolled
 // constants only, so nothing goes to scratch.
 //   - debig_png_resize_color_kernel: the tile, the axis tables, the LDS budget and pass 1 are those of debig_png_resize_kernel
-//     (the channels are independent there: items per SAMPLE).  Pass 2 takes an output PIXEL per item, lanes along x: the lane
-//     sums its 3 or 4 channels down the Hq rows (halfwords that lie side by side in LDS), mixes, converts and stores that many
-//     adjacent elements (HWC) or one element in each plane row, adjacent to its neighbour lanes' (CHW): the store shapes of
-//     the alpha kernel.
-//   - debig_png_warp_color_kernel: warp_rows of png_warp_kernel.inc with the per-channel store replaced by collect, mix, store.
-//     Picks, border rule and clamps are the warp kernel's; a CONSTANT border sample is mixed like any other sample.
+//     (rsz_tile_begin, rsz_sample_pass1; the channels are independent there: items per SAMPLE).  Pass 2 takes an output PIXEL
+//     per item, lanes along x: the lane sums its 3 or 4 channels down the Hq rows (halfwords that lie side by side in LDS),
+//     mixes, converts and stores that many adjacent elements (HWC) or one element in each plane row, adjacent to its neighbour
+//     lanes' (CHW): the store shapes of the alpha kernel.
+//   - debig_png_warp_color_kernel: the walk and the picks of png_warp_kernel.inc (warp_walk, warp_pick, warp_taps) with the
+//     per-channel store of warp_rows replaced by collect, mix, store.  Picks, border rule and clamps are the warp kernel's; a
+//     CONSTANT border sample is mixed like any other sample.
 // A task that breaks a bound -- those of the kernels they extend, channels other than 3 / 4, a color_off that is no multiple of
 // 8, a record beyond the quantiser's limits -- is skipped (never indexed out of range).  No atomics, no scratch, nothing shared
 // between workgroups; plain vector stores only.
+// This file holds the mix and the two bodies that apply it; it repeats no step of the kernels it extends.
 // Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_resize_kernel.inc and png_warp_kernel.inc in
 // front of it.
 
@@ -56,7 +58,7 @@ RSZ_UNROLL
 template <uint32_t P>
 DEV_INLINE void rsz_color_pass2(const RszLds &lds, const debig_png_resize_color_task &t,
                                 const debig_png_resize_color_task *__restrict__ tg, const debig_png_color_rec &cr,
-                                uint8_t *__restrict__ out, const uint32_t *ty, const int16_t *wyg, uint32_t mty, uint32_t tid)
+                                uint8_t *__restrict__ out, const RszAxes &ax, uint32_t tid)
 {
     constexpr uint32_t VMAX = ((1u << P) - 1u) << (30u - P);
     const uint32_t tw = t.tile_w, sc = t.channels, twc = tw * sc, n2 = t.tile_h * tw;
@@ -64,8 +66,8 @@ DEV_INLINE void rsz_color_pass2(const RszLds &lds, const debig_png_resize_color_
     uint8_t *o = out + t.out_off;
     for (uint32_t i = tid; i < n2; i += RSZ_THREADS) {
         const uint32_t yy = i / tw, x = i - yy * tw;
-        const uint32_t Y = t.tile_y + yy, fy = ty[2u + 2u * Y], cnt = ty[3u + 2u * Y];
-        const int16_t *w = wyg + (uint64_t)Y * mty;
+        const uint32_t Y = t.tile_y + yy, fy = ax.ty[2u + 2u * Y], cnt = ax.ty[3u + 2u * Y];
+        const int16_t *w = ax.wyg + (uint64_t)Y * ax.mty;
         const uint16_t *h = &lds.hq[(fy - t.src_y0) * twc + x * sc];
         uint32_t v[3], m[3], va = 0u;
 RSZ_UNROLL
@@ -93,59 +95,27 @@ debig_png_resize_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restri
     const uint32_t tid = threadIdx.x;
     for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
         const debig_png_resize_color_task t = tasks[ti];
-        const uint32_t *tx = reinterpret_cast<const uint32_t *>(weights + t.wx_off);
-        const uint32_t *ty = reinterpret_cast<const uint32_t *>(weights + t.wy_off);
-        const uint32_t mtx = tx[0], mty = ty[0], ch = t.channels, twc = t.tile_w * ch;
-        const int16_t *wxg = reinterpret_cast<const int16_t *>(tx + 2u + 2u * tx[1]);
-        const int16_t *wyg = reinterpret_cast<const int16_t *>(ty + 2u + 2u * ty[1]);
         // (uniform over the workgroup: every lane skips, or none)
-        if (t.tile_w == 0u || t.tile_w > DEBIG_PNG_RESIZE_TILE_W || (ch != 3u && ch != 4u) || (t.bits != 8u && t.bits != 16u) ||
-            t.dtype > 3u || (t.color_off & 7u) || (uint64_t)t.tile_w * mtx > DEBIG_PNG_RESIZE_WX_CAP ||
-            (uint64_t)t.src_rows * twc > DEBIG_PNG_RESIZE_HQ_CAP)
+        if ((t.channels != 3u && t.channels != 4u) || (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.color_off & 7u)) continue;
+        debig_png_color_rec cr;
+        RszAxes ax;
+        if (!rsz_tile_begin(lds, t, weights, tid, ax, [&] {
+                cr = *reinterpret_cast<const debig_png_color_rec *>(weights + t.color_off);
+                return color_rec_ok(cr, t.bits);
+            }))
             continue;
-        const debig_png_color_rec cr = *reinterpret_cast<const debig_png_color_rec *>(weights + t.color_off);
-        if (!color_rec_ok(cr, t.bits)) continue;
-        __syncthreads(); // the previous task's pass 2 has read its LDS
-        if (tid < t.tile_w) {
-            lds.fx[tid] = tx[2u + 2u * (t.tile_x + tid)];
-            lds.cx[tid] = tx[3u + 2u * (t.tile_x + tid)];
-        }
-        for (uint32_t i = tid; i < t.tile_w * mtx; i += RSZ_THREADS) lds.wx[i] = wxg[(uint64_t)t.tile_x * mtx + i];
-        __syncthreads();
-        // ---- pass 1 (that of debig_png_resize_kernel): Hq[r][x][c] = (sum_k wx[x][k] * s[r][fx[x] + k][c] + 2^(P-3)) >> (P-2)
-        const uint32_t n1 = t.src_rows * twc, sh1 = (uint32_t)t.bits - 2u, rnd1 = 1u << ((uint32_t)t.bits - 3u);
-        {
-            uint32_t r = tid / twc, e = tid - r * twc;
-            const uint32_t dr = RSZ_THREADS / twc, de = RSZ_THREADS - dr * twc;
-            for (uint32_t i = tid; i < n1; i += RSZ_THREADS) {
-                const uint32_t x = rsz_div_ch(e, ch), c = e - x * ch, cnt = lds.cx[x];
-                const uint64_t s0 = (uint64_t)(t.src_y0 + r) * t.src_pitch + (uint64_t)lds.fx[x] * ch + c;
-                const int16_t *w = &lds.wx[x * mtx];
-                uint32_t acc = 0u;
-                if (t.bits == 8u) {
-                    const uint8_t *p = src + t.src_off + s0;
-                    for (uint32_t k = 0; k < cnt; k++) acc += (uint32_t)w[k] * p[(uint64_t)k * ch];
-                } else {
-                    const uint16_t *p = reinterpret_cast<const uint16_t *>(src + t.src_off) + s0;
-                    for (uint32_t k = 0; k < cnt; k++) acc += (uint32_t)w[k] * p[(uint64_t)k * ch];
-                }
-                lds.hq[i] = (uint16_t)((acc + rnd1) >> sh1);
-                r += dr;
-                e += de;
-                if (e >= twc) { e -= twc; r++; }
-            }
-        }
+        rsz_sample_pass1(lds, t, src, ax.mtx, tid);
         __syncthreads();
         // ---- pass 2: v_c = sum_k wy[Y][k] * Hq[fy[Y] + k][x][c] of the pixel's channels, the mix, then the one conversion
-        if (t.bits == 8u) rsz_color_pass2<8u>(lds, t, &tasks[ti], cr, out, ty, wyg, mty, tid);
-        else rsz_color_pass2<16u>(lds, t, &tasks[ti], cr, out, ty, wyg, mty, tid);
+        if (t.bits == 8u) rsz_color_pass2<8u>(lds, t, &tasks[ti], cr, out, ax, tid);
+        else rsz_color_pass2<16u>(lds, t, &tasks[ti], cr, out, ax, tid);
     }
 }
 
 // ---- the warp with the matrix ------------------------------------------------------------------------------------------------------
 
-// the rows of one task at source precision P: warp_rows, the pixel's channels collected, mixed and stored; the channel count sc is a
-// run-time value as in rsz_color_pass2
+// the rows of one task at source precision P: the walk and the picks of warp_rows (png_warp_kernel.inc), the pixel's channels
+// collected, mixed and stored; the channel count sc is a run-time value as in rsz_color_pass2
 template <uint32_t P>
 DEV_INLINE void warp_color_rows(const debig_png_warp_color_task &t, const debig_png_warp_color_task *__restrict__ tg,
                                 const debig_png_color_rec &cr, const uint8_t *__restrict__ src, uint8_t *__restrict__ out, uint32_t tid)
@@ -154,68 +124,37 @@ DEV_INLINE void warp_color_rows(const debig_png_warp_color_task &t, const debig_
     constexpr uint32_t VMAX = ((1u << P) - 1u) << (30u - P);
     const sample_t *s = reinterpret_cast<const sample_t *>(src + t.src_off);
     uint8_t *o = out + t.out_off;
-    const uint32_t n = t.rows * t.out_w, sc = t.channels;
+    const uint32_t sc = t.channels;
     const bool alpha = sc == 4u;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    uint32_t r = tid / t.out_w, X = tid - r * t.out_w;
-    const uint32_t dr = WARP_THREADS / t.out_w, dx = WARP_THREADS - dr * t.out_w;
-    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
-        const uint32_t Y = t.row0 + r;
-        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
-        const int64_t U = t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], V = t.m[3] * cx + t.m[4] * cy + 2 * t.m[5];
+    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         uint32_t v[3], m[3], va = 0u;
         if (nearest) {
-            bool inx, iny;
-            const uint32_t jx = warp_clamp(U >> 17, t.crop_w, &inx), jy = warp_clamp(V >> 17, t.crop_h, &iny);
-            const bool keep = clamp || (inx && iny);
-            const uint64_t at = (uint64_t)jy * t.src_pitch + (uint64_t)jx * sc;
+            const WarpPick p = warp_pick(t, clamp, U, V);
+            const uint64_t at = (uint64_t)p.jy * t.src_pitch + (uint64_t)p.jx * sc;
 RSZ_UNROLL
             for (uint32_t c = 0; c < 3u; c++) {
                 uint32_t sv = s[at + c];
-                if (!keep) sv = tg->border[c];
+                if (!p.keep) sv = tg->border[c];
                 v[c] = sv << (30u - P);
             }
             if (alpha) {
                 uint32_t sv = s[at + 3u];
-                if (!keep) sv = tg->border[3];
+                if (!p.keep) sv = tg->border[3];
                 va = sv << (30u - P);
             }
         } else {
-            const int64_t tu = U - 65536, tv = V - 65536;
-            const int64_t ix = tu >> 17, iy = tv >> 17;
-            const uint32_t w1x = ((uint32_t)(tu & 0x1FFFF) + 4u) >> 3, w0x = 16384u - w1x;
-            const uint32_t w1y = ((uint32_t)(tv & 0x1FFFF) + 4u) >> 3, w0y = 16384u - w1y;
-            bool ix0, ix1, iy0, iy1;
-            const uint32_t x0 = warp_clamp(ix, t.crop_w, &ix0), x1 = warp_clamp(ix + 1, t.crop_w, &ix1);
-            const uint32_t y0 = warp_clamp(iy, t.crop_h, &iy0), y1 = warp_clamp(iy + 1, t.crop_h, &iy1);
-            const bool k00 = clamp || (ix0 && iy0), k01 = clamp || (ix1 && iy0), k10 = clamp || (ix0 && iy1), k11 = clamp || (ix1 && iy1);
-            const uint64_t r0 = (uint64_t)y0 * t.src_pitch, r1 = (uint64_t)y1 * t.src_pitch;
-            const uint64_t c0 = (uint64_t)x0 * sc, c1 = (uint64_t)x1 * sc;
-            // one channel's two-pass bilinear value
-            auto tap = [&](uint32_t c) -> uint32_t {
-                const uint32_t bd = tg->border[c];
-                uint32_t s00 = s[r0 + c0 + c], s01 = s[r0 + c1 + c], s10 = s[r1 + c0 + c], s11 = s[r1 + c1 + c];
-                if (!k00) s00 = bd;
-                if (!k01) s01 = bd;
-                if (!k10) s10 = bd;
-                if (!k11) s11 = bd;
-                const uint32_t h0 = (w0x * s00 + w1x * s01 + (1u << (P - 3u))) >> (P - 2u);
-                const uint32_t h1 = (w0x * s10 + w1x * s11 + (1u << (P - 3u))) >> (P - 2u);
-                return w0y * h0 + w1y * h1;
-            };
+            const WarpTaps q = warp_taps(t, clamp, U, V);
 RSZ_UNROLL
-            for (uint32_t c = 0; c < 3u; c++) v[c] = tap(c);
-            if (alpha) va = tap(3u);
+            for (uint32_t c = 0; c < 3u; c++) v[c] = q.value<P>(s, c, tg->border[c]);
+            if (alpha) va = q.value<P>(s, 3u, tg->border[3]);
         }
         color_mix(cr, VMAX, v, m);
 RSZ_UNROLL
         for (uint32_t c = 0; c < 3u; c++) rsz_cubic_store(t.dtype, P, tg->a[c], tg->b[c], o, el + (uint64_t)c * t.out_sc, m[c]);
         if (alpha) rsz_cubic_store(t.dtype, P, tg->a[3], tg->b[3], o, el + (uint64_t)3u * t.out_sc, va);
-        r += dr;
-        X += dx;
-        if (X >= t.out_w) { X -= t.out_w; r++; }
-    }
+    });
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)

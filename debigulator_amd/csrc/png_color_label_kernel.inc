@@ -21,7 +21,7 @@
 //     task goes to the image's counter.
 // A task that breaks a bound is skipped (never indexed out of range); PACK never touches the table or the counters.
 // No scratch (every per-item array is indexed by unrolled constants), no inline assembly.
-// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_spec_kernel.inc and png_label_kernel.inc
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_stage_common.inc and png_label_kernel.inc
 // in front of it.
 
 #define CLBL_THREADS 256u
@@ -60,59 +60,46 @@ DEV_INLINE uint32_t clbl_pick(const uint8_t *__restrict__ s0, uint64_t el, const
     return pv.val;
 }
 
-// the rows of one task: elements of ES bytes, E per item -> the lane's misses
+// the rows of one task: the row body of the raw-label gather (lbl_gather_rows) with the colour pick -> the lane's misses
 template <uint32_t ES, uint32_t E, bool MAP>
 DEV_INLINE uint32_t clbl_rows(const uint2 *tab, const debig_png_color_label_task &t, const uint8_t *__restrict__ src,
                               uint8_t *__restrict__ out, const uint32_t *__restrict__ sx, const uint32_t *__restrict__ sy, uint32_t tid)
 {
-    constexpr uint32_t ND = E * ES / 4u; /* dwords of a full item */
-    const uint32_t ipr = (t.out_w + E - 1u) / E, n = t.rows * ipr; /* items per row (<= 8192), items of the task */
-    uint32_t r = tid / ipr, g = tid - r * ipr, misses = 0u;
-    const uint32_t dr = CLBL_THREADS / ipr, dg = CLBL_THREADS - dr * ipr;
     const uint8_t *s0 = src + t.src_off;
     const uint32_t missing = (uint32_t)t.missing;
+    uint32_t misses = 0u;
     ClblPrev pv;
     pv.key = DEBIG_PNG_CMAP_EMPTY; pv.val = missing; pv.hit = 0u; /* no 24-bit key equals it */
-    for (uint32_t i = tid; i < n; i += CLBL_THREADS) {
-        const uint32_t Y = t.row0 + r, x = g * E;
-        const uint64_t srow = (uint64_t)sy[Y] * t.src_pitch;
-        uint8_t *o = out + t.out_off + ((uint64_t)Y * t.out_w + x) * ES;
-        if (x + E <= t.out_w) {
-            uint32_t ix[E], B[ND];
-            if (E == 2u) {
-                const uint2 q = *reinterpret_cast<const uint2 *>(sx + x);
-                ix[0] = q.x; ix[1] = q.y;
-            } else {
-DEV_UNROLL
-                for (uint32_t j = 0; j < E / 4u; j++) {
-                    const uint4 q = *reinterpret_cast<const uint4 *>(sx + x + 4u * j);
-                    ix[4u * j] = q.x; ix[4u * j + 1u] = q.y; ix[4u * j + 2u] = q.z; ix[4u * j + 3u] = q.w;
-                }
-            }
-DEV_UNROLL
-            for (uint32_t j = 0; j < ND; j++) B[j] = 0u;
-DEV_UNROLL
-            for (uint32_t j = 0; j < E; j++) {
-                const uint32_t v = clbl_pick<MAP>(s0, srow + ix[j], tab, t.map_slots, missing, pv, misses);
-                if (ES == 1u) B[j / 4u] |= (v & 0xffu) << (8u * (j & 3u));
-                else if (ES == 2u) B[j / 2u] |= (v & 0xffffu) << (16u * (j & 1u));
-                else if (ES == 4u) B[j] = v;
-                else { B[2u * j] = v; B[2u * j + 1u] = (uint32_t)((int32_t)v >> 31); }
-            }
-            spec_store_run<E * ES>(o, B);
-        } else {
-DEV_UNROLL
-            for (uint32_t j = 0; j < E; j++) {
-                if (x + j >= t.out_w) break;
-                const uint32_t v = clbl_pick<MAP>(s0, srow + sx[x + j], tab, t.map_slots, missing, pv, misses);
-                lbl_store1<ES>(o + j * ES, v);
-            }
-        }
-        r += dr;
-        g += dg;
-        if (g >= ipr) { g -= ipr; r++; }
-    }
+    lbl_gather_rows<ES, E>(t, out, sx, sy, tid,
+                           [&](uint64_t el) -> uint32_t { return clbl_pick<MAP>(s0, el, tab, t.map_slots, missing, pv, misses); });
     return misses;
+}
+
+// ---- what the two colour-label kernels share (this file, png_color_label_warp_kernel.inc) ---------------------------------------
+
+// the table a workgroup holds in LDS: staged when the task's table offset or slot count differs from the one held
+struct ClblHeld {
+    uint64_t off;   /* ~0: none yet */
+    uint32_t slots;
+};
+template <class Task>
+DEV_INLINE void clbl_hold_map(uint2 *lds_map, ClblHeld &held, const Task &t, const uint8_t *__restrict__ tables, uint32_t tid)
+{
+    if (t.map_off == held.off && t.map_slots == held.slots) return;
+    __syncthreads(); /* nobody still probes the table that goes */
+    const uint2 *gt = reinterpret_cast<const uint2 *>(tables + t.map_off);
+    for (uint32_t k = tid; k < t.map_slots; k += CLBL_THREADS) lds_map[k] = gt[k];
+    __syncthreads();
+    held.off = t.map_off;
+    held.slots = t.map_slots;
+}
+
+// the wavefront's misses of one task -> ONE atomicAdd; every lane must be here (the task loop is uniform)
+DEV_INLINE void clbl_add_misses(uint32_t *__restrict__ counter, uint32_t m, uint32_t tid)
+{
+DEV_UNROLL
+    for (uint32_t d = 32u; d >= 1u; d >>= 1) m += __shfl_xor(m, (int)d);
+    if ((tid & 63u) == 0u && m != 0u) atomicAdd(counter, m);
 }
 
 __global__ void __launch_bounds__(CLBL_THREADS)
@@ -123,8 +110,7 @@ debig_png_color_label_kernel(const uint8_t *__restrict__ src, uint8_t *__restric
     __shared__ uint2 lds_map[DEBIG_PNG_CMAP_MAX_SLOTS]; /* (key, value) per slot */
     const uint2 *tab = lds_map;
     const uint32_t tid = threadIdx.x;
-    uint64_t held_off = ~(uint64_t)0; /* the table in LDS: none yet */
-    uint32_t held_slots = 0u;
+    ClblHeld held = { ~(uint64_t)0, 0u };
     for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
         const debig_png_color_label_task t = tasks[ti];
         // (uniform over the workgroup: every lane skips, or none)
@@ -142,22 +128,12 @@ debig_png_color_label_kernel(const uint8_t *__restrict__ src, uint8_t *__restric
             else clbl_rows<8u, 2u, false>(tab, t, src, out, sx, sy, tid);
             continue;
         }
-        if (t.map_off != held_off || t.map_slots != held_slots) {
-            __syncthreads(); /* nobody still probes the table that goes */
-            const uint2 *gt = reinterpret_cast<const uint2 *>(tables + t.map_off);
-            for (uint32_t k = tid; k < t.map_slots; k += CLBL_THREADS) lds_map[k] = gt[k];
-            __syncthreads();
-            held_off = t.map_off;
-            held_slots = t.map_slots;
-        }
+        clbl_hold_map(lds_map, held, t, tables, tid);
         uint32_t m;
         if (t.dtype == 0u) m = clbl_rows<1u, 8u, true>(tab, t, src, out, sx, sy, tid);
         else if (t.dtype == 1u) m = clbl_rows<2u, 8u, true>(tab, t, src, out, sx, sy, tid);
         else if (t.dtype == 2u) m = clbl_rows<4u, 4u, true>(tab, t, src, out, sx, sy, tid);
         else m = clbl_rows<8u, 2u, true>(tab, t, src, out, sx, sy, tid);
-        // the wavefront's misses of this task: every lane is here (the task loop is uniform)
-DEV_UNROLL
-        for (uint32_t d = 32u; d >= 1u; d >>= 1) m += __shfl_xor(m, (int)d);
-        if ((tid & 63u) == 0u && m != 0u) atomicAdd(&unmatched[t.image], m);
+        clbl_add_misses(&unmatched[t.image], m, tid);
     }
 }

@@ -3,22 +3,22 @@
 // debig_hip_png_color_label_warp_batch).
 //
 // The colour-label gather (png_color_label_kernel.inc) with its sx / sy grid replaced by the pick of the label warp
-// (png_warp_kernel.inc): the same six int64 in the task, the same U, V in Q17, (jx, jy) = (U >> 17, V >> 17).
+// (png_warp_kernel.inc: warp_walk, warp_pick): the same six int64 in the task, the same U, V in Q17, (jx, jy) = (U >> 17, V >> 17).
 //   - one TASK is a run of output rows of one image, one workgroup of 256 lanes per task; an ITEM is one output element, the
 //     lanes run along X and on into the next row of the run (the decomposition of debig_png_label_warp_kernel);
 //   - both indices are clamped into the crop BEFORE they address memory, whatever the border mode; then three byte loads at
 //     src_off + (jy * src_pitch + jx) * 3: a pixel starts at any byte, and nothing outside the crop is read.  Under CONSTANT
 //     the looked-up value is replaced by border_label by a select: no branch diverges on the position;
 //   - the TABLE, its slot function and the probe are those of the gather (clbl_find), staged in LDS when the task's table
-//     offset or slot count differs from the one held, between the same two barriers;
+//     offset or slot count differs from the one held, between the same two barriers (clbl_hold_map);
 //   - no previous-key reuse: a lane's consecutive picks lie 256 output elements apart (other rows, other source pixels), and
 //     a wavefront skips its probe loop only when all 64 lanes repeat their key; what that could save is one ds_read_b64 and
 //     a multiply per element next to three dependent global byte loads (DESIGN.md has the reasoning);
 //   - misses are counted per lane over the task -- an element that took border_label is none --, summed over the wavefront
-//     with six shuffles, and ONE atomicAdd per wavefront and task goes to the image's counter.
+//     with six shuffles, and ONE atomicAdd per wavefront and task goes to the image's counter (clbl_add_misses).
 // A task that breaks a bound is skipped (never indexed out of range); PACK never touches the table or the counters.
 // No scratch, no inline assembly, plain vector stores only.
-// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_label_kernel.inc,
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_stage_common.inc,
 // png_color_label_kernel.inc and png_warp_kernel.inc in front of it.
 
 // the rows of one task: elements of ES bytes -> the lane's misses
@@ -27,31 +27,22 @@ DEV_INLINE uint32_t clbl_warp_rows(const uint2 *tab, const debig_png_color_label
                                    uint8_t *__restrict__ out, uint32_t tid)
 {
     const uint8_t *s0 = src + t.src_off;
-    const uint32_t n = t.rows * t.out_w, missing = (uint32_t)t.missing;
+    const uint32_t missing = (uint32_t)t.missing;
+    uint32_t misses = 0u;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
-    uint32_t r = tid / t.out_w, X = tid - r * t.out_w, misses = 0u;
-    const uint32_t dr = WARP_THREADS / t.out_w, dx = WARP_THREADS - dr * t.out_w;
-    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
-        const uint32_t Y = t.row0 + r;
-        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
-        const int64_t U = t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], V = t.m[3] * cx + t.m[4] * cy + 2 * t.m[5];
-        bool inx, iny;
-        const uint32_t jx = warp_clamp(U >> 17, t.crop_w, &inx), jy = warp_clamp(V >> 17, t.crop_h, &iny);
-        const bool keep = clamp || (inx && iny);
-        const uint8_t *p = s0 + ((uint64_t)jy * t.src_pitch + jx) * 3u;
+    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+        const WarpPick pk = warp_pick(t, clamp, U, V);
+        const uint8_t *p = s0 + ((uint64_t)pk.jy * t.src_pitch + pk.jx) * 3u;
         const uint32_t key = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
         uint32_t v = key;
         if (MAP) {
             v = missing;
             const bool hit = clbl_find(tab, t.map_slots, key, v);
-            misses += keep && !hit ? 1u : 0u;
+            misses += pk.keep && !hit ? 1u : 0u;
         }
-        if (!keep) v = (uint32_t)t.border_label;
+        if (!pk.keep) v = (uint32_t)t.border_label;
         lbl_store1<ES>(out + t.out_off + ((uint64_t)Y * t.out_w + X) * ES, v);
-        r += dr;
-        X += dx;
-        if (X >= t.out_w) { X -= t.out_w; r++; }
-    }
+    });
     return misses;
 }
 
@@ -63,8 +54,7 @@ debig_png_color_label_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__re
     __shared__ uint2 lds_map[DEBIG_PNG_CMAP_MAX_SLOTS]; /* (key, value) per slot */
     const uint2 *tab = lds_map;
     const uint32_t tid = threadIdx.x;
-    uint64_t held_off = ~(uint64_t)0; /* the table in LDS: none yet */
-    uint32_t held_slots = 0u;
+    ClblHeld held = { ~(uint64_t)0, 0u };
     for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
         const debig_png_color_label_warp_task t = tasks[ti];
         // (uniform over the workgroup: every lane skips, or none)
@@ -80,22 +70,12 @@ debig_png_color_label_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__re
             else clbl_warp_rows<8u, false>(tab, t, src, out, tid);
             continue;
         }
-        if (t.map_off != held_off || t.map_slots != held_slots) {
-            __syncthreads(); /* nobody still probes the table that goes */
-            const uint2 *gt = reinterpret_cast<const uint2 *>(tables + t.map_off);
-            for (uint32_t k = tid; k < t.map_slots; k += WARP_THREADS) lds_map[k] = gt[k];
-            __syncthreads();
-            held_off = t.map_off;
-            held_slots = t.map_slots;
-        }
+        clbl_hold_map(lds_map, held, t, tables, tid);
         uint32_t m;
         if (t.dtype == 0u) m = clbl_warp_rows<1u, true>(tab, t, src, out, tid);
         else if (t.dtype == 1u) m = clbl_warp_rows<2u, true>(tab, t, src, out, tid);
         else if (t.dtype == 2u) m = clbl_warp_rows<4u, true>(tab, t, src, out, tid);
         else m = clbl_warp_rows<8u, true>(tab, t, src, out, tid);
-        // the wavefront's misses of this task: every lane is here (the task loop is uniform)
-DEV_UNROLL
-        for (uint32_t d = 32u; d >= 1u; d >>= 1) m += __shfl_xor(m, (int)d);
-        if ((tid & 63u) == 0u && m != 0u) atomicAdd(&unmatched[t.image], m);
+        clbl_add_misses(&unmatched[t.image], m, tid);
     }
 }

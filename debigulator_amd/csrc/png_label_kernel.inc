@@ -20,39 +20,22 @@
 //     ds_read_b32 mostly hit one address (a broadcast); distinct labels conflict only when they are 32 entries apart.
 // A task that breaks a bound is skipped (never indexed out of range).  No atomics, no scratch (every per-item array is indexed
 // by unrolled constants), nothing shared between workgroups.
-// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_spec_kernel.inc in front of it.
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_spec_kernel.inc and png_stage_common.inc
+// in front of it.
 
 #define LBL_THREADS 256u
 
-// one element of ES bytes at p (aligned to ES)
-template <uint32_t ES>
-DEV_INLINE void lbl_store1(uint8_t *p, uint32_t v)
-{
-    if (ES == 1u) {
-        *p = (uint8_t)v;
-    } else if (ES == 2u) {
-        *reinterpret_cast<uint16_t *>(p) = (uint16_t)v;
-    } else if (ES == 4u) {
-        *reinterpret_cast<uint32_t *>(p) = v;
-    } else {
-        uint2 q;
-        q.x = v; q.y = (uint32_t)((int32_t)v >> 31);
-        *reinterpret_cast<uint2 *>(p) = q;
-    }
-}
-
-// the rows of one task: elements of ES bytes, E per item, source labels of SB bytes
-template <uint32_t ES, uint32_t E, uint32_t SB>
-DEV_INLINE void lbl_rows(const int32_t *lut, const debig_png_label_task &t, const uint8_t *__restrict__ src,
-                         uint8_t *__restrict__ out, const uint32_t *__restrict__ sx, const uint32_t *__restrict__ sy, uint32_t tid)
+// the rows of one task of either gather (this file, png_color_label_kernel.inc): elements of ES bytes, E per item;
+// pick(el) -> the element of the source pixel `el` of the crop.  A lane's picks come in the order of its elements.
+template <uint32_t ES, uint32_t E, class Task, class Pick>
+DEV_INLINE void lbl_gather_rows(const Task &t, uint8_t *__restrict__ out, const uint32_t *__restrict__ sx,
+                                const uint32_t *__restrict__ sy, uint32_t tid, Pick pick)
 {
     constexpr uint32_t ND = E * ES / 4u; /* dwords of a full item */
     const uint32_t ipr = (t.out_w + E - 1u) / E, n = t.rows * ipr; /* items per row (<= 8192), items of the task */
-    uint32_t r = tid / ipr, g = tid - r * ipr;
-    const uint32_t dr = LBL_THREADS / ipr, dg = LBL_THREADS - dr * ipr;
-    const uint8_t *s0 = src + t.src_off;
+    StageWalk wk(tid, ipr, LBL_THREADS);
     for (uint32_t i = tid; i < n; i += LBL_THREADS) {
-        const uint32_t Y = t.row0 + r, x = g * E;
+        const uint32_t Y = t.row0 + wk.r, x = wk.x * E;
         const uint64_t srow = (uint64_t)sy[Y] * t.src_pitch;
         uint8_t *o = out + t.out_off + ((uint64_t)Y * t.out_w + x) * ES;
         if (x + E <= t.out_w) {
@@ -71,8 +54,7 @@ DEV_UNROLL
             for (uint32_t j = 0; j < ND; j++) B[j] = 0u;
 DEV_UNROLL
             for (uint32_t j = 0; j < E; j++) {
-                uint32_t v = SB == 1u ? (uint32_t)s0[srow + ix[j]] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[srow + ix[j]];
-                if (lut) v = (uint32_t)lut[v & 255u];
+                const uint32_t v = pick(srow + ix[j]);
                 if (ES == 1u) B[j / 4u] |= (v & 0xffu) << (8u * (j & 3u));
                 else if (ES == 2u) B[j / 2u] |= (v & 0xffffu) << (16u * (j & 1u));
                 else if (ES == 4u) B[j] = v;
@@ -83,16 +65,23 @@ DEV_UNROLL
 DEV_UNROLL
             for (uint32_t j = 0; j < E; j++) {
                 if (x + j >= t.out_w) break;
-                const uint64_t el = srow + sx[x + j];
-                uint32_t v = SB == 1u ? (uint32_t)s0[el] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[el];
-                if (lut) v = (uint32_t)lut[v & 255u];
-                lbl_store1<ES>(o + j * ES, v);
+                lbl_store1<ES>(o + j * ES, pick(srow + sx[x + j]));
             }
         }
-        r += dr;
-        g += dg;
-        if (g >= ipr) { g -= ipr; r++; }
+        wk.next();
     }
+}
+
+// the raw-label pick: a source label of SB bytes, through the LUT when there is one
+template <uint32_t ES, uint32_t E, uint32_t SB>
+DEV_INLINE void lbl_rows(const int32_t *lut, const debig_png_label_task &t, const uint8_t *__restrict__ src,
+                         uint8_t *__restrict__ out, const uint32_t *__restrict__ sx, const uint32_t *__restrict__ sy, uint32_t tid)
+{
+    const uint8_t *s0 = src + t.src_off;
+    lbl_gather_rows<ES, E>(t, out, sx, sy, tid, [&](uint64_t el) -> uint32_t {
+        const uint32_t v = SB == 1u ? (uint32_t)s0[el] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[el];
+        return lut ? (uint32_t)lut[v & 255u] : v;
+    });
 }
 
 __global__ void __launch_bounds__(LBL_THREADS)

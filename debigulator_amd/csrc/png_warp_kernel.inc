@@ -27,8 +27,7 @@
 // png_label_kernel.inc.  A border pick stores border_label as it is (it does not pass through the LUT).
 // A task that breaks a bound is skipped (never indexed out of range).  No atomics, no scratch, nothing shared between
 // workgroups; plain vector stores only.
-// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_resize_kernel.inc and png_label_kernel.inc
-// in front of it.
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs png_stage_common.inc in front of it.
 
 #define WARP_THREADS 256u
 #define WARP_FILTER_BILINEAR 0u // decode_png.h: DEBIG_PNG_FILTER_BILINEAR
@@ -43,7 +42,8 @@ DEV_INLINE bool warp_matrix_ok(int64_t m00, int64_t m01, int64_t m02, int64_t m1
            m02 >= -tr && m02 <= tr && m12 >= -tr && m12 <= tr;
 }
 
-// the sizes every warp task shares
+// the sizes every warp task shares.  (The two gather kernels spell the first four tests out themselves: with one predicate
+// for all, the compiler lays the kernels' skips out differently; profiles/png_stage_kernels_refactor.txt has what that cost.)
 DEV_INLINE bool warp_sizes_ok(uint32_t out_w, uint32_t out_h, uint32_t row0, uint32_t rows, uint32_t crop_w, uint32_t crop_h)
 {
     return out_w != 0u && out_w <= 16384u && out_h <= 16384u && rows != 0u && row0 < out_h && rows <= out_h - row0 &&
@@ -57,6 +57,79 @@ DEV_INLINE uint32_t warp_clamp(int64_t j, uint32_t cl, bool *inside)
     return (uint32_t)(j < 0 ? 0 : j >= (int64_t)cl ? (int64_t)cl - 1 : j);
 }
 
+// ---- what the four warp kernels share (this file, png_color_kernel.inc, png_color_label_warp_kernel.inc): they differ only in
+// what they do with a picked sample ----------------------------------------------------------------------------------------------
+
+// the output pixels of one task, lanes along X and on into the next row of the run: body(X, Y, U, V) per pixel, (U, V) the
+// source position of its centre in Q17
+template <class Task, class Body>
+DEV_INLINE void warp_walk(const Task &t, uint32_t tid, Body body)
+{
+    const uint32_t n = t.rows * t.out_w;
+    StageWalk wk(tid, t.out_w, WARP_THREADS);
+    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
+        const uint32_t X = wk.x, Y = t.row0 + wk.r;
+        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
+        body(X, Y, t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], t.m[3] * cx + t.m[4] * cy + 2 * t.m[5]);
+        wk.next();
+    }
+}
+
+// the NEAREST pick of (U, V): the pixel (jx, jy), clamped into the crop, and whether its sample counts -- under CLAMP always,
+// under CONSTANT when the pick lay inside (else the border value takes its place, by a select).  clamp: the task's border mode
+// is CLAMP, found once per task by the caller, in front of its walk
+struct WarpPick {
+    uint32_t jx, jy;
+    bool keep;
+};
+template <class Task>
+DEV_INLINE WarpPick warp_pick(const Task &t, bool clamp, int64_t U, int64_t V)
+{
+    bool inx, iny;
+    WarpPick p;
+    p.jx = warp_clamp(U >> 17, t.crop_w, &inx);
+    p.jy = warp_clamp(V >> 17, t.crop_h, &iny);
+    p.keep = clamp || (inx && iny);
+    return p;
+}
+
+// the BILINEAR taps of (U, V): the sample offsets of the two rows and the two pixels, all four clamped into the crop, the
+// keep flag of each tap (clamp: as for warp_pick), the Q14 weights of both axes
+struct WarpTaps {
+    uint64_t r0, r1, c0, c1;
+    uint32_t w0x, w1x, w0y, w1y;
+    bool k00, k01, k10, k11;
+    // channel c at precision P: the horizontal pass rounded to 16 bits, the vertical pass into 30; bd: its border sample
+    template <uint32_t P, class Sample>
+    DEV_MEMBER_INLINE uint32_t value(const Sample *s, uint32_t c, uint32_t bd) const
+    {
+        uint32_t s00 = s[r0 + c0 + c], s01 = s[r0 + c1 + c], s10 = s[r1 + c0 + c], s11 = s[r1 + c1 + c];
+        if (!k00) s00 = bd;
+        if (!k01) s01 = bd;
+        if (!k10) s10 = bd;
+        if (!k11) s11 = bd;
+        const uint32_t h0 = (w0x * s00 + w1x * s01 + (1u << (P - 3u))) >> (P - 2u);
+        const uint32_t h1 = (w0x * s10 + w1x * s11 + (1u << (P - 3u))) >> (P - 2u);
+        return w0y * h0 + w1y * h1;
+    }
+};
+template <class Task>
+DEV_INLINE WarpTaps warp_taps(const Task &t, bool clamp, int64_t U, int64_t V)
+{
+    const int64_t tu = U - 65536, tv = V - 65536;
+    const int64_t ix = tu >> 17, iy = tv >> 17;
+    bool ix0, ix1, iy0, iy1;
+    const uint32_t x0 = warp_clamp(ix, t.crop_w, &ix0), x1 = warp_clamp(ix + 1, t.crop_w, &ix1);
+    const uint32_t y0 = warp_clamp(iy, t.crop_h, &iy0), y1 = warp_clamp(iy + 1, t.crop_h, &iy1);
+    WarpTaps q;
+    q.w1x = ((uint32_t)(tu & 0x1FFFF) + 4u) >> 3; q.w0x = 16384u - q.w1x;
+    q.w1y = ((uint32_t)(tv & 0x1FFFF) + 4u) >> 3; q.w0y = 16384u - q.w1y;
+    q.k00 = clamp || (ix0 && iy0); q.k01 = clamp || (ix1 && iy0); q.k10 = clamp || (ix0 && iy1); q.k11 = clamp || (ix1 && iy1);
+    q.r0 = (uint64_t)y0 * t.src_pitch; q.r1 = (uint64_t)y1 * t.src_pitch;
+    q.c0 = (uint64_t)x0 * t.channels; q.c1 = (uint64_t)x1 * t.channels;
+    return q;
+}
+
 // the rows of one task at source precision P
 template <uint32_t P>
 DEV_INLINE void warp_rows(const debig_png_warp_task &t, const debig_png_warp_task *__restrict__ tg, const uint8_t *__restrict__ src,
@@ -65,52 +138,24 @@ DEV_INLINE void warp_rows(const debig_png_warp_task &t, const debig_png_warp_tas
     typedef typename RszSample<P>::sample_t sample_t;
     const sample_t *s = reinterpret_cast<const sample_t *>(src + t.src_off);
     uint8_t *o = out + t.out_off;
-    const uint32_t ch = t.channels, n = t.rows * t.out_w;
+    const uint32_t ch = t.channels;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    uint32_t r = tid / t.out_w, X = tid - r * t.out_w;
-    const uint32_t dr = WARP_THREADS / t.out_w, dx = WARP_THREADS - dr * t.out_w;
-    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
-        const uint32_t Y = t.row0 + r;
-        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
-        const int64_t U = t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], V = t.m[3] * cx + t.m[4] * cy + 2 * t.m[5];
+    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         if (nearest) {
-            bool inx, iny;
-            const uint32_t jx = warp_clamp(U >> 17, t.crop_w, &inx), jy = warp_clamp(V >> 17, t.crop_h, &iny);
-            const bool keep = clamp || (inx && iny);
-            const uint64_t at = (uint64_t)jy * t.src_pitch + (uint64_t)jx * ch;
+            const WarpPick p = warp_pick(t, clamp, U, V);
+            const uint64_t at = (uint64_t)p.jy * t.src_pitch + (uint64_t)p.jx * ch;
             for (uint32_t c = 0; c < ch; c++) {
                 uint32_t v = s[at + c];
-                if (!keep) v = tg->border[c];
+                if (!p.keep) v = tg->border[c];
                 rsz_cubic_store(t.dtype, P, tg->a[c], tg->b[c], o, el + (uint64_t)c * t.out_sc, v << (30u - P));
             }
         } else {
-            const int64_t tu = U - 65536, tv = V - 65536;
-            const int64_t ix = tu >> 17, iy = tv >> 17;
-            const uint32_t w1x = ((uint32_t)(tu & 0x1FFFF) + 4u) >> 3, w0x = 16384u - w1x;
-            const uint32_t w1y = ((uint32_t)(tv & 0x1FFFF) + 4u) >> 3, w0y = 16384u - w1y;
-            bool ix0, ix1, iy0, iy1;
-            const uint32_t x0 = warp_clamp(ix, t.crop_w, &ix0), x1 = warp_clamp(ix + 1, t.crop_w, &ix1);
-            const uint32_t y0 = warp_clamp(iy, t.crop_h, &iy0), y1 = warp_clamp(iy + 1, t.crop_h, &iy1);
-            const bool k00 = clamp || (ix0 && iy0), k01 = clamp || (ix1 && iy0), k10 = clamp || (ix0 && iy1), k11 = clamp || (ix1 && iy1);
-            const uint64_t r0 = (uint64_t)y0 * t.src_pitch, r1 = (uint64_t)y1 * t.src_pitch;
-            const uint64_t c0 = (uint64_t)x0 * ch, c1 = (uint64_t)x1 * ch;
-            for (uint32_t c = 0; c < ch; c++) {
-                const uint32_t bd = tg->border[c];
-                uint32_t s00 = s[r0 + c0 + c], s01 = s[r0 + c1 + c], s10 = s[r1 + c0 + c], s11 = s[r1 + c1 + c];
-                if (!k00) s00 = bd;
-                if (!k01) s01 = bd;
-                if (!k10) s10 = bd;
-                if (!k11) s11 = bd;
-                const uint32_t h0 = (w0x * s00 + w1x * s01 + (1u << (P - 3u))) >> (P - 2u);
-                const uint32_t h1 = (w0x * s10 + w1x * s11 + (1u << (P - 3u))) >> (P - 2u);
-                rsz_cubic_store(t.dtype, P, tg->a[c], tg->b[c], o, el + (uint64_t)c * t.out_sc, w0y * h0 + w1y * h1);
-            }
+            const WarpTaps q = warp_taps(t, clamp, U, V);
+            for (uint32_t c = 0; c < ch; c++)
+                rsz_cubic_store(t.dtype, P, tg->a[c], tg->b[c], o, el + (uint64_t)c * t.out_sc, q.value<P>(s, c, tg->border[c]));
         }
-        r += dr;
-        X += dx;
-        if (X >= t.out_w) { X -= t.out_w; r++; }
-    }
+    });
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)
@@ -139,25 +184,15 @@ DEV_INLINE void warp_label_rows(const int32_t *lut, const debig_png_label_warp_t
                                 uint8_t *__restrict__ out, uint32_t tid)
 {
     const uint8_t *s0 = src + t.src_off;
-    const uint32_t n = t.rows * t.out_w;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
-    uint32_t r = tid / t.out_w, X = tid - r * t.out_w;
-    const uint32_t dr = WARP_THREADS / t.out_w, dx = WARP_THREADS - dr * t.out_w;
-    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
-        const uint32_t Y = t.row0 + r;
-        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
-        const int64_t U = t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], V = t.m[3] * cx + t.m[4] * cy + 2 * t.m[5];
-        bool inx, iny;
-        const uint32_t jx = warp_clamp(U >> 17, t.crop_w, &inx), jy = warp_clamp(V >> 17, t.crop_h, &iny);
-        const uint64_t at = (uint64_t)jy * t.src_pitch + jx;
+    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+        const WarpPick p = warp_pick(t, clamp, U, V);
+        const uint64_t at = (uint64_t)p.jy * t.src_pitch + p.jx;
         uint32_t v = SB == 1u ? (uint32_t)s0[at] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[at];
         if (lut) v = (uint32_t)lut[v & 255u];
-        if (!clamp && !(inx && iny)) v = (uint32_t)t.border_label;
+        if (!p.keep) v = (uint32_t)t.border_label;
         lbl_store1<ES>(out + t.out_off + ((uint64_t)Y * t.out_w + X) * ES, v);
-        r += dr;
-        X += dx;
-        if (X >= t.out_w) { X -= t.out_w; r++; }
-    }
+    });
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)

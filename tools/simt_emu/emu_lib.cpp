@@ -16,6 +16,7 @@
 #include "../../debigulator_amd/csrc/png_fused_kernel.inc"
 #include "../../debigulator_amd/csrc/png_spec_kernel.inc"
 #include "../../debigulator_amd/csrc/apng_kernel.inc"
+#include "../../debigulator_amd/csrc/png_stage_common.inc"
 #include "../../debigulator_amd/csrc/png_resize_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_label_kernel.inc"
