@@ -603,6 +603,62 @@ def _png_warps(warp, n):
     return ws
 
 
+class PngPersp(C.Structure):  # include/decode_png.h: debig_png_persp
+    _fields_ = [("m", C.c_double * 9)]
+
+
+PNG_PERSP_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+
+
+def png_perspective_from_warp(m2x3):
+    """the 3 x 3 matrix of `perspective=` that means what the 2 x 3 matrix of `warp=` means: (0, 0, 1) appended as row 2.  The
+    calls then give the bytes of their warp= form."""
+    v = [float(x) for x in np.asarray(m2x3, dtype=np.float64).reshape(-1)]
+    if len(v) != 6:
+        raise ValueError("png_perspective_from_warp takes a 2 x 3 matrix")
+    return (tuple(v[0:3]), tuple(v[3:6]), (0.0, 0.0, 1.0))
+
+
+def png_perspective_matrix(src_quad, out_size, dst_quad=None):
+    """the INVERSE 3 x 3 matrix (a tuple of three rows of three floats, M22 = 1) that `perspective=` takes, from four point pairs
+    (no GPU needed): the output point dst_quad[k] = (X, Y) maps to the crop point src_quad[k] = (x, y).  Both are continuous
+    coordinates in which pixel j covers [j, j + 1); dst_quad defaults to the corners of the out_size = (H, W) output in the order
+    (0, 0), (W, 0), (W, H), (0, H).  Solved in float64 (the eight-equation system of the homography); a degenerate
+    quadrilateral raises ValueError.  Whether the horizon stays clear of the output is decided by the decode call (status 16)."""
+    H, W = (float(v) for v in out_size)
+    src = np.asarray(src_quad, dtype=np.float64).reshape(-1)
+    dst = np.asarray(dst_quad if dst_quad is not None else ((0, 0), (W, 0), (W, H), (0, H)), dtype=np.float64).reshape(-1)
+    if src.size != 8 or dst.size != 8:
+        raise ValueError("png_perspective_matrix takes four (x, y) points per quadrilateral")
+    A, b = np.zeros((8, 8)), np.zeros(8)
+    for k in range(4):
+        X, Y, x, y = dst[2 * k], dst[2 * k + 1], src[2 * k], src[2 * k + 1]
+        A[2 * k] = (X, Y, 1, 0, 0, 0, -x * X, -x * Y)
+        A[2 * k + 1] = (0, 0, 0, X, Y, 1, -y * X, -y * Y)
+        b[2 * k], b[2 * k + 1] = x, y
+    try:
+        h = np.linalg.solve(A, b)
+    except np.linalg.LinAlgError:
+        raise ValueError("the quadrilaterals are degenerate") from None
+    if not np.isfinite(h).all():
+        raise ValueError("the quadrilaterals are degenerate")
+    h = [float(v) + 0.0 for v in h] + [1.0]
+    return (tuple(h[0:3]), tuple(h[3:6]), tuple(h[6:9]))
+
+
+def _png_persps(perspective, n):
+    """perspective: a sequence of n entries, each None (the identity) or a 3 x 3 matrix -> (PngPersp * n)"""
+    if len(perspective) != n:
+        raise ValueError("perspective needs one entry (a 3 x 3 matrix, or None) per file")
+    ps = (PngPersp * n)()
+    for i, m in enumerate(perspective):
+        v = PNG_PERSP_IDENTITY if m is None else [float(x) for x in np.asarray(m, dtype=np.float64).reshape(-1)]
+        if len(v) != 9:
+            raise ValueError(f"perspective[{i}] must be a 3 x 3 matrix")
+        ps[i].m[:] = v
+    return ps
+
+
 def png_warp_desc(filter="bilinear", border="constant", border_value=None, mode="rgb", depth=8, alpha="straight"):
     """the debig_png_warp_desc of png_decode_batch_tensor's warp arguments (no GPU needed).  filter: "bilinear" | "nearest";
     border: "constant" (a tap outside the crop is border_value: per channel on the [0, 1] scale, a number for every channel,
@@ -783,8 +839,8 @@ def _png_blurs(blur, n):
 
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
                             antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
-                            background=None, warp=None, border="constant", border_value=None, color=None, tone=None, blur=None,
-                            filter="bilinear"):
+                            background=None, warp=None, border="constant", border_value=None, color=None, tone=None, perspective=None,
+                            blur=None, filter="bilinear"):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
     (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
@@ -831,8 +887,19 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     `tone` included, to 8-bit samples, then through the filter in integers (Q14 taps, see png_blur_weights), then ONCE through the
     conversion with mean / std, so float outputs keep the precision below an 8-bit step.  A file whose entry is None gets, bit
     for bit, what the call without `blur` gives it.  It goes with depth 8 and alpha "straight" or "over"; a bad ksize, sigma or
-    factor: status 19 ("blur").  (By name, like `tone`.)"""
+    factor: status 19 ("blur").  (By name, like `tone`.)
+    perspective: None (everything above, unchanged), or one entry per file: None (the identity) or the INVERSE 3 x 3 matrix M of a
+    projective map: the centre p = (X + 1/2, Y + 1/2, 1) of an output pixel lies at (M0 . p / M2 . p, M1 . p / M2 . p) in the crop
+    (png_perspective_matrix makes one from two quadrilaterals, png_perspective_from_warp from a 2 x 3 matrix) --
+    debig_png_decode_batch_tensor_persp.  It takes the place of `warp` (both together: ValueError) with its filter, border,
+    border_value and alpha rules, goes with color, tone and blur exactly as warp does, and with row (0, 0, 1) gives the bytes of
+    warp=.  A matrix whose horizon crosses or nearly touches the output, or with a non-finite or too large entry: status 16
+    ("warp").  (By name, like `tone`.  It stands in front of `blur`, which with `filter` stays at the end of the list: `blur`, like
+    every argument behind `background`, is to be passed by name -- a positional `blur` would now land here and be refused.)"""
     import torch
+
+    if perspective is not None and warp is not None:
+        raise ValueError("perspective and warp exclude each other")
 
     if tone is not None:
         if depth != 8:
@@ -853,13 +920,13 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
         if mode not in ("rgb", "rgba"):
             raise ValueError(f"color needs mode 'rgb' or 'rgba', not {mode!r}")
     wd = None
-    if warp is not None:
+    if warp is not None or perspective is not None:
         wd = png_warp_desc(filter, border, border_value, mode, depth, alpha)
         if background is not None:
             raise ValueError("background needs alpha='over'")
         antialias = False
     elif border != "constant" or border_value is not None:
-        raise ValueError("border / border_value need warp")
+        raise ValueError("border / border_value need warp")  # (or perspective)
     d, ch, es = png_tensor_desc(size, mode, depth, dtype, layout, mean, std, antialias)
     ad = png_alpha_desc(alpha, background, mode, depth)
     fd = png_filter_desc(filter)
@@ -880,7 +947,17 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
     out = _png_dense_out(shape, tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if blur is not None:
+    if perspective is not None:
+        ps = _png_persps(perspective, n)
+        bs = _png_blurs(blur, n) if blur is not None else None
+        ts, tabs, n_tabs = _png_tones(tone, n) if tone is not None else (None, None, 0)
+        L.debig_png_decode_batch_tensor_persp.restype = C.c_int
+        L.debig_png_decode_batch_tensor_persp.argtypes = [C.c_void_p] * 8 + [C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + \
+            [C.c_void_p] * 2
+        rc = L.debig_png_decode_batch_tensor_persp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ps, cs, ts,
+                                                   tabs.ctypes.data if tabs is not None else None, n_tabs, bs, status, infos, n,
+                                                   PNG_FORCE_GENERAL if force_general else 0, C.byref(d), C.byref(wd))
+    elif blur is not None:
         bs = _png_blurs(blur, n)
         ts, tabs, n_tabs = _png_tones(tone, n) if tone is not None else (None, None, 0)
         L.debig_png_decode_batch_tensor_blur.restype = C.c_int
@@ -987,7 +1064,7 @@ def png_label_warp_desc(border="constant", border_label=None, dtype="int64"):
 
 
 def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fill=None, device="cuda:0", warp=None,
-                            border="constant", border_label=None):
+                            border="constant", border_label=None, perspective=None):
     """bytes of N label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_labels) -> (statuses, tensor, infos).  The label of a pixel is its palette index (colour type 3)
     or its raw grey sample (colour type 0, 1 to 16 bits): nothing is scaled, PLTE colours and tRNS are ignored.  size =
@@ -1001,11 +1078,17 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     png_decode_batch_tensor(warp=) -- debig_png_decode_batch_labels_warp: the pick is the one of that call's filter="nearest"
     under the same matrix, so an image and its mask stay aligned.  border: "constant" (a pick outside the crop stores
     border_label as it is, not through the lut: the ignore index; default 0) or "clamp".  A matrix with a non-finite or too
-    large entry: status 16 ("warp")."""
+    large entry: status 16 ("warp").
+    perspective (by name; the last parameter, so every older positional call means what it meant): in place of warp (both
+    together: ValueError), one entry per file: None (the identity) or the INVERSE 3 x 3 matrix of
+    png_decode_batch_tensor(perspective=) -- debig_png_decode_batch_labels_persp: the pick is again that call's
+    filter="nearest" under the same matrix; border and border_label as for warp.  A horizon across the output: status 16."""
     import torch
 
+    if perspective is not None and warp is not None:
+        raise ValueError("perspective and warp exclude each other")
     wd = None
-    if warp is not None:
+    if warp is not None or perspective is not None:
         wd = png_label_warp_desc(border, border_label, dtype)
     elif border != "constant" or border_label is not None:
         raise ValueError("border / border_label need warp")
@@ -1020,7 +1103,12 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     tdt = {"uint8": torch.uint8, "uint16": getattr(torch, "uint16", torch.int16), "int32": torch.int32, "int64": torch.int64}[dtype]
     out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if wd is not None:
+    if perspective is not None:
+        L.debig_png_decode_batch_labels_persp.restype = C.c_int
+        L.debig_png_decode_batch_labels_persp.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_labels_persp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, _png_persps(perspective, n),
+                                                   status, infos, n, 0, C.byref(d), C.byref(wd))
+    elif wd is not None:
         L.debig_png_decode_batch_labels_warp.restype = C.c_int
         L.debig_png_decode_batch_labels_warp.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         rc = L.debig_png_decode_batch_labels_warp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos, n, 0,
@@ -1108,7 +1196,7 @@ def png_color_label_desc(size, colors=None, missing=-1, dtype="int64", n=None):
 
 
 def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="int64", boxes=None, fill=None, device="cuda:0",
-                                  warp=None, border="constant", border_label=None):
+                                  perspective=None, warp=None, border="constant", border_label=None):
     """bytes of N colour-coded label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_color_labels) -> (statuses, tensor, infos, unmatched).  The colour of a pixel is what
     png_decode_batch(mode="rgb") gives for it (palette files through PLTE, grey replicated, alpha and tRNS dropped), packed as
@@ -1122,11 +1210,19 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     png_decode_batch_tensor(warp=) -- debig_png_decode_batch_color_labels_warp: the pick is the one of that call's
     filter="nearest" and of png_decode_batch_labels(warp=) under the same matrix, so an image and its colour mask stay aligned.
     border: "constant" (a pick outside the crop stores border_label as it is, not through the map, and is never counted in
-    unmatched: the ignore index; default 0) or "clamp".  A matrix with a non-finite or too large entry: status 16 ("warp")."""
+    unmatched: the ignore index; default 0) or "clamp".  A matrix with a non-finite or too large entry: status 16 ("warp").
+    perspective (by name): in place of warp (both together: ValueError), one entry per file: None (the identity) or the INVERSE
+    3 x 3 matrix of png_decode_batch_tensor(perspective=) -- debig_png_decode_batch_color_labels_persp: the same pick as that
+    call's filter="nearest" and png_decode_batch_labels(perspective=); border, border_label and unmatched as for warp.  A horizon
+    across the output: status 16.  NOTE: `perspective` stands in front of `warp` in the parameter list (`warp`, `border` and
+    `border_label` stay the last three), so `warp`, `border` and `border_label` are to be passed BY NAME from now on: a call that
+    passed `warp` as the ninth positional argument now hands it to `perspective` and is refused (a 2 x 3 entry is no 3 x 3 matrix)."""
     import torch
 
+    if perspective is not None and warp is not None:
+        raise ValueError("perspective and warp exclude each other")
     wd = None
-    if warp is not None:
+    if warp is not None or perspective is not None:
         wd = png_label_warp_desc(border, border_label, dtype)
     elif border != "constant" or border_label is not None:
         raise ValueError("border / border_label need warp")
@@ -1142,7 +1238,13 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
     unmatched = (C.c_uint32 * n)()
-    if wd is not None:
+    if perspective is not None:
+        L.debig_png_decode_batch_color_labels_persp.restype = C.c_int
+        L.debig_png_decode_batch_color_labels_persp.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = L.debig_png_decode_batch_color_labels_persp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx,
+                                                         _png_persps(perspective, n), status, infos, unmatched, n, 0, C.byref(d),
+                                                         C.byref(wd))
+    elif wd is not None:
         L.debig_png_decode_batch_color_labels_warp.restype = C.c_int
         L.debig_png_decode_batch_color_labels_warp.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         rc = L.debig_png_decode_batch_color_labels_warp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos,

@@ -22,6 +22,7 @@
 #include "png_warp_kernel.inc"
 #include "png_color_label_warp_kernel.inc"
 #include "png_color_kernel.inc"
+#include "png_persp_kernel.inc"
 #include "png_tone_kernel.inc"
 #include "png_blur_kernel.inc"
 #include "checksum_kernel.inc"
@@ -883,6 +884,35 @@ int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const d
 {
     return launch_stage(debig_png_warp_color_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
                         (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights);
+}
+
+// the four warp kernels under a projective map (png_persp_kernel.inc): the tasks, buffers and grid rule of their warp twins
+int debig_hip_png_persp_batch(const void *d_src_arena, void *d_out, const debig_png_persp_task *d_tasks, uint32_t n_tasks,
+                              void *hip_stream)
+{
+    return launch_stage(debig_png_persp_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena, (uint8_t *)d_out,
+                        d_tasks);
+}
+
+int debig_hip_png_persp_color_batch(const void *d_src_arena, void *d_out, const debig_png_persp_color_task *d_tasks,
+                                    const void *d_weights, uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_persp_color_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights);
+}
+
+int debig_hip_png_label_persp_batch(const void *d_src_arena, void *d_out, const debig_png_label_persp_task *d_tasks,
+                                    const int32_t *d_lut, uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_persp_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, d_lut);
+}
+
+int debig_hip_png_color_label_persp_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_persp_task *d_tasks,
+                                          const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_color_label_persp_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched);
 }
 
 // the tone curves of the tensor decode (png_tone_kernel.inc): one workgroup per pixel run, as many workgroups as tasks

@@ -1925,14 +1925,62 @@ DEBIG_API int debig_png_warp_quantise(const double M[6], int64_t m[6])
     return 1;
 }
 
-/* the files' matrices quantised (6 int64 each) and their E_WARP flags; -> 0 or 2 */
-static int warp_prepare(const debig_png_warp *warps, uint32_t n, int64_t **m, uint8_t **bad)
+DEBIG_API int debig_png_persp_quantise(const double M[9], int64_t m[9])
 {
-    *m = (int64_t *)calloc((size_t)n * 6u, sizeof(int64_t));
+    if (!debig_png_warp_quantise(M, m)) return 0; /* rows 0 and 1: the affine quantiser, its limits and its rounding */
+    for (uint32_t k = 6; k < 9; k++) {
+        uint64_t u;
+        memcpy(&u, &M[k], 8);
+        if ((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull) return 0; /* infinity or NaN */
+        if ((M[k] < 0 ? -M[k] : M[k]) > 4.0) return 0;
+        /* llround: the product is exact (a power of two) and at most 2^32, so is x - trunc(x); halves go away from zero */
+        const double x = M[k] * 1073741824.0;
+        int64_t q = (int64_t)x;
+        const double d = x - (double)q;
+        if (d >= 0.5) q++;
+        else if (d <= -0.5) q--;
+        m[k] = q;
+    }
+    return 1;
+}
+
+DEBIG_API int debig_png_persp_range(const int64_t m[9], uint32_t out_w, uint32_t out_h)
+{
+    if (out_w == 0 || out_w > 16384u || out_h == 0 || out_h > 16384u) return 0;
+    for (uint32_t k = 6; k < 9; k++)
+        if (m[k] < -((int64_t)1 << 32) || m[k] > ((int64_t)1 << 32)) return 0;
+    /* D is linear in X and Y: its extremes lie at the corner pixels (|D| < 2^49 there) */
+    for (uint32_t k = 0; k < 4; k++) {
+        const int64_t cx = k & 1u ? 2 * (int64_t)out_w - 1 : 1, cy = k & 2u ? 2 * (int64_t)out_h - 1 : 1;
+        const int64_t D = m[6] * cx + m[7] * cy + 2 * m[8];
+        if (D < ((int64_t)1 << 21) || D > ((int64_t)1 << 33) - 1) return 0;
+    }
+    return 1;
+}
+
+#define MAP_INTS 9u /* a file's quantised map: m[0..5] (both kinds), m[6..8] = p[] (the projective kind; else unused) */
+
+/* the files' maps quantised (MAP_INTS int64 each) and their E_WARP flags; exactly one of warps (affine) and persps (projective:
+ * the D range over the out_w x out_h output is part of the flag) is given; -> 0 or 2 */
+static int warp_prepare(const debig_png_warp *warps, const debig_png_persp *persps, uint32_t n, uint32_t out_w, uint32_t out_h,
+                        int64_t **m, uint8_t **bad)
+{
+    *m = (int64_t *)calloc((size_t)n * MAP_INTS, sizeof(int64_t));
     *bad = (uint8_t *)calloc(n, 1);
     if (!*m || !*bad) return 2;
-    for (uint32_t i = 0; i < n; i++) (*bad)[i] = !debig_png_warp_quantise(warps[i].m, *m + 6u * (size_t)i);
+    for (uint32_t i = 0; i < n; i++) {
+        int64_t *mi = *m + MAP_INTS * (size_t)i;
+        (*bad)[i] = persps ? !(debig_png_persp_quantise(persps[i].m, mi) && debig_png_persp_range(mi, out_w, out_h))
+                           : !debig_png_warp_quantise(warps[i].m, mi);
+    }
     return 0;
+}
+
+/* one task into the host array: its first `base` bytes (the warp task), then p[] where the map is projective */
+static void map_task_put(uint8_t *at, const void *task, size_t base, const int64_t *mi, int persp)
+{
+    memcpy(at, task, base);
+    if (persp) memcpy(at + base, mi + 6, 3 * sizeof(int64_t));
 }
 
 _Static_assert(offsetof(debig_png_warp_color_task, color_off) == sizeof(debig_png_warp_task) &&
@@ -1940,10 +1988,22 @@ _Static_assert(offsetof(debig_png_warp_color_task, color_off) == sizeof(debig_pn
                    offsetof(debig_png_warp_color_task, border) == offsetof(debig_png_warp_task, border) &&
                    sizeof(debig_png_warp_color_task) == 160,
                "debig_png_warp_color_task starts with debig_png_warp_task, field for field");
+_Static_assert(offsetof(debig_png_persp_task, p) == sizeof(debig_png_warp_task) && sizeof(debig_png_persp_task) == 176 &&
+                   offsetof(debig_png_persp_task, b) == offsetof(debig_png_warp_task, b) &&
+                   offsetof(debig_png_persp_color_task, p) == sizeof(debig_png_warp_color_task) &&
+                   offsetof(debig_png_persp_color_task, color_off) == offsetof(debig_png_warp_color_task, color_off) &&
+                   sizeof(debig_png_persp_color_task) == 184 &&
+                   offsetof(debig_png_label_persp_task, p) == sizeof(debig_png_label_warp_task) &&
+                   offsetof(debig_png_label_persp_task, border_mode) == offsetof(debig_png_label_warp_task, border_mode) &&
+                   sizeof(debig_png_label_persp_task) == 128 &&
+                   offsetof(debig_png_color_label_persp_task, p) == sizeof(debig_png_color_label_warp_task) &&
+                   offsetof(debig_png_color_label_persp_task, border_mode) == offsetof(debig_png_color_label_warp_task, border_mode) &&
+                   sizeof(debig_png_color_label_persp_task) == 144,
+               "each persp task is the warp task of its kernel, field for field, followed by p[3]");
 
 /* the checks of debig_png_decode_batch_tensor_warp (n > 0): those of debig_png_decode_batch_tensor first and unchanged, then the
  * warp's; all before any file is looked at -> 0 or the call's return value */
-static int tensor_warp_check(const void *d_out, const debig_png_warp *warps, const debig_png_tensor_desc *desc,
+static int tensor_warp_check(const void *d_out, const void *warps /* or the persps */, const debig_png_tensor_desc *desc,
                              const debig_png_warp_desc *wd)
 {
     const int badarg = tensor_args_check(d_out, desc);
@@ -1963,9 +2023,11 @@ static int tensor_warp_check(const void *d_out, const debig_png_warp *warps, con
  * With colors the tasks are debig_png_warp_color_task -- the warp task and the place of the image's record, which travels as the
  * launch's one table -- and go to the colour kernel.  tp != NULL (debig_png_decode_batch_tensor_tone, _blur): as in tensor_core, the
  * tasks of the tone and blur files come last, write UINT8 HWC into the tone arena through a launch of their own, and tone_run and
- * blur_run follow. */
+ * blur_run follow.  persps != NULL (then warps == NULL; debig_png_decode_batch_tensor_persp): the maps are projective, each task
+ * is followed by its p[] and goes to the persp kernel of the same kind; nothing else differs. */
 static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                            const debig_png_warp *warps, const debig_png_color *colors, uint32_t *status, debig_png_info *infos,
+                            const debig_png_warp *warps, const debig_png_persp *persps, const debig_png_color *colors,
+                            uint32_t *status, debig_png_info *infos,
                             uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd,
                             tone_plan *tp)
 {
@@ -1979,11 +2041,12 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     int64_t *m = NULL;
     uint8_t *wbad = NULL, *cbad = NULL, *tasks = NULL;
     debig_png_color_rec *crec = NULL;
-    const size_t elem = colors ? sizeof(debig_png_warp_color_task) : sizeof(debig_png_warp_task);
+    const size_t base = colors ? sizeof(debig_png_warp_color_task) : sizeof(debig_png_warp_task);
+    const size_t elem = base + (persps ? sizeof(((debig_png_persp_task *)0)->p) : 0);
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     int rc;
-    if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
+    if ((rc = warp_prepare(warps, persps, n, W, H, &m, &wbad))) goto done;
     if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
     if ((rc = tone_prepare(tp, n))) goto done;
     const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad, tp ? tp->bad : NULL, tp ? tp->blur_bad : NULL}; /* no crop-size cap */
@@ -2001,12 +2064,12 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
         const uint32_t pass = q >= n, i = (uint32_t)(pass ? q - n : q);
         if (q == n) n_direct = n_tasks;
         if (status[i] != DEBIG_PNG_OK || tone_is(tp, i) != (int)pass) continue;
-        debig_png_warp_color_task p; /* (the plain task: its first elem bytes) */
+        debig_png_warp_color_task p; /* (the plain task: its first `base` bytes) */
         memset(&p, 0, sizeof p);
         p.color_off = (uint64_t)i * sizeof *crec;
         p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * ch * sb;
         p.out_off = (uint64_t)i * slot;
-        memcpy(p.m, m + 6u * (size_t)i, sizeof p.m);
+        memcpy(p.m, m + MAP_INTS * (size_t)i, sizeof p.m);
         p.src_pitch = S.inf[i].width * ch;
         p.crop_w = S.box[i].w;
         p.crop_h = S.box[i].h;
@@ -2036,7 +2099,7 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
             if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
             p.rows = H - y0 < run ? H - y0 : run;
-            memcpy(tasks + n_tasks++ * elem, &p, elem);
+            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL);
         }
     }
     if (!tp) n_direct = n_tasks;
@@ -2050,10 +2113,15 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
         const uint64_t cnt = part ? n_tasks - n_direct : n_direct;
         void *out = part ? c->tone_px.ptr : d_out;
         if (cnt == 0) continue;
-        if ((rc = colors ? debig_hip_png_warp_color_batch(c->rsz_src.ptr, out, (const debig_png_warp_color_task *)d_tasks,
+        if (persps)
+            rc = colors ? debig_hip_png_persp_color_batch(c->rsz_src.ptr, out, (const debig_png_persp_color_task *)d_tasks,
                                                           c->rsz_weights.ptr, (uint32_t)cnt, NULL)
-                         : debig_hip_png_warp_batch(c->rsz_src.ptr, out, (const debig_png_warp_task *)d_tasks, (uint32_t)cnt, NULL)))
-            goto done;
+                        : debig_hip_png_persp_batch(c->rsz_src.ptr, out, (const debig_png_persp_task *)d_tasks, (uint32_t)cnt, NULL);
+        else
+            rc = colors ? debig_hip_png_warp_color_batch(c->rsz_src.ptr, out, (const debig_png_warp_color_task *)d_tasks,
+                                                         c->rsz_weights.ptr, (uint32_t)cnt, NULL)
+                        : debig_hip_png_warp_batch(c->rsz_src.ptr, out, (const debig_png_warp_task *)d_tasks, (uint32_t)cnt, NULL);
+        if (rc) goto done;
     }
     if ((rc = tone_run(tp, c, d_out, n, desc, lut_off)) || (rc = blur_run(tp, c, d_out, n, desc, lut_off))) goto done;
     rc = debig_hip_stream_sync(NULL);
@@ -2076,7 +2144,7 @@ DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, c
     if (n == 0) return 0;
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, n, flags, desc, wd, NULL);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, NULL, status, infos, n, flags, desc, wd, NULL);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2090,21 +2158,22 @@ DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inp
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
     if (!colors || !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd, NULL);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, colors, status, infos, n, flags, desc, wd, NULL);
 }
 
-/* debig_png_decode_batch_tensor_tone (blurs == NULL, blur_call == 0) and debig_png_decode_batch_tensor_blur */
+/* debig_png_decode_batch_tensor_tone (blurs == NULL, blur_call == 0) and debig_png_decode_batch_tensor_blur; persp_call (then
+ * warps == NULL): the same two behind debig_png_decode_batch_tensor_persp, the map projective, persps and wd required */
 static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                            const debig_png_warp *warps, const debig_png_color *colors, const debig_png_tone *tones,
-                            const uint8_t *tables, uint32_t n_tables, const debig_png_blur *blurs, int blur_call, uint32_t *status,
-                            debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                            const debig_png_warp *warps, const debig_png_persp *persps, const debig_png_color *colors, const debig_png_tone *tones,
+                            const uint8_t *tables, uint32_t n_tables, const debig_png_blur *blurs, int blur_call, int persp_call,
+                            uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
                             const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
 {
     /* every check of the call that is extended first, unchanged and in its order; then the call's own */
     if (n == 0) return 0;
     uint32_t amode = DEBIG_PNG_ALPHA_STRAIGHT;
-    if (warps || wd) {
-        const int badarg = tensor_warp_check(d_out, warps, desc, wd);
+    if (warps || persps || wd || persp_call) { /* (persp_call: the map and its descriptor are required, refused where the warp's are) */
+        const int badarg = tensor_warp_check(d_out, warps ? (const void *)warps : (const void *)persps, desc, wd);
         if (badarg) return badarg;
         if ((colors && !color_layout_ok(desc->out_format)) || alpha || filter) return DEBIG_PNG_BAD_ARG;
     } else if (colors) {
@@ -2127,7 +2196,8 @@ static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_
     tp.n_tables = n_tables;
     tp.blurs = blurs;
     tp.oc = fmt_channels(desc->out_format);
-    if (warps) return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, colors, status, infos, n, flags, desc, wd, &tp);
+    if (warps || persps)
+        return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, persps, colors, status, infos, n, flags, desc, wd, &tp);
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
                        filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors, &tp);
 }
@@ -2140,8 +2210,8 @@ DEBIG_API int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, c
                                                  const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter,
                                                  const debig_png_warp_desc *wd)
 {
-    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, colors, tones, tables, n_tables, NULL, 0, status, infos, n, flags,
-                            desc, alpha, filter, wd);
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, NULL, 0, 0, status, infos, n,
+                            flags, desc, alpha, filter, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2152,20 +2222,39 @@ DEBIG_API int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, c
                                                  const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha,
                                                  const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
 {
-    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, colors, tones, tables, n_tables, blurs, 1, status, infos, n, flags,
-                            desc, alpha, filter, wd);
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, blurs, 1, 0, status, infos, n,
+                            flags, desc, alpha, filter, wd);
 }
 
-DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                                 const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
-                                                 debig_png_info *infos, uint32_t n, uint32_t flags,
-                                                 const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
+DEBIG_API int debig_png_decode_batch_tensor_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                  const debig_png_box *boxes, const debig_png_persp *persps,
+                                                  const debig_png_color *colors, const debig_png_tone *tones, const uint8_t *tables,
+                                                  uint32_t n_tables, const debig_png_blur *blurs, uint32_t *status,
+                                                  debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                  const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
+{
+    /* the affine call that the given arguments name, its checks in its order: _tensor_blur with blurs, _tensor_tone with tones,
+     * else _tensor_warp_color or _tensor_warp */
+    if (tones || blurs)
+        return tensor_post_call(inputs, input_sizes, d_out, boxes, NULL, persps, colors, tones, tables, n_tables, blurs, blurs != NULL,
+                                1, status, infos, n, flags, desc, NULL, NULL, wd);
+    if (n == 0) return 0;
+    const int badarg = tensor_warp_check(d_out, persps, desc, wd);
+    if (badarg) return badarg;
+    if (colors && !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, colors, status, infos, n, flags, desc, wd, NULL);
+}
+
+/* debig_png_decode_batch_labels_warp (warps) and debig_png_decode_batch_labels_persp (persps): exactly one of the two may be given */
+static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
+                            const debig_png_warp *warps, const debig_png_persp *persps, uint32_t *status, debig_png_info *infos,
+                            uint32_t n, uint32_t flags, const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
     /* every check of debig_png_decode_batch_labels first and unchanged, then the warp's; all before any file is looked at */
     if (n == 0) return 0;
     const int badarg = label_args_check(d_out, desc);
     if (badarg) return badarg;
-    if (!warps || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) return DEBIG_PNG_BAD_ARG;
+    if ((!warps && !persps) || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) return DEBIG_PNG_BAD_ARG;
     if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
         (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
         return DEBIG_PNG_BAD_ARG;
@@ -2174,12 +2263,12 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     int64_t *m = NULL;
-    uint8_t *wbad = NULL;
-    debig_png_label_warp_task *tasks = NULL;
+    uint8_t *wbad = NULL, *tasks = NULL;
+    const size_t base = sizeof(debig_png_label_warp_task), elem = base + (persps ? sizeof(((debig_png_label_persp_task *)0)->p) : 0);
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     int rc;
-    if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
+    if ((rc = warp_prepare(warps, persps, n, W, H, &m, &wbad))) goto done;
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
     const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL, NULL, NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
@@ -2191,7 +2280,7 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
         p.src_bytes = S.inf[i].bit_depth == 16 ? 2u : 1u;
         p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * p.src_bytes;
         p.out_off = (uint64_t)i * H * W * es;
-        memcpy(p.m, m + 6u * (size_t)i, sizeof p.m);
+        memcpy(p.m, m + MAP_INTS * (size_t)i, sizeof p.m);
         p.src_pitch = S.inf[i].width;
         p.crop_w = S.box[i].w;
         p.crop_h = S.box[i].h;
@@ -2201,19 +2290,22 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
         p.dtype = (uint8_t)desc->dtype;
         p.border_mode = (uint8_t)wd->border_mode;
         for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof p)) goto done;
+            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
             p.rows = H - y0 < run ? H - y0 : run;
-            tasks[n_tasks++] = p;
+            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL);
         }
     }
     rc = 0;
     if (n_tasks == 0) goto done;
     const dev_table lut = {desc->lut, 1024, 0}; /* the LUT (or its room) */
-    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, &lut, 1, &rc);
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, &lut, 1, &rc);
     if (!c) goto done;
-    if ((rc = debig_hip_png_label_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_warp_task *)c->rsz_tasks.ptr,
-                                             desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL, (uint32_t)n_tasks, NULL)))
+    const int32_t *d_lut = desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL;
+    if ((rc = persps ? debig_hip_png_label_persp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_persp_task *)c->rsz_tasks.ptr,
+                                                       d_lut, (uint32_t)n_tasks, NULL)
+                     : debig_hip_png_label_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_warp_task *)c->rsz_tasks.ptr,
+                                                      d_lut, (uint32_t)n_tasks, NULL)))
         goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
@@ -2224,11 +2316,28 @@ done:
     return rc;
 }
 
-DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
-                                                       const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
-                                                       debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
-                                                       const debig_png_color_label_desc *desc,
-                                                       const debig_png_label_warp_desc *wd)
+DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                 const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                 debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                 const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
+{
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, n, flags, desc, wd);
+}
+
+DEBIG_API int debig_png_decode_batch_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                  const debig_png_box *boxes, const debig_png_persp *persps, uint32_t *status,
+                                                  debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                  const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
+{
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, status, infos, n, flags, desc, wd);
+}
+
+/* debig_png_decode_batch_color_labels_warp (warps) and debig_png_decode_batch_color_labels_persp (persps): exactly one of the
+ * two may be given */
+static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
+                                  const debig_png_warp *warps, const debig_png_persp *persps, uint32_t *status,
+                                  debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
+                                  const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
     /* every check of debig_png_decode_batch_color_labels first and unchanged, then the warp's; all before any file is looked at */
     if (n == 0) return 0;
@@ -2236,14 +2345,15 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
     uint32_t *cnt = NULL;
     stage S = {NULL, NULL, NULL, NULL, NULL};
     int64_t *m = NULL;
-    uint8_t *wbad = NULL;
-    debig_png_color_label_warp_task *tasks = NULL;
+    uint8_t *wbad = NULL, *tasks = NULL;
+    const size_t base = sizeof(debig_png_color_label_warp_task),
+                 elem = base + (persps ? sizeof(((debig_png_color_label_persp_task *)0)->p) : 0);
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     int rc;
     if ((rc = clbl_args_check(d_out, desc, n, &M))) goto done;
     rc = DEBIG_PNG_BAD_ARG;
-    if (!warps || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) goto done;
+    if ((!warps && !persps) || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) goto done;
     if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
         (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
         goto done;
@@ -2255,7 +2365,7 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
     rc = 2;
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
     if (!cnt) goto done;
-    if ((rc = warp_prepare(warps, n, &m, &wbad))) goto done;
+    if ((rc = warp_prepare(warps, persps, n, W, H, &m, &wbad))) goto done;
     const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
@@ -2268,7 +2378,7 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
         memset(&p, 0, sizeof p);
         p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * 3u;
         p.out_off = (uint64_t)i * H * W * es;
-        memcpy(p.m, m + 6u * (size_t)i, sizeof p.m);
+        memcpy(p.m, m + MAP_INTS * (size_t)i, sizeof p.m);
         p.src_pitch = S.inf[i].width;
         p.crop_w = S.box[i].w;
         p.crop_h = S.box[i].h;
@@ -2285,20 +2395,24 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
             p.missing = desc->missing;
         }
         for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, sizeof p)) goto done;
+            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
             p.rows = H - y0 < run ? H - y0 : run;
-            tasks[n_tasks++] = p;
+            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL);
         }
     }
     rc = 0;
     if (n_tasks == 0) goto done;
-    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, tab, 2, &rc);
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, 2, &rc);
     if (!c) goto done;
     uint32_t *d_cnt = map_mode ? (uint32_t *)((uint8_t *)c->rsz_weights.ptr + tab[1].off) : NULL;
     if ((d_cnt && (rc = debig_hip_memset(d_cnt, 0, tab[1].bytes, NULL))) ||
-        (rc = debig_hip_png_color_label_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_color_label_warp_task *)c->rsz_tasks.ptr,
-                                                   c->rsz_weights.ptr, d_cnt, (uint32_t)n_tasks, NULL)) ||
+        (rc = persps ? debig_hip_png_color_label_persp_batch(c->rsz_src.ptr, d_out,
+                                                             (const debig_png_color_label_persp_task *)c->rsz_tasks.ptr,
+                                                             c->rsz_weights.ptr, d_cnt, (uint32_t)n_tasks, NULL)
+                     : debig_hip_png_color_label_warp_batch(c->rsz_src.ptr, d_out,
+                                                            (const debig_png_color_label_warp_task *)c->rsz_tasks.ptr,
+                                                            c->rsz_weights.ptr, d_cnt, (uint32_t)n_tasks, NULL)) ||
         (d_cnt && (rc = debig_hip_memcpy_d2h(cnt, d_cnt, tab[1].bytes, NULL))) ||
         (rc = debig_hip_stream_sync(NULL)))
         goto done;
@@ -2311,4 +2425,22 @@ done:
     free(wbad);
     free(tasks);
     return rc;
+}
+
+DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                       const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                       debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
+                                                       const debig_png_color_label_desc *desc,
+                                                       const debig_png_label_warp_desc *wd)
+{
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, unmatched, n, flags, desc, wd);
+}
+
+DEBIG_API int debig_png_decode_batch_color_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                        const debig_png_box *boxes, const debig_png_persp *persps, uint32_t *status,
+                                                        debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
+                                                        const debig_png_color_label_desc *desc,
+                                                        const debig_png_label_warp_desc *wd)
+{
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, status, infos, unmatched, n, flags, desc, wd);
 }

@@ -116,9 +116,9 @@ debig_png_resize_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restri
 
 // the rows of one task at source precision P: the walk and the picks of warp_rows (png_warp_kernel.inc), the pixel's channels
 // collected, mixed and stored; the channel count sc is a run-time value as in rsz_color_pass2
-template <uint32_t P>
-DEV_INLINE void warp_color_rows(const debig_png_warp_color_task &t, const debig_png_warp_color_task *__restrict__ tg,
-                                const debig_png_color_rec &cr, const uint8_t *__restrict__ src, uint8_t *__restrict__ out, uint32_t tid)
+template <uint32_t P, class Walk, class Task>
+DEV_INLINE void warp_color_rows(const Task &t, const Task *__restrict__ tg, const debig_png_color_rec &cr,
+                                const uint8_t *__restrict__ src, uint8_t *__restrict__ out, uint32_t tid)
 {
     typedef typename RszSample<P>::sample_t sample_t;
     constexpr uint32_t VMAX = ((1u << P) - 1u) << (30u - P);
@@ -127,7 +127,7 @@ DEV_INLINE void warp_color_rows(const debig_png_warp_color_task &t, const debig_
     const uint32_t sc = t.channels;
     const bool alpha = sc == 4u;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         uint32_t v[3], m[3], va = 0u;
         if (nearest) {
@@ -172,7 +172,7 @@ debig_png_warp_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict
             continue;
         const debig_png_color_rec cr = *reinterpret_cast<const debig_png_color_rec *>(weights + t.color_off);
         if (!color_rec_ok(cr, t.bits)) continue;
-        if (t.bits == 8u) warp_color_rows<8u>(t, &tasks[ti], cr, src, out, tid);
-        else warp_color_rows<16u>(t, &tasks[ti], cr, src, out, tid);
+        if (t.bits == 8u) warp_color_rows<8u, WarpAffine>(t, &tasks[ti], cr, src, out, tid);
+        else warp_color_rows<16u, WarpAffine>(t, &tasks[ti], cr, src, out, tid);
     }
 }

@@ -22,15 +22,15 @@
 // png_color_label_kernel.inc and png_warp_kernel.inc in front of it.
 
 // the rows of one task: elements of ES bytes -> the lane's misses
-template <uint32_t ES, bool MAP>
-DEV_INLINE uint32_t clbl_warp_rows(const uint2 *tab, const debig_png_color_label_warp_task &t, const uint8_t *__restrict__ src,
-                                   uint8_t *__restrict__ out, uint32_t tid)
+template <uint32_t ES, bool MAP, class Walk, class Task>
+DEV_INLINE uint32_t clbl_warp_rows(const uint2 *tab, const Task &t, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                                   uint32_t tid)
 {
     const uint8_t *s0 = src + t.src_off;
     const uint32_t missing = (uint32_t)t.missing;
     uint32_t misses = 0u;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
-    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const WarpPick pk = warp_pick(t, clamp, U, V);
         const uint8_t *p = s0 + ((uint64_t)pk.jy * t.src_pitch + pk.jx) * 3u;
         const uint32_t key = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
@@ -66,16 +66,16 @@ debig_png_color_label_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__re
                             (t.map_off & 15u) || !unmatched))
             continue;
         if (t.mode == 0u) {
-            if (t.dtype == 2u) clbl_warp_rows<4u, false>(tab, t, src, out, tid);
-            else clbl_warp_rows<8u, false>(tab, t, src, out, tid);
+            if (t.dtype == 2u) clbl_warp_rows<4u, false, WarpAffine>(tab, t, src, out, tid);
+            else clbl_warp_rows<8u, false, WarpAffine>(tab, t, src, out, tid);
             continue;
         }
         clbl_hold_map(lds_map, held, t, tables, tid);
         uint32_t m;
-        if (t.dtype == 0u) m = clbl_warp_rows<1u, true>(tab, t, src, out, tid);
-        else if (t.dtype == 1u) m = clbl_warp_rows<2u, true>(tab, t, src, out, tid);
-        else if (t.dtype == 2u) m = clbl_warp_rows<4u, true>(tab, t, src, out, tid);
-        else m = clbl_warp_rows<8u, true>(tab, t, src, out, tid);
+        if (t.dtype == 0u) m = clbl_warp_rows<1u, true, WarpAffine>(tab, t, src, out, tid);
+        else if (t.dtype == 1u) m = clbl_warp_rows<2u, true, WarpAffine>(tab, t, src, out, tid);
+        else if (t.dtype == 2u) m = clbl_warp_rows<4u, true, WarpAffine>(tab, t, src, out, tid);
+        else m = clbl_warp_rows<8u, true, WarpAffine>(tab, t, src, out, tid);
         clbl_add_misses(&unmatched[t.image], m, tid);
     }
 }

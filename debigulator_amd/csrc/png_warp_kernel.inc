@@ -75,6 +75,12 @@ DEV_INLINE void warp_walk(const Task &t, uint32_t tid, Body body)
     }
 }
 
+// the affine walk as the policy the row bodies below take (png_persp_kernel.inc has the projective one)
+struct WarpAffine {
+    template <class Task, class Body>
+    static DEV_MEMBER_INLINE void walk(const Task &t, uint32_t tid, Body body) { warp_walk(t, tid, body); }
+};
+
 // the NEAREST pick of (U, V): the pixel (jx, jy), clamped into the crop, and whether its sample counts -- under CLAMP always,
 // under CONSTANT when the pick lay inside (else the border value takes its place, by a select).  clamp: the task's border mode
 // is CLAMP, found once per task by the caller, in front of its walk
@@ -130,17 +136,17 @@ DEV_INLINE WarpTaps warp_taps(const Task &t, bool clamp, int64_t U, int64_t V)
     return q;
 }
 
-// the rows of one task at source precision P
-template <uint32_t P>
-DEV_INLINE void warp_rows(const debig_png_warp_task &t, const debig_png_warp_task *__restrict__ tg, const uint8_t *__restrict__ src,
-                          uint8_t *__restrict__ out, uint32_t tid)
+// the rows of one task at source precision P, its pixels and their (U, V) from Walk
+template <uint32_t P, class Walk, class Task>
+DEV_INLINE void warp_rows(const Task &t, const Task *__restrict__ tg, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                          uint32_t tid)
 {
     typedef typename RszSample<P>::sample_t sample_t;
     const sample_t *s = reinterpret_cast<const sample_t *>(src + t.src_off);
     uint8_t *o = out + t.out_off;
     const uint32_t ch = t.channels;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         if (nearest) {
             const WarpPick p = warp_pick(t, clamp, U, V);
@@ -171,21 +177,21 @@ debig_png_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out
             t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
             (t.src_off & ((uint32_t)t.bits / 8u - 1u)))
             continue;
-        if (t.bits == 8u) warp_rows<8u>(t, &tasks[ti], src, out, tid);
-        else warp_rows<16u>(t, &tasks[ti], src, out, tid);
+        if (t.bits == 8u) warp_rows<8u, WarpAffine>(t, &tasks[ti], src, out, tid);
+        else warp_rows<16u, WarpAffine>(t, &tasks[ti], src, out, tid);
     }
 }
 
 // ---- the same warp of raw labels: nearest only, the picks of the image kernel's NEAREST filter ---------------------------------
 
 // the rows of one task: elements of ES bytes, source labels of SB bytes
-template <uint32_t ES, uint32_t SB>
-DEV_INLINE void warp_label_rows(const int32_t *lut, const debig_png_label_warp_task &t, const uint8_t *__restrict__ src,
-                                uint8_t *__restrict__ out, uint32_t tid)
+template <uint32_t ES, uint32_t SB, class Walk, class Task>
+DEV_INLINE void warp_label_rows(const int32_t *lut, const Task &t, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                                uint32_t tid)
 {
     const uint8_t *s0 = src + t.src_off;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
-    warp_walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const WarpPick p = warp_pick(t, clamp, U, V);
         const uint64_t at = (uint64_t)p.jy * t.src_pitch + p.jx;
         uint32_t v = SB == 1u ? (uint32_t)s0[at] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[at];
@@ -212,14 +218,14 @@ debig_png_label_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict
             !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || (t.src_off & (t.src_bytes - 1u)))
             continue;
         if (t.src_bytes == 1u) {
-            if (t.dtype == 0u) warp_label_rows<1u, 1u>(L, t, src, out, tid);
-            else if (t.dtype == 1u) warp_label_rows<2u, 1u>(L, t, src, out, tid);
-            else if (t.dtype == 2u) warp_label_rows<4u, 1u>(L, t, src, out, tid);
-            else warp_label_rows<8u, 1u>(L, t, src, out, tid);
+            if (t.dtype == 0u) warp_label_rows<1u, 1u, WarpAffine>(L, t, src, out, tid);
+            else if (t.dtype == 1u) warp_label_rows<2u, 1u, WarpAffine>(L, t, src, out, tid);
+            else if (t.dtype == 2u) warp_label_rows<4u, 1u, WarpAffine>(L, t, src, out, tid);
+            else warp_label_rows<8u, 1u, WarpAffine>(L, t, src, out, tid);
         } else {
-            if (t.dtype == 1u) warp_label_rows<2u, 2u>(L, t, src, out, tid);
-            else if (t.dtype == 2u) warp_label_rows<4u, 2u>(L, t, src, out, tid);
-            else warp_label_rows<8u, 2u>(L, t, src, out, tid);
+            if (t.dtype == 1u) warp_label_rows<2u, 2u, WarpAffine>(L, t, src, out, tid);
+            else if (t.dtype == 2u) warp_label_rows<4u, 2u, WarpAffine>(L, t, src, out, tid);
+            else warp_label_rows<8u, 2u, WarpAffine>(L, t, src, out, tid);
         }
     }
 }

@@ -202,7 +202,7 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * its own switch, DEBIG_FUSED_FLAGS & 2.) */
 /* DEBIG_STAGE_GRID (environment variable, read at every call; tests): the launchers below whose kernels loop over their
  * tasks -- debig_hip_apng_composite_batch, debig_hip_png_resize_batch / _resize_alpha / _resize_cubic / _resize_color,
- * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _tone_hist / _tone_apply and _blur --
+ * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp, _tone_hist / _tone_apply and _blur --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -689,6 +689,83 @@ typedef struct debig_png_warp_color_task {
 } debig_png_warp_color_task;
 int debig_hip_png_warp_color_batch(const void *d_src_arena, void *d_out, const debig_png_warp_color_task *d_tasks,
                                    const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
+/* ---- the four warp kernels under a projective map (csrc/png_persp_kernel.inc, behind debig_png_decode_batch_tensor_persp,
+ * _labels_persp and _color_labels_persp in decode_png.h, which has the rule).  Each task is the warp task of the kernel it
+ * mirrors, field for field, followed by p[]: row 2 of the inverse map as debig_png_persp_quantise gives it (Q30, |p[k]| <= 2^32).
+ * m[] holds rows 0 and 1, with the limits of the warp tasks.  Per output pixel D = p[0] cx + p[1] cy + 2 p[2] (Q31) and
+ * (U, V) = (floor(NU 2^31 / D), floor(NV 2^31 / D)), NU and NV being the affine U and V of m[]; everything behind (U, V), the
+ * tasks' rows, the workgroups, the lane mapping, the buffers and the grid rule are those of the warp launcher of the same kind.
+ * A task is skipped when it breaks a bound of its warp counterpart, when a |p[k]| exceeds 2^32, or when D leaves
+ * [2^21, 2^33 - 1] at one of the four corner pixels of the out_w x out_h output (D is linear, so that covers every pixel). */
+typedef struct debig_png_persp_task {
+    uint64_t src_off, out_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    uint32_t out_sx, out_sy, out_sc;
+    uint8_t channels;       /* 1..4                                                                                           */
+    uint8_t bits, dtype, filter, border_mode;
+    uint8_t reserved[3];
+    uint16_t border[4];
+    float a[4], b[4];
+    int64_t p[3];           /* row 2 of the inverse map, Q30                                                                  */
+} debig_png_persp_task;
+int debig_hip_png_persp_batch(const void *d_src_arena, void *d_out, const debig_png_persp_task *d_tasks, uint32_t n_tasks,
+                              void *hip_stream);
+
+typedef struct debig_png_persp_color_task {
+    uint64_t src_off, out_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    uint32_t out_sx, out_sy, out_sc;
+    uint8_t channels;       /* 3 or 4                                                                                         */
+    uint8_t bits, dtype, filter, border_mode;
+    uint8_t reserved[3];
+    uint16_t border[4];
+    float a[4], b[4];
+    uint64_t color_off;
+    int64_t p[3];
+} debig_png_persp_color_task;
+int debig_hip_png_persp_color_batch(const void *d_src_arena, void *d_out, const debig_png_persp_color_task *d_tasks,
+                                    const void *d_weights, uint32_t n_tasks, void *hip_stream);
+
+typedef struct debig_png_label_persp_task {
+    uint64_t src_off, out_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    int32_t border_label;
+    uint8_t src_bytes, dtype, border_mode, reserved;
+    uint32_t reserved2;
+    int64_t p[3];
+} debig_png_label_persp_task;
+int debig_hip_png_label_persp_batch(const void *d_src_arena, void *d_out, const debig_png_label_persp_task *d_tasks,
+                                    const int32_t *d_lut, uint32_t n_tasks, void *hip_stream);
+
+typedef struct debig_png_color_label_persp_task {
+    uint64_t src_off, out_off, map_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    int32_t border_label;
+    uint32_t map_slots;
+    int32_t missing;
+    uint32_t image;
+    uint8_t dtype, mode, border_mode, reserved;
+    int64_t p[3];
+} debig_png_color_label_persp_task;
+int debig_hip_png_color_label_persp_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_persp_task *d_tasks,
+                                          const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream);
 
 /* ---- tone curves of the tensor decodes (csrc/png_tone_kernel.inc, behind debig_png_decode_batch_tensor_tone in decode_png.h,
  * which has the rule).  The first stage writes every tone file as UINT8 HWC into an arena; one TASK of both kernels is a run of

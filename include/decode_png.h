@@ -518,8 +518,9 @@ uint32_t debig_png_color_map_table(const debig_png_color_map *map, uint32_t *tab
  * U16: 0 .. 65535; under CLAMP border_label is not read).  The colour-label warp leaves unmatched unwritten as well.  Per image: statuses, their order, infos and the untouched slot of a failed file are those of the call
  * that is extended, with E_WARP as above.
  * Not provided: antialiasing under a shrinking warp (shrink with the resize calls, or accept aliasing), bicubic, the OVER and
- * PREMULTIPLIED alpha modes together with a warp (alpha is warped like a colour channel, as in debig_png_decode_batch_tensor),
- * perspective maps.  (Colour jitter under a warp: debig_png_decode_batch_tensor_warp_color below.) */
+ * PREMULTIPLIED alpha modes together with a warp (alpha is warped like a colour channel, as in debig_png_decode_batch_tensor).
+ * (Colour jitter under a warp: debig_png_decode_batch_tensor_warp_color below; perspective maps: the _persp calls further
+ * down.) */
 #define DEBIG_PNG_E_WARP 16 /* the warp matrix (rules above) */
 enum { DEBIG_PNG_BORDER_CONSTANT = 0, DEBIG_PNG_BORDER_CLAMP = 1 };
 typedef struct debig_png_warp { double m[6]; } debig_png_warp; /* the inverse map, row major: (m00 m01 m02) (m10 m11 m12) */
@@ -726,6 +727,63 @@ int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, const uint6
                                        const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha /* may be NULL */,
                                        const debig_png_filter_desc *filter /* may be NULL */,
                                        const debig_png_warp_desc *warp_desc /* exactly when warps is given */);
+
+/* ---- perspective warp: keystone, homography, RandomPerspective in the tensor and both label decodes -------------------------------
+ * debig_png_decode_batch_tensor_persp, debig_png_decode_batch_labels_persp and debig_png_decode_batch_color_labels_persp are the
+ * affine-warp calls with the map made projective: persps[i].m is the INVERSE 3 x 3 matrix M of file i, row major.  The output
+ * pixel centre p = (X + 1/2, Y + 1/2, 1) maps to
+ *     (u, v) = (M0 . p / M2 . p,  M1 . p / M2 . p)
+ * in pixel units of the CROP, source pixel j covering [j, j + 1): the conventions of the affine warp.
+ * The host quantises once (debig_png_persp_quantise): rows 0 and 1 exactly as debig_png_warp_quantise does (Q16, the same limits);
+ * row 2 as p_k = llround(M_2k * 2^30), halves away from zero.  A non-finite entry or |M_2k| > 4 fails the quantisation.
+ * Per output pixel, all in int64, with cx = 2X + 1 and cy = 2Y + 1:
+ *     NU = m00 cx + m01 cy + 2 m02,  NV = m10 cx + m11 cy + 2 m12    (the affine U and V: |N| < 2^48)
+ *     D  = p0 cx + p1 cy + 2 p2                                        (Q31: 1.0 is 2^31)
+ * D must lie in [2^21, 2^33 - 1] for EVERY pixel of the output.  D is linear in X and Y, so it is checked at the four corner
+ * pixels of the out_w x out_h output (debig_png_persp_range): by the host per file, by the kernel per task.  A file that fails
+ * the quantisation or the range gets DEBIG_PNG_E_WARP, at the rank and moment of the affine E_WARP: this is the case of a
+ * horizon that crosses or nearly touches the output.  So no pixel ever meets a horizon, and CLAMP has no special case.
+ *     U = floor(NU 2^31 / D)   in Q17, without 128-bit arithmetic:
+ *         q1 = floor(NU / D)                       (floor, not truncation: NU may be negative, D > 0)
+ *         r1 = NU - q1 D                           (in [0, D))
+ *         U  = (q1 << 31) + ((uint64)r1 << 31) / D
+ *     r1 << 31 < 2^64 because D < 2^33; |q1| <= 2^27 because D >= 2^21, so |U| < 2^59.  V likewise from NV.
+ * Everything behind (U, V) is the affine warp's, word for word: the NEAREST pick (U >> 17, V >> 17), the BILINEAR taps and Q14
+ * weights from U - 65536, the CONSTANT and CLAMP borders decided in int64 before anything is narrowed, the horizontal pass
+ * rounded to 16 bits, the vertical pass into 30, the ONE conversion; labels, colour labels, border_label and unmatched.
+ * Consequences: with row 2 = (0, 0, 1), D is 2^31 at every pixel and U, V are the affine rule's bit for bit, so such a matrix
+ * gives the bytes of the _warp call of the same kind; multiplying all nine entries by 2 or by 1/2 changes no U or V (while the
+ * limits hold); an image under NEAREST, its label map and its colour-coded mask pick the same source pixel under one matrix.
+ * debig_png_decode_batch_tensor_persp takes the arguments of debig_png_decode_batch_tensor_blur with persps (required) in place of
+ * warps and without the alpha and filter descriptors: filter, border and alpha mode are warp_desc's (required).  colors, tones,
+ * tables / n_tables and blurs may each be NULL / 0; what is given selects the affine call whose argument checks (in their order),
+ * statuses, infos, untouched slot of a failed file and colour / tone / blur semantics hold: _tensor_blur with blurs, else
+ * _tensor_tone with tones, else _tensor_warp_color with colors, else _tensor_warp.  The two label calls take the arguments and
+ * rules of debig_png_decode_batch_labels_warp and debig_png_decode_batch_color_labels_warp.  One launch warps all images
+ * (debig_hip_png_persp_batch / _persp_color / _label_persp / _color_label_persp: the warp kernels with four 64-bit divisions per
+ * pixel in their walk).
+ * Not provided: what the affine warp does not provide, and homographies whose horizon crosses the output (E_WARP, above). */
+typedef struct debig_png_persp { double m[9]; } debig_png_persp; /* the inverse map, row major */
+/* Host only: m[0 .. 5] as debig_png_warp_quantise, m[6 + k] = llround(M[6 + k] * 2^30) -> 1, or 0 (m unspecified). */
+int debig_png_persp_quantise(const double M[9], int64_t m[9]);
+/* Host only: 1 when |m[6 + k]| <= 2^32, out_w and out_h are 1 .. 16384 and D lies in [2^21, 2^33 - 1] at the four corner pixels
+ * of the out_w x out_h output, else 0. */
+int debig_png_persp_range(const int64_t m[9], uint32_t out_w, uint32_t out_h);
+int debig_png_decode_batch_tensor_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                        const debig_png_box *boxes /* may be NULL */, const debig_png_persp *persps,
+                                        const debig_png_color *colors /* may be NULL */, const debig_png_tone *tones /* may be NULL */,
+                                        const uint8_t *tables /* n_tables x 256 bytes; may be NULL when n_tables == 0 */,
+                                        uint32_t n_tables, const debig_png_blur *blurs /* may be NULL */, uint32_t *status,
+                                        debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                        const debig_png_tensor_desc *desc, const debig_png_warp_desc *warp_desc);
+int debig_png_decode_batch_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                        const debig_png_box *boxes /* may be NULL */, const debig_png_persp *persps, uint32_t *status,
+                                        debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                        const debig_png_label_desc *desc, const debig_png_label_warp_desc *warp_desc);
+int debig_png_decode_batch_color_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+        const debig_png_box *boxes /* may be NULL */, const debig_png_persp *persps, uint32_t *status,
+        debig_png_info *infos /* may be NULL */, uint32_t *unmatched /* may be NULL */, uint32_t n, uint32_t flags,
+        const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *warp_desc);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

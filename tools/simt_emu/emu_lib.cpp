@@ -23,6 +23,7 @@
 #include "../../debigulator_amd/csrc/png_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_label_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_kernel.inc"
+#include "../../debigulator_amd/csrc/png_persp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_tone_kernel.inc"
 #include "../../debigulator_amd/csrc/png_blur_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
@@ -454,6 +455,41 @@ extern "C" int emu_png_warp_color_batch(const void *src_arena, void *out, const 
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_warp_color_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
                       (const uint8_t *)weights, n);
+    return 0;
+}
+
+/* the four warp kernels under a projective map (png_persp_kernel.inc), as debig_hip_png_persp_batch, _persp_color, _label_persp
+ * and _color_label_persp launch them: the arguments of their warp twins above */
+extern "C" int emu_png_persp_batch(const void *src_arena, void *out, const debig_png_persp_task *tasks, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_persp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks, n);
+    return 0;
+}
+
+extern "C" int emu_png_persp_color_batch(const void *src_arena, void *out, const debig_png_persp_color_task *tasks, const void *weights,
+                                         uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_persp_color_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)weights, n);
+    return 0;
+}
+
+extern "C" int emu_png_label_persp_batch(const void *src_arena, void *out, const debig_png_label_persp_task *tasks, const int32_t *lut,
+                                         uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_persp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks, lut, n);
+    return 0;
+}
+
+extern "C" int emu_png_color_label_persp_batch(const void *src_arena, void *out, const debig_png_color_label_persp_task *tasks,
+                                               const void *tables, uint32_t *unmatched, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_color_label_persp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)tables, unmatched, n);
     return 0;
 }
 
