@@ -659,6 +659,82 @@ def _png_persps(perspective, n):
     return ps
 
 
+class PngElastic(C.Structure):  # include/decode_png.h: debig_png_elastic
+    _fields_ = [("nodes", C.c_void_p)]
+
+
+class PngElasticDesc(C.Structure):  # include/decode_png.h: debig_png_elastic_desc
+    _fields_ = [("grid_w", C.c_uint32), ("grid_h", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def png_elastic_field(size, alpha, sigma, grid=None, rng=None):
+    """a random displacement field for `elastic=` (numpy only, no GPU needed): an array of shape (grid_h, grid_w, 2) holding
+    (dx, dy) per node IN OUTPUT PIXELS for an output of size = (H, W).  Uniform noise in [-1, 1] is drawn on the node grid,
+    smoothed by a Gaussian of `sigma` output pixels (expressed in node spacings, edges replicated), scaled by `alpha` (a number, or
+    (alpha_x, alpha_y)) and clipped to +-4096.  grid = (grid_h, grid_w), each 2 .. 33; by default the node spacing is about
+    sigma.  rng: a numpy Generator, a seed, or None.  This is a GENERATOR in the spirit of torchvision's ElasticTransform, not a
+    parity target: it does not reproduce that transform's random numbers or its full-resolution blur."""
+    H, W = (int(v) for v in size)
+    sigma = float(sigma)
+    if H < 1 or W < 1 or not sigma > 0.0:
+        raise ValueError("png_elastic_field needs a size of at least 1 x 1 and sigma > 0")
+    if grid is None:
+        grid = tuple(int(min(33, max(2, round(v / sigma) + 1))) for v in (H, W))
+    gh, gw = (int(v) for v in grid)
+    if not (2 <= gh <= 33 and 2 <= gw <= 33):
+        raise ValueError("grid dimensions must lie in 2 .. 33")
+    ax, ay = (float(v) for v in (alpha if hasattr(alpha, "__len__") else (alpha, alpha)))
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    f = rng.uniform(-1.0, 1.0, size=(gh, gw, 2))
+    for axis, (g, extent) in enumerate(((gh, H), (gw, W))):
+        s = sigma * (g - 1) / extent  # sigma in node spacings
+        r = int(min(g - 1, np.ceil(3.0 * s)))
+        if r < 1:
+            continue
+        k = np.exp(-0.5 * (np.arange(-r, r + 1) / s) ** 2)
+        k /= k.sum()
+        idx = np.clip(np.arange(g)[:, None] + np.arange(-r, r + 1)[None, :], 0, g - 1)  # (g, 2r + 1), edges replicated
+        f = np.moveaxis(np.tensordot(k, np.moveaxis(f, axis, 0)[idx], axes=([0], [1])), 0, axis)
+    f = f * np.array((ax, ay))
+    return np.clip(f, -4096.0, 4096.0)
+
+
+def _png_elastics(elastic, n):
+    """elastic: a sequence of n entries, each None (no field) or an array of shape (grid_h, grid_w, 2), all of one shape ->
+    (PngElastic * n) (which keeps the arrays alive), PngElasticDesc"""
+    if len(elastic) != n:
+        raise ValueError("elastic needs one entry (a (grid_h, grid_w, 2) array, or None) per file")
+    es = (PngElastic * n)()
+    keep, shape = [], None
+    for i, e in enumerate(elastic):
+        if e is None:
+            continue
+        a = np.ascontiguousarray(e, dtype=np.float64)
+        if a.ndim != 3 or a.shape[2] != 2 or not (2 <= a.shape[0] <= 33 and 2 <= a.shape[1] <= 33):
+            raise ValueError(f"elastic[{i}] must have the shape (grid_h, grid_w, 2) with grid_h and grid_w in 2 .. 33")
+        if shape is not None and a.shape != shape:
+            raise ValueError(f"elastic[{i}] has the shape {a.shape}, an earlier entry {shape}: one grid size per call")
+        shape = a.shape
+        keep.append(a)
+        es[i].nodes = a.ctypes.data
+    es._keep = keep
+    gh, gw = shape[:2] if shape is not None else (2, 2)
+    return es, PngElasticDesc(gw, gh, (C.c_uint32 * 2)(0, 0))
+
+
+def _png_fit_warps(datas, boxes, size):
+    """what `elastic=` without `warp=` takes as its matrices: per file png_warp_matrix((crop_w, crop_h), size), which puts the
+    crop's centre on the output's centre at the crop's own scale; a file whose header cannot be read gets the identity (and its
+    decode status)"""
+    ws = []
+    for i, x in enumerate(datas):
+        st, inf = png_info(x)
+        b = boxes[i] if boxes is not None else None
+        cw, ch = (int(b[2]), int(b[3])) if b is not None and (int(b[2]) or int(b[3])) else (inf["width"], inf["height"])
+        ws.append(png_warp_matrix((cw, ch), size) if st == 0 and cw > 0 and ch > 0 else None)
+    return ws
+
+
 def png_warp_desc(filter="bilinear", border="constant", border_value=None, mode="rgb", depth=8, alpha="straight"):
     """the debig_png_warp_desc of png_decode_batch_tensor's warp arguments (no GPU needed).  filter: "bilinear" | "nearest";
     border: "constant" (a tap outside the crop is border_value: per channel on the [0, 1] scale, a number for every channel,
@@ -840,7 +916,7 @@ def _png_blurs(blur, n):
 def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", layout="chw", mean=None, std=None, boxes=None,
                             antialias=True, device="cuda:0", fill=None, force_general=False, alpha="straight",
                             background=None, warp=None, border="constant", border_value=None, color=None, tone=None, perspective=None,
-                            blur=None, filter="bilinear"):
+                            elastic=None, blur=None, filter="bilinear"):
     """bytes of N PNG files -> ONE dense tensor on the GPU, cropped, resized to size = (H, W), converted and normalised
     (include/decode_png.h: debig_png_decode_batch_tensor) -> (statuses, tensor, infos).  tensor: (N, C, H, W), or
     (N, H, W, C) with layout="hwc", one allocation; dtype "float32" | "float16" | "bfloat16" (value = sample01 / std -
@@ -895,11 +971,28 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     border_value and alpha rules, goes with color, tone and blur exactly as warp does, and with row (0, 0, 1) gives the bytes of
     warp=.  A matrix whose horizon crosses or nearly touches the output, or with a non-finite or too large entry: status 16
     ("warp").  (By name, like `tone`.  It stands in front of `blur`, which with `filter` stays at the end of the list: `blur`, like
-    every argument behind `background`, is to be passed by name -- a positional `blur` would now land here and be refused.)"""
+    every argument behind `background`, is to be passed by name -- a positional `blur` would now land here and be refused.)
+    elastic (by name, like `perspective`, behind which it stands): None (everything above, unchanged), or one entry per file: None (no field) or an array
+    of shape (grid_h, grid_w, 2), the displacement (dx, dy) IN OUTPUT PIXELS at each node of a grid that spans the output from edge
+    to edge (png_elastic_field draws one); all entries of a call share one shape, grid_h and grid_w in 2 .. 33 --
+    debig_png_decode_batch_tensor_elastic.  The field is interpolated with Catmull-Rom weights in integers and displaces the output
+    sampling point BEFORE the matrix of `warp` maps it into the crop: one resampling.  Without `warp` each file takes
+    png_warp_matrix((crop_w, crop_h), size), the crop centred on the output at its own scale (to resize, pass warp= with a scale).  filter, border, border_value, alpha, color, tone
+    and blur follow the rules of `warp`; an entry of None or of zeros gives the bytes of the call without `elastic`, and the same
+    field given to png_decode_batch_labels / _color_labels picks the same source pixels as filter="nearest" here.  With
+    `perspective`: ValueError.  A non-finite node or one above 4096 pixels in magnitude: status 16 ("warp")."""
     import torch
 
     if perspective is not None and warp is not None:
         raise ValueError("perspective and warp exclude each other")
+    if elastic is not None:
+        if perspective is not None:
+            raise ValueError("elastic and perspective exclude each other")
+        els, eld = _png_elastics(elastic, len(datas))
+        if boxes is not None and len(boxes) != len(datas):
+            raise ValueError("boxes needs one entry (or None) per file")
+        if warp is None:
+            warp = _png_fit_warps(datas, boxes, size)
 
     if tone is not None:
         if depth != 8:
@@ -947,7 +1040,17 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     shape = (n, ch, H, W) if d.out_layout else (n, H, W, ch)
     out = _png_dense_out(shape, tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if perspective is not None:
+    if elastic is not None:
+        bs = _png_blurs(blur, n) if blur is not None else None
+        ts, tabs, n_tabs = _png_tones(tone, n) if tone is not None else (None, None, 0)
+        L.debig_png_decode_batch_tensor_elastic.restype = C.c_int
+        L.debig_png_decode_batch_tensor_elastic.argtypes = [C.c_void_p] * 8 + [C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + \
+            [C.c_void_p] * 4
+        rc = L.debig_png_decode_batch_tensor_elastic(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, cs, ts,
+                                                     tabs.ctypes.data if tabs is not None else None, n_tabs, bs, status, infos, n,
+                                                     PNG_FORCE_GENERAL if force_general else 0, C.byref(d), C.byref(wd), els,
+                                                     C.byref(eld))
+    elif perspective is not None:
         ps = _png_persps(perspective, n)
         bs = _png_blurs(blur, n) if blur is not None else None
         ts, tabs, n_tabs = _png_tones(tone, n) if tone is not None else (None, None, 0)
@@ -1064,7 +1167,7 @@ def png_label_warp_desc(border="constant", border_label=None, dtype="int64"):
 
 
 def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fill=None, device="cuda:0", warp=None,
-                            border="constant", border_label=None, perspective=None):
+                            border="constant", border_label=None, perspective=None, elastic=None):
     """bytes of N label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_labels) -> (statuses, tensor, infos).  The label of a pixel is its palette index (colour type 3)
     or its raw grey sample (colour type 0, 1 to 16 bits): nothing is scaled, PLTE colours and tRNS are ignored.  size =
@@ -1082,11 +1185,23 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     perspective (by name; the last parameter, so every older positional call means what it meant): in place of warp (both
     together: ValueError), one entry per file: None (the identity) or the INVERSE 3 x 3 matrix of
     png_decode_batch_tensor(perspective=) -- debig_png_decode_batch_labels_persp: the pick is again that call's
-    filter="nearest" under the same matrix; border and border_label as for warp.  A horizon across the output: status 16."""
+    filter="nearest" under the same matrix; border and border_label as for warp.  A horizon across the output: status 16.
+    elastic (by name; the last parameter): None, or one entry per file: None or a (grid_h, grid_w, 2) displacement field, as
+    png_decode_batch_tensor(elastic=) takes it -- debig_png_decode_batch_labels_elastic: the pick is that call's filter="nearest"
+    under the same matrix and field.  It goes with warp; without warp each file takes png_warp_matrix((crop_w, crop_h), size).  With
+    perspective: ValueError.  A bad node: status 16."""
     import torch
 
     if perspective is not None and warp is not None:
         raise ValueError("perspective and warp exclude each other")
+    if elastic is not None:
+        if perspective is not None:
+            raise ValueError("elastic and perspective exclude each other")
+        els, eld = _png_elastics(elastic, len(datas))
+        if boxes is not None and len(boxes) != len(datas):
+            raise ValueError("boxes needs one entry (or None) per file")
+        if warp is None:
+            warp = _png_fit_warps(datas, boxes, size)
     wd = None
     if warp is not None or perspective is not None:
         wd = png_label_warp_desc(border, border_label, dtype)
@@ -1103,7 +1218,12 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     tdt = {"uint8": torch.uint8, "uint16": getattr(torch, "uint16", torch.int16), "int32": torch.int32, "int64": torch.int64}[dtype]
     out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
-    if perspective is not None:
+    if elastic is not None:
+        L.debig_png_decode_batch_labels_elastic.restype = C.c_int
+        L.debig_png_decode_batch_labels_elastic.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+        rc = L.debig_png_decode_batch_labels_elastic(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos, n, 0,
+                                                     C.byref(d), C.byref(wd), els, C.byref(eld))
+    elif perspective is not None:
         L.debig_png_decode_batch_labels_persp.restype = C.c_int
         L.debig_png_decode_batch_labels_persp.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         rc = L.debig_png_decode_batch_labels_persp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, _png_persps(perspective, n),
@@ -1196,7 +1316,7 @@ def png_color_label_desc(size, colors=None, missing=-1, dtype="int64", n=None):
 
 
 def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="int64", boxes=None, fill=None, device="cuda:0",
-                                  perspective=None, warp=None, border="constant", border_label=None):
+                                  perspective=None, elastic=None, warp=None, border="constant", border_label=None):
     """bytes of N colour-coded label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_color_labels) -> (statuses, tensor, infos, unmatched).  The colour of a pixel is what
     png_decode_batch(mode="rgb") gives for it (palette files through PLTE, grey replicated, alpha and tRNS dropped), packed as
@@ -1216,11 +1336,24 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     call's filter="nearest" and png_decode_batch_labels(perspective=); border, border_label and unmatched as for warp.  A horizon
     across the output: status 16.  NOTE: `perspective` stands in front of `warp` in the parameter list (`warp`, `border` and
     `border_label` stay the last three), so `warp`, `border` and `border_label` are to be passed BY NAME from now on: a call that
-    passed `warp` as the ninth positional argument now hands it to `perspective` and is refused (a 2 x 3 entry is no 3 x 3 matrix)."""
+    passed `warp` as the ninth positional argument now hands it to `perspective` and is refused (a 2 x 3 entry is no 3 x 3 matrix).
+    elastic (by name; it stands behind `perspective`, so `warp`, `border` and `border_label` stay the last three): None, or one
+    entry per file: None or a (grid_h, grid_w, 2) displacement field, as png_decode_batch_tensor(elastic=) takes it --
+    debig_png_decode_batch_color_labels_elastic: the same pick as that call's filter="nearest" and
+    png_decode_batch_labels(elastic=); border, border_label and unmatched as for warp.  It goes with warp; without warp each
+    file takes png_warp_matrix((crop_w, crop_h), size).  With perspective: ValueError.  A bad node: status 16."""
     import torch
 
     if perspective is not None and warp is not None:
         raise ValueError("perspective and warp exclude each other")
+    if elastic is not None:
+        if perspective is not None:
+            raise ValueError("elastic and perspective exclude each other")
+        els, eld = _png_elastics(elastic, len(datas))
+        if boxes is not None and len(boxes) != len(datas):
+            raise ValueError("boxes needs one entry (or None) per file")
+        if warp is None:
+            warp = _png_fit_warps(datas, boxes, size)
     wd = None
     if warp is not None or perspective is not None:
         wd = png_label_warp_desc(border, border_label, dtype)
@@ -1238,7 +1371,12 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     out = _png_dense_out((n, d.out_h, d.out_w), tdt, fill, dev)
     in_ptrs, in_sizes, bx, status, infos = args
     unmatched = (C.c_uint32 * n)()
-    if perspective is not None:
+    if elastic is not None:
+        L.debig_png_decode_batch_color_labels_elastic.restype = C.c_int
+        L.debig_png_decode_batch_color_labels_elastic.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+        rc = L.debig_png_decode_batch_color_labels_elastic(in_ptrs, in_sizes, out.data_ptr() if n else None, bx, ws, status, infos,
+                                                           unmatched, n, 0, C.byref(d), C.byref(wd), els, C.byref(eld))
+    elif perspective is not None:
         L.debig_png_decode_batch_color_labels_persp.restype = C.c_int
         L.debig_png_decode_batch_color_labels_persp.argtypes = [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         rc = L.debig_png_decode_batch_color_labels_persp(in_ptrs, in_sizes, out.data_ptr() if n else None, bx,

@@ -23,6 +23,7 @@
 #include "png_color_label_warp_kernel.inc"
 #include "png_color_kernel.inc"
 #include "png_persp_kernel.inc"
+#include "png_elastic_kernel.inc"
 #include "png_tone_kernel.inc"
 #include "png_blur_kernel.inc"
 #include "checksum_kernel.inc"
@@ -913,6 +914,37 @@ int debig_hip_png_color_label_persp_batch(const void *d_src_arena, void *d_out, 
 {
     return launch_stage(debig_png_color_label_persp_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
                         (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched);
+}
+
+// the four warp kernels under an elastic deformation (png_elastic_kernel.inc): the tasks, buffers and grid rule of their warp
+// twins, and the nodes of the fields
+int debig_hip_png_elastic_batch(const void *d_src_arena, void *d_out, const debig_png_elastic_task *d_tasks, const void *d_fields,
+                                uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_elastic_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena, (uint8_t *)d_out,
+                        d_tasks, (const uint8_t *)d_fields);
+}
+
+int debig_hip_png_elastic_color_batch(const void *d_src_arena, void *d_out, const debig_png_elastic_color_task *d_tasks,
+                                      const void *d_weights, const void *d_fields, uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_elastic_color_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_weights, (const uint8_t *)d_fields);
+}
+
+int debig_hip_png_label_elastic_batch(const void *d_src_arena, void *d_out, const debig_png_label_elastic_task *d_tasks,
+                                      const int32_t *d_lut, const void *d_fields, uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_elastic_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, d_lut, (const uint8_t *)d_fields);
+}
+
+int debig_hip_png_color_label_elastic_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_elastic_task *d_tasks,
+                                            const void *d_tables, uint32_t *d_unmatched, const void *d_fields, uint32_t n_tasks,
+                                            void *hip_stream)
+{
+    return launch_stage(debig_png_color_label_elastic_kernel, WARP_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src_arena,
+                        (uint8_t *)d_out, d_tasks, (const uint8_t *)d_tables, d_unmatched, (const uint8_t *)d_fields);
 }
 
 // the tone curves of the tensor decode (png_tone_kernel.inc): one workgroup per pixel run, as many workgroups as tasks

@@ -1958,13 +1958,108 @@ DEBIG_API int debig_png_persp_range(const int64_t m[9], uint32_t out_w, uint32_t
     return 1;
 }
 
+/* ---- the elastic deformation of the three warp calls (decode_png.h has the rule; csrc/png_elastic_kernel.inc restates it) ------- */
+
+DEBIG_API int debig_png_elastic_quantise(const double *v, uint64_t count, int32_t *q)
+{
+    for (uint64_t k = 0; k < count; k++) {
+        uint64_t u;
+        memcpy(&u, &v[k], 8);
+        if ((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull) return 0; /* infinity or NaN */
+        if ((v[k] < 0 ? -v[k] : v[k]) > 4096.0) return 0;
+        q[k] = (int32_t)color_llround(v[k] * 65536.0); /* (the product is exact: a power of two; at most 2^28) */
+    }
+    return 1;
+}
+
+DEBIG_API void debig_png_elastic_cell(uint32_t X, uint32_t W, uint32_t g, uint32_t *k, uint32_t *t)
+{
+    const uint32_t num = (2u * X + 1u) * (g - 1u), den = 2u * W;
+    *k = num / den;
+    *t = ((num - *k * den) * 16384u + W) / den;
+}
+
+DEBIG_API void debig_png_elastic_weights(uint32_t t, int32_t w[4])
+{
+    const int64_t T = (int64_t)t, t2 = T * T, t3 = t2 * T, half = (int64_t)1 << 28;
+    /* (>> of a negative int64 is an arithmetic shift with gcc and clang, which build this file) */
+    w[0] = (int32_t)((-t3 + 2 * t2 * 16384 - T * ((int64_t)1 << 28) + half) >> 29);
+    w[1] = (int32_t)((3 * t3 - 5 * t2 * 16384 + ((int64_t)1 << 43) + half) >> 29);
+    w[2] = (int32_t)((-3 * t3 + 4 * t2 * 16384 + T * ((int64_t)1 << 28) + half) >> 29);
+    w[3] = (int32_t)((t3 - t2 * 16384 + half) >> 29);
+    if (t < 8192u) w[1] = 16384 - (w[0] + w[2] + w[3]);
+    else w[2] = 16384 - (w[0] + w[1] + w[3]);
+}
+
+DEBIG_API int debig_png_elastic_displacement(const int32_t *q, uint32_t grid_w, uint32_t grid_h, uint32_t out_w, uint32_t out_h,
+                                             uint32_t X, uint32_t Y, int64_t *Dx, int64_t *Dy)
+{
+    if (!q || grid_w < 2 || grid_w > 33 || grid_h < 2 || grid_h > 33 || out_w == 0 || out_w > 16384u || out_h == 0 ||
+        out_h > 16384u || X >= out_w || Y >= out_h)
+        return 0;
+    uint32_t kx, tx, ky, ty;
+    int32_t wx[4], wy[4];
+    debig_png_elastic_cell(X, out_w, grid_w, &kx, &tx);
+    debig_png_elastic_cell(Y, out_h, grid_h, &ky, &ty);
+    debig_png_elastic_weights(tx, wx);
+    debig_png_elastic_weights(ty, wy);
+    int64_t sx = 0, sy = 0;
+    for (uint32_t i = 0; i < 4; i++) {
+        const int64_t r = (int64_t)ky - 1 + i, ry = r < 0 ? 0 : r > (int64_t)grid_h - 1 ? (int64_t)grid_h - 1 : r;
+        for (uint32_t j = 0; j < 4; j++) {
+            const int64_t c = (int64_t)kx - 1 + j, cx = c < 0 ? 0 : c > (int64_t)grid_w - 1 ? (int64_t)grid_w - 1 : c;
+            const int32_t *d = q + 2 * (ry * grid_w + cx);
+            if (d[0] < -(1 << 28) || d[0] > (1 << 28) || d[1] < -(1 << 28) || d[1] > (1 << 28)) return 0;
+            sx += (int64_t)wy[i] * wx[j] * d[0];
+            sy += (int64_t)wy[i] * wx[j] * d[1];
+        }
+    }
+    *Dx = (sx + ((int64_t)1 << 27)) >> 28;
+    *Dy = (sy + ((int64_t)1 << 27)) >> 28;
+    return 1;
+}
+
+/* the fields of one elastic call: the caller's entries, the grid, the quantised nodes of all files (rec bytes each, zeros where a
+ * file has none) and where they land in c->rsz_weights */
+typedef struct ela_plan {
+    const debig_png_elastic *fields;
+    uint32_t gw, gh;
+    int32_t *q;
+    uint64_t rec, off;
+} ela_plan;
+
+/* the elastic arguments of a call, behind the checks of its affine call -> 0 (and *ela ready) or DEBIG_PNG_BAD_ARG */
+static int ela_check(ela_plan *ela, const debig_png_elastic *elastics, const debig_png_elastic_desc *ed)
+{
+    if (!elastics || !ed || ed->grid_w < 2 || ed->grid_w > 33 || ed->grid_h < 2 || ed->grid_h > 33 || ed->reserved[0] != 0 ||
+        ed->reserved[1] != 0)
+        return DEBIG_PNG_BAD_ARG;
+    memset(ela, 0, sizeof *ela);
+    ela->fields = elastics;
+    ela->gw = ed->grid_w;
+    ela->gh = ed->grid_h;
+    ela->rec = (uint64_t)ed->grid_w * ed->grid_h * 2u * sizeof(int32_t);
+    return 0;
+}
+
+/* the fields as the last table of a launch: its offset rounded up to the 8 bytes a node takes */
+static void ela_place(ela_plan *ela, dev_table *t, uint32_t n)
+{
+    t->src = ela->q;
+    t->bytes = (uint64_t)n * ela->rec;
+    t->off = (t->off + 7u) & ~(uint64_t)7u;
+    ela->off = t->off;
+}
+
 #define MAP_INTS 9u /* a file's quantised map: m[0..5] (both kinds), m[6..8] = p[] (the projective kind; else unused) */
 
 /* the files' maps quantised (MAP_INTS int64 each) and their E_WARP flags; exactly one of warps (affine) and persps (projective:
- * the D range over the out_w x out_h output is part of the flag) is given; -> 0 or 2 */
-static int warp_prepare(const debig_png_warp *warps, const debig_png_persp *persps, uint32_t n, uint32_t out_w, uint32_t out_h,
-                        int64_t **m, uint8_t **bad)
+ * the D range over the out_w x out_h output is part of the flag) is given; ela (with warps): the fields quantised as well, a
+ * node out of range part of the flag; -> 0 or 2 */
+static int warp_prepare(const debig_png_warp *warps, const debig_png_persp *persps, ela_plan *ela, uint32_t n, uint32_t out_w,
+                        uint32_t out_h, int64_t **m, uint8_t **bad)
 {
+    if (ela && !(ela->q = (int32_t *)calloc((size_t)n * (size_t)(ela->rec / sizeof(int32_t)), sizeof(int32_t)))) return 2;
     *m = (int64_t *)calloc((size_t)n * MAP_INTS, sizeof(int64_t));
     *bad = (uint8_t *)calloc(n, 1);
     if (!*m || !*bad) return 2;
@@ -1972,15 +2067,27 @@ static int warp_prepare(const debig_png_warp *warps, const debig_png_persp *pers
         int64_t *mi = *m + MAP_INTS * (size_t)i;
         (*bad)[i] = persps ? !(debig_png_persp_quantise(persps[i].m, mi) && debig_png_persp_range(mi, out_w, out_h))
                            : !debig_png_warp_quantise(warps[i].m, mi);
+        if (ela && ela->fields[i].nodes &&
+            !debig_png_elastic_quantise(ela->fields[i].nodes, ela->rec / sizeof(int32_t), ela->q + (size_t)i * (ela->rec / sizeof(int32_t))))
+            (*bad)[i] = 1;
     }
     return 0;
 }
 
-/* one task into the host array: its first `base` bytes (the warp task), then p[] where the map is projective */
-static void map_task_put(uint8_t *at, const void *task, size_t base, const int64_t *mi, int persp)
+#define ELA_TAIL 16u /* what an elastic task adds to its warp task: field_off, grid_w, grid_h, a reserved word */
+
+/* one task of file i into the host array: its first `base` bytes (the warp task), then p[] where the map is projective, or the
+ * place of the file's field and the grid size where the call is elastic */
+static void map_task_put(uint8_t *at, const void *task, size_t base, const int64_t *mi, int persp, const ela_plan *ela, uint32_t i)
 {
     memcpy(at, task, base);
     if (persp) memcpy(at + base, mi + 6, 3 * sizeof(int64_t));
+    if (ela) {
+        const uint64_t off = ela->fields[i].nodes ? ela->off + (uint64_t)i * ela->rec : UINT64_MAX;
+        const uint16_t g[4] = {(uint16_t)ela->gw, (uint16_t)ela->gh, 0, 0};
+        memcpy(at + base, &off, 8);
+        memcpy(at + base + 8, g, 8);
+    }
 }
 
 _Static_assert(offsetof(debig_png_warp_color_task, color_off) == sizeof(debig_png_warp_task) &&
@@ -2000,6 +2107,20 @@ _Static_assert(offsetof(debig_png_persp_task, p) == sizeof(debig_png_warp_task) 
                    offsetof(debig_png_color_label_persp_task, border_mode) == offsetof(debig_png_color_label_warp_task, border_mode) &&
                    sizeof(debig_png_color_label_persp_task) == 144,
                "each persp task is the warp task of its kernel, field for field, followed by p[3]");
+_Static_assert(offsetof(debig_png_elastic_task, field_off) == sizeof(debig_png_warp_task) &&
+                   offsetof(debig_png_elastic_task, grid_w) == sizeof(debig_png_warp_task) + 8 &&
+                   sizeof(debig_png_elastic_task) == sizeof(debig_png_warp_task) + ELA_TAIL &&
+                   offsetof(debig_png_elastic_task, b) == offsetof(debig_png_warp_task, b) &&
+                   offsetof(debig_png_elastic_color_task, field_off) == sizeof(debig_png_warp_color_task) &&
+                   offsetof(debig_png_elastic_color_task, color_off) == offsetof(debig_png_warp_color_task, color_off) &&
+                   sizeof(debig_png_elastic_color_task) == sizeof(debig_png_warp_color_task) + ELA_TAIL &&
+                   offsetof(debig_png_label_elastic_task, field_off) == sizeof(debig_png_label_warp_task) &&
+                   offsetof(debig_png_label_elastic_task, border_mode) == offsetof(debig_png_label_warp_task, border_mode) &&
+                   sizeof(debig_png_label_elastic_task) == sizeof(debig_png_label_warp_task) + ELA_TAIL &&
+                   offsetof(debig_png_color_label_elastic_task, field_off) == sizeof(debig_png_color_label_warp_task) &&
+                   offsetof(debig_png_color_label_elastic_task, border_mode) == offsetof(debig_png_color_label_warp_task, border_mode) &&
+                   sizeof(debig_png_color_label_elastic_task) == sizeof(debig_png_color_label_warp_task) + ELA_TAIL,
+               "each elastic task is the warp task of its kernel, field for field, followed by field_off and the grid size");
 
 /* the checks of debig_png_decode_batch_tensor_warp (n > 0): those of debig_png_decode_batch_tensor first and unchanged, then the
  * warp's; all before any file is looked at -> 0 or the call's return value */
@@ -2024,9 +2145,11 @@ static int tensor_warp_check(const void *d_out, const void *warps /* or the pers
  * launch's one table -- and go to the colour kernel.  tp != NULL (debig_png_decode_batch_tensor_tone, _blur): as in tensor_core, the
  * tasks of the tone and blur files come last, write UINT8 HWC into the tone arena through a launch of their own, and tone_run and
  * blur_run follow.  persps != NULL (then warps == NULL; debig_png_decode_batch_tensor_persp): the maps are projective, each task
- * is followed by its p[] and goes to the persp kernel of the same kind; nothing else differs. */
+ * is followed by its p[] and goes to the persp kernel of the same kind; nothing else differs.  ela != NULL (with warps;
+ * debig_png_decode_batch_tensor_elastic): each task is followed by the place of its file's field, the quantised fields are the
+ * launch's last table, and the tasks go to the elastic kernel of the same kind. */
 static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                            const debig_png_warp *warps, const debig_png_persp *persps, const debig_png_color *colors,
+                            const debig_png_warp *warps, const debig_png_persp *persps, ela_plan *ela, const debig_png_color *colors,
                             uint32_t *status, debig_png_info *infos,
                             uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd,
                             tone_plan *tp)
@@ -2042,21 +2165,23 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     uint8_t *wbad = NULL, *cbad = NULL, *tasks = NULL;
     debig_png_color_rec *crec = NULL;
     const size_t base = colors ? sizeof(debig_png_warp_color_task) : sizeof(debig_png_warp_task);
-    const size_t elem = base + (persps ? sizeof(((debig_png_persp_task *)0)->p) : 0);
+    const size_t elem = base + (persps ? sizeof(((debig_png_persp_task *)0)->p) : ela ? ELA_TAIL : 0);
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     int rc;
-    if ((rc = warp_prepare(warps, persps, n, W, H, &m, &wbad))) goto done;
+    if ((rc = warp_prepare(warps, persps, ela, n, W, H, &m, &wbad))) goto done;
     if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
     if ((rc = tone_prepare(tp, n))) goto done;
     const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad, tp ? tp->bad : NULL, tp ? tp->blur_bad : NULL}; /* no crop-size cap */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if ((rc = tone_place(tp, status, n, W, H))) goto done;
     /* the plain warp has no tables (the six int64 travel in the task); with colours the records are the first table, at offset 0;
-     * the tone call's tables follow */
-    dev_table tab[2] = {{crec, colors ? (uint64_t)n * sizeof *crec : 0, 0}, {tp ? tp->lut : NULL, tone_table_bytes(tp), 0}};
-    const uint32_t n_tab = tp ? 2u : 1u;
+     * the tone call's tables follow; the fields come last */
+    dev_table tab[3] = {{crec, colors ? (uint64_t)n * sizeof *crec : 0, 0}, {tp ? tp->lut : NULL, tone_table_bytes(tp), 0}, {NULL, 0, 0}};
+    const uint32_t n_tab = (tp ? 2u : 1u) + (ela ? 1u : 0u);
+    if (ela && !tp) tab[1] = tab[2];
     dev_tables_place(tab, n_tab);
+    if (ela) ela_place(ela, &tab[n_tab - 1], n);
     const uint64_t lut_off = tp ? tone_fill(tp, n, tab[1].off) : 0;
     uint64_t n_direct = 0; /* with tp: the tasks in front of those of the tone files */
     rc = 2;
@@ -2099,7 +2224,7 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
             if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
             p.rows = H - y0 < run ? H - y0 : run;
-            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL);
+            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL, ela, i);
         }
     }
     if (!tp) n_direct = n_tasks;
@@ -2113,7 +2238,12 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
         const uint64_t cnt = part ? n_tasks - n_direct : n_direct;
         void *out = part ? c->tone_px.ptr : d_out;
         if (cnt == 0) continue;
-        if (persps)
+        if (ela)
+            rc = colors ? debig_hip_png_elastic_color_batch(c->rsz_src.ptr, out, (const debig_png_elastic_color_task *)d_tasks,
+                                                            c->rsz_weights.ptr, c->rsz_weights.ptr, (uint32_t)cnt, NULL)
+                        : debig_hip_png_elastic_batch(c->rsz_src.ptr, out, (const debig_png_elastic_task *)d_tasks,
+                                                      c->rsz_weights.ptr, (uint32_t)cnt, NULL);
+        else if (persps)
             rc = colors ? debig_hip_png_persp_color_batch(c->rsz_src.ptr, out, (const debig_png_persp_color_task *)d_tasks,
                                                           c->rsz_weights.ptr, (uint32_t)cnt, NULL)
                         : debig_hip_png_persp_batch(c->rsz_src.ptr, out, (const debig_png_persp_task *)d_tasks, (uint32_t)cnt, NULL);
@@ -2133,6 +2263,7 @@ done:
     free(crec);
     free(cbad);
     free(tasks);
+    if (ela) free(ela->q);
     return rc;
 }
 
@@ -2144,7 +2275,7 @@ DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, c
     if (n == 0) return 0;
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, NULL, status, infos, n, flags, desc, wd, NULL);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, NULL, NULL, status, infos, n, flags, desc, wd, NULL);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2158,15 +2289,17 @@ DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inp
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
     if (!colors || !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, colors, status, infos, n, flags, desc, wd, NULL);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, NULL, colors, status, infos, n, flags, desc, wd, NULL);
 }
 
 /* debig_png_decode_batch_tensor_tone (blurs == NULL, blur_call == 0) and debig_png_decode_batch_tensor_blur; persp_call (then
- * warps == NULL): the same two behind debig_png_decode_batch_tensor_persp, the map projective, persps and wd required */
+ * warps == NULL): the same two behind debig_png_decode_batch_tensor_persp, the map projective, persps and wd required; ela_call
+ * (with persp_call, then persps == NULL): behind debig_png_decode_batch_tensor_elastic, warps and wd required, the elastic
+ * arguments checked behind everything else */
 static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
                             const debig_png_warp *warps, const debig_png_persp *persps, const debig_png_color *colors, const debig_png_tone *tones,
                             const uint8_t *tables, uint32_t n_tables, const debig_png_blur *blurs, int blur_call, int persp_call,
-                            uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                            int ela_call, const debig_png_elastic *elastics, const debig_png_elastic_desc *ed, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
                             const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
 {
     /* every check of the call that is extended first, unchanged and in its order; then the call's own */
@@ -2189,6 +2322,8 @@ static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_
     if ((blur_call ? !blurs : !tones) || (desc->out_format & DEBIG_PNG_FMT_16) || amode == DEBIG_PNG_ALPHA_PREMULTIPLIED ||
         (!tables && n_tables > 0))
         return DEBIG_PNG_BAD_ARG;
+    ela_plan ela;
+    if (ela_call && ela_check(&ela, elastics, ed)) return DEBIG_PNG_BAD_ARG;
     tone_plan tp;
     memset(&tp, 0, sizeof tp);
     tp.tones = tones;
@@ -2197,7 +2332,8 @@ static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_
     tp.blurs = blurs;
     tp.oc = fmt_channels(desc->out_format);
     if (warps || persps)
-        return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, persps, colors, status, infos, n, flags, desc, wd, &tp);
+        return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, persps, ela_call ? &ela : NULL, colors, status, infos, n, flags,
+                                desc, wd, &tp);
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
                        filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors, &tp);
 }
@@ -2210,7 +2346,7 @@ DEBIG_API int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, c
                                                  const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter,
                                                  const debig_png_warp_desc *wd)
 {
-    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, NULL, 0, 0, status, infos, n,
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, NULL, 0, 0, 0, NULL, NULL, status, infos, n,
                             flags, desc, alpha, filter, wd);
 }
 
@@ -2222,7 +2358,7 @@ DEBIG_API int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, c
                                                  const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha,
                                                  const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
 {
-    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, blurs, 1, 0, status, infos, n,
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, blurs, 1, 0, 0, NULL, NULL, status, infos, n,
                             flags, desc, alpha, filter, wd);
 }
 
@@ -2237,18 +2373,43 @@ DEBIG_API int debig_png_decode_batch_tensor_persp(const uint8_t *const *inputs, 
      * else _tensor_warp_color or _tensor_warp */
     if (tones || blurs)
         return tensor_post_call(inputs, input_sizes, d_out, boxes, NULL, persps, colors, tones, tables, n_tables, blurs, blurs != NULL,
-                                1, status, infos, n, flags, desc, NULL, NULL, wd);
+                                1, 0, NULL, NULL, status, infos, n, flags, desc, NULL, NULL, wd);
     if (n == 0) return 0;
     const int badarg = tensor_warp_check(d_out, persps, desc, wd);
     if (badarg) return badarg;
     if (colors && !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, colors, status, infos, n, flags, desc, wd, NULL);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, NULL, colors, status, infos, n, flags, desc, wd, NULL);
 }
 
-/* debig_png_decode_batch_labels_warp (warps) and debig_png_decode_batch_labels_persp (persps): exactly one of the two may be given */
+DEBIG_API int debig_png_decode_batch_tensor_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                    const debig_png_box *boxes, const debig_png_warp *warps,
+                                                    const debig_png_color *colors, const debig_png_tone *tones, const uint8_t *tables,
+                                                    uint32_t n_tables, const debig_png_blur *blurs, uint32_t *status,
+                                                    debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                    const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd,
+                                                    const debig_png_elastic *elastics, const debig_png_elastic_desc *ed)
+{
+    /* the affine call that the given arguments name, its checks in its order (as debig_png_decode_batch_tensor_persp); then the
+     * elastic arguments */
+    if (tones || blurs)
+        return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, blurs, blurs != NULL,
+                                1, 1, elastics, ed, status, infos, n, flags, desc, NULL, NULL, wd);
+    if (n == 0) return 0;
+    const int badarg = tensor_warp_check(d_out, warps, desc, wd);
+    if (badarg) return badarg;
+    if (colors && !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
+    ela_plan ela;
+    if (ela_check(&ela, elastics, ed)) return DEBIG_PNG_BAD_ARG;
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, &ela, colors, status, infos, n, flags, desc, wd, NULL);
+}
+
+/* debig_png_decode_batch_labels_warp (warps) and debig_png_decode_batch_labels_persp (persps): exactly one of the two may be
+ * given; ela_call (with warps): debig_png_decode_batch_labels_elastic, its two arguments checked behind the warp's */
 static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                            const debig_png_warp *warps, const debig_png_persp *persps, uint32_t *status, debig_png_info *infos,
-                            uint32_t n, uint32_t flags, const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
+                            const debig_png_warp *warps, const debig_png_persp *persps, int ela_call,
+                            const debig_png_elastic *elastics, const debig_png_elastic_desc *ed, uint32_t *status,
+                            debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_label_desc *desc,
+                            const debig_png_label_warp_desc *wd)
 {
     /* every check of debig_png_decode_batch_labels first and unchanged, then the warp's; all before any file is looked at */
     if (n == 0) return 0;
@@ -2258,17 +2419,24 @@ static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
         (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
         return DEBIG_PNG_BAD_ARG;
+    ela_plan ela_store, *ela = ela_call ? &ela_store : NULL;
+    if (ela && ela_check(ela, elastics, ed)) return DEBIG_PNG_BAD_ARG;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
     const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     int64_t *m = NULL;
     uint8_t *wbad = NULL, *tasks = NULL;
-    const size_t base = sizeof(debig_png_label_warp_task), elem = base + (persps ? sizeof(((debig_png_label_persp_task *)0)->p) : 0);
+    const size_t base = sizeof(debig_png_label_warp_task),
+                 elem = base + (persps ? sizeof(((debig_png_label_persp_task *)0)->p) : ela ? ELA_TAIL : 0);
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     int rc;
-    if ((rc = warp_prepare(warps, persps, n, W, H, &m, &wbad))) goto done;
+    if ((rc = warp_prepare(warps, persps, ela, n, W, H, &m, &wbad))) goto done;
+    dev_table tab[2] = {{desc->lut, 1024, 0}, {NULL, 0, 0}}; /* the LUT (or its room), the fields */
+    const uint32_t n_tab = ela ? 2u : 1u;
+    dev_tables_place(tab, n_tab);
+    if (ela) ela_place(ela, &tab[1], n);
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
     const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL, NULL, NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
@@ -2293,16 +2461,17 @@ static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_
             if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
             p.rows = H - y0 < run ? H - y0 : run;
-            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL);
+            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL, ela, i);
         }
     }
     rc = 0;
     if (n_tasks == 0) goto done;
-    const dev_table lut = {desc->lut, 1024, 0}; /* the LUT (or its room) */
-    debig_ctx *c = dev_upload(tasks, n_tasks, elem, &lut, 1, &rc);
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
     if (!c) goto done;
     const int32_t *d_lut = desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL;
-    if ((rc = persps ? debig_hip_png_label_persp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_persp_task *)c->rsz_tasks.ptr,
+    if ((rc = ela    ? debig_hip_png_label_elastic_batch(c->rsz_src.ptr, d_out, (const debig_png_label_elastic_task *)c->rsz_tasks.ptr,
+                                                         d_lut, c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
+              : persps ? debig_hip_png_label_persp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_persp_task *)c->rsz_tasks.ptr,
                                                        d_lut, (uint32_t)n_tasks, NULL)
                      : debig_hip_png_label_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_warp_task *)c->rsz_tasks.ptr,
                                                       d_lut, (uint32_t)n_tasks, NULL)))
@@ -2313,6 +2482,7 @@ done:
     free(m);
     free(wbad);
     free(tasks);
+    if (ela) free(ela->q);
     return rc;
 }
 
@@ -2321,7 +2491,7 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
                                                  debig_png_info *infos, uint32_t n, uint32_t flags,
                                                  const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
-    return labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, n, flags, desc, wd);
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 0, NULL, NULL, status, infos, n, flags, desc, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2329,13 +2499,23 @@ DEBIG_API int debig_png_decode_batch_labels_persp(const uint8_t *const *inputs, 
                                                   debig_png_info *infos, uint32_t n, uint32_t flags,
                                                   const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
-    return labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, status, infos, n, flags, desc, wd);
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, 0, NULL, NULL, status, infos, n, flags, desc, wd);
+}
+
+DEBIG_API int debig_png_decode_batch_labels_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                    const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                    debig_png_info *infos, uint32_t n, uint32_t flags,
+                                                    const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd,
+                                                    const debig_png_elastic *elastics, const debig_png_elastic_desc *ed)
+{
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 1, elastics, ed, status, infos, n, flags, desc, wd);
 }
 
 /* debig_png_decode_batch_color_labels_warp (warps) and debig_png_decode_batch_color_labels_persp (persps): exactly one of the
- * two may be given */
+ * two may be given; ela_call (with warps): debig_png_decode_batch_color_labels_elastic, its two arguments checked behind the warp's */
 static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                                  const debig_png_warp *warps, const debig_png_persp *persps, uint32_t *status,
+                                  const debig_png_warp *warps, const debig_png_persp *persps, int ela_call,
+                                  const debig_png_elastic *elastics, const debig_png_elastic_desc *ed, uint32_t *status,
                                   debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
                                   const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
@@ -2346,8 +2526,9 @@ static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *
     stage S = {NULL, NULL, NULL, NULL, NULL};
     int64_t *m = NULL;
     uint8_t *wbad = NULL, *tasks = NULL;
+    ela_plan ela_store, *ela = NULL;
     const size_t base = sizeof(debig_png_color_label_warp_task),
-                 elem = base + (persps ? sizeof(((debig_png_color_label_persp_task *)0)->p) : 0);
+                 elem = base + (persps ? sizeof(((debig_png_color_label_persp_task *)0)->p) : ela_call ? ELA_TAIL : 0);
     uint64_t n_tasks = 0;
     uint32_t cap_tasks = 0;
     int rc;
@@ -2357,19 +2538,23 @@ static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *
     if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
         (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
         goto done;
+    if (ela_call && ela_check(&ela_store, elastics, ed)) goto done;
+    if (ela_call) ela = &ela_store;
     const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
     const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
     /* the maps' tables (first: map_off needs no base), the counters (16-byte aligned: a table is a multiple of 16 bytes) */
-    dev_table tab[2] = {{M.tab, M.bytes, 0}, {NULL, (uint64_t)n * sizeof(uint32_t), 0}};
+    dev_table tab[3] = {{M.tab, M.bytes, 0}, {NULL, (uint64_t)n * sizeof(uint32_t), 0}, {NULL, 0, 0}}; /* (the fields come last) */
+    const uint32_t n_tab = ela ? 3u : 2u;
     rc = 2;
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
     if (!cnt) goto done;
-    if ((rc = warp_prepare(warps, persps, n, W, H, &m, &wbad))) goto done;
+    if ((rc = warp_prepare(warps, persps, ela, n, W, H, &m, &wbad))) goto done;
     const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
-    dev_tables_place(tab, 2);
+    dev_tables_place(tab, n_tab);
+    if (ela) ela_place(ela, &tab[2], n);
     rc = 2;
     for (uint32_t i = 0; i < n; i++) {
         if (status[i] != DEBIG_PNG_OK) continue;
@@ -2398,16 +2583,19 @@ static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *
             if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
             p.row0 = y0;
             p.rows = H - y0 < run ? H - y0 : run;
-            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL);
+            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL, ela, i);
         }
     }
     rc = 0;
     if (n_tasks == 0) goto done;
-    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, 2, &rc);
+    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
     if (!c) goto done;
     uint32_t *d_cnt = map_mode ? (uint32_t *)((uint8_t *)c->rsz_weights.ptr + tab[1].off) : NULL;
     if ((d_cnt && (rc = debig_hip_memset(d_cnt, 0, tab[1].bytes, NULL))) ||
-        (rc = persps ? debig_hip_png_color_label_persp_batch(c->rsz_src.ptr, d_out,
+        (rc = ela    ? debig_hip_png_color_label_elastic_batch(c->rsz_src.ptr, d_out,
+                                                               (const debig_png_color_label_elastic_task *)c->rsz_tasks.ptr,
+                                                               c->rsz_weights.ptr, d_cnt, c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
+              : persps ? debig_hip_png_color_label_persp_batch(c->rsz_src.ptr, d_out,
                                                              (const debig_png_color_label_persp_task *)c->rsz_tasks.ptr,
                                                              c->rsz_weights.ptr, d_cnt, (uint32_t)n_tasks, NULL)
                      : debig_hip_png_color_label_warp_batch(c->rsz_src.ptr, d_out,
@@ -2424,6 +2612,7 @@ done:
     free(m);
     free(wbad);
     free(tasks);
+    if (ela) free(ela->q);
     return rc;
 }
 
@@ -2433,7 +2622,8 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
                                                        const debig_png_color_label_desc *desc,
                                                        const debig_png_label_warp_desc *wd)
 {
-    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, status, infos, unmatched, n, flags, desc, wd);
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 0, NULL, NULL, status, infos, unmatched, n, flags, desc,
+                                  wd);
 }
 
 DEBIG_API int debig_png_decode_batch_color_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2442,5 +2632,17 @@ DEBIG_API int debig_png_decode_batch_color_labels_persp(const uint8_t *const *in
                                                         const debig_png_color_label_desc *desc,
                                                         const debig_png_label_warp_desc *wd)
 {
-    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, status, infos, unmatched, n, flags, desc, wd);
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, 0, NULL, NULL, status, infos, unmatched, n, flags, desc,
+                                  wd);
+}
+
+DEBIG_API int debig_png_decode_batch_color_labels_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                                          const debig_png_box *boxes, const debig_png_warp *warps, uint32_t *status,
+                                                          debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
+                                                          const debig_png_color_label_desc *desc,
+                                                          const debig_png_label_warp_desc *wd, const debig_png_elastic *elastics,
+                                                          const debig_png_elastic_desc *ed)
+{
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 1, elastics, ed, status, infos, unmatched, n, flags,
+                                  desc, wd);
 }

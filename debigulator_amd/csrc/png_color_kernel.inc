@@ -118,7 +118,8 @@ debig_png_resize_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restri
 // collected, mixed and stored; the channel count sc is a run-time value as in rsz_color_pass2
 template <uint32_t P, class Walk, class Task>
 DEV_INLINE void warp_color_rows(const Task &t, const Task *__restrict__ tg, const debig_png_color_rec &cr,
-                                const uint8_t *__restrict__ src, uint8_t *__restrict__ out, uint32_t tid)
+                                const uint8_t *__restrict__ src, uint8_t *__restrict__ out, uint32_t tid,
+                                const Walk &walk = Walk())
 {
     typedef typename RszSample<P>::sample_t sample_t;
     constexpr uint32_t VMAX = ((1u << P) - 1u) << (30u - P);
@@ -127,7 +128,7 @@ DEV_INLINE void warp_color_rows(const Task &t, const Task *__restrict__ tg, cons
     const uint32_t sc = t.channels;
     const bool alpha = sc == 4u;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    walk.walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         uint32_t v[3], m[3], va = 0u;
         if (nearest) {

@@ -24,13 +24,13 @@
 // the rows of one task: elements of ES bytes -> the lane's misses
 template <uint32_t ES, bool MAP, class Walk, class Task>
 DEV_INLINE uint32_t clbl_warp_rows(const uint2 *tab, const Task &t, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-                                   uint32_t tid)
+                                   uint32_t tid, const Walk &walk = Walk())
 {
     const uint8_t *s0 = src + t.src_off;
     const uint32_t missing = (uint32_t)t.missing;
     uint32_t misses = 0u;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
-    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    walk.walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const WarpPick pk = warp_pick(t, clamp, U, V);
         const uint8_t *p = s0 + ((uint64_t)pk.jy * t.src_pitch + pk.jx) * 3u;
         const uint32_t key = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);

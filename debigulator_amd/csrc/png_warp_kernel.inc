@@ -75,7 +75,9 @@ DEV_INLINE void warp_walk(const Task &t, uint32_t tid, Body body)
     }
 }
 
-// the affine walk as the policy the row bodies below take (png_persp_kernel.inc has the projective one)
+// the affine walk as the policy the row bodies below take (png_persp_kernel.inc has the projective one).  The bodies take the
+// walk as an OBJECT, their last argument: these two have no state and are default-constructed, png_elastic_kernel.inc's carries
+// the pointer to its grid in LDS
 struct WarpAffine {
     template <class Task, class Body>
     static DEV_MEMBER_INLINE void walk(const Task &t, uint32_t tid, Body body) { warp_walk(t, tid, body); }
@@ -139,14 +141,14 @@ DEV_INLINE WarpTaps warp_taps(const Task &t, bool clamp, int64_t U, int64_t V)
 // the rows of one task at source precision P, its pixels and their (U, V) from Walk
 template <uint32_t P, class Walk, class Task>
 DEV_INLINE void warp_rows(const Task &t, const Task *__restrict__ tg, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-                          uint32_t tid)
+                          uint32_t tid, const Walk &walk = Walk())
 {
     typedef typename RszSample<P>::sample_t sample_t;
     const sample_t *s = reinterpret_cast<const sample_t *>(src + t.src_off);
     uint8_t *o = out + t.out_off;
     const uint32_t ch = t.channels;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    walk.walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         if (nearest) {
             const WarpPick p = warp_pick(t, clamp, U, V);
@@ -187,11 +189,11 @@ debig_png_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out
 // the rows of one task: elements of ES bytes, source labels of SB bytes
 template <uint32_t ES, uint32_t SB, class Walk, class Task>
 DEV_INLINE void warp_label_rows(const int32_t *lut, const Task &t, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-                                uint32_t tid)
+                                uint32_t tid, const Walk &walk = Walk())
 {
     const uint8_t *s0 = src + t.src_off;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
-    Walk::walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    walk.walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const WarpPick p = warp_pick(t, clamp, U, V);
         const uint64_t at = (uint64_t)p.jy * t.src_pitch + p.jx;
         uint32_t v = SB == 1u ? (uint32_t)s0[at] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[at];

@@ -202,7 +202,8 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * its own switch, DEBIG_FUSED_FLAGS & 2.) */
 /* DEBIG_STAGE_GRID (environment variable, read at every call; tests): the launchers below whose kernels loop over their
  * tasks -- debig_hip_apng_composite_batch, debig_hip_png_resize_batch / _resize_alpha / _resize_cubic / _resize_color,
- * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp, _tone_hist / _tone_apply and _blur --
+ * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp,
+ * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply and _blur --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -766,6 +767,95 @@ typedef struct debig_png_color_label_persp_task {
 } debig_png_color_label_persp_task;
 int debig_hip_png_color_label_persp_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_persp_task *d_tasks,
                                           const void *d_tables, uint32_t *d_unmatched, uint32_t n_tasks, void *hip_stream);
+
+/* ---- the four warp kernels under an elastic deformation (csrc/png_elastic_kernel.inc, behind
+ * debig_png_decode_batch_tensor_elastic, _labels_elastic and _color_labels_elastic in decode_png.h, which has the rule).  Each task
+ * is the warp task of the kernel it mirrors, field for field, followed by field_off and the grid size.  field_off: where the
+ * task's grid_h x grid_w nodes lie, in bytes from d_fields, a multiple of 8; a node is two int32 (dx, dy) as
+ * debig_png_elastic_quantise gives them (Q16, at most 2^28 in magnitude), the grid row major.  UINT64_MAX: no field (d_fields is
+ * then not read for the task: it takes a field of zeros and gives the bytes of its warp twin).  Per output pixel the displacement
+ * (Dx, Dy) is interpolated from the grid, which the workgroup holds in LDS while consecutive tasks name the same field_off and
+ * grid size, and (U, V) = (NU, NV) + the linear part of m[] applied to (Dx, Dy); everything behind (U, V), the tasks' rows, the
+ * workgroups, the lane mapping, the other buffers and the grid rule are those of the warp launcher of the same kind.  A task is
+ * skipped when it breaks a bound of its warp counterpart, when grid_w or grid_h lies outside 2 .. 33, when field_off is
+ * misaligned, or when one of its nodes exceeds 2^28 in magnitude. */
+typedef struct debig_png_elastic_task {
+    uint64_t src_off, out_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    uint32_t out_sx, out_sy, out_sc;
+    uint8_t channels;       /* 1..4                                                                                           */
+    uint8_t bits, dtype, filter, border_mode;
+    uint8_t reserved[3];
+    uint16_t border[4];
+    float a[4], b[4];
+    uint64_t field_off;     /* bytes from d_fields, 8-byte aligned; UINT64_MAX: no field                                      */
+    uint16_t grid_w, grid_h; /* 2 .. 33                                                                                       */
+    uint32_t reserved3;
+} debig_png_elastic_task;
+int debig_hip_png_elastic_batch(const void *d_src_arena, void *d_out, const debig_png_elastic_task *d_tasks, const void *d_fields,
+                                uint32_t n_tasks, void *hip_stream);
+
+typedef struct debig_png_elastic_color_task {
+    uint64_t src_off, out_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    uint32_t out_sx, out_sy, out_sc;
+    uint8_t channels;       /* 3 or 4                                                                                         */
+    uint8_t bits, dtype, filter, border_mode;
+    uint8_t reserved[3];
+    uint16_t border[4];
+    float a[4], b[4];
+    uint64_t color_off;
+    uint64_t field_off;
+    uint16_t grid_w, grid_h;
+    uint32_t reserved3;
+} debig_png_elastic_color_task;
+int debig_hip_png_elastic_color_batch(const void *d_src_arena, void *d_out, const debig_png_elastic_color_task *d_tasks,
+                                      const void *d_weights, const void *d_fields, uint32_t n_tasks, void *hip_stream);
+
+typedef struct debig_png_label_elastic_task {
+    uint64_t src_off, out_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    int32_t border_label;
+    uint8_t src_bytes, dtype, border_mode, reserved;
+    uint32_t reserved2;
+    uint64_t field_off;
+    uint16_t grid_w, grid_h;
+    uint32_t reserved3;
+} debig_png_label_elastic_task;
+int debig_hip_png_label_elastic_batch(const void *d_src_arena, void *d_out, const debig_png_label_elastic_task *d_tasks,
+                                      const int32_t *d_lut, const void *d_fields, uint32_t n_tasks, void *hip_stream);
+
+typedef struct debig_png_color_label_elastic_task {
+    uint64_t src_off, out_off, map_off;
+    int64_t m[6];
+    uint32_t src_pitch;
+    uint32_t crop_w, crop_h;
+    uint32_t out_w, out_h;
+    uint32_t row0, rows;
+    int32_t border_label;
+    uint32_t map_slots;
+    int32_t missing;
+    uint32_t image;
+    uint8_t dtype, mode, border_mode, reserved;
+    uint64_t field_off;
+    uint16_t grid_w, grid_h;
+    uint32_t reserved3;
+} debig_png_color_label_elastic_task;
+int debig_hip_png_color_label_elastic_batch(const void *d_src_arena, void *d_out, const debig_png_color_label_elastic_task *d_tasks,
+                                            const void *d_tables, uint32_t *d_unmatched, const void *d_fields, uint32_t n_tasks,
+                                            void *hip_stream);
 
 /* ---- tone curves of the tensor decodes (csrc/png_tone_kernel.inc, behind debig_png_decode_batch_tensor_tone in decode_png.h,
  * which has the rule).  The first stage writes every tone file as UINT8 HWC into an arena; one TASK of both kernels is a run of

@@ -785,6 +785,86 @@ int debig_png_decode_batch_color_labels_persp(const uint8_t *const *inputs, cons
         debig_png_info *infos /* may be NULL */, uint32_t *unmatched /* may be NULL */, uint32_t n, uint32_t flags,
         const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *warp_desc);
 
+/* ---- elastic deformation: ElasticTransform, Rand2DElastic, the U-Net augmentation, in the tensor and both label decodes -----------
+ * debig_png_decode_batch_tensor_elastic, debig_png_decode_batch_labels_elastic and debig_png_decode_batch_color_labels_elastic are
+ * the affine-warp calls with a smooth displacement FIELD per file added in front of the map.  A field is a grid of
+ * grid_h x grid_w nodes (elastic_desc: each 2 .. 33, the same for every file of the call); a node holds a displacement (dx, dy)
+ * IN OUTPUT PIXELS.  Node j of an axis lies at output coordinate j W / (grid_w - 1) (j H / (grid_h - 1)): the nodes span the
+ * output from edge to edge, so ONE field serves an image and its masks even when their source resolutions differ.  The field
+ * composes with the affine map: the output sampling point is displaced first, then mapped into the crop -- one resampling, not
+ * two.
+ * The host quantises once (debig_png_elastic_quantise): d = llround(v * 65536), halves away from zero; v must be finite with
+ * |v| <= 4096, so |d| <= 2^28.  A file with a node that fails gets DEBIG_PNG_E_WARP, at the rank and moment of the affine E_WARP
+ * (no new status; E_LABEL > E_BOX > E_WARP > later, as before).
+ * Cell and fraction per axis (debig_png_elastic_cell), shown for X with g = grid_w; Y likewise with H and grid_h:
+ *     num = (2X + 1)(g - 1),  den = 2W,  k = num / den (always <= g - 2),  rem = num - k den,
+ *     t   = (rem * 16384 + W) / den                                    (Q14, 0 .. 16384)
+ * Weights (debig_png_elastic_weights): the Keys kernel with a = -1/2 (Catmull-Rom) from t in integers, t2 = t t, t3 = t2 t (int64):
+ *     n_-1 = -t3 + 2 t2 2^14 - t 2^28          n_0 = 3 t3 - 5 t2 2^14 + 2 2^42
+ *     n_1  = -3 t3 + 4 t2 2^14 + t 2^28        n_2 = t3 - t2 2^14
+ *     w_j  = (n_j + 2^28) >> 29 (arithmetic) for three of the four; the fourth, the ANCHOR (w_0 when t < 8192, else w_1), is
+ *     16384 - (the sum of the other three).
+ * For every t: the sum is exactly 16384; t = 0 gives (0, 16384, 0, 0); w_j(t) = w_(1-j)(16384 - t); sum |w_j| <= 20480; every
+ * weight lies within 1.5 units of 2^-14 of the real polynomial.
+ * Displacement (debig_png_elastic_displacement): the nodes k - 1 .. k + 2 of each axis clamped into the grid (the edge nodes are
+ * replicated),
+ *     S = sum_i sum_j wy_i wx_j d[i][j]   (int64, |S| < 2^57; nothing is rounded in between, so the order does not matter)
+ *     D = (S + 2^27) >> 28                (arithmetic; Q16, |D| < 2^29)
+ * once for dx and once for dy.  Position, NU and NV being the affine U and V of m[]:
+ *     U = NU + ((m00 Dx + m01 Dy + 2^14) >> 15),   V = NV + ((m10 Dx + m11 Dy + 2^14) >> 15)   (arithmetic; |sum| < 2^62)
+ * Everything behind (U, V) is the affine warp's, word for word (picks, taps, borders, colour, labels, unmatched, the ONE
+ * conversion).  Consequences:
+ *   (a) a file without a field (nodes == NULL), or with a field of zeros, gets the bytes of the _warp call of the same kind;
+ *   (b) a field whose nodes all hold the same whole number of pixels (a, b) gives the bytes of _warp with m02 + m00 a + m01 b and
+ *       m12 + m10 a + m11 b (exact for matrices whose entries are multiples of 2^-16);
+ *   (c) where t = 0 on both axes D is the node's value exactly: a 4 x 4 output under a 9 x 9 grid puts the centre of pixel (X, Y)
+ *       on node (2Y + 1, 2X + 1);
+ *   (d) an image under NEAREST, its label map and its colour-coded mask pick the same source pixel under one matrix and one field.
+ * debig_png_decode_batch_tensor_elastic takes the arguments of debig_png_decode_batch_tensor_persp with warps (required, the affine
+ * maps) in place of persps, followed by elastics (required, one entry per file) and elastic_desc (required).  colors, tones,
+ * tables / n_tables and blurs may each be NULL / 0; what is given selects the affine call whose argument checks (in their
+ * order), statuses, infos, untouched slot of a failed file and colour / tone / blur semantics hold: _tensor_blur with blurs, else
+ * _tensor_tone with tones, else _tensor_warp_color with colors, else _tensor_warp.  The two label calls take the arguments and
+ * rules of debig_png_decode_batch_labels_warp and debig_png_decode_batch_color_labels_warp, followed by the same two.  Behind the
+ * checks of the affine call: elastics == NULL, elastic_desc == NULL, a grid dimension outside 2 .. 33 or a non-zero reserved word
+ * is DEBIG_PNG_BAD_ARG.  One launch warps all images (debig_hip_png_elastic_batch / _elastic_color / _label_elastic /
+ * _color_label_elastic); the quantised fields travel beside the tasks.
+ * Not provided: elastic together with perspective, bicubic, the alpha modes the affine warp does not take, per-file grid sizes,
+ * full-resolution or device-resident fields. */
+typedef struct debig_png_elastic { const double *nodes; } debig_png_elastic; /* grid_h x grid_w x 2 doubles, row major, (dx, dy)
+                                                                              * per node; NULL: no field */
+typedef struct debig_png_elastic_desc { uint32_t grid_w, grid_h, reserved[2]; } debig_png_elastic_desc;
+/* Host only: count values (2 per node) -> q[k] = llround(v[k] * 65536) -> 1, or 0 when one is not finite or above 4096 in
+ * magnitude (q unspecified). */
+int debig_png_elastic_quantise(const double *v, uint64_t count, int32_t *q);
+/* Host only: the cell *k and the Q14 fraction *t of coordinate X on an axis of W pixels (X < W <= 16384) and g nodes (2 .. 33). */
+void debig_png_elastic_cell(uint32_t X, uint32_t W, uint32_t g, uint32_t *k, uint32_t *t);
+/* Host only: the four Q14 weights of the nodes k - 1 .. k + 2 at fraction t (0 .. 16384). */
+void debig_png_elastic_weights(uint32_t t, int32_t w[4]);
+/* Host only: the displacement (*Dx, *Dy), Q16, of output pixel (X, Y) of an out_w x out_h output under the quantised nodes q
+ * (grid_h x grid_w x 2, as debig_png_elastic_quantise gives them) -> 1, or 0 when a size, X, Y or a node breaks its bound.  The
+ * rule above restated; callers who move keypoints with the field can use it. */
+int debig_png_elastic_displacement(const int32_t *q, uint32_t grid_w, uint32_t grid_h, uint32_t out_w, uint32_t out_h, uint32_t X,
+                                   uint32_t Y, int64_t *Dx, int64_t *Dy);
+int debig_png_decode_batch_tensor_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                          const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps,
+                                          const debig_png_color *colors /* may be NULL */, const debig_png_tone *tones /* may be NULL */,
+                                          const uint8_t *tables /* n_tables x 256 bytes; may be NULL when n_tables == 0 */,
+                                          uint32_t n_tables, const debig_png_blur *blurs /* may be NULL */, uint32_t *status,
+                                          debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                          const debig_png_tensor_desc *desc, const debig_png_warp_desc *warp_desc,
+                                          const debig_png_elastic *elastics, const debig_png_elastic_desc *elastic_desc);
+int debig_png_decode_batch_labels_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+                                          const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps, uint32_t *status,
+                                          debig_png_info *infos /* may be NULL */, uint32_t n, uint32_t flags,
+                                          const debig_png_label_desc *desc, const debig_png_label_warp_desc *warp_desc,
+                                          const debig_png_elastic *elastics, const debig_png_elastic_desc *elastic_desc);
+int debig_png_decode_batch_color_labels_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
+        const debig_png_box *boxes /* may be NULL */, const debig_png_warp *warps, uint32_t *status,
+        debig_png_info *infos /* may be NULL */, uint32_t *unmatched /* may be NULL */, uint32_t n, uint32_t flags,
+        const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *warp_desc,
+        const debig_png_elastic *elastics, const debig_png_elastic_desc *elastic_desc);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

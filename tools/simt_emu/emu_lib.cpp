@@ -24,6 +24,7 @@
 #include "../../debigulator_amd/csrc/png_color_label_warp_kernel.inc"
 #include "../../debigulator_amd/csrc/png_color_kernel.inc"
 #include "../../debigulator_amd/csrc/png_persp_kernel.inc"
+#include "../../debigulator_amd/csrc/png_elastic_kernel.inc"
 #include "../../debigulator_amd/csrc/png_tone_kernel.inc"
 #include "../../debigulator_amd/csrc/png_blur_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
@@ -490,6 +491,45 @@ extern "C" int emu_png_color_label_persp_batch(const void *src_arena, void *out,
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_color_label_persp_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
                       (const uint8_t *)tables, unmatched, n);
+    return 0;
+}
+
+/* the four warp kernels under an elastic deformation (png_elastic_kernel.inc), as debig_hip_png_elastic_batch, _elastic_color,
+ * _label_elastic and _color_label_elastic launch them: the arguments of their warp twins above, and the fields' nodes */
+extern "C" int emu_png_elastic_batch(const void *src_arena, void *out, const debig_png_elastic_task *tasks, const void *fields,
+                                     uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_elastic_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)fields, n);
+    return 0;
+}
+
+extern "C" int emu_png_elastic_color_batch(const void *src_arena, void *out, const debig_png_elastic_color_task *tasks,
+                                           const void *weights, const void *fields, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_elastic_color_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)weights, (const uint8_t *)fields, n);
+    return 0;
+}
+
+extern "C" int emu_png_label_elastic_batch(const void *src_arena, void *out, const debig_png_label_elastic_task *tasks,
+                                           const int32_t *lut, const void *fields, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_elastic_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks, lut,
+                      (const uint8_t *)fields, n);
+    return 0;
+}
+
+extern "C" int emu_png_color_label_elastic_batch(const void *src_arena, void *out, const debig_png_color_label_elastic_task *tasks,
+                                                 const void *tables, uint32_t *unmatched, const void *fields, uint32_t n,
+                                                 uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_color_label_elastic_kernel, grid, WARP_THREADS, (const uint8_t *)src_arena, (uint8_t *)out, tasks,
+                      (const uint8_t *)tables, unmatched, (const uint8_t *)fields, n);
     return 0;
 }
 
