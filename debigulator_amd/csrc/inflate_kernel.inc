@@ -132,6 +132,7 @@ template <int NW_> struct __attribute__((aligned(16))) WaveLdsT {
 typedef WaveLdsT<1> WaveLds;
 
 #ifdef DEBIG_EMU
+static unsigned long long debig_emu_slow_probes; /* emulator only: lengths tried by huff_slow's canonical probe (tests/test_emu_table_shapes.py) */
 #define DEV_INLINE static inline
 #define DEV_MEMBER static inline
 #define DEV_MEMBER_INLINE inline
@@ -373,6 +374,9 @@ template <class LDS> DEV_INLINE uint32_t huff_slow(uint32_t bits, const LDS &S, 
     uint32_t hi = S.t.qmax[c] < 15u ? S.t.qmax[c] : 15u;
     uint32_t rv = __brev(bits);
     for (uint32_t len = lo; len <= hi; len++) {
+#ifdef DEBIG_EMU
+        debig_emu_slow_probes++;
+#endif
         uint32_t code = rv >> (32u - len);
         uint32_t d = code - S.t.first[c][len];
         if (code >= S.t.first[c][len] && d < S.t.count[c][len]) {

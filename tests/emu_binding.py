@@ -42,7 +42,14 @@ def load_emu(asan=False):
     L.emu_inflate_chunked_batch.restype = C.c_int
     L.emu_inflate_chunked_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                                             C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.emu_slow_probes.restype = C.c_ulonglong
+    L.emu_slow_probes.argtypes = [C.c_int]
     return L
+
+
+def slow_probes(L, reset=True):
+    """lengths tried by huff_slow's canonical probe (the SLOW route of the tables) in the calls since the last reset"""
+    return int(L.emu_slow_probes(1 if reset else 0))
 
 
 CHUNKED = 0x20  # nw code of the chunk-parallel path (include/debig_hip.h: DEBIG_WAVES_CHUNKED)

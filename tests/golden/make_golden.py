@@ -90,6 +90,34 @@ def token_corpus():
     print("corpus_tokens.json:", len(keep), "cases; reference deaths:", w.crashes)
 
 
+def tables_corpus():
+    """9. streams whose Huffman tables have a chosen shape (tests/table_shapes.py: golden_subset) through the
+    reference: ladders of every code length with the 48-bit token, second-level runs of every size, the 256-entry
+    second-level area filled exactly and overflowed, block sequences, incomplete codes and codes outside the probe
+    range of :437-463 (Q7).  Build A answers in a child process; build B answers the streams A dies on (more than 500
+    long-code probe slots, Q8) and the failing ones."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import table_shapes as ts
+    from ref_worker import RefWorker
+
+    w = RefWorker()
+    keep = []
+    for c in ts.golden_subset():
+        which = "A" if c.legal else "B"
+        r = w.inflate(which, c.raw, c.cap)
+        if r is None and which == "A":
+            which = "B"
+            r = w.inflate(which, c.raw, c.cap)
+        good, final, digest = r
+        assert (good, final, digest) == (int(c.legal), len(c.plain), sha(c.plain)), c.name
+        keep.append({"name": c.name, "raw_hex": c.raw.hex(), "recipient_size": c.cap, "good": int(good), "final": final,
+                     "out_sha256": digest, "oracle": which})
+    w.close()
+    assert [k["name"] for k in keep if k["oracle"] == "B" and k["good"]] == [ts.Q8_CASE]
+    json.dump(keep, open(os.path.join(HERE, "corpus_tables.json"), "w"))
+    print("corpus_tables.json:", len(keep), "cases; reference deaths:", w.crashes)
+
+
 def vs_reference():
     """7. the reference's answers (digests) to exactly the inputs of tests/test_oracle_vs_reference.py, recorded by
     running that module's tests against the live reference (build A in process, build B in a child process)."""
@@ -115,6 +143,8 @@ def main():
         return vs_reference()
     if "--only-tokens" in sys.argv:
         return token_corpus()
+    if "--only-tables" in sys.argv:
+        return tables_corpus()
     A = binding.Reference("A")  # silent, asserts on (canonical)
     B = binding.Reference("B")  # silent, asserts off (inputs on which A aborts)
 
@@ -206,6 +236,7 @@ def main():
     corrupt_corpus()
     vs_reference()
     token_corpus()
+    tables_corpus()
     print("golden fixtures written:", sorted(os.listdir(HERE)))
 
 

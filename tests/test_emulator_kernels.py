@@ -3,6 +3,7 @@
 source that hipcc builds for gfx950 -- indexing, tiling, speculation, LZ77 resolve,
 de-filter -- on machines without a GPU.  (The emulator says nothing about speed.)"""
 import ctypes as C
+import functools
 import hashlib
 import json
 import os
@@ -618,14 +619,12 @@ def test_split_path_hands_back_what_does_not_fit_its_workspace(emu, oracle):
     assert max(seen) >= len(raws) - 1
 
 
-@pytest.mark.parametrize("nw", [1, 2, 8, eb.SPLIT, eb.STRAND])
-def test_long_codes_take_the_second_level_tables(emu, oracle, nw):
-    """Codes longer than the direct tables (10/11 bits literal/length, 9 bits distance) are decoded
-    through second-level tables linked from the direct table (CodeTabsT::sub_tab): geometric byte
-    distributions give literal codes up to 15 bits, far distances with rare lengths give long
-    distance codes; a pathological code whose second-level tables do not fit takes the canonical
-    probe.  Every kernel width, against the oracle (which is pinned to the reference on K9's 13..15
-    bit codes and on the zlib corpus)."""
+@functools.lru_cache(maxsize=None)
+def _long_code_streams():
+    """seven zlib streams -> (raws, caps, {geometry: {(alphabet, route)} of the symbols they decode}); the routes are
+    those of tests/table_shapes.py: classify over the code lengths of every dynamic block"""
+    import table_shapes as ts
+
     rng = np.random.default_rng(77)
     raws, caps = [], []
     for it in range(6):
@@ -637,7 +636,7 @@ def test_long_codes_take_the_second_level_tables(emu, oracle, nw):
         c = zlib.compressobj(9, zlib.DEFLATED, -15, 9, strat)
         raws.append(c.compress(data) + c.flush())
         caps.append(n + 1)
-    # long distance codes: most matches at a handful of distances, a few anywhere in 32 KiB
+    # most matches at a handful of distances, a few anywhere in 32 KiB
     base = rng.integers(0, 256, 40000, dtype=np.uint8)
     buf = bytearray(base.tobytes())
     for k in range(3000):
@@ -647,13 +646,45 @@ def test_long_codes_take_the_second_level_tables(emu, oracle, nw):
     c = zlib.compressobj(9, zlib.DEFLATED, -15, 9)
     raws.append(c.compress(bytes(buf)) + c.flush())
     caps.append(len(buf) + 1)
+    reached = {}
+    for gname, g in ts.GEOMETRIES.items():
+        reached[gname] = set()
+        for raw in raws:
+            for ll, dl, ul, ud in ts.walk(raw):
+                lit, dist = ts.classify(ll, dl, g)
+                reached[gname] |= {("lit", lit[s]) for s in ul} | {("dist", dist[s]) for s in ud}
+    return raws, caps, reached
+
+
+@pytest.mark.parametrize("nw", [1, 2, 4, 8, eb.SPLIT, eb.SPLIT_QUEUED, eb.STRAND, eb.STRAND_PIPE])
+def test_long_codes_take_the_second_level_tables(emu, oracle, nw):
+    """Codes longer than the direct tables (10/11 bits literal/length, 9 bits distance) are decoded through second-level
+    tables linked from the direct table (CodeTabsT::sub_tab).  Seven zlib streams: geometric byte distributions give
+    literal/length codes up to 15 bits -- links of every size, 1..5 index bits behind the 10-bit table and 1..4 behind
+    the 11-bit one --, rare far distances give a few distance codes of 10, 12 and 13 bits (links of 1, 3 and 4 bits).
+    What they do NOT reach, by the model of tests/table_shapes.py and asserted below: the canonical probe (no stream of
+    zlib's overflows the second-level area), distance links of 2, 5 or 6 bits, and long distance codes in the seventh
+    stream, whose distance codes all fit the 9-bit table; tests/test_emu_table_shapes.py reaches those on purpose.  Every
+    kernel width, against the oracle (which is pinned to the reference on K9's 13..15 bit codes and on the zlib corpus);
+    no stream is skipped: none carries a flag of UB_EXCLUDED (over-subscribed lengths, a repeat code at position 0 --
+    zlib writes neither)."""
+    import table_shapes as ts
+    from handback_corpus import UB_EXCLUDED
+
+    raws, caps, reached = _long_code_streams()
+    assert len(raws) == 7
     want = [oracle.inflate(r, c, want_stats=True) for r, c in zip(raws, caps)]
+    assert [i for i, w in enumerate(want) if w[3].ub_flags & UB_EXCLUDED] == []
+    assert {r for a, r in reached["g10"] if a == "lit"} == {ts.DIRECT} | {ts.LINK(k) for k in range(1, 6)}
+    assert {r for a, r in reached["g11"] if a == "lit"} == {ts.DIRECT} | {ts.LINK(k) for k in range(1, 5)}
+    assert {r for a, r in reached["g10"] if a == "dist"} == {r for a, r in reached["g11"] if a == "dist"} == \
+        {ts.DIRECT, ts.LINK(1), ts.LINK(3), ts.LINK(4)}
+    eb.slow_probes(emu)
     outs, arena, offs = eb.emu_inflate(emu, raws, caps, nw=nw, out_misalign=5)
     for i, ((good, final, out, r), (g, f, o, st)) in enumerate(zip(outs, want)):
-        if st.ub_flags:
-            continue
         assert (good, final, out) == (g, f, o), (nw, i)
     assert sum(1 for w in want if w[0] == 1) >= 5
+    assert eb.slow_probes(emu) == 0  # no SLOW mark in any table, so the probe loop never ran
 
 
 # ---------------------------------------------------------------- chunk-parallel path (inflate_chunk_kernel.inc)

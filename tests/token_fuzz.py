@@ -10,12 +10,15 @@ A token is
     an int 0..255            a literal byte
     (length, distance)       a match, 3 <= length <= 258, 1 <= distance <= 32 768
     Block(kind)              a block boundary; kind is "stored", "fixed" or "dynamic"
+    Stop(code, nbits)        (tests/table_shapes.py only) a bit pattern of a Huffman block that the
+                             reference finds no code for: written like a code, it ends the decode
 and a token list starts with a Block.  A stored block holds the literals up to the next boundary
 (LEN = their number, 0 included).  decode_tokens() applies a token list to a bytearray in plain
 Python: the witness beside the oracle and zlib.
 
 Only legal codes are written: complete prefix codes from header_fuzz.random_lengths (or a lone 1-bit
-distance symbol under HDIST >= 2, Q6), no code longer than 12 bits (Q8), no repeat code at position
+distance symbol under HDIST >= 2, Q6), no seeded code longer than max_len = 12 bits (Q8; a Block's
+explicit lengths, which tests/table_shapes.py chooses, go up to 15 and may be incomplete), no repeat code at position
 0, no run behind the last length, no symbols 286 / 287.  Every case is padded with bytes(8), so the
 tail rule (Q2) and the 4-byte over-read (Q3) decide nothing.  All of it is deterministic from seeds."""
 import functools
@@ -40,14 +43,28 @@ class Block:
         return f"Block({self.kind})"
 
 
+class Stop:
+    """`nbits` bits, written first bit first like a Huffman code, where a literal/length code (or, with
+    length= a match length, the distance code behind that length) is due -- and for which the block's
+    tables hold no code, or none inside the reference's probe range (Q7): the decode ends in front of
+    it with good = 0"""
+
+    def __init__(self, code, nbits, length=None):
+        self.code, self.nbits, self.length = code, nbits, length
+
+    def __repr__(self):
+        return f"Stop({self.code:#x}, {self.nbits})"
+
+
 class Case:
-    def __init__(self, name, tokens, seed, cap=None, slack=1):
+    def __init__(self, name, tokens, seed, cap=None, slack=1, max_len=12):
         self.name, self.tokens = name, tokens
         self.family = name.split("/")[0]
         self.plain, self.legal = decode_tokens(tokens)
-        enc = encode(tokens, seed)
+        self.tok_bits = []  # the first bit of every token that is no Block, in order
+        enc = encode(tokens, seed, max_len, self.tok_bits)
         self.raw = enc.raw + PAD
-        self.data_bit0, self.n_bits, self.blocks = enc.data_bit0, enc.n_bits, enc.blocks
+        self.data_bit0, self.n_bits, self.blocks, self.codes = enc.data_bit0, enc.n_bits, enc.blocks, enc.codes
         # Q1 / Q12: recipient_size >= max(D + 1, C) unless the case is about recipient_size itself
         self.cap = cap if cap is not None else max(len(self.plain) + slack, len(self.raw))
         assert self.cap >= len(self.raw), name
@@ -64,6 +81,8 @@ def decode_tokens(tokens):
     for t in tokens:
         if isinstance(t, Block):
             continue
+        if isinstance(t, Stop):
+            return bytes(out), False
         if isinstance(t, tuple):
             n, d = t
             if d > len(out):
@@ -92,6 +111,9 @@ class _Writer(BitWriter):
             self.done += (self.acc & ((1 << (8 * k)) - 1)).to_bytes(k, "little")
             self.acc >>= 8 * k
             self.n -= 8 * k
+
+    def put_code(self, code, nbits):  # the same bits as BitWriter.put_code, in one step
+        self.put(int(format(code, "b").zfill(nbits)[::-1], 2) if nbits else 0, nbits)
 
     def bitpos(self):
         return 8 * len(self.done) + self.n
@@ -125,10 +147,18 @@ _FIXED_LL = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
 _FIXED_LC = canonical(_FIXED_LL)
 
 
-def _put_tokens(w, toks, ll, lc, dl, dc):
+def _put_tokens(w, toks, ll, lc, dl, dc, marks=None):
     """the symbols of one Huffman block; dl = None: the fixed 5-bit distance codes"""
     for t in toks:
-        if isinstance(t, tuple):
+        if marks is not None:
+            marks.append(w.bitpos())
+        if isinstance(t, Stop):
+            if t.length is not None:
+                ls, le = _LEN_SYM[t.length]
+                w.put_code(lc[257 + ls], ll[257 + ls])
+                w.put(le, LEN_EXTRA[ls])
+            w.put_code(t.code, t.nbits)
+        elif isinstance(t, tuple):
             ls, le = _LEN_SYM[t[0]]
             ds, de = _dist_sym(t[1])
             w.put_code(lc[257 + ls], ll[257 + ls])
@@ -148,7 +178,10 @@ def _dynamic_codes(rng, blk, toks, max_len):
     distance length below HDIST (Q6)"""
     used_lit, used_dist = {256}, set()
     for t in toks:
-        if isinstance(t, tuple):
+        if isinstance(t, Stop):
+            if t.length is not None:
+                used_lit.add(257 + _LEN_SYM[t.length][0])
+        elif isinstance(t, tuple):
             used_lit.add(257 + _LEN_SYM[t[0]][0])
             used_dist.add(_dist_sym(t[1])[0])
         else:
@@ -205,9 +238,12 @@ class _Encoded:
     pass
 
 
-def encode(tokens, seed, max_len=12):
+def encode(tokens, seed, max_len=12, marks=None):
     """the raw DEFLATE stream of a token list (no padding).  .blocks = [(kind, first bit of the
-    block header, bytes produced in front of it)], .data_bit0 = first bit behind the first header."""
+    block header, bytes produced in front of it)], .data_bit0 = first bit behind the first header.
+    max_len: the longest seeded random code (a Block's explicit lengths go up to 15 whatever it is);
+    marks: a list that receives the first bit of every token that is no Block; .codes = per block
+    (ll, dl) of a dynamic block, else None."""
     rng = random.Random(seed)
     assert isinstance(tokens[0], Block)
     groups = []
@@ -218,7 +254,7 @@ def encode(tokens, seed, max_len=12):
             groups[-1][1].append(t)
     w = _Writer()
     e = _Encoded()
-    e.blocks, e.data_bit0, pos = [], None, 0
+    e.blocks, e.codes, e.data_bit0, pos = [], [], None, 0
     for gi, (blk, toks) in enumerate(groups):
         e.blocks.append((blk.kind, w.bitpos(), pos))
         w.put(1 if gi == len(groups) - 1 else 0, 1)
@@ -231,18 +267,23 @@ def encode(tokens, seed, max_len=12):
             w.align()
             if e.data_bit0 is None:
                 e.data_bit0 = w.bitpos()
+            if marks is not None:
+                marks.extend(w.bitpos() + 8 * k for k in range(len(toks)))
             w.put_bytes(bytes(toks))
+            e.codes.append(None)
         elif blk.kind == "fixed":
             if e.data_bit0 is None:
                 e.data_bit0 = w.bitpos()
-            _put_tokens(w, toks, _FIXED_LL, _FIXED_LC, None, None)
+            _put_tokens(w, toks, _FIXED_LL, _FIXED_LC, None, None, marks)
+            e.codes.append(None)
         else:
             ll, dl, hlit, hdist = _dynamic_codes(rng, blk, toks, max_len)
             _put_dynamic_header(rng, w, ll, dl, hlit, hdist)
             if e.data_bit0 is None:
                 e.data_bit0 = w.bitpos()
-            _put_tokens(w, toks, ll, canonical(ll), dl, canonical(dl))
-        pos += sum(t[0] if isinstance(t, tuple) else 1 for t in toks)
+            _put_tokens(w, toks, ll, canonical(ll), dl, canonical(dl), marks)
+            e.codes.append((ll, dl))
+        pos += sum(t[0] if isinstance(t, tuple) else 0 if isinstance(t, Stop) else 1 for t in toks)
     e.n_bits = w.bitpos()
     e.raw = w.bytes()
     return e

@@ -36,6 +36,14 @@ static bool emu_no_handback()
     return e && *e && !(e[0] == '0' && e[1] == 0);
 }
 
+/* the lengths huff_slow's canonical probe has tried since the last reset, over every kernel of this library */
+extern "C" unsigned long long emu_slow_probes(int reset)
+{
+    const unsigned long long v = debig_emu_slow_probes;
+    if (reset) debig_emu_slow_probes = 0;
+    return v;
+}
+
 /* cls: DEBIG_CLASS_ALL / _SMALL / _LARGE (streams outside the class are left untouched) */
 extern "C" int emu_inflate_batch_cls(const void *in, void *out, const debig_stream *streams,
                                      debig_result *results, uint32_t n, uint32_t grid, uint32_t nw, uint32_t cls);
