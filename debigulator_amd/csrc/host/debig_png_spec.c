@@ -2019,75 +2019,103 @@ DEBIG_API int debig_png_elastic_displacement(const int32_t *q, uint32_t grid_w, 
     return 1;
 }
 
-/* the fields of one elastic call: the caller's entries, the grid, the quantised nodes of all files (rec bytes each, zeros where a
- * file has none) and where they land in c->rsz_weights */
-typedef struct ela_plan {
-    const debig_png_elastic *fields;
-    uint32_t gw, gh;
-    int32_t *q;
-    uint64_t rec, off;
-} ela_plan;
-
-/* the elastic arguments of a call, behind the checks of its affine call -> 0 (and *ela ready) or DEBIG_PNG_BAD_ARG */
-static int ela_check(ela_plan *ela, const debig_png_elastic *elastics, const debig_png_elastic_desc *ed)
-{
-    if (!elastics || !ed || ed->grid_w < 2 || ed->grid_w > 33 || ed->grid_h < 2 || ed->grid_h > 33 || ed->reserved[0] != 0 ||
-        ed->reserved[1] != 0)
-        return DEBIG_PNG_BAD_ARG;
-    memset(ela, 0, sizeof *ela);
-    ela->fields = elastics;
-    ela->gw = ed->grid_w;
-    ela->gh = ed->grid_h;
-    ela->rec = (uint64_t)ed->grid_w * ed->grid_h * 2u * sizeof(int32_t);
-    return 0;
-}
-
-/* the fields as the last table of a launch: its offset rounded up to the 8 bytes a node takes */
-static void ela_place(ela_plan *ela, dev_table *t, uint32_t n)
-{
-    t->src = ela->q;
-    t->bytes = (uint64_t)n * ela->rec;
-    t->off = (t->off + 7u) & ~(uint64_t)7u;
-    ela->off = t->off;
-}
-
-#define MAP_INTS 9u /* a file's quantised map: m[0..5] (both kinds), m[6..8] = p[] (the projective kind; else unused) */
-
-/* the files' maps quantised (MAP_INTS int64 each) and their E_WARP flags; exactly one of warps (affine) and persps (projective:
- * the D range over the out_w x out_h output is part of the flag) is given; ela (with warps): the fields quantised as well, a
- * node out of range part of the flag; -> 0 or 2 */
-static int warp_prepare(const debig_png_warp *warps, const debig_png_persp *persps, ela_plan *ela, uint32_t n, uint32_t out_w,
-                        uint32_t out_h, int64_t **m, uint8_t **bad)
-{
-    if (ela && !(ela->q = (int32_t *)calloc((size_t)n * (size_t)(ela->rec / sizeof(int32_t)), sizeof(int32_t)))) return 2;
-    *m = (int64_t *)calloc((size_t)n * MAP_INTS, sizeof(int64_t));
-    *bad = (uint8_t *)calloc(n, 1);
-    if (!*m || !*bad) return 2;
-    for (uint32_t i = 0; i < n; i++) {
-        int64_t *mi = *m + MAP_INTS * (size_t)i;
-        (*bad)[i] = persps ? !(debig_png_persp_quantise(persps[i].m, mi) && debig_png_persp_range(mi, out_w, out_h))
-                           : !debig_png_warp_quantise(warps[i].m, mi);
-        if (ela && ela->fields[i].nodes &&
-            !debig_png_elastic_quantise(ela->fields[i].nodes, ela->rec / sizeof(int32_t), ela->q + (size_t)i * (ela->rec / sizeof(int32_t))))
-            (*bad)[i] = 1;
-    }
-    return 0;
-}
-
+#define MAP_INTS 9u /* a file's quantised map: m[0..5] (every kind), m[6..8] = p[] (the projective kind; else unused) */
 #define ELA_TAIL 16u /* what an elastic task adds to its warp task: field_off, grid_w, grid_h, a reserved word */
 
-/* one task of file i into the host array: its first `base` bytes (the warp task), then p[] where the map is projective, or the
- * place of the file's field and the grid size where the call is elastic */
-static void map_task_put(uint8_t *at, const void *task, size_t base, const int64_t *mi, int persp, const ela_plan *ela, uint32_t i)
+/* the map of one warp call: its kind and the caller's arrays (warps: affine and elastic; persps: projective; elastics and ed:
+ * elastic); behind map_prepare the files' quantised maps (MAP_INTS int64 each) and their E_WARP flags, and of an elastic call the
+ * quantised nodes of all files (rec bytes each, zeros where a file has none) and, behind map_place, where they land in
+ * c->rsz_weights.  A new map is a kind here, an arm in map_prepare, map_tail_bytes and map_task_runs and one in each map_launch_* */
+typedef enum map_kind { MAP_AFFINE, MAP_PERSP, MAP_ELASTIC } map_kind;
+typedef struct warp_map {
+    map_kind kind;
+    const debig_png_warp *warps;
+    const debig_png_persp *persps;
+    const debig_png_elastic *elastics;
+    const debig_png_elastic_desc *ed;
+    int64_t *m;
+    uint8_t *bad;
+    int32_t *q;
+    uint64_t rec, off;
+} warp_map;
+
+/* the map of a call as its public entry point makes it (a compound literal: it lives until the entry point returns) */
+#define MAP_OF(kind_, ...) (&(warp_map){.kind = kind_, __VA_ARGS__})
+
+/* the caller's array of per-file matrices (NULL: not given) */
+static const void *map_given(const warp_map *mp) { return mp->kind == MAP_PERSP ? (const void *)mp->persps : (const void *)mp->warps; }
+
+/* what a task of this map adds to its warp task */
+static size_t map_tail_bytes(const warp_map *mp) { return mp->kind == MAP_PERSP ? 3 * sizeof(int64_t) : mp->kind == MAP_ELASTIC ? ELA_TAIL : 0; }
+
+/* check and prepare, behind every check of the affine call: the elastic arguments (-> DEBIG_PNG_BAD_ARG), then the files' maps
+ * quantised and flagged -- projective: the D range over the out_w x out_h output is part of the flag; elastic: the fields
+ * quantised as well, a node out of range part of the flag -> 0, DEBIG_PNG_BAD_ARG or 2 */
+static int map_prepare(warp_map *mp, uint32_t n, uint32_t out_w, uint32_t out_h)
 {
-    memcpy(at, task, base);
-    if (persp) memcpy(at + base, mi + 6, 3 * sizeof(int64_t));
-    if (ela) {
-        const uint64_t off = ela->fields[i].nodes ? ela->off + (uint64_t)i * ela->rec : UINT64_MAX;
-        const uint16_t g[4] = {(uint16_t)ela->gw, (uint16_t)ela->gh, 0, 0};
-        memcpy(at + base, &off, 8);
-        memcpy(at + base + 8, g, 8);
+    const debig_png_elastic_desc *ed = mp->ed;
+    size_t per = 0; /* the int32 of one field */
+    if (mp->kind == MAP_ELASTIC) {
+        if (!mp->elastics || !ed || ed->grid_w < 2 || ed->grid_w > 33 || ed->grid_h < 2 || ed->grid_h > 33 || ed->reserved[0] != 0 ||
+            ed->reserved[1] != 0)
+            return DEBIG_PNG_BAD_ARG;
+        per = (size_t)ed->grid_w * ed->grid_h * 2u;
+        mp->rec = per * sizeof(int32_t);
+        if (!(mp->q = (int32_t *)calloc((size_t)n * per, sizeof(int32_t)))) return 2;
     }
+    mp->m = (int64_t *)calloc((size_t)n * MAP_INTS, sizeof(int64_t));
+    mp->bad = (uint8_t *)calloc(n, 1);
+    if (!mp->m || !mp->bad) return 2;
+    for (uint32_t i = 0; i < n; i++) {
+        int64_t *mi = mp->m + MAP_INTS * (size_t)i;
+        mp->bad[i] = mp->kind == MAP_PERSP ? !(debig_png_persp_quantise(mp->persps[i].m, mi) && debig_png_persp_range(mi, out_w, out_h))
+                                           : !debig_png_warp_quantise(mp->warps[i].m, mi);
+        if (per && mp->elastics[i].nodes && !debig_png_elastic_quantise(mp->elastics[i].nodes, per, mp->q + (size_t)i * per))
+            mp->bad[i] = 1;
+    }
+    return 0;
+}
+
+static void map_release(warp_map *mp) { free(mp->m); free(mp->bad); free(mp->q); }
+
+/* the elastic fields as the last table of a launch (no other map has a table): its offset rounded up to the 8 bytes a node takes */
+static void map_place(warp_map *mp, dev_table *t, uint32_t n)
+{
+    if (mp->kind != MAP_ELASTIC) return;
+    t->src = mp->q;
+    t->bytes = (uint64_t)n * mp->rec;
+    mp->off = t->off = (t->off + 7u) & ~(uint64_t)7u;
+}
+
+/* the host array of a call's tasks: `base` bytes of warp task and the map's tail each */
+typedef struct map_tasks {
+    uint8_t *v;
+    uint64_t n;
+    uint32_t cap;
+    size_t base, elem;
+} map_tasks;
+
+/* the tasks of file i: the prototype `task` (base bytes; row0 and rows point into it) once per run of `run` of the H output rows,
+ * each followed by p[] where the map is projective, or by the place of the file's field and the grid size where it is elastic
+ * -> 0: no memory, or too many tasks */
+static int map_task_runs(map_tasks *T, const warp_map *mp, const void *task, uint32_t *row0, uint32_t *rows, uint32_t H, uint32_t run,
+                         uint32_t i)
+{
+    for (uint32_t y0 = 0; y0 < H; y0 += run) {
+        if (T->n >= 0x7fffffffu || !grow((void **)&T->v, &T->cap, (uint32_t)T->n, T->elem)) return 0;
+        uint8_t *at = T->v + T->n++ * T->elem;
+        *row0 = y0;
+        *rows = H - y0 < run ? H - y0 : run;
+        memcpy(at, task, T->base);
+        if (mp->kind == MAP_PERSP) memcpy(at + T->base, mp->m + MAP_INTS * (size_t)i + 6, 3 * sizeof(int64_t));
+        if (mp->kind == MAP_ELASTIC) {
+            const uint64_t off = mp->elastics[i].nodes ? mp->off + (uint64_t)i * mp->rec : UINT64_MAX;
+            const uint16_t g[4] = {(uint16_t)mp->ed->grid_w, (uint16_t)mp->ed->grid_h, 0, 0};
+            memcpy(at + T->base, &off, 8);
+            memcpy(at + T->base + 8, g, 8);
+        }
+    }
+    return 1;
 }
 
 _Static_assert(offsetof(debig_png_warp_color_task, color_off) == sizeof(debig_png_warp_task) &&
@@ -2140,17 +2168,30 @@ static int tensor_warp_check(const void *d_out, const void *warps /* or the pers
     return 0;
 }
 
+/* the launch of the image kind under the call's map; rec: the colour records are given, and the tasks are the colour kernel's */
+static int map_launch_image(const warp_map *mp, const void *rec, const debig_ctx *c, void *out, const void *t, uint32_t cnt)
+{
+    const uint8_t *src = c->rsz_src.ptr, *w = c->rsz_weights.ptr;
+    switch (mp->kind) {
+    case MAP_ELASTIC: return rec ? debig_hip_png_elastic_color_batch(src, out, (const debig_png_elastic_color_task *)t, w, w, cnt, NULL)
+                                 : debig_hip_png_elastic_batch(src, out, (const debig_png_elastic_task *)t, w, cnt, NULL);
+    case MAP_PERSP: return rec ? debig_hip_png_persp_color_batch(src, out, (const debig_png_persp_color_task *)t, w, cnt, NULL)
+                               : debig_hip_png_persp_batch(src, out, (const debig_png_persp_task *)t, cnt, NULL);
+    default: return rec ? debig_hip_png_warp_color_batch(src, out, (const debig_png_warp_color_task *)t, w, cnt, NULL)
+                        : debig_hip_png_warp_batch(src, out, (const debig_png_warp_task *)t, cnt, NULL);
+    }
+}
+
 /* debig_png_decode_batch_tensor_warp (colors == NULL) and debig_png_decode_batch_tensor_warp_color behind their argument checks.
  * With colors the tasks are debig_png_warp_color_task -- the warp task and the place of the image's record, which travels as the
  * launch's one table -- and go to the colour kernel.  tp != NULL (debig_png_decode_batch_tensor_tone, _blur): as in tensor_core, the
  * tasks of the tone and blur files come last, write UINT8 HWC into the tone arena through a launch of their own, and tone_run and
- * blur_run follow.  persps != NULL (then warps == NULL; debig_png_decode_batch_tensor_persp): the maps are projective, each task
- * is followed by its p[] and goes to the persp kernel of the same kind; nothing else differs.  ela != NULL (with warps;
- * debig_png_decode_batch_tensor_elastic): each task is followed by the place of its file's field, the quantised fields are the
- * launch's last table, and the tasks go to the elastic kernel of the same kind. */
+ * blur_run follow.  mp: the call's map, not yet prepared.  Projective (debig_png_decode_batch_tensor_persp): each task is followed
+ * by its p[] and goes to the persp kernel of the same kind; nothing else differs.  Elastic (debig_png_decode_batch_tensor_elastic):
+ * the elastic arguments are checked here, behind everything else; each task is followed by the place of its file's field, the
+ * quantised fields are the launch's last table, and the tasks go to the elastic kernel of the same kind. */
 static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                            const debig_png_warp *warps, const debig_png_persp *persps, ela_plan *ela, const debig_png_color *colors,
-                            uint32_t *status, debig_png_info *infos,
+                            warp_map *mp, const debig_png_color *colors, uint32_t *status, debig_png_info *infos,
                             uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd,
                             tone_plan *tp)
 {
@@ -2159,20 +2200,18 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? sb : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
     const uint64_t slot = (uint64_t)H * W * ch * es;
     const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
+    const int ela = mp->kind == MAP_ELASTIC;
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
-    int64_t *m = NULL;
-    uint8_t *wbad = NULL, *cbad = NULL, *tasks = NULL;
+    uint8_t *cbad = NULL;
     debig_png_color_rec *crec = NULL;
-    const size_t base = colors ? sizeof(debig_png_warp_color_task) : sizeof(debig_png_warp_task);
-    const size_t elem = base + (persps ? sizeof(((debig_png_persp_task *)0)->p) : ela ? ELA_TAIL : 0);
-    uint64_t n_tasks = 0;
-    uint32_t cap_tasks = 0;
+    map_tasks T = {NULL, 0, 0, colors ? sizeof(debig_png_warp_color_task) : sizeof(debig_png_warp_task), 0};
+    T.elem = T.base + map_tail_bytes(mp);
     int rc;
-    if ((rc = warp_prepare(warps, persps, ela, n, W, H, &m, &wbad))) goto done;
+    if ((rc = map_prepare(mp, n, W, H))) goto done;
     if (colors && (rc = color_prepare(colors, n, bits, &crec, &cbad))) goto done;
     if ((rc = tone_prepare(tp, n))) goto done;
-    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, wbad, cbad, tp ? tp->bad : NULL, tp ? tp->blur_bad : NULL}; /* no crop-size cap */
+    const stage_rule rule = {fmt, 0, 0, 0, 0, 0, mp->bad, cbad, tp ? tp->bad : NULL, tp ? tp->blur_bad : NULL}; /* no crop-size cap */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if ((rc = tone_place(tp, status, n, W, H))) goto done;
     /* the plain warp has no tables (the six int64 travel in the task); with colours the records are the first table, at offset 0;
@@ -2181,20 +2220,20 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     const uint32_t n_tab = (tp ? 2u : 1u) + (ela ? 1u : 0u);
     if (ela && !tp) tab[1] = tab[2];
     dev_tables_place(tab, n_tab);
-    if (ela) ela_place(ela, &tab[n_tab - 1], n);
+    map_place(mp, &tab[n_tab - 1], n);
     const uint64_t lut_off = tp ? tone_fill(tp, n, tab[1].off) : 0;
     uint64_t n_direct = 0; /* with tp: the tasks in front of those of the tone files */
     rc = 2;
     for (uint64_t q = 0; q < (tp ? 2u : 1u) * (uint64_t)n; q++) { /* (with tp: every file twice, the tone files the second time) */
         const uint32_t pass = q >= n, i = (uint32_t)(pass ? q - n : q);
-        if (q == n) n_direct = n_tasks;
+        if (q == n) n_direct = T.n;
         if (status[i] != DEBIG_PNG_OK || tone_is(tp, i) != (int)pass) continue;
         debig_png_warp_color_task p; /* (the plain task: its first `base` bytes) */
         memset(&p, 0, sizeof p);
         p.color_off = (uint64_t)i * sizeof *crec;
         p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * ch * sb;
         p.out_off = (uint64_t)i * slot;
-        memcpy(p.m, m + MAP_INTS * (size_t)i, sizeof p.m);
+        memcpy(p.m, mp->m + MAP_INTS * (size_t)i, sizeof p.m);
         p.src_pitch = S.inf[i].width * ch;
         p.crop_w = S.box[i].w;
         p.crop_h = S.box[i].h;
@@ -2220,50 +2259,29 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
             p.out_sc = 1u;
             p.dtype = DEBIG_PNG_T_UINT;
         }
-        for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
-            p.row0 = y0;
-            p.rows = H - y0 < run ? H - y0 : run;
-            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL, ela, i);
-        }
+        if (!map_task_runs(&T, mp, &p, &p.row0, &p.rows, H, run, i)) goto done;
     }
-    if (!tp) n_direct = n_tasks;
+    if (!tp) n_direct = T.n;
     rc = 0;
-    if (n_tasks == 0) goto done;
-    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
+    if (T.n == 0) goto done;
+    debig_ctx *c = dev_upload(T.v, T.n, T.elem, tab, n_tab, &rc);
     if (!c) goto done;
-    if (n_tasks > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, tone_arena_bytes(tp)))) goto done;
+    if (T.n > n_direct && (rc = debig_devbuf_reserve(&c->tone_px, tone_arena_bytes(tp)))) goto done;
     for (uint32_t part = 0; part < 2; part++) { /* the caller's tensor, then the tone arena */
-        const uint8_t *d_tasks = (const uint8_t *)c->rsz_tasks.ptr + (part ? n_direct * elem : 0);
-        const uint64_t cnt = part ? n_tasks - n_direct : n_direct;
-        void *out = part ? c->tone_px.ptr : d_out;
+        const uint8_t *d_tasks = (const uint8_t *)c->rsz_tasks.ptr + (part ? n_direct * T.elem : 0);
+        const uint64_t cnt = part ? T.n - n_direct : n_direct;
         if (cnt == 0) continue;
-        if (ela)
-            rc = colors ? debig_hip_png_elastic_color_batch(c->rsz_src.ptr, out, (const debig_png_elastic_color_task *)d_tasks,
-                                                            c->rsz_weights.ptr, c->rsz_weights.ptr, (uint32_t)cnt, NULL)
-                        : debig_hip_png_elastic_batch(c->rsz_src.ptr, out, (const debig_png_elastic_task *)d_tasks,
-                                                      c->rsz_weights.ptr, (uint32_t)cnt, NULL);
-        else if (persps)
-            rc = colors ? debig_hip_png_persp_color_batch(c->rsz_src.ptr, out, (const debig_png_persp_color_task *)d_tasks,
-                                                          c->rsz_weights.ptr, (uint32_t)cnt, NULL)
-                        : debig_hip_png_persp_batch(c->rsz_src.ptr, out, (const debig_png_persp_task *)d_tasks, (uint32_t)cnt, NULL);
-        else
-            rc = colors ? debig_hip_png_warp_color_batch(c->rsz_src.ptr, out, (const debig_png_warp_color_task *)d_tasks,
-                                                         c->rsz_weights.ptr, (uint32_t)cnt, NULL)
-                        : debig_hip_png_warp_batch(c->rsz_src.ptr, out, (const debig_png_warp_task *)d_tasks, (uint32_t)cnt, NULL);
-        if (rc) goto done;
+        if ((rc = map_launch_image(mp, colors, c, part ? c->tone_px.ptr : d_out, d_tasks, (uint32_t)cnt))) goto done;
     }
     if ((rc = tone_run(tp, c, d_out, n, desc, lut_off)) || (rc = blur_run(tp, c, d_out, n, desc, lut_off))) goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
     stage_free(&S);
     tone_free(tp);
-    free(m);
-    free(wbad);
+    map_release(mp);
     free(crec);
     free(cbad);
-    free(tasks);
-    if (ela) free(ela->q);
+    free(T.v);
     return rc;
 }
 
@@ -2275,7 +2293,7 @@ DEBIG_API int debig_png_decode_batch_tensor_warp(const uint8_t *const *inputs, c
     if (n == 0) return 0;
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, NULL, NULL, status, infos, n, flags, desc, wd, NULL);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_AFFINE, .warps = warps), NULL, status, infos, n, flags, desc, wd, NULL);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2289,24 +2307,27 @@ DEBIG_API int debig_png_decode_batch_tensor_warp_color(const uint8_t *const *inp
     const int badarg = tensor_warp_check(d_out, warps, desc, wd);
     if (badarg) return badarg;
     if (!colors || !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, NULL, colors, status, infos, n, flags, desc, wd, NULL);
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_AFFINE, .warps = warps), colors, status, infos, n, flags, desc, wd, NULL);
 }
 
-/* debig_png_decode_batch_tensor_tone (blurs == NULL, blur_call == 0) and debig_png_decode_batch_tensor_blur; persp_call (then
- * warps == NULL): the same two behind debig_png_decode_batch_tensor_persp, the map projective, persps and wd required; ela_call
- * (with persp_call, then persps == NULL): behind debig_png_decode_batch_tensor_elastic, warps and wd required, the elastic
- * arguments checked behind everything else */
+/* which of the two calls with work behind the tensor a public entry point is: the tone call requires tones, the blur call blurs */
+typedef enum post_kind { POST_TONE, POST_BLUR } post_kind;
+
+/* debig_png_decode_batch_tensor_tone and debig_png_decode_batch_tensor_blur (post says which), under the call's map.  An affine
+ * map whose warps are NULL, with wd NULL: the resize route.  A projective or elastic map: the same two calls behind
+ * debig_png_decode_batch_tensor_persp and _elastic -- the map's array and wd are required, refused where the warp's are; the
+ * elastic arguments are checked behind everything else (map_prepare, the first step of tensor_warp_core) */
 static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                            const debig_png_warp *warps, const debig_png_persp *persps, const debig_png_color *colors, const debig_png_tone *tones,
-                            const uint8_t *tables, uint32_t n_tables, const debig_png_blur *blurs, int blur_call, int persp_call,
-                            int ela_call, const debig_png_elastic *elastics, const debig_png_elastic_desc *ed, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
+                            warp_map *mp, const debig_png_color *colors, post_kind post, const debig_png_tone *tones,
+                            const uint8_t *tables, uint32_t n_tables, const debig_png_blur *blurs, uint32_t *status,
+                            debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_tensor_desc *desc,
                             const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
 {
     /* every check of the call that is extended first, unchanged and in its order; then the call's own */
     if (n == 0) return 0;
     uint32_t amode = DEBIG_PNG_ALPHA_STRAIGHT;
-    if (warps || persps || wd || persp_call) { /* (persp_call: the map and its descriptor are required, refused where the warp's are) */
-        const int badarg = tensor_warp_check(d_out, warps ? (const void *)warps : (const void *)persps, desc, wd);
+    if (map_given(mp) || wd || mp->kind != MAP_AFFINE) { /* (not affine: the map and its descriptor are required) */
+        const int badarg = tensor_warp_check(d_out, map_given(mp), desc, wd);
         if (badarg) return badarg;
         if ((colors && !color_layout_ok(desc->out_format)) || alpha || filter) return DEBIG_PNG_BAD_ARG;
     } else if (colors) {
@@ -2319,11 +2340,9 @@ static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_
         if (badarg) return badarg;
         if (filter && (filter->filter > DEBIG_PNG_FILTER_NEAREST || filter->reserved != 0)) return DEBIG_PNG_BAD_ARG;
     }
-    if ((blur_call ? !blurs : !tones) || (desc->out_format & DEBIG_PNG_FMT_16) || amode == DEBIG_PNG_ALPHA_PREMULTIPLIED ||
+    if ((post == POST_BLUR ? !blurs : !tones) || (desc->out_format & DEBIG_PNG_FMT_16) || amode == DEBIG_PNG_ALPHA_PREMULTIPLIED ||
         (!tables && n_tables > 0))
         return DEBIG_PNG_BAD_ARG;
-    ela_plan ela;
-    if (ela_call && ela_check(&ela, elastics, ed)) return DEBIG_PNG_BAD_ARG;
     tone_plan tp;
     memset(&tp, 0, sizeof tp);
     tp.tones = tones;
@@ -2331,9 +2350,7 @@ static int tensor_post_call(const uint8_t *const *inputs, const uint64_t *input_
     tp.n_tables = n_tables;
     tp.blurs = blurs;
     tp.oc = fmt_channels(desc->out_format);
-    if (warps || persps)
-        return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, persps, ela_call ? &ela : NULL, colors, status, infos, n, flags,
-                                desc, wd, &tp);
+    if (map_given(mp)) return tensor_warp_core(inputs, input_sizes, d_out, boxes, mp, colors, status, infos, n, flags, desc, wd, &tp);
     return tensor_core(inputs, input_sizes, d_out, boxes, status, infos, n, flags, desc, amode, alpha ? alpha->background : NULL,
                        filter ? filter->filter : DEBIG_PNG_FILTER_BILINEAR, colors, &tp);
 }
@@ -2346,8 +2363,8 @@ DEBIG_API int debig_png_decode_batch_tensor_tone(const uint8_t *const *inputs, c
                                                  const debig_png_alpha_desc *alpha, const debig_png_filter_desc *filter,
                                                  const debig_png_warp_desc *wd)
 {
-    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, NULL, 0, 0, 0, NULL, NULL, status, infos, n,
-                            flags, desc, alpha, filter, wd);
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_AFFINE, .warps = warps), colors, POST_TONE, tones,
+                            tables, n_tables, NULL, status, infos, n, flags, desc, alpha, filter, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2358,8 +2375,26 @@ DEBIG_API int debig_png_decode_batch_tensor_blur(const uint8_t *const *inputs, c
                                                  const debig_png_tensor_desc *desc, const debig_png_alpha_desc *alpha,
                                                  const debig_png_filter_desc *filter, const debig_png_warp_desc *wd)
 {
-    return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, blurs, 1, 0, 0, NULL, NULL, status, infos, n,
-                            flags, desc, alpha, filter, wd);
+    return tensor_post_call(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_AFFINE, .warps = warps), colors, POST_BLUR, tones,
+                            tables, n_tables, blurs, status, infos, n, flags, desc, alpha, filter, wd);
+}
+
+/* debig_png_decode_batch_tensor_persp and _elastic behind the making of their map: the affine call that the given arguments name,
+ * its checks in its order: _tensor_blur with blurs, _tensor_tone with tones, else _tensor_warp_color or _tensor_warp; then the
+ * map's own arguments (map_prepare) */
+static int tensor_map_call(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
+                           warp_map *mp, const debig_png_color *colors, const debig_png_tone *tones, const uint8_t *tables,
+                           uint32_t n_tables, const debig_png_blur *blurs, uint32_t *status, debig_png_info *infos, uint32_t n,
+                           uint32_t flags, const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
+{
+    if (tones || blurs)
+        return tensor_post_call(inputs, input_sizes, d_out, boxes, mp, colors, blurs ? POST_BLUR : POST_TONE, tones, tables, n_tables,
+                                blurs, status, infos, n, flags, desc, NULL, NULL, wd);
+    if (n == 0) return 0;
+    const int badarg = tensor_warp_check(d_out, map_given(mp), desc, wd);
+    if (badarg) return badarg;
+    if (colors && !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
+    return tensor_warp_core(inputs, input_sizes, d_out, boxes, mp, colors, status, infos, n, flags, desc, wd, NULL);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2369,16 +2404,8 @@ DEBIG_API int debig_png_decode_batch_tensor_persp(const uint8_t *const *inputs, 
                                                   debig_png_info *infos, uint32_t n, uint32_t flags,
                                                   const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd)
 {
-    /* the affine call that the given arguments name, its checks in its order: _tensor_blur with blurs, _tensor_tone with tones,
-     * else _tensor_warp_color or _tensor_warp */
-    if (tones || blurs)
-        return tensor_post_call(inputs, input_sizes, d_out, boxes, NULL, persps, colors, tones, tables, n_tables, blurs, blurs != NULL,
-                                1, 0, NULL, NULL, status, infos, n, flags, desc, NULL, NULL, wd);
-    if (n == 0) return 0;
-    const int badarg = tensor_warp_check(d_out, persps, desc, wd);
-    if (badarg) return badarg;
-    if (colors && !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, NULL, colors, status, infos, n, flags, desc, wd, NULL);
+    return tensor_map_call(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_PERSP, .persps = persps), colors, tones, tables,
+                           n_tables, blurs, status, infos, n, flags, desc, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_tensor_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2389,56 +2416,57 @@ DEBIG_API int debig_png_decode_batch_tensor_elastic(const uint8_t *const *inputs
                                                     const debig_png_tensor_desc *desc, const debig_png_warp_desc *wd,
                                                     const debig_png_elastic *elastics, const debig_png_elastic_desc *ed)
 {
-    /* the affine call that the given arguments name, its checks in its order (as debig_png_decode_batch_tensor_persp); then the
-     * elastic arguments */
-    if (tones || blurs)
-        return tensor_post_call(inputs, input_sizes, d_out, boxes, warps, NULL, colors, tones, tables, n_tables, blurs, blurs != NULL,
-                                1, 1, elastics, ed, status, infos, n, flags, desc, NULL, NULL, wd);
-    if (n == 0) return 0;
-    const int badarg = tensor_warp_check(d_out, warps, desc, wd);
-    if (badarg) return badarg;
-    if (colors && !color_layout_ok(desc->out_format)) return DEBIG_PNG_BAD_ARG;
-    ela_plan ela;
-    if (ela_check(&ela, elastics, ed)) return DEBIG_PNG_BAD_ARG;
-    return tensor_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, &ela, colors, status, infos, n, flags, desc, wd, NULL);
+    return tensor_map_call(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_ELASTIC, .warps = warps, .elastics = elastics, .ed = ed), colors, tones, tables,
+                           n_tables, blurs, status, infos, n, flags, desc, wd);
 }
 
-/* debig_png_decode_batch_labels_warp (warps) and debig_png_decode_batch_labels_persp (persps): exactly one of the two may be
- * given; ela_call (with warps): debig_png_decode_batch_labels_elastic, its two arguments checked behind the warp's */
+/* the warp arguments of the two label calls, behind the checks of the call without a warp: the map's array, wd, the border mode,
+ * and a CONSTANT border label that the dtype holds -> 0 or DEBIG_PNG_BAD_ARG */
+static int label_warp_check(const warp_map *mp, const debig_png_label_warp_desc *wd, uint32_t dtype)
+{
+    if (!map_given(mp) || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) return DEBIG_PNG_BAD_ARG;
+    if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && dtype <= DEBIG_PNG_L_U16 &&
+        (wd->border_label < 0 || wd->border_label > (dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
+        return DEBIG_PNG_BAD_ARG;
+    return 0;
+}
+
+/* the launch of the label kind under the call's map */
+static int map_launch_labels(const warp_map *mp, const debig_ctx *c, void *d_out, const int32_t *d_lut, uint32_t cnt)
+{
+    const uint8_t *src = c->rsz_src.ptr, *w = c->rsz_weights.ptr;
+    const void *t = c->rsz_tasks.ptr;
+    switch (mp->kind) {
+    case MAP_ELASTIC: return debig_hip_png_label_elastic_batch(src, d_out, (const debig_png_label_elastic_task *)t, d_lut, w, cnt, NULL);
+    case MAP_PERSP: return debig_hip_png_label_persp_batch(src, d_out, (const debig_png_label_persp_task *)t, d_lut, cnt, NULL);
+    default: return debig_hip_png_label_warp_batch(src, d_out, (const debig_png_label_warp_task *)t, d_lut, cnt, NULL);
+    }
+}
+
+/* debig_png_decode_batch_labels_warp, _labels_persp and _labels_elastic under their map (not yet prepared); the elastic
+ * arguments are checked behind the warp's */
 static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                            const debig_png_warp *warps, const debig_png_persp *persps, int ela_call,
-                            const debig_png_elastic *elastics, const debig_png_elastic_desc *ed, uint32_t *status,
-                            debig_png_info *infos, uint32_t n, uint32_t flags, const debig_png_label_desc *desc,
-                            const debig_png_label_warp_desc *wd)
+                            warp_map *mp, uint32_t *status, debig_png_info *infos, uint32_t n, uint32_t flags,
+                            const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
     /* every check of debig_png_decode_batch_labels first and unchanged, then the warp's; all before any file is looked at */
     if (n == 0) return 0;
     const int badarg = label_args_check(d_out, desc);
     if (badarg) return badarg;
-    if ((!warps && !persps) || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) return DEBIG_PNG_BAD_ARG;
-    if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
-        (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
-        return DEBIG_PNG_BAD_ARG;
-    ela_plan ela_store, *ela = ela_call ? &ela_store : NULL;
-    if (ela && ela_check(ela, elastics, ed)) return DEBIG_PNG_BAD_ARG;
+    if (label_warp_check(mp, wd, desc->dtype)) return DEBIG_PNG_BAD_ARG;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
     const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
-    int64_t *m = NULL;
-    uint8_t *wbad = NULL, *tasks = NULL;
-    const size_t base = sizeof(debig_png_label_warp_task),
-                 elem = base + (persps ? sizeof(((debig_png_label_persp_task *)0)->p) : ela ? ELA_TAIL : 0);
-    uint64_t n_tasks = 0;
-    uint32_t cap_tasks = 0;
+    map_tasks T = {NULL, 0, 0, sizeof(debig_png_label_warp_task), sizeof(debig_png_label_warp_task) + map_tail_bytes(mp)};
     int rc;
-    if ((rc = warp_prepare(warps, persps, ela, n, W, H, &m, &wbad))) goto done;
+    if ((rc = map_prepare(mp, n, W, H))) goto done;
     dev_table tab[2] = {{desc->lut, 1024, 0}, {NULL, 0, 0}}; /* the LUT (or its room), the fields */
-    const uint32_t n_tab = ela ? 2u : 1u;
+    const uint32_t n_tab = mp->kind == MAP_ELASTIC ? 2u : 1u;
     dev_tables_place(tab, n_tab);
-    if (ela) ela_place(ela, &tab[1], n);
+    map_place(mp, &tab[1], n);
     /* E_LABEL: colour type 2, 4 or 6; a 16-bit file with dtype U8 or with a lut */
-    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, wbad, NULL, NULL, NULL};
+    const stage_rule rule = {DEBIG_PNG_FMT_GRAY | DEBIG_PNG_FMT_NATIVE_DEPTH, 1, 1, desc->dtype == DEBIG_PNG_L_U8 || desc->lut, 0, 0, mp->bad, NULL, NULL, NULL};
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     rc = 2;
     for (uint32_t i = 0; i < n; i++) {
@@ -2448,7 +2476,7 @@ static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_
         p.src_bytes = S.inf[i].bit_depth == 16 ? 2u : 1u;
         p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * p.src_bytes;
         p.out_off = (uint64_t)i * H * W * es;
-        memcpy(p.m, m + MAP_INTS * (size_t)i, sizeof p.m);
+        memcpy(p.m, mp->m + MAP_INTS * (size_t)i, sizeof p.m);
         p.src_pitch = S.inf[i].width;
         p.crop_w = S.box[i].w;
         p.crop_h = S.box[i].h;
@@ -2457,32 +2485,18 @@ static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_
         p.border_label = wd->border_label;
         p.dtype = (uint8_t)desc->dtype;
         p.border_mode = (uint8_t)wd->border_mode;
-        for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
-            p.row0 = y0;
-            p.rows = H - y0 < run ? H - y0 : run;
-            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL, ela, i);
-        }
+        if (!map_task_runs(&T, mp, &p, &p.row0, &p.rows, H, run, i)) goto done;
     }
     rc = 0;
-    if (n_tasks == 0) goto done;
-    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
+    if (T.n == 0) goto done;
+    debig_ctx *c = dev_upload(T.v, T.n, T.elem, tab, n_tab, &rc);
     if (!c) goto done;
-    const int32_t *d_lut = desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL;
-    if ((rc = ela    ? debig_hip_png_label_elastic_batch(c->rsz_src.ptr, d_out, (const debig_png_label_elastic_task *)c->rsz_tasks.ptr,
-                                                         d_lut, c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
-              : persps ? debig_hip_png_label_persp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_persp_task *)c->rsz_tasks.ptr,
-                                                       d_lut, (uint32_t)n_tasks, NULL)
-                     : debig_hip_png_label_warp_batch(c->rsz_src.ptr, d_out, (const debig_png_label_warp_task *)c->rsz_tasks.ptr,
-                                                      d_lut, (uint32_t)n_tasks, NULL)))
-        goto done;
+    if ((rc = map_launch_labels(mp, c, d_out, desc->lut ? (const int32_t *)c->rsz_weights.ptr : NULL, (uint32_t)T.n))) goto done;
     rc = debig_hip_stream_sync(NULL);
 done:
     stage_free(&S);
-    free(m);
-    free(wbad);
-    free(tasks);
-    if (ela) free(ela->q);
+    map_release(mp);
+    free(T.v);
     return rc;
 }
 
@@ -2491,7 +2505,7 @@ DEBIG_API int debig_png_decode_batch_labels_warp(const uint8_t *const *inputs, c
                                                  debig_png_info *infos, uint32_t n, uint32_t flags,
                                                  const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
-    return labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 0, NULL, NULL, status, infos, n, flags, desc, wd);
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_AFFINE, .warps = warps), status, infos, n, flags, desc, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2499,7 +2513,7 @@ DEBIG_API int debig_png_decode_batch_labels_persp(const uint8_t *const *inputs, 
                                                   debig_png_info *infos, uint32_t n, uint32_t flags,
                                                   const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
-    return labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, 0, NULL, NULL, status, infos, n, flags, desc, wd);
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_PERSP, .persps = persps), status, infos, n, flags, desc, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_labels_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2508,53 +2522,52 @@ DEBIG_API int debig_png_decode_batch_labels_elastic(const uint8_t *const *inputs
                                                     const debig_png_label_desc *desc, const debig_png_label_warp_desc *wd,
                                                     const debig_png_elastic *elastics, const debig_png_elastic_desc *ed)
 {
-    return labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 1, elastics, ed, status, infos, n, flags, desc, wd);
+    return labels_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_ELASTIC, .warps = warps, .elastics = elastics, .ed = ed), status,
+                            infos, n, flags, desc, wd);
 }
 
-/* debig_png_decode_batch_color_labels_warp (warps) and debig_png_decode_batch_color_labels_persp (persps): exactly one of the
- * two may be given; ela_call (with warps): debig_png_decode_batch_color_labels_elastic, its two arguments checked behind the warp's */
+/* the launch of the colour-label kind under the call's map; the maps' tables are the first table of the launch */
+static int map_launch_color_labels(const warp_map *mp, const debig_ctx *c, void *d_out, uint32_t *d_cnt, uint32_t cnt)
+{
+    const uint8_t *src = c->rsz_src.ptr, *w = c->rsz_weights.ptr;
+    const void *t = c->rsz_tasks.ptr;
+    switch (mp->kind) {
+    case MAP_ELASTIC: return debig_hip_png_color_label_elastic_batch(src, d_out, (const debig_png_color_label_elastic_task *)t, w, d_cnt, w, cnt, NULL);
+    case MAP_PERSP: return debig_hip_png_color_label_persp_batch(src, d_out, (const debig_png_color_label_persp_task *)t, w, d_cnt, cnt, NULL);
+    default: return debig_hip_png_color_label_warp_batch(src, d_out, (const debig_png_color_label_warp_task *)t, w, d_cnt, cnt, NULL);
+    }
+}
+
+/* debig_png_decode_batch_color_labels_warp, _color_labels_persp and _color_labels_elastic under their map (not yet prepared); the
+ * elastic arguments are checked behind the warp's */
 static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out, const debig_png_box *boxes,
-                                  const debig_png_warp *warps, const debig_png_persp *persps, int ela_call,
-                                  const debig_png_elastic *elastics, const debig_png_elastic_desc *ed, uint32_t *status,
-                                  debig_png_info *infos, uint32_t *unmatched, uint32_t n, uint32_t flags,
-                                  const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *wd)
+                                  warp_map *mp, uint32_t *status, debig_png_info *infos, uint32_t *unmatched, uint32_t n,
+                                  uint32_t flags, const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *wd)
 {
     /* every check of debig_png_decode_batch_color_labels first and unchanged, then the warp's; all before any file is looked at */
     if (n == 0) return 0;
     clbl_maps M = {NULL, NULL, 0, NULL};
     uint32_t *cnt = NULL;
     stage S = {NULL, NULL, NULL, NULL, NULL};
-    int64_t *m = NULL;
-    uint8_t *wbad = NULL, *tasks = NULL;
-    ela_plan ela_store, *ela = NULL;
-    const size_t base = sizeof(debig_png_color_label_warp_task),
-                 elem = base + (persps ? sizeof(((debig_png_color_label_persp_task *)0)->p) : ela_call ? ELA_TAIL : 0);
-    uint64_t n_tasks = 0;
-    uint32_t cap_tasks = 0;
+    map_tasks T = {NULL, 0, 0, sizeof(debig_png_color_label_warp_task), sizeof(debig_png_color_label_warp_task) + map_tail_bytes(mp)};
     int rc;
     if ((rc = clbl_args_check(d_out, desc, n, &M))) goto done;
-    rc = DEBIG_PNG_BAD_ARG;
-    if ((!warps && !persps) || !wd || wd->border_mode > DEBIG_PNG_BORDER_CLAMP) goto done;
-    if (wd->border_mode == DEBIG_PNG_BORDER_CONSTANT && desc->dtype <= DEBIG_PNG_L_U16 &&
-        (wd->border_label < 0 || wd->border_label > (desc->dtype == DEBIG_PNG_L_U8 ? 255 : 65535)))
-        goto done;
-    if (ela_call && ela_check(&ela_store, elastics, ed)) goto done;
-    if (ela_call) ela = &ela_store;
+    if ((rc = label_warp_check(mp, wd, desc->dtype))) goto done;
     const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
     const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
     /* the maps' tables (first: map_off needs no base), the counters (16-byte aligned: a table is a multiple of 16 bytes) */
     dev_table tab[3] = {{M.tab, M.bytes, 0}, {NULL, (uint64_t)n * sizeof(uint32_t), 0}, {NULL, 0, 0}}; /* (the fields come last) */
-    const uint32_t n_tab = ela ? 3u : 2u;
+    const uint32_t n_tab = mp->kind == MAP_ELASTIC ? 3u : 2u;
+    if ((rc = map_prepare(mp, n, W, H))) goto done;
     rc = 2;
     cnt = (uint32_t *)calloc(n, sizeof(uint32_t));
     if (!cnt) goto done;
-    if ((rc = warp_prepare(warps, persps, ela, n, W, H, &m, &wbad))) goto done;
-    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, wbad, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
+    const stage_rule rule = {DEBIG_PNG_FMT_RGB | DEBIG_PNG_FMT_8, 0, 0, 1, 0, 0, mp->bad, NULL, NULL, NULL}; /* E_LABEL: a 16-bit file */
     if ((rc = stage_decode(&S, &rule, inputs, input_sizes, boxes, status, infos, n, flags))) goto done;
     if (unmatched) memset(unmatched, 0, (size_t)n * sizeof(uint32_t));
     dev_tables_place(tab, n_tab);
-    if (ela) ela_place(ela, &tab[2], n);
+    map_place(mp, &tab[2], n);
     rc = 2;
     for (uint32_t i = 0; i < n; i++) {
         if (status[i] != DEBIG_PNG_OK) continue;
@@ -2563,7 +2576,7 @@ static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *
         memset(&p, 0, sizeof p);
         p.src_off = S.offs[i] + ((uint64_t)S.box[i].y * S.inf[i].width + S.box[i].x) * 3u;
         p.out_off = (uint64_t)i * H * W * es;
-        memcpy(p.m, m + MAP_INTS * (size_t)i, sizeof p.m);
+        memcpy(p.m, mp->m + MAP_INTS * (size_t)i, sizeof p.m);
         p.src_pitch = S.inf[i].width;
         p.crop_w = S.box[i].w;
         p.crop_h = S.box[i].h;
@@ -2579,28 +2592,15 @@ static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *
             p.map_slots = M.slots[mk];
             p.missing = desc->missing;
         }
-        for (uint32_t y0 = 0; y0 < H; y0 += run) {
-            if (n_tasks >= 0x7fffffffu || !grow((void **)&tasks, &cap_tasks, (uint32_t)n_tasks, elem)) goto done;
-            p.row0 = y0;
-            p.rows = H - y0 < run ? H - y0 : run;
-            map_task_put(tasks + n_tasks++ * elem, &p, base, m + MAP_INTS * (size_t)i, persps != NULL, ela, i);
-        }
+        if (!map_task_runs(&T, mp, &p, &p.row0, &p.rows, H, run, i)) goto done;
     }
     rc = 0;
-    if (n_tasks == 0) goto done;
-    debig_ctx *c = dev_upload(tasks, n_tasks, elem, tab, n_tab, &rc);
+    if (T.n == 0) goto done;
+    debig_ctx *c = dev_upload(T.v, T.n, T.elem, tab, n_tab, &rc);
     if (!c) goto done;
     uint32_t *d_cnt = map_mode ? (uint32_t *)((uint8_t *)c->rsz_weights.ptr + tab[1].off) : NULL;
     if ((d_cnt && (rc = debig_hip_memset(d_cnt, 0, tab[1].bytes, NULL))) ||
-        (rc = ela    ? debig_hip_png_color_label_elastic_batch(c->rsz_src.ptr, d_out,
-                                                               (const debig_png_color_label_elastic_task *)c->rsz_tasks.ptr,
-                                                               c->rsz_weights.ptr, d_cnt, c->rsz_weights.ptr, (uint32_t)n_tasks, NULL)
-              : persps ? debig_hip_png_color_label_persp_batch(c->rsz_src.ptr, d_out,
-                                                             (const debig_png_color_label_persp_task *)c->rsz_tasks.ptr,
-                                                             c->rsz_weights.ptr, d_cnt, (uint32_t)n_tasks, NULL)
-                     : debig_hip_png_color_label_warp_batch(c->rsz_src.ptr, d_out,
-                                                            (const debig_png_color_label_warp_task *)c->rsz_tasks.ptr,
-                                                            c->rsz_weights.ptr, d_cnt, (uint32_t)n_tasks, NULL)) ||
+        (rc = map_launch_color_labels(mp, c, d_out, d_cnt, (uint32_t)T.n)) ||
         (d_cnt && (rc = debig_hip_memcpy_d2h(cnt, d_cnt, tab[1].bytes, NULL))) ||
         (rc = debig_hip_stream_sync(NULL)))
         goto done;
@@ -2609,10 +2609,8 @@ done:
     clbl_maps_free(&M);
     free(cnt);
     stage_free(&S);
-    free(m);
-    free(wbad);
-    free(tasks);
-    if (ela) free(ela->q);
+    map_release(mp);
+    free(T.v);
     return rc;
 }
 
@@ -2622,8 +2620,8 @@ DEBIG_API int debig_png_decode_batch_color_labels_warp(const uint8_t *const *inp
                                                        const debig_png_color_label_desc *desc,
                                                        const debig_png_label_warp_desc *wd)
 {
-    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 0, NULL, NULL, status, infos, unmatched, n, flags, desc,
-                                  wd);
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_AFFINE, .warps = warps), status, infos,
+                                  unmatched, n, flags, desc, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_color_labels_persp(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2632,8 +2630,8 @@ DEBIG_API int debig_png_decode_batch_color_labels_persp(const uint8_t *const *in
                                                         const debig_png_color_label_desc *desc,
                                                         const debig_png_label_warp_desc *wd)
 {
-    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, NULL, persps, 0, NULL, NULL, status, infos, unmatched, n, flags, desc,
-                                  wd);
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_PERSP, .persps = persps), status, infos,
+                                  unmatched, n, flags, desc, wd);
 }
 
 DEBIG_API int debig_png_decode_batch_color_labels_elastic(const uint8_t *const *inputs, const uint64_t *input_sizes, void *d_out,
@@ -2643,6 +2641,6 @@ DEBIG_API int debig_png_decode_batch_color_labels_elastic(const uint8_t *const *
                                                           const debig_png_label_warp_desc *wd, const debig_png_elastic *elastics,
                                                           const debig_png_elastic_desc *ed)
 {
-    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, warps, NULL, 1, elastics, ed, status, infos, unmatched, n, flags,
-                                  desc, wd);
+    return color_labels_warp_core(inputs, input_sizes, d_out, boxes, MAP_OF(MAP_ELASTIC, .warps = warps, .elastics = elastics, .ed = ed), status, infos,
+                                  unmatched, n, flags, desc, wd);
 }

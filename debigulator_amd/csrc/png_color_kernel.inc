@@ -17,7 +17,8 @@
 //     mixes, converts and stores that many adjacent elements (HWC) or one element in each plane row, adjacent to its neighbour
 //     lanes' (CHW): the store shapes of the alpha kernel.
 //   - debig_png_warp_color_kernel: the walk and the picks of png_warp_kernel.inc (warp_walk, warp_pick, warp_taps) with the
-//     per-channel store of warp_rows replaced by collect, mix, store.  Picks, border rule and clamps are the warp kernel's; a
+//     per-channel store of warp_rows replaced by collect, mix, store; its task loop (warp_color_tasks) is a template over the
+//     task and the map, which png_persp_kernel.inc and png_elastic_kernel.inc instantiate again.  Picks, border rule and clamps are the warp kernel's; a
 //     CONSTANT border sample is mixed like any other sample.
 // A task that breaks a bound -- those of the kernels they extend, channels other than 3 / 4, a color_off that is no multiple of
 // 8, a record beyond the quantiser's limits -- is skipped (never indexed out of range).  No atomics, no scratch, nothing shared
@@ -116,10 +117,9 @@ debig_png_resize_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restri
 
 // the rows of one task at source precision P: the walk and the picks of warp_rows (png_warp_kernel.inc), the pixel's channels
 // collected, mixed and stored; the channel count sc is a run-time value as in rsz_color_pass2
-template <uint32_t P, class Walk, class Task>
-DEV_INLINE void warp_color_rows(const Task &t, const Task *__restrict__ tg, const debig_png_color_rec &cr,
-                                const uint8_t *__restrict__ src, uint8_t *__restrict__ out, uint32_t tid,
-                                const Walk &walk = Walk())
+template <uint32_t P, class Map, class Task>
+DEV_INLINE void warp_color_rows(const Map &map, const Task &t, const Task *__restrict__ tg, const debig_png_color_rec &cr,
+                                const uint8_t *__restrict__ src, uint8_t *__restrict__ out, uint32_t tid)
 {
     typedef typename RszSample<P>::sample_t sample_t;
     constexpr uint32_t VMAX = ((1u << P) - 1u) << (30u - P);
@@ -128,7 +128,7 @@ DEV_INLINE void warp_color_rows(const Task &t, const Task *__restrict__ tg, cons
     const uint32_t sc = t.channels;
     const bool alpha = sc == 4u;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    walk.walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    warp_walk(map, t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         uint32_t v[3], m[3], va = 0u;
         if (nearest) {
@@ -158,22 +158,32 @@ RSZ_UNROLL
     });
 }
 
-__global__ void __launch_bounds__(WARP_THREADS)
-debig_png_warp_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-                            const debig_png_warp_color_task *__restrict__ tasks, const uint8_t *__restrict__ weights, uint32_t n_tasks)
+// the colour kind: the task loop of debig_png_warp_color_kernel, _persp_color_kernel and _elastic_color_kernel.  The record is
+// read and checked in front of the map's hold step
+template <class Task, class Map>
+DEV_INLINE void warp_color_tasks(Map map, const uint8_t *__restrict__ src, uint8_t *__restrict__ out, const Task *__restrict__ tasks,
+                                 const uint8_t *__restrict__ weights, uint32_t n_tasks)
 {
     const uint32_t tid = threadIdx.x;
     for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_warp_color_task t = tasks[ti];
+        const Task t = tasks[ti];
         // (uniform over the workgroup: every lane skips, or none)
         if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || (t.channels != 3u && t.channels != 4u) ||
             (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.filter != WARP_FILTER_BILINEAR && t.filter != WARP_FILTER_NEAREST) ||
             t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
-            (t.src_off & ((uint32_t)t.bits / 8u - 1u)) || (t.color_off & 7u))
+            (t.src_off & ((uint32_t)t.bits / 8u - 1u)) || (t.color_off & 7u) || !map.task_ok(t))
             continue;
         const debig_png_color_rec cr = *reinterpret_cast<const debig_png_color_rec *>(weights + t.color_off);
         if (!color_rec_ok(cr, t.bits)) continue;
-        if (t.bits == 8u) warp_color_rows<8u, WarpAffine>(t, &tasks[ti], cr, src, out, tid);
-        else warp_color_rows<16u, WarpAffine>(t, &tasks[ti], cr, src, out, tid);
+        if (!map.hold(t, tid)) continue;
+        if (t.bits == 8u) warp_color_rows<8u>(map, t, &tasks[ti], cr, src, out, tid);
+        else warp_color_rows<16u>(map, t, &tasks[ti], cr, src, out, tid);
     }
+}
+
+__global__ void __launch_bounds__(WARP_THREADS)
+debig_png_warp_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                            const debig_png_warp_color_task *__restrict__ tasks, const uint8_t *__restrict__ weights, uint32_t n_tasks)
+{
+    warp_color_tasks(WarpAffine(), src, out, tasks, weights, n_tasks);
 }

@@ -10,16 +10,16 @@
 // the Q14 fraction t by two 32-bit divisions, four Catmull-Rom weights from t in integers (their sum is exactly 16384), then
 // D = (sum_i sum_j wy_i wx_j d[i][j] + 2^27) >> 28 over the 4 x 4 nodes around the cell, edge nodes replicated, in int64 with
 // nothing rounded in between.  (U, V) = the affine (NU, NV) of m[] plus the linear part of m[] applied to (Dx, Dy).  Everything
-// behind (U, V) is the affine warp's, word for word: the row bodies of png_warp_kernel.inc, png_color_kernel.inc and
-// png_color_label_warp_kernel.inc are instantiated with the walk of this file (WarpElastic).
+// around (U, V) is the affine warp's, word for word: the kernel bodies of png_warp_kernel.inc, png_color_kernel.inc and
+// png_color_label_warp_kernel.inc are instantiated with the map policy of this file (WarpElastic).
 //   - a TASK is the warp task of the kernel it mirrors, field for field, followed by field_off (bytes from the launch's `fields`
 //     argument, 8-byte aligned; UINT64_MAX: no field, which is a field of zeros) and grid_w, grid_h; tasks, workgroups and the
 //     lane mapping are the warp kernels' (one lane per output pixel, lanes along X and on into the next row, 256 lanes);
 //   - the workgroup STAGES its task's grid in LDS (at most 33 x 33 x 8 = 8712 bytes) and keeps it while consecutive tasks name
 //     the same field_off and grid size (ela_hold_grid, the scheme of clbl_hold_map); the staging pass compares every node with
 //     the limit and the workgroup votes through one LDS word, so a task with a node out of range is skipped by every lane;
-//   - the walk is an OBJECT here (it carries the LDS pointer); the row bodies take it as their last argument, which the affine
-//     and projective walks default to an empty value;
+//   - the map policy has STATE here (the LDS pointers, the fields, what is held); the bodies take it by value, and the affine and
+//     projective policies are empty types whose hold step is `true`;
 //   - per pixel: four 32-bit divisions, two weight quadruples (a few 64-bit multiplies), 16 eight-byte LDS reads at addresses
 //     that neighbouring lanes share or that lie in neighbouring nodes (a wavefront covers at most a few cells of a row: the
 //     reads are broadcasts), 32 multiply-adds of int32 x int32 into int64 and 8 of int64 x int32.
@@ -94,27 +94,6 @@ DEV_INLINE void ela_displacement(const ElaNode *grid, const Task &t, uint32_t X,
     Dy = (sy + ((int64_t)1 << 27)) >> 28;
 }
 
-// the elastic walk: the output pixels of one task as warp_walk hands them out, (U, V) displaced; the caller holds the task's
-// grid in LDS (ela_hold_grid returned true)
-struct WarpElastic {
-    const ElaNode *grid;
-    template <class Task, class Body>
-    DEV_MEMBER_INLINE void walk(const Task &t, uint32_t tid, Body body) const
-    {
-        const uint32_t n = t.rows * t.out_w;
-        StageWalk wk(tid, t.out_w, WARP_THREADS);
-        for (uint32_t i = tid; i < n; i += WARP_THREADS) {
-            const uint32_t X = wk.x, Y = t.row0 + wk.r;
-            const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
-            int64_t Dx, Dy;
-            ela_displacement(grid, t, X, Y, Dx, Dy);
-            body(X, Y, t.m[0] * cx + t.m[1] * cy + 2 * t.m[2] + ((t.m[0] * Dx + t.m[1] * Dy + 16384) >> 15),
-                 t.m[3] * cx + t.m[4] * cy + 2 * t.m[5] + ((t.m[3] * Dx + t.m[4] * Dy + 16384) >> 15));
-            wk.next();
-        }
-    }
-};
-
 // what a task adds to the bounds of its warp twin, as far as the task alone tells (uniform over the workgroup)
 template <class Task>
 DEV_INLINE bool ela_task_ok(const Task &t)
@@ -160,7 +139,30 @@ DEV_INLINE bool ela_hold_grid(ElaNode *lds_grid, uint32_t *lds_bad, ElaHeld &hel
     return held.ok;
 }
 
-// ---- the four kernels: each is its warp twin with the walk replaced, ela_task_ok among the skips and the grid held ---------------
+// the elastic map as the policy the kernel bodies take (png_warp_kernel.inc has the scheme): ela_task_ok among the skips, the
+// task's grid held in LDS that the kernel owns, (U, V) displaced -- behind hold(), which returned true.  The one policy with state
+struct WarpElastic {
+    ElaNode *grid;
+    uint32_t *bad;
+    const uint8_t *fields;
+    ElaHeld held;
+    DEV_MEMBER_INLINE WarpElastic(ElaNode *lds_grid, uint32_t *lds_bad, const uint8_t *fields_)
+        : grid(lds_grid), bad(lds_bad), fields(fields_), held{0u, 0u, 0u, false} {}
+    template <class Task>
+    static DEV_MEMBER_INLINE bool task_ok(const Task &t) { return ela_task_ok(t); }
+    template <class Task> // (forced inline in the emulator build as well, which would otherwise export it)
+    __device__ __forceinline__ bool hold(const Task &t, uint32_t tid) { return ela_hold_grid(grid, bad, held, t, fields, tid); }
+    template <class Task>
+    DEV_MEMBER_INLINE void uv(const Task &t, uint32_t X, uint32_t Y, int64_t cx, int64_t cy, int64_t &U, int64_t &V) const
+    {
+        int64_t Dx, Dy;
+        ela_displacement(grid, t, X, Y, Dx, Dy);
+        U = warp_nu(t, cx, cy) + ((t.m[0] * Dx + t.m[1] * Dy + 16384) >> 15);
+        V = warp_nv(t, cx, cy) + ((t.m[3] * Dx + t.m[4] * Dy + 16384) >> 15);
+    }
+};
+
+// ---- the four kernels: the body of each kind under the elastic map, the grid and the vote in LDS of their own --------------------
 
 __global__ void __launch_bounds__(WARP_THREADS)
 debig_png_elastic_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, const debig_png_elastic_task *__restrict__ tasks,
@@ -168,21 +170,7 @@ debig_png_elastic_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ 
 {
     __shared__ ElaNode lds_grid[ELA_GRID_MAX * ELA_GRID_MAX];
     __shared__ uint32_t lds_bad;
-    const uint32_t tid = threadIdx.x;
-    ElaHeld held = { 0u, 0u, 0u, false };
-    WarpElastic walk = { lds_grid };
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_elastic_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || t.channels == 0u || t.channels > 4u ||
-            (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.filter != WARP_FILTER_BILINEAR && t.filter != WARP_FILTER_NEAREST) ||
-            t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
-            (t.src_off & ((uint32_t)t.bits / 8u - 1u)) || !ela_task_ok(t))
-            continue;
-        if (!ela_hold_grid(lds_grid, &lds_bad, held, t, fields, tid)) continue;
-        if (t.bits == 8u) warp_rows<8u, WarpElastic>(t, &tasks[ti], src, out, tid, walk);
-        else warp_rows<16u, WarpElastic>(t, &tasks[ti], src, out, tid, walk);
-    }
+    warp_image_tasks(WarpElastic(lds_grid, &lds_bad, fields), src, out, tasks, n_tasks);
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)
@@ -192,23 +180,7 @@ debig_png_elastic_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restr
 {
     __shared__ ElaNode lds_grid[ELA_GRID_MAX * ELA_GRID_MAX];
     __shared__ uint32_t lds_bad;
-    const uint32_t tid = threadIdx.x;
-    ElaHeld held = { 0u, 0u, 0u, false };
-    WarpElastic walk = { lds_grid };
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_elastic_color_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || (t.channels != 3u && t.channels != 4u) ||
-            (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.filter != WARP_FILTER_BILINEAR && t.filter != WARP_FILTER_NEAREST) ||
-            t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
-            (t.src_off & ((uint32_t)t.bits / 8u - 1u)) || (t.color_off & 7u) || !ela_task_ok(t))
-            continue;
-        const debig_png_color_rec cr = *reinterpret_cast<const debig_png_color_rec *>(weights + t.color_off);
-        if (!color_rec_ok(cr, t.bits)) continue;
-        if (!ela_hold_grid(lds_grid, &lds_bad, held, t, fields, tid)) continue;
-        if (t.bits == 8u) warp_color_rows<8u, WarpElastic>(t, &tasks[ti], cr, src, out, tid, walk);
-        else warp_color_rows<16u, WarpElastic>(t, &tasks[ti], cr, src, out, tid, walk);
-    }
+    warp_color_tasks(WarpElastic(lds_grid, &lds_bad, fields), src, out, tasks, weights, n_tasks);
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)
@@ -219,31 +191,7 @@ debig_png_label_elastic_kernel(const uint8_t *__restrict__ src, uint8_t *__restr
     __shared__ int32_t lds_lut[256];
     __shared__ ElaNode lds_grid[ELA_GRID_MAX * ELA_GRID_MAX];
     __shared__ uint32_t lds_bad;
-    const uint32_t tid = threadIdx.x;
-    if (lut) lds_lut[tid & 255u] = lut[tid & 255u];
-    __syncthreads();
-    const int32_t *L = lut ? lds_lut : nullptr;
-    ElaHeld held = { 0u, 0u, 0u, false };
-    WarpElastic walk = { lds_grid };
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_label_elastic_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || (t.src_bytes != 1u && t.src_bytes != 2u) ||
-            t.dtype > 3u || (t.dtype == 0u && t.src_bytes == 2u) || (lut && t.src_bytes == 2u) || t.border_mode > WARP_BORDER_CLAMP ||
-            !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || (t.src_off & (t.src_bytes - 1u)) || !ela_task_ok(t))
-            continue;
-        if (!ela_hold_grid(lds_grid, &lds_bad, held, t, fields, tid)) continue;
-        if (t.src_bytes == 1u) {
-            if (t.dtype == 0u) warp_label_rows<1u, 1u, WarpElastic>(L, t, src, out, tid, walk);
-            else if (t.dtype == 1u) warp_label_rows<2u, 1u, WarpElastic>(L, t, src, out, tid, walk);
-            else if (t.dtype == 2u) warp_label_rows<4u, 1u, WarpElastic>(L, t, src, out, tid, walk);
-            else warp_label_rows<8u, 1u, WarpElastic>(L, t, src, out, tid, walk);
-        } else {
-            if (t.dtype == 1u) warp_label_rows<2u, 2u, WarpElastic>(L, t, src, out, tid, walk);
-            else if (t.dtype == 2u) warp_label_rows<4u, 2u, WarpElastic>(L, t, src, out, tid, walk);
-            else warp_label_rows<8u, 2u, WarpElastic>(L, t, src, out, tid, walk);
-        }
-    }
+    warp_label_tasks(WarpElastic(lds_grid, &lds_bad, fields), lds_lut, src, out, tasks, lut, n_tasks);
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)
@@ -254,33 +202,5 @@ debig_png_color_label_elastic_kernel(const uint8_t *__restrict__ src, uint8_t *_
     __shared__ uint2 lds_map[DEBIG_PNG_CMAP_MAX_SLOTS]; /* (key, value) per slot */
     __shared__ ElaNode lds_grid[ELA_GRID_MAX * ELA_GRID_MAX];
     __shared__ uint32_t lds_bad;
-    const uint2 *tab = lds_map;
-    const uint32_t tid = threadIdx.x;
-    ClblHeld held = { ~(uint64_t)0, 0u };
-    ElaHeld gheld = { 0u, 0u, 0u, false };
-    WarpElastic walk = { lds_grid };
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_color_label_elastic_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || t.dtype > 3u || t.mode > 1u ||
-            t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || !ela_task_ok(t))
-            continue;
-        if (t.mode == 0u ? t.dtype < 2u
-                         : (t.map_slots < 2u || t.map_slots > DEBIG_PNG_CMAP_MAX_SLOTS || (t.map_slots & (t.map_slots - 1u)) ||
-                            (t.map_off & 15u) || !unmatched))
-            continue;
-        if (!ela_hold_grid(lds_grid, &lds_bad, gheld, t, fields, tid)) continue;
-        if (t.mode == 0u) {
-            if (t.dtype == 2u) clbl_warp_rows<4u, false, WarpElastic>(tab, t, src, out, tid, walk);
-            else clbl_warp_rows<8u, false, WarpElastic>(tab, t, src, out, tid, walk);
-            continue;
-        }
-        clbl_hold_map(lds_map, held, t, tables, tid);
-        uint32_t m;
-        if (t.dtype == 0u) m = clbl_warp_rows<1u, true, WarpElastic>(tab, t, src, out, tid, walk);
-        else if (t.dtype == 1u) m = clbl_warp_rows<2u, true, WarpElastic>(tab, t, src, out, tid, walk);
-        else if (t.dtype == 2u) m = clbl_warp_rows<4u, true, WarpElastic>(tab, t, src, out, tid, walk);
-        else m = clbl_warp_rows<8u, true, WarpElastic>(tab, t, src, out, tid, walk);
-        clbl_add_misses(&unmatched[t.image], m, tid);
-    }
+    clbl_warp_tasks(WarpElastic(lds_grid, &lds_bad, fields), lds_map, src, out, tasks, tables, unmatched, n_tasks);
 }

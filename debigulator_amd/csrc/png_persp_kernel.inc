@@ -7,10 +7,11 @@
 // The arithmetic is fixed by decode_png.h: the numerators NU, NV are the affine U, V of the task's six int64 (below 2^48 in
 // magnitude), the denominator D = p0 cx + p1 cy + 2 p2 is Q31 and lies in [2^21, 2^33 - 1] on the whole output, and the source
 // position is U = floor(NU 2^31 / D) in Q17 (below 2^59 in magnitude), V likewise -- each by one floor division, one remainder and
-// one unsigned division, all in 64 bits (persp_div).  Everything behind (U, V) is the affine warp's, word for word: the row bodies
-// of png_warp_kernel.inc, png_color_kernel.inc and png_color_label_warp_kernel.inc are instantiated with the walk of this file
-// (WarpPersp), so picks, taps, weights, borders, the colour mix, the LUT in LDS, the table probe and the per-wavefront
-// `unmatched` add exist once.
+// one unsigned division, all in 64 bits (persp_div).  Everything around (U, V) is the affine warp's, word for word: the kernel bodies
+// of png_warp_kernel.inc, png_color_kernel.inc and png_color_label_warp_kernel.inc (warp_image_tasks, warp_color_tasks,
+// warp_label_tasks, clbl_warp_tasks) are instantiated with the map policy of this file (WarpPersp), so the task loop, the skips,
+// the ladders, the pixel walk, picks, taps, weights, borders, the colour mix, the LUT in LDS, the table probe and the
+// per-wavefront `unmatched` add exist once.
 //   - a TASK is the warp task of the kernel it mirrors, field for field, followed by int64 p[3]; tasks, workgroups and the lane
 //     mapping are the warp kernels' (one lane per output pixel, lanes along X and on into the next row, 256 lanes);
 //   - D is linear in X and Y, so its range over the out_w x out_h output is checked at the four corner pixels, once per task
@@ -48,64 +49,36 @@ DEV_INLINE bool persp_ok(const Task &t)
            d01 <= PERSP_D_MAX && d11 >= PERSP_D_MIN && d11 <= PERSP_D_MAX;
 }
 
-// the output pixels of one task as warp_walk hands them out, (U, V) through the division; the caller has checked persp_ok
-template <class Task, class Body>
-DEV_INLINE void persp_walk(const Task &t, uint32_t tid, Body body)
-{
-    const uint32_t n = t.rows * t.out_w;
-    StageWalk wk(tid, t.out_w, WARP_THREADS);
-    for (uint32_t i = tid; i < n; i += WARP_THREADS) {
-        const uint32_t X = wk.x, Y = t.row0 + wk.r;
-        const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
-        const int64_t D = t.p[0] * cx + t.p[1] * cy + 2 * t.p[2];
-        body(X, Y, persp_div(t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], D), persp_div(t.m[3] * cx + t.m[4] * cy + 2 * t.m[5], D));
-        wk.next();
-    }
-}
-
+// the projective map as the policy the kernel bodies take (png_warp_kernel.inc has the scheme): persp_ok among the skips, nothing
+// to hold, (U, V) through the division -- behind persp_ok, which the bodies have tested by then
 struct WarpPersp {
-    template <class Task, class Body>
-    static DEV_MEMBER_INLINE void walk(const Task &t, uint32_t tid, Body body) { persp_walk(t, tid, body); }
+    template <class Task>
+    static DEV_MEMBER_INLINE bool task_ok(const Task &t) { return persp_ok(t); }
+    template <class Task>
+    static DEV_MEMBER_INLINE bool hold(const Task &, uint32_t) { return true; }
+    template <class Task>
+    static DEV_MEMBER_INLINE void uv(const Task &t, uint32_t, uint32_t, int64_t cx, int64_t cy, int64_t &U, int64_t &V)
+    {
+        const int64_t D = t.p[0] * cx + t.p[1] * cy + 2 * t.p[2];
+        U = persp_div(warp_nu(t, cx, cy), D);
+        V = persp_div(warp_nv(t, cx, cy), D);
+    }
 };
 
-// ---- the four kernels: each is its warp twin with the walk replaced and persp_ok among the skips -------------------------------
+// ---- the four kernels: the body of each kind under the projective map -----------------------------------------------------------
 
 __global__ void __launch_bounds__(WARP_THREADS)
 debig_png_persp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, const debig_png_persp_task *__restrict__ tasks,
                        uint32_t n_tasks)
 {
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_persp_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || t.channels == 0u || t.channels > 4u ||
-            (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.filter != WARP_FILTER_BILINEAR && t.filter != WARP_FILTER_NEAREST) ||
-            t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
-            (t.src_off & ((uint32_t)t.bits / 8u - 1u)) || !persp_ok(t))
-            continue;
-        if (t.bits == 8u) warp_rows<8u, WarpPersp>(t, &tasks[ti], src, out, tid);
-        else warp_rows<16u, WarpPersp>(t, &tasks[ti], src, out, tid);
-    }
+    warp_image_tasks(WarpPersp(), src, out, tasks, n_tasks);
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)
 debig_png_persp_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
                              const debig_png_persp_color_task *__restrict__ tasks, const uint8_t *__restrict__ weights, uint32_t n_tasks)
 {
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_persp_color_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || (t.channels != 3u && t.channels != 4u) ||
-            (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.filter != WARP_FILTER_BILINEAR && t.filter != WARP_FILTER_NEAREST) ||
-            t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
-            (t.src_off & ((uint32_t)t.bits / 8u - 1u)) || (t.color_off & 7u) || !persp_ok(t))
-            continue;
-        const debig_png_color_rec cr = *reinterpret_cast<const debig_png_color_rec *>(weights + t.color_off);
-        if (!color_rec_ok(cr, t.bits)) continue;
-        if (t.bits == 8u) warp_color_rows<8u, WarpPersp>(t, &tasks[ti], cr, src, out, tid);
-        else warp_color_rows<16u, WarpPersp>(t, &tasks[ti], cr, src, out, tid);
-    }
+    warp_color_tasks(WarpPersp(), src, out, tasks, weights, n_tasks);
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)
@@ -113,28 +86,7 @@ debig_png_label_persp_kernel(const uint8_t *__restrict__ src, uint8_t *__restric
                              const debig_png_label_persp_task *__restrict__ tasks, const int32_t *__restrict__ lut, uint32_t n_tasks)
 {
     __shared__ int32_t lds_lut[256];
-    const uint32_t tid = threadIdx.x;
-    if (lut) lds_lut[tid & 255u] = lut[tid & 255u];
-    __syncthreads();
-    const int32_t *L = lut ? lds_lut : nullptr;
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_label_persp_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || (t.src_bytes != 1u && t.src_bytes != 2u) ||
-            t.dtype > 3u || (t.dtype == 0u && t.src_bytes == 2u) || (lut && t.src_bytes == 2u) || t.border_mode > WARP_BORDER_CLAMP ||
-            !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || (t.src_off & (t.src_bytes - 1u)) || !persp_ok(t))
-            continue;
-        if (t.src_bytes == 1u) {
-            if (t.dtype == 0u) warp_label_rows<1u, 1u, WarpPersp>(L, t, src, out, tid);
-            else if (t.dtype == 1u) warp_label_rows<2u, 1u, WarpPersp>(L, t, src, out, tid);
-            else if (t.dtype == 2u) warp_label_rows<4u, 1u, WarpPersp>(L, t, src, out, tid);
-            else warp_label_rows<8u, 1u, WarpPersp>(L, t, src, out, tid);
-        } else {
-            if (t.dtype == 1u) warp_label_rows<2u, 2u, WarpPersp>(L, t, src, out, tid);
-            else if (t.dtype == 2u) warp_label_rows<4u, 2u, WarpPersp>(L, t, src, out, tid);
-            else warp_label_rows<8u, 2u, WarpPersp>(L, t, src, out, tid);
-        }
-    }
+    warp_label_tasks(WarpPersp(), lds_lut, src, out, tasks, lut, n_tasks);
 }
 
 __global__ void __launch_bounds__(WARP_THREADS)
@@ -143,30 +95,5 @@ debig_png_color_label_persp_kernel(const uint8_t *__restrict__ src, uint8_t *__r
                                    uint32_t *__restrict__ unmatched, uint32_t n_tasks)
 {
     __shared__ uint2 lds_map[DEBIG_PNG_CMAP_MAX_SLOTS]; /* (key, value) per slot */
-    const uint2 *tab = lds_map;
-    const uint32_t tid = threadIdx.x;
-    ClblHeld held = { ~(uint64_t)0, 0u };
-    for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_color_label_persp_task t = tasks[ti];
-        // (uniform over the workgroup: every lane skips, or none)
-        if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || t.dtype > 3u || t.mode > 1u ||
-            t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || !persp_ok(t))
-            continue;
-        if (t.mode == 0u ? t.dtype < 2u
-                         : (t.map_slots < 2u || t.map_slots > DEBIG_PNG_CMAP_MAX_SLOTS || (t.map_slots & (t.map_slots - 1u)) ||
-                            (t.map_off & 15u) || !unmatched))
-            continue;
-        if (t.mode == 0u) {
-            if (t.dtype == 2u) clbl_warp_rows<4u, false, WarpPersp>(tab, t, src, out, tid);
-            else clbl_warp_rows<8u, false, WarpPersp>(tab, t, src, out, tid);
-            continue;
-        }
-        clbl_hold_map(lds_map, held, t, tables, tid);
-        uint32_t m;
-        if (t.dtype == 0u) m = clbl_warp_rows<1u, true, WarpPersp>(tab, t, src, out, tid);
-        else if (t.dtype == 1u) m = clbl_warp_rows<2u, true, WarpPersp>(tab, t, src, out, tid);
-        else if (t.dtype == 2u) m = clbl_warp_rows<4u, true, WarpPersp>(tab, t, src, out, tid);
-        else m = clbl_warp_rows<8u, true, WarpPersp>(tab, t, src, out, tid);
-        clbl_add_misses(&unmatched[t.image], m, tid);
-    }
+    clbl_warp_tasks(WarpPersp(), lds_map, src, out, tasks, tables, unmatched, n_tasks);
 }

@@ -16,7 +16,7 @@ struct StageWalk {
     uint32_t r, x, dr, dx, w;
     DEV_MEMBER_INLINE StageWalk(uint32_t tid, uint32_t w_, uint32_t threads)
         : r(tid / w_), x(tid - r * w_), dr(threads / w_), dx(threads - dr * w_), w(w_) {}
-    DEV_MEMBER_INLINE void next()
+    __device__ __forceinline__ void next() // (forced inline in the emulator build as well, which would otherwise export it)
     {
         r += dr;
         x += dx;

@@ -57,31 +57,59 @@ DEV_INLINE uint32_t warp_clamp(int64_t j, uint32_t cl, bool *inside)
     return (uint32_t)(j < 0 ? 0 : j >= (int64_t)cl ? (int64_t)cl - 1 : j);
 }
 
-// ---- what the four warp kernels share (this file, png_color_kernel.inc, png_color_label_warp_kernel.inc): they differ only in
-// what they do with a picked sample ----------------------------------------------------------------------------------------------
+// ---- what the twelve warp kernels share (this file, png_color_kernel.inc, png_color_label_warp_kernel.inc, png_persp_kernel.inc,
+// png_elastic_kernel.inc).  They are KIND x MAP: four kinds -- image (warp_image_tasks, here), image + colour matrix
+// (warp_color_tasks, png_color_kernel.inc), label (warp_label_tasks, here), colour label (clbl_warp_tasks,
+// png_color_label_warp_kernel.inc) -- which differ in what they do with a picked sample, under three maps, which differ in how
+// (U, V) comes about.  A kind's body is written once, as a template over the task type and the map; a __global__ kernel declares
+// its LDS and calls the body with its map, which the body takes BY VALUE (by reference the colour-label elastic kernel spilled
+// three more scalar registers; profiles/png_warp_maps_refactor.txt).
+//
+// A MAP POLICY provides three things and nothing else:
+//   task_ok(t)                     what the map adds to the bounds of a task (uniform over the workgroup); the bodies test it
+//                                  last in their first predicate
+//   hold(t, tid)                   the step in front of a task's walk, reached by every lane of the workgroup -> false: the task
+//                                  is skipped
+//   uv(t, X, Y, cx, cy, U, V)      the source position (U, V), Q17, of output pixel (X, Y) with centre (cx, cy) = (2X + 1, 2Y + 1)
+// WarpAffine (below) and WarpPersp (png_persp_kernel.inc) are empty types: their hold is `true`, so their kernels have no barrier,
+// no LDS and no branch of it.  WarpElastic (png_elastic_kernel.inc) carries the pointers to its grid in LDS and what it holds.
+// A new map is a fourth policy and four __global__ kernels of one call each; a new kind is one body and a kernel per map.
+
+// the affine numerators of one output pixel from the task's six int64: every map starts from them
+template <class Task>
+DEV_INLINE int64_t warp_nu(const Task &t, int64_t cx, int64_t cy) { return t.m[0] * cx + t.m[1] * cy + 2 * t.m[2]; }
+template <class Task>
+DEV_INLINE int64_t warp_nv(const Task &t, int64_t cx, int64_t cy) { return t.m[3] * cx + t.m[4] * cy + 2 * t.m[5]; }
+
+struct WarpAffine {
+    template <class Task>
+    static DEV_MEMBER_INLINE bool task_ok(const Task &) { return true; }
+    template <class Task>
+    static DEV_MEMBER_INLINE bool hold(const Task &, uint32_t) { return true; }
+    template <class Task>
+    static DEV_MEMBER_INLINE void uv(const Task &t, uint32_t, uint32_t, int64_t cx, int64_t cy, int64_t &U, int64_t &V)
+    {
+        U = warp_nu(t, cx, cy);
+        V = warp_nv(t, cx, cy);
+    }
+};
 
 // the output pixels of one task, lanes along X and on into the next row of the run: body(X, Y, U, V) per pixel, (U, V) the
-// source position of its centre in Q17
-template <class Task, class Body>
-DEV_INLINE void warp_walk(const Task &t, uint32_t tid, Body body)
+// source position of its centre in Q17 under the map.  The ONE pixel loop of the family
+template <class Map, class Task, class Body>
+DEV_INLINE void warp_walk(const Map &map, const Task &t, uint32_t tid, Body body)
 {
     const uint32_t n = t.rows * t.out_w;
     StageWalk wk(tid, t.out_w, WARP_THREADS);
     for (uint32_t i = tid; i < n; i += WARP_THREADS) {
         const uint32_t X = wk.x, Y = t.row0 + wk.r;
         const int64_t cx = 2 * (int64_t)X + 1, cy = 2 * (int64_t)Y + 1;
-        body(X, Y, t.m[0] * cx + t.m[1] * cy + 2 * t.m[2], t.m[3] * cx + t.m[4] * cy + 2 * t.m[5]);
+        int64_t U, V;
+        map.uv(t, X, Y, cx, cy, U, V);
+        body(X, Y, U, V);
         wk.next();
     }
 }
-
-// the affine walk as the policy the row bodies below take (png_persp_kernel.inc has the projective one).  The bodies take the
-// walk as an OBJECT, their last argument: these two have no state and are default-constructed, png_elastic_kernel.inc's carries
-// the pointer to its grid in LDS
-struct WarpAffine {
-    template <class Task, class Body>
-    static DEV_MEMBER_INLINE void walk(const Task &t, uint32_t tid, Body body) { warp_walk(t, tid, body); }
-};
 
 // the NEAREST pick of (U, V): the pixel (jx, jy), clamped into the crop, and whether its sample counts -- under CLAMP always,
 // under CONSTANT when the pick lay inside (else the border value takes its place, by a select).  clamp: the task's border mode
@@ -138,17 +166,17 @@ DEV_INLINE WarpTaps warp_taps(const Task &t, bool clamp, int64_t U, int64_t V)
     return q;
 }
 
-// the rows of one task at source precision P, its pixels and their (U, V) from Walk
-template <uint32_t P, class Walk, class Task>
-DEV_INLINE void warp_rows(const Task &t, const Task *__restrict__ tg, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-                          uint32_t tid, const Walk &walk = Walk())
+// the rows of one task at source precision P, its pixels and their (U, V) from the map
+template <uint32_t P, class Map, class Task>
+DEV_INLINE void warp_rows(const Map &map, const Task &t, const Task *__restrict__ tg, const uint8_t *__restrict__ src,
+                          uint8_t *__restrict__ out, uint32_t tid)
 {
     typedef typename RszSample<P>::sample_t sample_t;
     const sample_t *s = reinterpret_cast<const sample_t *>(src + t.src_off);
     uint8_t *o = out + t.out_off;
     const uint32_t ch = t.channels;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP, nearest = t.filter == WARP_FILTER_NEAREST;
-    walk.walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    warp_walk(map, t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const uint64_t el = (uint64_t)X * t.out_sx + (uint64_t)Y * t.out_sy;
         if (nearest) {
             const WarpPick p = warp_pick(t, clamp, U, V);
@@ -166,34 +194,43 @@ DEV_INLINE void warp_rows(const Task &t, const Task *__restrict__ tg, const uint
     });
 }
 
-__global__ void __launch_bounds__(WARP_THREADS)
-debig_png_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, const debig_png_warp_task *__restrict__ tasks,
-                      uint32_t n_tasks)
+// the image kind: the task loop of debig_png_warp_kernel, _persp_kernel and _elastic_kernel
+template <class Task, class Map>
+DEV_INLINE void warp_image_tasks(Map map, const uint8_t *__restrict__ src, uint8_t *__restrict__ out, const Task *__restrict__ tasks,
+                                 uint32_t n_tasks)
 {
     const uint32_t tid = threadIdx.x;
     for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_warp_task t = tasks[ti];
+        const Task t = tasks[ti];
         // (uniform over the workgroup: every lane skips, or none)
         if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || t.channels == 0u || t.channels > 4u ||
             (t.bits != 8u && t.bits != 16u) || t.dtype > 3u || (t.filter != WARP_FILTER_BILINEAR && t.filter != WARP_FILTER_NEAREST) ||
             t.border_mode > WARP_BORDER_CLAMP || !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) ||
-            (t.src_off & ((uint32_t)t.bits / 8u - 1u)))
+            (t.src_off & ((uint32_t)t.bits / 8u - 1u)) || !map.task_ok(t))
             continue;
-        if (t.bits == 8u) warp_rows<8u, WarpAffine>(t, &tasks[ti], src, out, tid);
-        else warp_rows<16u, WarpAffine>(t, &tasks[ti], src, out, tid);
+        if (!map.hold(t, tid)) continue;
+        if (t.bits == 8u) warp_rows<8u>(map, t, &tasks[ti], src, out, tid);
+        else warp_rows<16u>(map, t, &tasks[ti], src, out, tid);
     }
+}
+
+__global__ void __launch_bounds__(WARP_THREADS)
+debig_png_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, const debig_png_warp_task *__restrict__ tasks,
+                      uint32_t n_tasks)
+{
+    warp_image_tasks(WarpAffine(), src, out, tasks, n_tasks);
 }
 
 // ---- the same warp of raw labels: nearest only, the picks of the image kernel's NEAREST filter ---------------------------------
 
 // the rows of one task: elements of ES bytes, source labels of SB bytes
-template <uint32_t ES, uint32_t SB, class Walk, class Task>
-DEV_INLINE void warp_label_rows(const int32_t *lut, const Task &t, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-                                uint32_t tid, const Walk &walk = Walk())
+template <uint32_t ES, uint32_t SB, class Map, class Task>
+DEV_INLINE void warp_label_rows(const Map &map, const int32_t *lut, const Task &t, const uint8_t *__restrict__ src,
+                                uint8_t *__restrict__ out, uint32_t tid)
 {
     const uint8_t *s0 = src + t.src_off;
     const bool clamp = t.border_mode == WARP_BORDER_CLAMP;
-    walk.walk(t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
+    warp_walk(map, t, tid, [&](uint32_t X, uint32_t Y, int64_t U, int64_t V) {
         const WarpPick p = warp_pick(t, clamp, U, V);
         const uint64_t at = (uint64_t)p.jy * t.src_pitch + p.jx;
         uint32_t v = SB == 1u ? (uint32_t)s0[at] : (uint32_t)reinterpret_cast<const uint16_t *>(s0)[at];
@@ -203,31 +240,41 @@ DEV_INLINE void warp_label_rows(const int32_t *lut, const Task &t, const uint8_t
     });
 }
 
-__global__ void __launch_bounds__(WARP_THREADS)
-debig_png_label_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-                            const debig_png_label_warp_task *__restrict__ tasks, const int32_t *__restrict__ lut, uint32_t n_tasks)
+// the label kind: the task loop of debig_png_label_warp_kernel, _label_persp_kernel and _label_elastic_kernel; lds_lut: 256 words
+// of LDS that the kernel owns
+template <class Task, class Map>
+DEV_INLINE void warp_label_tasks(Map map, int32_t *lds_lut, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                                 const Task *__restrict__ tasks, const int32_t *__restrict__ lut, uint32_t n_tasks)
 {
-    __shared__ int32_t lds_lut[256];
     const uint32_t tid = threadIdx.x;
     if (lut) lds_lut[tid & 255u] = lut[tid & 255u];
     __syncthreads();
     const int32_t *L = lut ? lds_lut : nullptr;
     for (uint32_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
-        const debig_png_label_warp_task t = tasks[ti];
+        const Task t = tasks[ti];
         // (uniform over the workgroup: every lane skips, or none)
         if (!warp_sizes_ok(t.out_w, t.out_h, t.row0, t.rows, t.crop_w, t.crop_h) || (t.src_bytes != 1u && t.src_bytes != 2u) ||
             t.dtype > 3u || (t.dtype == 0u && t.src_bytes == 2u) || (lut && t.src_bytes == 2u) || t.border_mode > WARP_BORDER_CLAMP ||
-            !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || (t.src_off & (t.src_bytes - 1u)))
+            !warp_matrix_ok(t.m[0], t.m[1], t.m[2], t.m[3], t.m[4], t.m[5]) || (t.src_off & (t.src_bytes - 1u)) || !map.task_ok(t))
             continue;
+        if (!map.hold(t, tid)) continue;
         if (t.src_bytes == 1u) {
-            if (t.dtype == 0u) warp_label_rows<1u, 1u, WarpAffine>(L, t, src, out, tid);
-            else if (t.dtype == 1u) warp_label_rows<2u, 1u, WarpAffine>(L, t, src, out, tid);
-            else if (t.dtype == 2u) warp_label_rows<4u, 1u, WarpAffine>(L, t, src, out, tid);
-            else warp_label_rows<8u, 1u, WarpAffine>(L, t, src, out, tid);
+            if (t.dtype == 0u) warp_label_rows<1u, 1u>(map, L, t, src, out, tid);
+            else if (t.dtype == 1u) warp_label_rows<2u, 1u>(map, L, t, src, out, tid);
+            else if (t.dtype == 2u) warp_label_rows<4u, 1u>(map, L, t, src, out, tid);
+            else warp_label_rows<8u, 1u>(map, L, t, src, out, tid);
         } else {
-            if (t.dtype == 1u) warp_label_rows<2u, 2u, WarpAffine>(L, t, src, out, tid);
-            else if (t.dtype == 2u) warp_label_rows<4u, 2u, WarpAffine>(L, t, src, out, tid);
-            else warp_label_rows<8u, 2u, WarpAffine>(L, t, src, out, tid);
+            if (t.dtype == 1u) warp_label_rows<2u, 2u>(map, L, t, src, out, tid);
+            else if (t.dtype == 2u) warp_label_rows<4u, 2u>(map, L, t, src, out, tid);
+            else warp_label_rows<8u, 2u>(map, L, t, src, out, tid);
         }
     }
+}
+
+__global__ void __launch_bounds__(WARP_THREADS)
+debig_png_label_warp_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+                            const debig_png_label_warp_task *__restrict__ tasks, const int32_t *__restrict__ lut, uint32_t n_tasks)
+{
+    __shared__ int32_t lds_lut[256];
+    warp_label_tasks(WarpAffine(), lds_lut, src, out, tasks, lut, n_tasks);
 }

@@ -37,6 +37,10 @@ KERNELS = {
     "png_tone_apply": (IN, OUT, TASKS, IN, IN),
     "png_blur": (IN, OUT, TASKS, IN),
 }
+# the warp kernels under the other two maps: a persp kernel has the buffers of its warp twin, an elastic kernel its twin's and the fields
+for _w in ("png_warp", "png_warp_color", "png_label_warp", "png_color_label_warp"):
+    KERNELS[_w.replace("warp", "persp")] = KERNELS[_w]
+    KERNELS[_w.replace("warp", "elastic")] = KERNELS[_w] + (IN,)
 backend = "emu"
 record = None  # a list: every launch appends (kernel name, the task array, n_tasks, grid), for tests that assert what ran
 SLACK, GUARD = 64, 0xA5

@@ -1,6 +1,6 @@
 """The four kernels of the perspective warp (csrc/png_persp_kernel.inc) on the CPU lock-step emulator, BIT FOR BIT against the
 numpy restatement tests/png_persp_ref.py.  The runners, sources, crops, output sizes, arenas and sentinels are those of the warp
-batteries (test_emu_png_warp, test_emu_png_color, test_emu_png_color_labels_warp): tests/persp_launch.py extends their tasks by p[]
+batteries (test_emu_png_warp, test_emu_png_color, test_emu_png_color_labels_warp): tests/map_launch.py extends their tasks by p[]
 and launches the persp twin, so the shapes are the smallest at which these kernels go wrong --
   * crops of 1 x 1, 1 x 9 and 13 x 7 inside a larger image at odd arena offsets; output widths 1, 7, 64, 65 and 257; task runs that
     do not divide out_h; fewer workgroups than tasks; channels 1 - 4, P = 8 / 16, all dtypes, both layouts, filters and borders;
@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import persp_launch as PL  # noqa: E402
+import map_launch as PL  # noqa: E402
 import png_label_ref as LR  # noqa: E402
 import png_persp_ref as PR  # noqa: E402
 import png_resize_ref as Z  # noqa: E402

@@ -1,6 +1,8 @@
-"""The fourteen tensor-stage launchers whose kernels loop over their tasks (include/debig_hip.h: debig_hip_apng_composite_batch,
+"""The twenty-two tensor-stage launchers whose kernels loop over their tasks (include/debig_hip.h: debig_hip_apng_composite_batch,
 debig_hip_png_resize / _resize_alpha / _resize_cubic / _resize_color / _label_gather / _color_label / _warp / _warp_color /
-_label_warp / _color_label_warp / _tone_hist / _tone_apply / _blur _batch) called DIRECTLY on the MI355X, with fewer workgroups than
+_label_warp / _color_label_warp / _tone_hist / _tone_apply / _blur _batch, and the four warp launchers again under the projective
+and the elastic map: _persp / _persp_color / _label_persp / _color_label_persp, _elastic / _elastic_color / _label_elastic /
+_color_label_elastic) called DIRECTLY on the MI355X, with fewer workgroups than
 tasks (DEBIG_STAGE_GRID) and with tiles and runs the host never cuts.  The whole-call tests give every workgroup exactly one task,
 so the top-of-task barriers, the tables and counters the kernels keep in LDS from one task to the next and the task shapes beyond
 the host's otherwise run on the CPU emulator only, which runs one workgroup at a time and knows nothing of the machine's memory
@@ -9,8 +11,12 @@ model.
   * test_battery runs the emulator batteries (tests/test_emu_png_*.py, tests/test_emu_apng.py) as they are -- the same run*() /
     _check() / check() functions, shapes, grids and BIT FOR BIT comparisons with the numpy restatements (png_resize_ref,
     png_alpha_ref, png_filter_ref, png_color_ref, png_warp_ref, png_label_ref, png_color_label_ref, png_color_label_warp_ref,
-    png_tone_ref, png_blur_ref, apng_ref) -- with the launch seam tests/stage_launch.py switched to the product library.  Nothing
-    is compared with the emulator's output; the emulator library is neither built nor loaded.
+    png_tone_ref, png_blur_ref, png_persp_ref, png_elastic_ref, apng_ref) -- with the launch seam tests/stage_launch.py switched to the product library.  Nothing
+    is compared with the emulator's output; the emulator library is neither built nor loaded.  The persp and elastic batteries
+    (MAPPED) go through the runners of the warp batteries (tests/map_launch.py); every case of theirs outside FULL_GRID must have
+    launched with fewer workgroups than tasks, and the elastic battery has one workgroup alternate between two files' fields.
+    Their cases are collected in tests/test_gpu_png_persp_kernels.py and tests/test_gpu_png_elastic_kernels.py, under the ids they
+    have had since they were written; tables, sets and assertions are this file's (MODULES, EXCLUDED, ..., run_case).
   * the *_kept_and_replaced cases order the tasks so that one workgroup both keeps a table for the next task and replaces it, and
     assert from the task list that it does; test_tone_hist_flat_beside_noisy_in_one_workgroup is about the histogram counters of
     all four wavefronts; test_blur_other_tiles_through_few_workgroups joins other tiles than the host's with few workgroups.
@@ -52,7 +58,10 @@ MODULES = {
     "test_emu_png_color_labels_warp": {"png_color_label_warp"},
     "test_emu_png_tone": {"png_tone_hist", "png_tone_apply"},
     "test_emu_png_blur": {"png_blur"},
+    "test_emu_png_persp": {"png_persp", "png_persp_color", "png_label_persp", "png_color_label_persp"},
+    "test_emu_png_elastic": {"png_elastic", "png_elastic_color", "png_label_elastic", "png_color_label_elastic"},
 }
+MAPPED = ("test_emu_png_persp", "test_emu_png_elastic")
 BOUND = "hands the kernel tasks that break a bound on purpose"
 ASAN = "the emulator under ASan in a child process: no GPU code"
 INDEX = "debig_hip_png_spec_defilter_index_batch: one workgroup per task, no task loop"
@@ -73,13 +82,25 @@ EXCLUDED = {
     "test_emu_png_tone::test_tasks_that_break_a_bound_are_skipped": BOUND,
     "test_emu_png_blur::test_tasks_that_break_a_bound_are_skipped": BOUND,
     "test_emu_png_blur::test_the_remaining_bounds": BOUND + " (its tasks within the bounds: test_blur_tasks_at_the_limits)",
+    "test_emu_png_persp::test_tasks_that_break_a_bound_are_skipped": BOUND,
+    "test_emu_png_elastic::test_tasks_that_break_a_bound_are_skipped": BOUND,
     "test_emu_png_labels::test_index_defilter_every_label_format": INDEX,
     "test_emu_png_labels::test_index_defilter_every_filter_type_and_widths_1_to_70": INDEX,
     "test_emu_png_labels::test_index_past_the_palette_and_other_colour_types_fail_the_task": INDEX,
 }
 # tests of a module's own sources and of the restatement: they launch nothing, here as there
 NO_LAUNCH = {"test_emu_png_blur::test_the_sources_take_every_path_of_the_rule", "test_emu_png_tone::test_the_sources_take_every_path_of_the_rule",
-             "test_emu_png_warp::test_the_special_matrices_hit_what_they_are_for"}
+             "test_emu_png_warp::test_the_special_matrices_hit_what_they_are_for",
+             "test_emu_png_persp::test_the_special_matrices_hit_what_they_are_for", "test_emu_png_elastic::test_the_special_fields_hit_what_they_are_for"}
+# the cases of the MAPPED batteries whose launches all start one workgroup per task
+FULL_GRID = {"test_emu_png_persp::test_numerators_near_2_48_over_the_smallest_denominator",
+             "test_emu_png_persp::test_far_positions_are_border_or_an_edge_pixel",
+             "test_emu_png_persp::test_uint_bilinear_against_the_rounded_float64_map",
+             "test_emu_png_persp::test_the_label_pick_is_the_image_nearest_pick", "test_emu_png_elastic::test_the_label_pick_is_the_image_nearest_pick"}
+# the cases that compare with the OUTPUT of the warp kernels launch those as well
+WARPS = {"png_warp", "png_warp_color", "png_label_warp", "png_color_label_warp"}
+ALSO_WARP = {"test_emu_png_persp::test_affine_matrices_give_the_output_of_the_warp_kernels": WARPS,
+             "test_emu_png_elastic::test_no_field_and_zeros_give_the_output_of_the_warp_kernels": WARPS}
 
 
 def _battery_tests():
@@ -108,14 +129,18 @@ def _word(v):
     return "x".join(_word(e) for e in v) if isinstance(v, (tuple, list)) else str(v)
 
 
-def _cases():
+def _cases(mods=None):
+    """the cases of the modules `mods` (default: all of MODULES).  The cases of a MAPPED module keep the ids they have always had,
+    the bare test name, in tests/test_gpu_png_persp_kernels.py and tests/test_gpu_png_elastic_kernels.py, which hold nothing else"""
     out = []
     for key, fn in _battery_tests().items():
-        if key in EXCLUDED:
+        mod = key.split("::")[0]
+        if key in EXCLUDED or mod not in (MODULES if mods is None else mods):
             continue
+        stem = key.split("::test_")[1] if mod in MAPPED else key.replace("test_emu_", "").replace("::test_", ":")
         for kw in _param_sets(fn):
             assert set(kw) == set(inspect.signature(fn).parameters), (key, "an argument that no parametrize mark gives")
-            out.append(pytest.param(key, kw, id=key.replace("test_emu_", "").replace("::test_", ":") + "".join("-" + _word(v) for v in kw.values())))
+            out.append(pytest.param(key, kw, id=stem + "".join("-" + _word(v) for v in kw.values())))
     return out
 
 
@@ -134,17 +159,24 @@ def test_every_battery_case_runs_or_is_excluded():
     assert ran | set(EXCLUDED) == set(tests) and not ran & set(EXCLUDED)
     assert all(EXCLUDED[k] for k in EXCLUDED) and NO_LAUNCH <= ran
     # every launcher of the header belongs to a module whose cases run
-    assert set().union(*MODULES.values()) == set(SL.KERNELS) and len(SL.KERNELS) == 14
+    assert set().union(*MODULES.values()) == set(SL.KERNELS) and len(SL.KERNELS) == 22
     for mod in MODULES:
-        assert any(k.startswith(mod + "::") for k in ran), mod
+        assert sum(k.startswith(mod + "::") for k in ran) >= (10 if mod in MAPPED else 1), mod
 
 
-@pytest.mark.parametrize("key,kw", _cases())
-def test_battery(key, kw, on_the_gpu):
+def run_case(key, kw, on_the_gpu):
     _battery_tests()[key](**kw)
+    mod = key.split("::")[0]
     names = {r[0] for r in on_the_gpu}
-    assert names <= MODULES[key.split("::")[0]]
-    assert bool(names) != (key in NO_LAUNCH), (key, "no launch reached the GPU")
+    assert names <= MODULES[mod] | ALSO_WARP.get(key, set())
+    assert bool(names & MODULES[mod]) != (key in NO_LAUNCH), (key, "no launch reached the GPU")
+    if mod in MAPPED and key not in NO_LAUNCH | FULL_GRID:
+        assert any(0 < g < n for k, _, n, g in on_the_gpu if k in MODULES[mod]), (key, "no launch with fewer workgroups than tasks")
+
+
+@pytest.mark.parametrize("key,kw", _cases([m for m in MODULES if m not in MAPPED]))
+def test_battery(key, kw, on_the_gpu):
+    run_case(key, kw, on_the_gpu)
 
 
 # ---- tables and counters held from one task to the next ------------------------------------------------------------------------

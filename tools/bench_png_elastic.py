@@ -51,7 +51,7 @@ def fields(api, out, zeros=False):
 def kernels_alone(api, out, reps, warmup):
     """-> [(pair name, tasks, elastic [ms], warp [ms], copy [ms])]"""
     import torch
-    import elastic_launch as EL
+    import map_launch as EL
     import png_elastic_ref as ER
     import png_warp_ref as WR
     from test_emu_png_color import ColorRec, WarpColorTask
@@ -109,8 +109,8 @@ def kernels_alone(api, out, reps, warmup):
         def elastic(zeros):
             buf, offs = EL.fields_buffer([ER.quantise_field(f) for f in fields(api, out, zeros)], lead=0)
             d_fields = torch.from_numpy(buf.copy()).cuda()
-            d_tasks = torch.from_numpy(np.frombuffer(bytes(EL.extend(warp_tasks, n, offs, GRID)), np.uint8).copy()).cuda()
-            return launcher(EL.TWIN[name], d_tasks, o1, (d_fields.data_ptr(),)), (d_fields, d_tasks)
+            d_tasks = torch.from_numpy(np.frombuffer(bytes(EL.extend(warp_tasks, n, EL.ElasticTail, EL.elastic_fill(offs, GRID))[0]), np.uint8).copy()).cuda()
+            return launcher(EL.TWIN["elastic"][name], d_tasks, o1, (d_fields.data_ptr(),)), (d_fields, d_tasks)
 
         warp = launcher(name, d_warp, o2)
         go, keep = elastic(True)
@@ -121,7 +121,7 @@ def kernels_alone(api, out, reps, warmup):
         go, keep = elastic(False)
         o3 = torch.empty_like(o1)
         te, tw, tc = B._events([go, warp, lambda: o3.copy_(o1)], 4 * reps, warmup)
-        rows.append((EL.TWIN[name] + " / " + name, n, te, tw, tc))
+        rows.append((EL.TWIN["elastic"][name] + " / " + name, n, te, tw, tc))
     return rows
 
 

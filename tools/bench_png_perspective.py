@@ -114,7 +114,7 @@ def _events(fns, reps, warmup):
 def kernels_alone(api, out, reps, warmup):
     """-> [(pair name, tasks, persp [ms], warp [ms], copy [ms])]"""
     import torch
-    import persp_launch as PL
+    import map_launch as PL
     import png_warp_ref as WR
     from test_emu_png_color import ColorRec, WarpColorTask
     from test_emu_png_color_labels_warp import ColorLabelWarpTask
@@ -147,7 +147,7 @@ def kernels_alone(api, out, reps, warmup):
                 tasks.append(t)
         n = len(tasks)
         warp_tasks = (T * n)(*tasks)
-        persp_tasks = PL.extend(warp_tasks, n, [(0, 0, 1 << 30)] * N_FILES)
+        persp_tasks, _ = PL.extend(warp_tasks, n, PL.PerspTail, PL.persp_fill([(0, 0, 1 << 30)] * N_FILES))
         d_warp = torch.from_numpy(np.frombuffer(bytes(warp_tasks), np.uint8).copy()).cuda()
         d_persp = torch.from_numpy(np.frombuffer(bytes(persp_tasks), np.uint8).copy()).cuda()
         src = torch.randint(0, CLASSES if ch == 1 else 256, (N_FILES * SIDE * SIDE * ch,), dtype=torch.uint8, device="cuda")
@@ -170,9 +170,9 @@ def kernels_alone(api, out, reps, warmup):
             return go
 
         o3 = torch.empty_like(o1)
-        tp, tw, tc = _events([launcher(PL.TWIN[name], d_persp, o1), launcher(name, d_warp, o2), lambda: o3.copy_(o1)], 4 * reps, warmup)
+        tp, tw, tc = _events([launcher(PL.TWIN["persp"][name], d_persp, o1), launcher(name, d_warp, o2), lambda: o3.copy_(o1)], 4 * reps, warmup)
         assert torch.equal(o1, o2), (name, "row 2 = (0, 0, 1) must give the warp kernel's bytes")
-        rows.append((PL.TWIN[name] + " / " + name, n, tp, tw, tc))
+        rows.append((PL.TWIN["persp"][name] + " / " + name, n, tp, tw, tc))
     return rows
 
 
