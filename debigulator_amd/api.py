@@ -1119,6 +1119,65 @@ def png_decode_batch_tensor(datas, size, mode="rgb", depth=8, dtype="float32", l
     return [int(s) for s in status], out, [_info_dict(i) for i in infos]
 
 
+PNG_LABEL_STATS_MAX_IDS = 1024  # include/decode_png.h: DEBIG_PNG_LABEL_STATS_MAX_IDS
+
+
+def _png_stats_ids(num_ids):
+    """the num_ids of png_label_stats and of the decode calls' stats= (None: no statistics) -> the int, or ValueError"""
+    if num_ids is None:
+        return None
+    if isinstance(num_ids, bool) or not isinstance(num_ids, (int, np.integer)) or not 1 <= int(num_ids) <= PNG_LABEL_STATS_MAX_IDS:
+        raise ValueError(f"num_ids must be an integer in 1 .. {PNG_LABEL_STATS_MAX_IDS}, not {num_ids!r}")
+    return int(num_ids)
+
+
+def png_label_stats(labels, num_ids, status=None):
+    """per-id pixel counts and bounding boxes of a dense (N, H, W) label tensor on the GPU (include/decode_png.h:
+    debig_png_label_stats, which has the rule) -> a numpy int64 array (N, num_ids + 1, 5) of (count, x0, y0, x1, y1): record
+    k < num_ids for the elements equal to k, record num_ids ("other") for every element that is negative or >= num_ids (a border
+    label of -1, an ignore value of 255, a packed colour); the box is [x0, x1) x [y0, y1) in output pixels, an id that does not
+    occur has five zeros.  labels: a contiguous tensor of torch.uint8, uint16 (or int16, read as the uint16 bits, which is how
+    the label calls hand out uint16), int32 or int64 on the current device -- the tensor of png_decode_batch_labels /
+    png_decode_batch_color_labels under any of their maps, or one made otherwise.  num_ids: 1 .. 1024.  status: None, or one
+    entry per image: the records of an image whose entry is not 0 stay zero.  One kernel launch reads the tensor once; the call
+    waits for the work queued on the device before it, and for its own."""
+    import torch
+
+    num_ids = _png_stats_ids(num_ids)
+    if num_ids is None:
+        raise ValueError("num_ids must be an integer")
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be a (N, H, W) tensor")
+    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = 1
+    if labels.dtype not in codes:
+        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
+    if not labels.is_contiguous():
+        raise ValueError("labels must be contiguous")
+    if labels.device.type != "cuda":
+        raise ValueError("labels must be on the GPU")
+    n, H, W = (int(v) for v in labels.shape)
+    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
+    if status is not None and len(status) != n:
+        raise ValueError("status needs one entry per image")
+    out = np.zeros((n, num_ids + 1, 5), np.uint32)
+    if n == 0:
+        return out.astype(np.int64)
+    L = _png_spec_lib()
+    _png_device(L, labels.device)
+    L.debig_png_label_stats.restype = C.c_int
+    L.debig_png_label_stats.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p]
+    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
+    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
+    rc = L.debig_png_label_stats(labels.data_ptr(), n, W, H, codes[labels.dtype], num_ids, st, out.ctypes.data)
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"debig_png_label_stats rejected its arguments ({rc})")
+    N.check(rc, "debig_png_label_stats")
+    return out.astype(np.int64)
+
+
 class PngLabelDesc(C.Structure):  # include/decode_png.h: debig_png_label_desc
     _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("dtype", C.c_uint32), ("reserved", C.c_uint32),
                 ("lut", C.POINTER(C.c_int32))]
@@ -1167,7 +1226,7 @@ def png_label_warp_desc(border="constant", border_label=None, dtype="int64"):
 
 
 def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fill=None, device="cuda:0", warp=None,
-                            border="constant", border_label=None, perspective=None, elastic=None):
+                            border="constant", border_label=None, perspective=None, elastic=None, stats=None):
     """bytes of N label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_labels) -> (statuses, tensor, infos).  The label of a pixel is its palette index (colour type 3)
     or its raw grey sample (colour type 0, 1 to 16 bits): nothing is scaled, PLTE colours and tRNS are ignored.  size =
@@ -1189,9 +1248,13 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     elastic (by name; the last parameter): None, or one entry per file: None or a (grid_h, grid_w, 2) displacement field, as
     png_decode_batch_tensor(elastic=) takes it -- debig_png_decode_batch_labels_elastic: the pick is that call's filter="nearest"
     under the same matrix and field.  It goes with warp; without warp each file takes png_warp_matrix((crop_w, crop_h), size).  With
-    perspective: ValueError.  A bad node: status 16."""
+    perspective: ValueError.  A bad node: status 16.
+    stats (by name; the last parameter): None (everything above, the return value included), or num_ids: the call runs
+    png_label_stats(tensor, num_ids, statuses) on the tensor it has just written and returns (statuses, tensor, infos, records);
+    the tensor is the one of the same call without stats."""
     import torch
 
+    _png_stats_ids(stats)
     if perspective is not None and warp is not None:
         raise ValueError("perspective and warp exclude each other")
     if elastic is not None:
@@ -1238,7 +1301,8 @@ def png_decode_batch_labels(datas, size, dtype="int64", boxes=None, lut=None, fi
     if rc == PNG_BAD_ARG:
         raise ValueError(f"debig_png_decode_batch_labels rejected its arguments ({rc})")
     N.check(rc, "debig_png_decode_batch_labels")
-    return [int(s) for s in status], out, [_info_dict(i) for i in infos]
+    res = [int(s) for s in status], out, [_info_dict(i) for i in infos]
+    return res if stats is None else res + (png_label_stats(out, stats, res[0]),)
 
 
 class PngColorMap(C.Structure):  # include/decode_png.h: debig_png_color_map
@@ -1316,7 +1380,7 @@ def png_color_label_desc(size, colors=None, missing=-1, dtype="int64", n=None):
 
 
 def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="int64", boxes=None, fill=None, device="cuda:0",
-                                  perspective=None, elastic=None, warp=None, border="constant", border_label=None):
+                                  perspective=None, elastic=None, stats=None, warp=None, border="constant", border_label=None):
     """bytes of N colour-coded label PNGs -> ONE dense (N, H, W) integer tensor on the GPU (include/decode_png.h:
     debig_png_decode_batch_color_labels) -> (statuses, tensor, infos, unmatched).  The colour of a pixel is what
     png_decode_batch(mode="rgb") gives for it (palette files through PLTE, grey replicated, alpha and tRNS dropped), packed as
@@ -1341,9 +1405,14 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     entry per file: None or a (grid_h, grid_w, 2) displacement field, as png_decode_batch_tensor(elastic=) takes it --
     debig_png_decode_batch_color_labels_elastic: the same pick as that call's filter="nearest" and
     png_decode_batch_labels(elastic=); border, border_label and unmatched as for warp.  It goes with warp; without warp each
-    file takes png_warp_matrix((crop_w, crop_h), size).  With perspective: ValueError.  A bad node: status 16."""
+    file takes png_warp_matrix((crop_w, crop_h), size).  With perspective: ValueError.  A bad node: status 16.
+    stats (by name; it stands behind `elastic`, so `warp`, `border` and `border_label` stay the last three): None (everything
+    above, the return value included), or num_ids: the call runs png_label_stats(tensor, num_ids, statuses) on the tensor it has
+    just written and returns (statuses, tensor, infos, unmatched, records).  Under a map, record "other" of an image counts its `missing` elements (when missing is no id below num_ids) and
+    the border picks alike; packed colours (colors=None) are ids like any other, so most of them are "other"."""
     import torch
 
+    _png_stats_ids(stats)
     if perspective is not None and warp is not None:
         raise ValueError("perspective and warp exclude each other")
     if elastic is not None:
@@ -1393,7 +1462,8 @@ def png_decode_batch_color_labels(datas, size, colors=None, missing=-1, dtype="i
     if rc == PNG_BAD_ARG:
         raise ValueError(f"debig_png_decode_batch_color_labels rejected its arguments ({rc})")
     N.check(rc, "debig_png_decode_batch_color_labels")
-    return [int(s) for s in status], out, [_info_dict(i) for i in infos], [int(u) for u in unmatched]
+    res = [int(s) for s in status], out, [_info_dict(i) for i in infos], [int(u) for u in unmatched]
+    return res if stats is None else res + (png_label_stats(out, stats, res[0]),)
 
 
 class ApngFrame(C.Structure):  # include/decode_png.h: debig_apng_frame

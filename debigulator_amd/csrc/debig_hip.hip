@@ -26,6 +26,7 @@
 #include "png_elastic_kernel.inc"
 #include "png_tone_kernel.inc"
 #include "png_blur_kernel.inc"
+#include "png_label_stats_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -967,6 +968,15 @@ int debig_hip_png_blur_batch(const void *d_src, void *d_out, const debig_png_blu
 {
     return launch_stage(debig_png_blur_kernel, BLUR_THREADS, n_tasks, hip_stream, (const uint8_t *)d_src, (uint8_t *)d_out, d_tasks,
                         (const uint8_t *)d_tables);
+}
+
+// per-id counts and bounding boxes of a dense label tensor (png_label_stats_kernel.inc): one workgroup per row run, as many
+// workgroups as tasks; d_stats is cleared by the caller
+int debig_hip_png_label_stats_batch(const void *d_labels, void *d_stats, const debig_png_label_stats_task *d_tasks, uint32_t n_tasks,
+                                    void *hip_stream)
+{
+    return launch_stage(debig_png_label_stats_kernel, LST_THREADS, n_tasks, hip_stream, (const uint8_t *)d_labels, (uint8_t *)d_stats,
+                        d_tasks);
 }
 
 // inflate -> de-filter in one kernel (png_fused_kernel.inc).  Per group of at most SPLIT_GROUP

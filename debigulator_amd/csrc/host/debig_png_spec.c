@@ -1902,6 +1902,70 @@ done:
     return rc;
 }
 
+/* ---- debig_png_label_stats: per-id counts and bounding boxes of a dense label tensor (decode_png.h) -------------------------- */
+
+_Static_assert(sizeof(debig_png_label_stat) == 20 && sizeof(debig_png_label_box) == 20 && sizeof(debig_png_label_stats_task) == 40,
+               "the raw record is five uint32, and so is the public one");
+
+DEBIG_API void debig_png_label_stat_box(const uint32_t raw[5], uint32_t out_w, uint32_t out_h, debig_png_label_box *box)
+{
+    memset(box, 0, sizeof *box);
+    if (raw[0] == 0) return; /* the id does not occur: the extremes of an empty record mean nothing */
+    box->count = raw[0];
+    box->x0 = out_w - raw[3];
+    box->y0 = out_h - raw[4];
+    box->x1 = raw[1];
+    box->y1 = raw[2];
+}
+
+DEBIG_API int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype, uint32_t n_ids,
+                                    const uint32_t *status, debig_png_label_box *out)
+{
+    if (n == 0) return 0;
+    if (!d_labels || !out || dtype > DEBIG_PNG_L_I64 || n_ids == 0 || n_ids > DEBIG_PNG_LABEL_STATS_MAX_IDS || out_w == 0 ||
+        out_w > 16384u || out_h == 0 || out_h > 16384u || ((uintptr_t)d_labels & ((1u << dtype) - 1u)))
+        return DEBIG_PNG_BAD_ARG;
+    const uint32_t es = 1u << dtype, recs = n_ids + 1u;
+    const uint32_t run = out_w >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / out_w, per = (out_h + run - 1u) / run;
+    uint64_t n_good = 0;
+    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
+    if (n_good * per >= 0x7fffffffu) return 2;
+    memset(out, 0, (size_t)n * recs * sizeof *out);
+    if (n_good == 0) return 0;
+    int rc = 2;
+    debig_png_label_stats_task *tasks = (debig_png_label_stats_task *)malloc((size_t)(n_good * per) * sizeof *tasks);
+    dev_table tab[1] = {{NULL, (uint64_t)n * recs * sizeof(debig_png_label_stat), 0}}; /* the raw records: space only */
+    uint32_t *raw = (uint32_t *)malloc((size_t)tab[0].bytes);
+    uint64_t n_tasks = 0;
+    if (!tasks || !raw) goto done;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status && status[i] != 0) continue;
+        for (uint32_t y0 = 0; y0 < out_h; y0 += run) {
+            debig_png_label_stats_task *t = &tasks[n_tasks++];
+            t->label_off = ((uint64_t)i * out_h + y0) * out_w * es;
+            t->stat_off = (uint64_t)i * recs * sizeof(debig_png_label_stat);
+            t->out_w = out_w;
+            t->out_h = out_h;
+            t->row0 = y0;
+            t->rows = out_h - y0 < run ? out_h - y0 : run;
+            t->n_ids = n_ids;
+            t->dtype = dtype;
+        }
+    }
+    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, tab, 1, &rc);
+    if (!c) goto done;
+    if ((rc = debig_hip_memset(c->rsz_weights.ptr, 0, tab[0].bytes, NULL)) ||
+        (rc = debig_hip_png_label_stats_batch(d_labels, c->rsz_weights.ptr, (const debig_png_label_stats_task *)c->rsz_tasks.ptr,
+                                              (uint32_t)n_tasks, NULL)) ||
+        (rc = debig_hip_memcpy_d2h(raw, c->rsz_weights.ptr, tab[0].bytes, NULL)) || (rc = debig_hip_stream_sync(NULL)))
+        goto done;
+    for (uint64_t k = 0; k < (uint64_t)n * recs; k++) debig_png_label_stat_box(raw + 5u * k, out_w, out_h, &out[k]);
+done:
+    free(tasks);
+    free(raw);
+    return rc;
+}
+
 /* ---- the affine warp of the tensor and the label decode (decode_png.h) ------------------------------------------------------ */
 
 #define WARP_TASK_PIXELS 4096u /* output pixels of one warp task (a run of whole rows; one row when it is wider): 16 per lane */

@@ -203,7 +203,7 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
 /* DEBIG_STAGE_GRID (environment variable, read at every call; tests): the launchers below whose kernels loop over their
  * tasks -- debig_hip_apng_composite_batch, debig_hip_png_resize_batch / _resize_alpha / _resize_cubic / _resize_color,
  * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp,
- * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply and _blur --
+ * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur and _label_stats --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -922,6 +922,36 @@ typedef struct debig_png_blur_task {
 } debig_png_blur_task;
 int debig_hip_png_blur_batch(const void *d_src, void *d_out, const debig_png_blur_task *d_tasks, const void *d_tables,
                              uint32_t n_tasks, void *hip_stream);
+
+/* ---- per-id pixel counts and bounding boxes of a dense label tensor (csrc/png_label_stats_kernel.inc, behind
+ * debig_png_label_stats in decode_png.h, which has the rule).  An image of out_w x out_h elements has n_ids + 1 RAW records, 20
+ * bytes each, at stat_off in d_stats: record k < n_ids for the elements equal to k, record n_ids ("other") for every element that
+ * is negative or >= n_ids (an int64 is compared whole: 2^32 + 3 is "other", not 3).  Every field of a raw record only grows, by an
+ * add or a max, and all zeros is the empty record: the caller clears d_stats before the launch, no kernel initialises it, and a
+ * second launch over other rows of the image accumulates into the same records.  One TASK is a run of whole rows of one image,
+ * contiguous in the dense tensor, for one workgroup of 256 lanes; integer adds and maxima commute, so the records do not depend on
+ * the grid, the order of the tasks or where the runs are cut.
+ * A task is skipped when dtype is above 3, n_ids is 0 or above DEBIG_PNG_LABEL_STATS_MAX_IDS, out_w or out_h is 0 or above 16384,
+ * rows is 0 or row0 + rows exceeds out_h, stat_off is not a multiple of 4, or label_off is not a multiple of the element size. */
+#define DEBIG_PNG_LABEL_STATS_MAX_IDS 1024u
+#define DEBIG_PNG_LABEL_STATS_RUN 16384u /* elements of a task as the host cuts them (the gather kernels' unit)                   */
+typedef struct debig_png_label_stat {
+    uint32_t count;         /* elements of the id                                                                              */
+    uint32_t x_end;         /* max x + 1                                                                                       */
+    uint32_t y_end;         /* max y + 1                                                                                       */
+    uint32_t x_rev;         /* out_w - min x                                                                                   */
+    uint32_t y_rev;         /* out_h - min y                                                                                   */
+} debig_png_label_stat;
+typedef struct debig_png_label_stats_task {
+    uint64_t label_off;     /* the run's first element (row row0, x 0), in bytes rel. to d_labels                              */
+    uint64_t stat_off;      /* the image's n_ids + 1 raw records, in bytes rel. to d_stats                                     */
+    uint32_t out_w, out_h;  /* the image                                                                                       */
+    uint32_t row0, rows;    /* the run                                                                                         */
+    uint32_t n_ids;
+    uint32_t dtype;         /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                         */
+} debig_png_label_stats_task;
+int debig_hip_png_label_stats_batch(const void *d_labels, void *d_stats, const debig_png_label_stats_task *d_tasks, uint32_t n_tasks,
+                                    void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

@@ -865,6 +865,34 @@ int debig_png_decode_batch_color_labels_elastic(const uint8_t *const *inputs, co
         const debig_png_color_label_desc *desc, const debig_png_label_warp_desc *warp_desc,
         const debig_png_elastic *elastics, const debig_png_elastic_desc *elastic_desc);
 
+/* ---- per-id pixel counts and bounding boxes of a label tensor -----------------------------------------------------------------------
+ * What a detection, instance or panoptic loader reads off the mask after the crop and the warp: which ids are left, how many
+ * pixels each keeps, and each id's tight box.  d_labels is a dense (n, out_h, out_w) tensor of DEBIG_PNG_L_* elements in device
+ * memory -- what debig_png_decode_batch_labels, debig_png_decode_batch_color_labels and their _warp / _persp / _elastic forms
+ * write, or any other tensor of that shape; how it was made does not matter.
+ * THE RULE.  Image i has n_ids + 1 records, out[i * (n_ids + 1) + k]:
+ *   - record k < n_ids covers the elements equal to k;
+ *   - record n_ids ("other") covers every element that is negative or >= n_ids: a border label or `missing` of -1, an ignore
+ *     value of 255, an int64 such as 2^32 + 3 (elements are compared whole, never truncated);
+ *   - count is the number of elements covered, [x0, x1) x [y0, y1) their tight box in output pixels;
+ *   - an id that does not occur has all five fields 0, and so has every record of an image whose status[i] != 0 (the files
+ *     the decode calls left out; status NULL: no image is left out).
+ * All fields are exact integers, and integer sums and maxima do not depend on order: the result is the same whatever the launch.
+ * On the device a record is kept RAW (debig_hip.h: debig_png_label_stat), in a form whose empty state is all zeros and whose every
+ * update is an add or a max; debig_png_label_stat_box converts one raw record of an out_w x out_h image.
+ * n == 0: returns 0 and touches nothing.  DEBIG_PNG_BAD_ARG, with out unwritten, for d_labels or out NULL with n > 0, d_labels
+ * not aligned to the element size, n_ids 0 or above DEBIG_PNG_LABEL_STATS_MAX_IDS, dtype above DEBIG_PNG_L_I64, out_w or out_h 0
+ * or above 16384.  The call cuts row runs of 16384 elements, clears the raw records, launches once
+ * (debig_hip_png_label_stats_batch) and copies them back; it is synchronous on the library's stream, like the decode calls, and
+ * the caller makes sure that whoever wrote d_labels on another stream has finished.  Otherwise 0 or an error code of the device
+ * layer.  Not thread safe against the tensor decodes of the same process (it uses their arenas). */
+#define DEBIG_PNG_LABEL_STATS_MAX_IDS 1024u
+typedef struct debig_png_label_box { uint32_t count, x0, y0, x1, y1; } debig_png_label_box;
+/* raw: the five uint32 of one debig_png_label_stat (count, x_end, y_end, x_rev, y_rev) */
+void debig_png_label_stat_box(const uint32_t raw[5], uint32_t out_w, uint32_t out_h, debig_png_label_box *box);
+int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype, uint32_t n_ids,
+                          const uint32_t *status /* host, may be NULL */, debig_png_label_box *out /* host, n * (n_ids + 1) */);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

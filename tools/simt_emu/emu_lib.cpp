@@ -27,6 +27,7 @@
 #include "../../debigulator_amd/csrc/png_elastic_kernel.inc"
 #include "../../debigulator_amd/csrc/png_tone_kernel.inc"
 #include "../../debigulator_amd/csrc/png_blur_kernel.inc"
+#include "../../debigulator_amd/csrc/png_label_stats_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
@@ -565,5 +566,15 @@ extern "C" int emu_png_blur_batch(const void *src, void *out, const debig_png_bl
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_blur_kernel, grid, BLUR_THREADS, (const uint8_t *)src, (uint8_t *)out, tasks, (const uint8_t *)tables, n);
+    return 0;
+}
+
+/* per-id counts and bounding boxes of a dense label tensor (png_label_stats_kernel.inc), as debig_hip_png_label_stats_batch launches
+ * it (stats: the raw records, cleared by the caller; grid as above) */
+extern "C" int emu_png_label_stats_batch(const void *labels, void *stats, const debig_png_label_stats_task *tasks, uint32_t n,
+                                         uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_stats_kernel, grid, LST_THREADS, (const uint8_t *)labels, (uint8_t *)stats, tasks, n);
     return 0;
 }
