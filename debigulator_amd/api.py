@@ -1178,6 +1178,94 @@ def png_label_stats(labels, num_ids, status=None):
     return out.astype(np.int64)
 
 
+PNG_LABEL_BOUNDARY_MAX_RADIUS = 16  # include/decode_png.h: DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS
+_PNG_BOUNDARY_SHAPES = {"square": 0, "diamond": 1, "disk": 2}  # DEBIG_PNG_BOUNDARY_*
+_PNG_BOUNDARY_MODES = {"ring": 0, "edge": 1}
+
+
+def _png_boundary_shape(radius, shape):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= PNG_LABEL_BOUNDARY_MAX_RADIUS:
+        raise ValueError(f"radius must be an integer in 1 .. {PNG_LABEL_BOUNDARY_MAX_RADIUS}, not {radius!r}")
+    if not isinstance(shape, str) or shape not in _PNG_BOUNDARY_SHAPES:
+        raise ValueError(f"shape must be one of {sorted(_PNG_BOUNDARY_SHAPES)}, not {shape!r}")
+    return int(radius), _PNG_BOUNDARY_SHAPES[shape]
+
+
+def png_label_boundary_reach(radius, shape="square"):
+    """the reach table of a boundary shape (include/decode_png.h: debig_png_label_boundary_reach) -> [reach[0], ..., reach[radius]]:
+    the half-width of the window at a row distance of d.  "square": radius (Chebyshev ball), "diamond": radius - d (L1 ball),
+    "disk": isqrt(radius^2 - d^2) (Euclidean ball)."""
+    radius, code = _png_boundary_shape(radius, shape)
+    L = _png_spec_lib()
+    L.debig_png_label_boundary_reach.restype = None
+    L.debig_png_label_boundary_reach.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+    table = (C.c_uint8 * 17)()
+    L.debig_png_label_boundary_reach(radius, code, table)
+    return [int(v) for v in table[: radius + 1]]
+
+
+def png_label_boundary(labels, radius=1, shape="square", mode="ring", value=255, status=None):
+    """boundary bands of a dense (N, H, W) label tensor on the GPU (include/decode_png.h: debig_png_label_boundary, which has the
+    rule) -> a NEW device tensor: Pascal-VOC-style void rings, trimaps, edge targets.  An element is a boundary element iff an
+    element of the image at (x + dx, y + dy) with |dy| <= radius and |dx| <= reach[|dy|] (png_label_boundary_reach) differs from
+    it: both sides of an edge are marked, the window is clipped at the image, elements are compared whole (exact for packed
+    colours and int64 ids).  mode="ring": boundary ? value : the element, in the dtype of the input (value must fit it; it may equal
+    an id); mode="edge": a uint8 tensor of 1 / 0.  labels: a contiguous tensor of torch.uint8, uint16 (or int16, read as the uint16
+    bits, value in 0 .. 65535, returned as int16), int32 or int64 on the current device -- the tensor of png_decode_batch_labels /
+    png_decode_batch_color_labels under any of their maps, or one made otherwise.  A ring cannot be carried through a warp, so the
+    documented use is labels -> png_label_boundary -> png_label_stats: decode (and warp) first, make the ring from the tensor that
+    came back, then take the statistics, where a ring value of 255 counts as "other".  radius: 1 .. 16; shape: "square", "diamond"
+    or "disk".  status: None, or one entry per image: an image whose entry is not 0 is not looked at and comes back as its input
+    under "ring", as zeros under "edge".  One kernel launch reads the tensor once and writes the result once; the call waits for
+    the work queued on the device before it, and for its own."""
+    import torch
+
+    radius, shape_code = _png_boundary_shape(radius, shape)
+    if not isinstance(mode, str) or mode not in _PNG_BOUNDARY_MODES:
+        raise ValueError(f"mode must be one of {sorted(_PNG_BOUNDARY_MODES)}, not {mode!r}")
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be a (N, H, W) tensor")
+    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = 1
+    if labels.dtype not in codes:
+        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
+    code = codes[labels.dtype]
+    if mode == "ring":
+        lo, hi = [(0, 255), (0, 65535), (-2 ** 31, 2 ** 31 - 1), (-2 ** 63, 2 ** 63 - 1)][code]
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+            raise ValueError(f"value must be an integer in {lo} .. {hi} for {labels.dtype}, not {value!r}")
+    if not labels.is_contiguous():
+        raise ValueError("labels must be contiguous")
+    if labels.device.type != "cuda":
+        raise ValueError("labels must be on the GPU")
+    n, H, W = (int(v) for v in labels.shape)
+    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
+    if status is not None and len(status) != n:
+        raise ValueError("status needs one entry per image")
+    out = torch.empty((n, H, W), dtype=torch.uint8 if mode == "edge" else labels.dtype, device=labels.device)
+    if n == 0:
+        return out
+    L = _png_spec_lib()
+    _png_device(L, labels.device)
+    L.debig_png_label_boundary.restype = C.c_int
+    L.debig_png_label_boundary.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_int64, C.c_void_p]
+    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
+    for i in ([] if status is None else [i for i in range(n) if st[i] != 0]):  # the images the library leaves alone, and only they
+        if mode == "edge":
+            out[i].zero_()
+        else:
+            out[i].copy_(labels[i])
+    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
+    rc = L.debig_png_label_boundary(labels.data_ptr(), out.data_ptr(), n, W, H, code, radius, shape_code, _PNG_BOUNDARY_MODES[mode],
+                                    int(value) if mode == "ring" else 0, st)
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"debig_png_label_boundary rejected its arguments ({rc})")
+    N.check(rc, "debig_png_label_boundary")
+    return out
+
+
 class PngLabelDesc(C.Structure):  # include/decode_png.h: debig_png_label_desc
     _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("dtype", C.c_uint32), ("reserved", C.c_uint32),
                 ("lut", C.POINTER(C.c_int32))]

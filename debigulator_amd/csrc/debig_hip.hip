@@ -27,6 +27,7 @@
 #include "png_tone_kernel.inc"
 #include "png_blur_kernel.inc"
 #include "png_label_stats_kernel.inc"
+#include "png_label_boundary_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -976,6 +977,14 @@ int debig_hip_png_label_stats_batch(const void *d_labels, void *d_stats, const d
                                     void *hip_stream)
 {
     return launch_stage(debig_png_label_stats_kernel, LST_THREADS, n_tasks, hip_stream, (const uint8_t *)d_labels, (uint8_t *)d_stats,
+                        d_tasks);
+}
+
+// boundary bands of a dense label tensor (png_label_boundary_kernel.inc): one workgroup per tile, as many workgroups as tasks
+int debig_hip_png_label_boundary_batch(const void *d_labels, void *d_out, const debig_png_label_boundary_task *d_tasks, uint32_t n_tasks,
+                                       void *hip_stream)
+{
+    return launch_stage(debig_png_label_boundary_kernel, LBD_THREADS, n_tasks, hip_stream, (const uint8_t *)d_labels, (uint8_t *)d_out,
                         d_tasks);
 }
 

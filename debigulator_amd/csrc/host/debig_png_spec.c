@@ -1966,6 +1966,93 @@ done:
     return rc;
 }
 
+/* ---- debig_png_label_boundary: ignore rings and edge maps of a dense label tensor (decode_png.h) -------------------------------- */
+
+_Static_assert(sizeof(debig_png_label_boundary_task) == 80 && offsetof(debig_png_label_boundary_task, reach) == 60,
+               "three 64-bit fields, nine uint32, the reach table, padded to a multiple of 8");
+
+DEBIG_API void debig_png_label_boundary_reach(uint32_t radius, uint32_t shape, uint8_t reach[17])
+{
+    memset(reach, 0, 17);
+    if (radius > DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS || shape > DEBIG_PNG_BOUNDARY_DISK) return;
+    for (uint32_t d = 0; d <= radius; d++) {
+        uint32_t v = radius;
+        if (shape == DEBIG_PNG_BOUNDARY_DIAMOND) v = radius - d;
+        if (shape == DEBIG_PNG_BOUNDARY_DISK) /* the largest v with v * v + d * d <= radius * radius */
+            while (v * v + d * d > radius * radius) v--;
+        reach[d] = (uint8_t)v;
+    }
+}
+
+/* the tile of the call: the largest of 128 x 64, 64 x 64, 64 x 32, 32 x 32 whose planes fit the kernel's LDS */
+static void boundary_tile(uint32_t dtype, uint32_t radius, uint32_t *tw, uint32_t *th)
+{
+    *tw = 128u;
+    *th = 64u;
+    while (DEBIG_PNG_LABEL_BOUNDARY_TILE_BYTES(*tw, *th, dtype, radius) > DEBIG_PNG_LABEL_BOUNDARY_LDS_BYTES) {
+        if (*tw > *th) *tw /= 2u;
+        else *th /= 2u;
+    }
+}
+
+DEBIG_API int debig_png_label_boundary(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
+                                       uint32_t radius, uint32_t shape, uint32_t mode, int64_t value, const uint32_t *status)
+{
+    if (n == 0) return 0;
+    if (!d_labels || !d_out || dtype > DEBIG_PNG_L_I64 || radius == 0 || radius > DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS ||
+        shape > DEBIG_PNG_BOUNDARY_DISK || mode > DEBIG_PNG_BOUNDARY_EDGE || out_w == 0 || out_w > 16384u || out_h == 0 || out_h > 16384u)
+        return DEBIG_PNG_BAD_ARG;
+    const uint32_t es = 1u << dtype, os = mode == DEBIG_PNG_BOUNDARY_RING ? es : 1u;
+    if (((uintptr_t)d_labels & (es - 1u)) || ((uintptr_t)d_out & (os - 1u))) return DEBIG_PNG_BAD_ARG;
+    if (mode == DEBIG_PNG_BOUNDARY_RING &&
+        ((dtype == DEBIG_PNG_L_U8 && (value < 0 || value > 255)) || (dtype == DEBIG_PNG_L_U16 && (value < 0 || value > 65535)) ||
+         (dtype == DEBIG_PNG_L_I32 && (value < INT32_MIN || value > INT32_MAX))))
+        return DEBIG_PNG_BAD_ARG;
+    const uint64_t img = (uint64_t)out_w * out_h, in_bytes = (uint64_t)n * img * es, out_bytes = (uint64_t)n * img * os;
+    if ((uintptr_t)d_out < (uintptr_t)d_labels + in_bytes && (uintptr_t)d_labels < (uintptr_t)d_out + out_bytes) return DEBIG_PNG_BAD_ARG;
+    uint32_t tw, th;
+    boundary_tile(dtype, radius, &tw, &th);
+    const uint64_t per = (uint64_t)((out_w + tw - 1u) / tw) * ((out_h + th - 1u) / th);
+    uint64_t n_good = 0;
+    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
+    if (n_good * per >= 0x7fffffffu) return 2;
+    if (n_good == 0) return 0;
+    int rc = 2;
+    debig_png_label_boundary_task *tasks = (debig_png_label_boundary_task *)calloc((size_t)(n_good * per), sizeof *tasks);
+    dev_table tab[1] = {{NULL, 0, 0}}; /* no tables */
+    uint64_t n_tasks = 0;
+    if (!tasks) goto done;
+    for (uint32_t i = 0; i < n; i++) {
+        if (status && status[i] != 0) continue;
+        for (uint32_t y0 = 0; y0 < out_h; y0 += th)
+            for (uint32_t x0 = 0; x0 < out_w; x0 += tw) {
+                debig_png_label_boundary_task *t = &tasks[n_tasks++];
+                t->label_off = (uint64_t)i * img * es;
+                t->out_off = (uint64_t)i * img * os;
+                t->value = value;
+                t->w = out_w;
+                t->h = out_h;
+                t->x0 = x0;
+                t->y0 = y0;
+                t->tile_w = out_w - x0 < tw ? out_w - x0 : tw;
+                t->tile_h = out_h - y0 < th ? out_h - y0 : th;
+                t->dtype = dtype;
+                t->mode = mode;
+                t->radius = radius;
+                debig_png_label_boundary_reach(radius, shape, t->reach);
+            }
+    }
+    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, tab, 1, &rc);
+    if (!c) goto done;
+    if ((rc = debig_hip_png_label_boundary_batch(d_labels, d_out, (const debig_png_label_boundary_task *)c->rsz_tasks.ptr, (uint32_t)n_tasks,
+                                                 NULL)))
+        goto done;
+    rc = debig_hip_stream_sync(NULL);
+done:
+    free(tasks);
+    return rc;
+}
+
 /* ---- the affine warp of the tensor and the label decode (decode_png.h) ------------------------------------------------------ */
 
 #define WARP_TASK_PIXELS 4096u /* output pixels of one warp task (a run of whole rows; one row when it is wider): 16 per lane */

@@ -203,7 +203,8 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
 /* DEBIG_STAGE_GRID (environment variable, read at every call; tests): the launchers below whose kernels loop over their
  * tasks -- debig_hip_apng_composite_batch, debig_hip_png_resize_batch / _resize_alpha / _resize_cubic / _resize_color,
  * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp,
- * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur and _label_stats --
+ * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur, _label_stats and
+ * _label_boundary --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -952,6 +953,42 @@ typedef struct debig_png_label_stats_task {
 } debig_png_label_stats_task;
 int debig_hip_png_label_stats_batch(const void *d_labels, void *d_stats, const debig_png_label_stats_task *d_tasks, uint32_t n_tasks,
                                     void *hip_stream);
+
+/* ---- boundary bands of a dense label tensor: ignore rings and edge maps (csrc/png_label_boundary_kernel.inc, behind
+ * debig_png_label_boundary in decode_png.h, which has the rule).  Element (x, y) of an image of w x h elements is a BOUNDARY element
+ * iff an element at (x + dx, y + dy) with |dy| <= radius, |dx| <= reach[|dy|], inside the image, differs from it (elements are
+ * compared whole).  mode 0 (RING) writes `boundary ? value : the element` in the dtype of the input, mode 1 (EDGE) one byte 1 / 0.
+ * One TASK is a tile of one image for one workgroup of 256 lanes, which stages the tile and a halo of `radius` elements in LDS:
+ * the output is a pure function of the input, whatever the tiling, the grid and the order of the tasks.  d_out must not overlap
+ * d_labels (a tile reads what its neighbours write).  The kernel takes the reach table as it is and knows nothing about shapes.
+ * A task is skipped when dtype is above 3, mode above 1, radius 0 or above DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS, a reach entry
+ * 0 .. radius exceeds the radius, w or h is 0 or above 16384, tile_w or tile_h is 0 or above DEBIG_PNG_LABEL_BOUNDARY_MAX_TILE or
+ * the tile leaves the image, the two staged planes exceed DEBIG_PNG_LABEL_BOUNDARY_LDS_BYTES (DEBIG_PNG_LABEL_BOUNDARY_TILE_BYTES
+ * of the largest window; a tile of 32 x 32 fits for every dtype and radius), `value` is outside the dtype under RING, or an offset
+ * or address is not a multiple of the element size (of 1 for the output of EDGE). */
+#define DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS 16u
+#define DEBIG_PNG_LABEL_BOUNDARY_MAX_TILE 128u      /* columns and rows of a tile                                                */
+#define DEBIG_PNG_LABEL_BOUNDARY_LDS_BYTES 40960u   /* the value plane and the dist plane of one task                            */
+typedef struct debig_png_label_boundary_task {
+    uint64_t label_off;     /* the image's first element, in bytes rel. to d_labels                                            */
+    uint64_t out_off;       /* the image's first output element, in bytes rel. to d_out                                        */
+    int64_t value;          /* RING: what a boundary element becomes                                                           */
+    uint32_t w, h;          /* the image                                                                                       */
+    uint32_t x0, y0, tile_w, tile_h; /* the tile                                                                               */
+    uint32_t dtype;         /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                         */
+    uint32_t mode;          /* 0 RING, 1 EDGE                                                                                  */
+    uint32_t radius;        /* 1 .. 16                                                                                         */
+    uint8_t reach[17];      /* reach[d], d = 0 .. radius: the half-width of the window at a row distance of d                  */
+    uint8_t reserved[3];
+} debig_png_label_boundary_task;
+/* the LDS bytes a tile of tile_w x tile_h elements of 1 << dtype bytes takes at most (a window that no image edge clips):
+ * rows x (pitch + dpitch), pitch = ((tile_w + 2 radius) * es + 30) & ~15, dpitch = (pitch / es + 15) & ~15 */
+#define DEBIG_PNG_LABEL_BOUNDARY_TILE_BYTES(tile_w, tile_h, dtype, radius)                                                         \
+    (((tile_h) + 2u * (radius)) *                                                                                                  \
+     ((((((tile_w) + 2u * (radius)) << (dtype)) + 30u) & ~15u) +                                                                   \
+      ((((((((tile_w) + 2u * (radius)) << (dtype)) + 30u) & ~15u) >> (dtype)) + 15u) & ~15u)))
+int debig_hip_png_label_boundary_batch(const void *d_labels, void *d_out, const debig_png_label_boundary_task *d_tasks, uint32_t n_tasks,
+                                       void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

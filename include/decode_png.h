@@ -893,6 +893,46 @@ void debig_png_label_stat_box(const uint32_t raw[5], uint32_t out_w, uint32_t ou
 int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype, uint32_t n_ids,
                           const uint32_t *status /* host, may be NULL */, debig_png_label_box *out /* host, n * (n_ids + 1) */);
 
+/* ---- boundary bands of a label tensor: ignore rings, trimaps, edge targets ------------------------------------------------------------
+ * Pascal-VOC-style void rings around every object, DeepLab trimaps, boundary targets, the U-Net border emphasis.  A ring cannot be
+ * carried through a warp (a nearest-picked ring of width 1 or 2 is torn by rotation, doubled by magnification, lost under
+ * shrinking), so it is made from the warped map: d_labels is a dense (n, out_h, out_w) tensor of DEBIG_PNG_L_* elements in device
+ * memory, as for debig_png_label_stats -- what any of the label calls wrote, or a tensor made otherwise.
+ * THE RULE.  A shape of radius r (1 .. 16) is its REACH TABLE reach[0 .. r], a half-width per row distance
+ * (debig_png_label_boundary_reach):
+ *   - DEBIG_PNG_BOUNDARY_SQUARE:  reach[d] = r                  (Chebyshev ball; 8-connected at r = 1)
+ *   - DEBIG_PNG_BOUNDARY_DIAMOND: reach[d] = r - d              (L1 ball; 4-connected at r = 1: scikit-image's find_boundaries default)
+ *   - DEBIG_PNG_BOUNDARY_DISK:    reach[d] = isqrt(r*r - d*d)   (Euclidean ball, integer square root)
+ * Element (x, y) is a BOUNDARY element iff there is a dy with |dy| <= r and 0 <= y + dy < out_h and a dx with |dx| <= reach[|dy|]
+ * and 0 <= x + dx < out_w such that the element at (x + dx, y + dy) differs from the element at (x, y).  Elements are compared
+ * whole (3 and 2^32 + 3 differ); positions outside the image never make a boundary (the window is clipped, not padded); the rule
+ * is symmetric, so both sides of an edge are marked (find_boundaries(mode="thick")); it equals "min != max over the clipped
+ * footprint".
+ *   - DEBIG_PNG_BOUNDARY_RING: out = boundary ? value : in, in the dtype of the input; `value` must be representable in it (it may
+ *     equal an existing id);
+ *   - DEBIG_PNG_BOUNDARY_EDGE: out = boundary ? 1 : 0, a dense uint8 (n, out_h, out_w).
+ * The result is a pure function of the input.  The slot in d_out of an image whose status[i] != 0 is not written (status NULL: no
+ * image is left out).  n == 0: returns 0 and touches nothing.  DEBIG_PNG_BAD_ARG, before any device work, for d_labels or d_out
+ * NULL with n > 0 or not aligned to their element size, radius 0 or above 16, shape above DISK, mode above EDGE, dtype above
+ * DEBIG_PNG_L_I64, out_w or out_h 0 or above 16384, a `value` outside the dtype under RING, and d_out's byte range overlapping
+ * d_labels's (neighbouring tiles read what others write: in place is not defined).  The call cuts every image into tiles (32 x 32,
+ * or larger where dtype and radius allow), launches once (debig_hip_png_label_boundary_batch) and is synchronous on the
+ * library's stream, like debig_png_label_stats; the caller makes sure that whoever wrote d_labels on another stream has finished.
+ * Otherwise 0 or an error code of the device layer.  Not thread safe against the tensor decodes of the same process (it uses
+ * their arenas).  Not provided: a "transparent" value that never forms a boundary, inner- or outer-only bands, distance maps,
+ * radii above 16, in-place operation, host tensors. */
+#define DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS 16u
+#define DEBIG_PNG_BOUNDARY_SQUARE 0u
+#define DEBIG_PNG_BOUNDARY_DIAMOND 1u
+#define DEBIG_PNG_BOUNDARY_DISK 2u
+#define DEBIG_PNG_BOUNDARY_RING 0u
+#define DEBIG_PNG_BOUNDARY_EDGE 1u
+/* reach[0 .. radius] of the shape, the entries behind them 0; host only, integers only.  radius above 16 or an unknown shape:
+ * seventeen zeros */
+void debig_png_label_boundary_reach(uint32_t radius, uint32_t shape, uint8_t reach[17]);
+int debig_png_label_boundary(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
+                             uint32_t radius, uint32_t shape, uint32_t mode, int64_t value, const uint32_t *status /* host, may be NULL */);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

@@ -28,6 +28,7 @@
 #include "../../debigulator_amd/csrc/png_tone_kernel.inc"
 #include "../../debigulator_amd/csrc/png_blur_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_stats_kernel.inc"
+#include "../../debigulator_amd/csrc/png_label_boundary_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
@@ -576,5 +577,15 @@ extern "C" int emu_png_label_stats_batch(const void *labels, void *stats, const 
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_label_stats_kernel, grid, LST_THREADS, (const uint8_t *)labels, (uint8_t *)stats, tasks, n);
+    return 0;
+}
+
+/* boundary bands of a dense label tensor (png_label_boundary_kernel.inc), as debig_hip_png_label_boundary_batch launches it (grid as
+ * above) */
+extern "C" int emu_png_label_boundary_batch(const void *labels, void *out, const debig_png_label_boundary_task *tasks, uint32_t n,
+                                            uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_boundary_kernel, grid, LBD_THREADS, (const uint8_t *)labels, (uint8_t *)out, tasks, n);
     return 0;
 }
