@@ -1266,6 +1266,71 @@ def png_label_boundary(labels, radius=1, shape="square", mode="ring", value=255,
     return out
 
 
+PNG_LABEL_DISTANCE_MAX_CAP = 32767  # include/decode_png.h: DEBIG_PNG_LABEL_DISTANCE_MAX_CAP
+_PNG_DISTANCE_FORMATS = {"squared": 0, "root": 1}  # DEBIG_PNG_DISTANCE_SQUARED / _ROOT
+
+
+def png_label_distance(labels, to=None, cap=None, out="squared", status=None):
+    """exact Euclidean distance maps of a dense (N, H, W) label tensor on the GPU (include/decode_png.h: debig_png_label_distance,
+    which has the rule) -> a NEW device tensor: what scipy.ndimage.distance_transform_edt gives image by image on the host -- U-Net
+    border weights, signed distance maps for boundary losses, truncated distance targets, centre-ness, trimaps wider than 16.
+    D2(x, y) is the smallest (x - x')^2 + (y - y')^2 over the SITES of the element, an exact integer.  to=None: the sites are the
+    elements of the image that differ from it (on a binary mask both halves of a signed distance map at once, on a multi-class map
+    the inside distance of every class); to=<int>: the elements equal to it (distance_transform_edt(labels != to); those elements
+    get 0; a value the dtype cannot hold matches nothing).  Elements are compared whole (exact for packed colours and int64 ids);
+    positions outside the image are never sites.  cap: None, or 1 .. 32767: the result is min(D2, cap^2).  out="squared": torch.int32,
+    D2 itself; an element without any site (a flat image, an absent value) gets cap^2, or 2^31 - 1 without a cap.  out="root":
+    torch.float32, the float32 nearest to the square root (exactly np.sqrt(d2.astype(float64)).astype(float32)); without a site cap,
+    or +inf without a cap.  labels: a contiguous tensor of torch.uint8, uint16 (or int16, read as the uint16 bits: to is then
+    0 .. 65535), int32 or int64 on the current device -- the tensor of png_decode_batch_labels / png_decode_batch_color_labels under
+    any of their maps, or one made otherwise.  A distance map cannot be carried through a warp, so the documented use is labels ->
+    png_label_distance: decode (and warp) first, then measure the tensor that came back.  png_label_distance(t) <= r * r is
+    png_label_boundary(t, r, "disk", "edge") for r = 1 .. 16.  status: None, or one entry per image: an image whose entry is not 0
+    is not looked at and comes back as zeros.  Two kernel launches, each linear in the image whatever it holds; the call waits for
+    the work queued on the device before it, and for its own."""
+    import torch
+
+    if to is not None and (isinstance(to, bool) or not isinstance(to, (int, np.integer)) or not -2 ** 63 <= int(to) < 2 ** 63):
+        raise ValueError(f"to must be None or an integer that fits 64 bits, not {to!r}")
+    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= int(cap) <= PNG_LABEL_DISTANCE_MAX_CAP):
+        raise ValueError(f"cap must be None or an integer in 1 .. {PNG_LABEL_DISTANCE_MAX_CAP}, not {cap!r}")
+    if not isinstance(out, str) or out not in _PNG_DISTANCE_FORMATS:
+        raise ValueError(f"out must be one of {sorted(_PNG_DISTANCE_FORMATS)}, not {out!r}")
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be a (N, H, W) tensor")
+    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = 1
+    if labels.dtype not in codes:
+        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
+    if not labels.is_contiguous():
+        raise ValueError("labels must be contiguous")
+    if labels.device.type != "cuda":
+        raise ValueError("labels must be on the GPU")
+    n, H, W = (int(v) for v in labels.shape)
+    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
+    if status is not None and len(status) != n:
+        raise ValueError("status needs one entry per image")
+    res = torch.empty((n, H, W), dtype=torch.int32 if out == "squared" else torch.float32, device=labels.device)
+    if n == 0:
+        return res
+    L = _png_spec_lib()
+    _png_device(L, labels.device)
+    L.debig_png_label_distance.restype = C.c_int
+    L.debig_png_label_distance.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_int64, C.c_uint32, C.c_uint32, C.c_void_p]
+    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
+    for i in ([] if status is None else [i for i in range(n) if st[i] != 0]):  # the images the library leaves alone, and only they
+        res[i].zero_()
+    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
+    rc = L.debig_png_label_distance(labels.data_ptr(), res.data_ptr(), n, W, H, codes[labels.dtype], 0 if to is None else 1,
+                                    0 if to is None else int(to), 0 if cap is None else int(cap), _PNG_DISTANCE_FORMATS[out], st)
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"debig_png_label_distance rejected its arguments ({rc})")
+    N.check(rc, "debig_png_label_distance")
+    return res
+
+
 class PngLabelDesc(C.Structure):  # include/decode_png.h: debig_png_label_desc
     _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("dtype", C.c_uint32), ("reserved", C.c_uint32),
                 ("lut", C.POINTER(C.c_int32))]

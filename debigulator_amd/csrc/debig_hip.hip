@@ -28,6 +28,7 @@
 #include "png_blur_kernel.inc"
 #include "png_label_stats_kernel.inc"
 #include "png_label_boundary_kernel.inc"
+#include "png_label_distance_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -985,6 +986,22 @@ int debig_hip_png_label_boundary_batch(const void *d_labels, void *d_out, const 
                                        void *hip_stream)
 {
     return launch_stage(debig_png_label_boundary_kernel, LBD_THREADS, n_tasks, hip_stream, (const uint8_t *)d_labels, (uint8_t *)d_out,
+                        d_tasks);
+}
+
+// distance maps of a dense label tensor (png_label_distance_kernel.inc): the row-distance plane, one workgroup per run of rows ...
+int debig_hip_png_label_distance_rows_batch(const void *d_labels, void *d_g, const debig_png_label_distance_rows_task *d_tasks,
+                                            uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_distance_rows_kernel, LDR_THREADS, n_tasks, hip_stream, (const uint8_t *)d_labels, (uint8_t *)d_g,
+                        d_tasks);
+}
+
+// ... and the column pass over it, one wavefront per strip of 64 columns
+int debig_hip_png_label_distance_cols_batch(const void *d_g, void *d_out, const debig_png_label_distance_cols_task *d_tasks, uint32_t n_tasks,
+                                            void *hip_stream)
+{
+    return launch_stage(debig_png_label_distance_cols_kernel, LDC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_g, (uint8_t *)d_out,
                         d_tasks);
 }
 

@@ -2053,6 +2053,81 @@ done:
     return rc;
 }
 
+/* ---- debig_png_label_distance: exact squared Euclidean distance maps of a dense label tensor (decode_png.h) --------------------- */
+
+_Static_assert(sizeof(debig_png_label_distance_rows_task) == 48 && offsetof(debig_png_label_distance_rows_task, w) == 24,
+               "three 64-bit fields, six uint32");
+_Static_assert(sizeof(debig_png_label_distance_cols_task) == 40 && offsetof(debig_png_label_distance_cols_task, w) == 16,
+               "two 64-bit fields, six uint32");
+
+DEBIG_API int debig_png_label_distance(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
+                                       uint32_t sites, int64_t value, uint32_t cap, uint32_t format, const uint32_t *status)
+{
+    if (n == 0) return 0;
+    if (!d_labels || !d_out || dtype > DEBIG_PNG_L_I64 || sites > DEBIG_PNG_DISTANCE_TO_VALUE || format > DEBIG_PNG_DISTANCE_ROOT ||
+        cap > DEBIG_PNG_LABEL_DISTANCE_MAX_CAP || out_w == 0 || out_w > 16384u || out_h == 0 || out_h > 16384u)
+        return DEBIG_PNG_BAD_ARG;
+    const uint32_t es = 1u << dtype;
+    if (((uintptr_t)d_labels & (es - 1u)) || ((uintptr_t)d_out & 3u)) return DEBIG_PNG_BAD_ARG;
+    const uint64_t img = (uint64_t)out_w * out_h, in_bytes = (uint64_t)n * img * es, out_bytes = (uint64_t)n * img * 4u;
+    if ((uintptr_t)d_out < (uintptr_t)d_labels + in_bytes && (uintptr_t)d_labels < (uintptr_t)d_out + out_bytes) return DEBIG_PNG_BAD_ARG;
+    /* a rows task: a run of whole rows of at most DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS elements; a cols task: a strip of 64 columns */
+    const uint32_t run = out_w >= DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS ? 1u : DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS / out_w;
+    const uint64_t per_r = (out_h + run - 1u) / run, per_c = (out_w + DEBIG_PNG_LABEL_DISTANCE_COLS - 1u) / DEBIG_PNG_LABEL_DISTANCE_COLS;
+    uint64_t n_good = 0;
+    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
+    if (n_good * per_r >= 0x7fffffffu || n_good * per_c >= 0x7fffffffu) return 2;
+    if (n_good == 0) return 0;
+    int rc = 2;
+    /* both task lists in one upload: the rows tasks, the cols tasks behind them (48 is a multiple of 8) */
+    const uint64_t n_r = n_good * per_r, n_c = n_good * per_c;
+    const uint64_t bytes = n_r * sizeof(debig_png_label_distance_rows_task) + n_c * sizeof(debig_png_label_distance_cols_task);
+    uint8_t *blob = (uint8_t *)calloc((size_t)bytes, 1);
+    dev_table tab[1] = {{NULL, n_good * img * 2u, 0}}; /* the g planes of the images that are looked at: space only */
+    if (!blob) goto done;
+    debig_png_label_distance_rows_task *tr = (debig_png_label_distance_rows_task *)blob;
+    debig_png_label_distance_cols_task *tc = (debig_png_label_distance_cols_task *)(blob + n_r * sizeof *tr);
+    uint64_t k = 0; /* the image's place among the good ones */
+    for (uint32_t i = 0; i < n; i++) {
+        if (status && status[i] != 0) continue;
+        for (uint32_t y0 = 0; y0 < out_h; y0 += run, tr++) {
+            tr->label_off = (uint64_t)i * img * es;
+            tr->g_off = k * img * 2u;
+            tr->value = value;
+            tr->w = out_w;
+            tr->h = out_h;
+            tr->row0 = y0;
+            tr->rows = out_h - y0 < run ? out_h - y0 : run;
+            tr->dtype = dtype;
+            tr->sites = sites;
+        }
+        for (uint32_t x0 = 0; x0 < out_w; x0 += DEBIG_PNG_LABEL_DISTANCE_COLS, tc++) {
+            tc->g_off = k * img * 2u;
+            tc->out_off = (uint64_t)i * img * 4u;
+            tc->w = out_w;
+            tc->h = out_h;
+            tc->x0 = x0;
+            tc->cols = out_w - x0 < DEBIG_PNG_LABEL_DISTANCE_COLS ? out_w - x0 : DEBIG_PNG_LABEL_DISTANCE_COLS;
+            tc->cap = cap;
+            tc->format = format;
+        }
+        k++;
+    }
+    debig_ctx *c = dev_upload(blob, bytes, 1, tab, 1, &rc);
+    if (!c) goto done;
+    const uint8_t *d_tasks = (const uint8_t *)c->rsz_tasks.ptr;
+    if ((rc = debig_hip_png_label_distance_rows_batch(d_labels, c->rsz_weights.ptr, (const debig_png_label_distance_rows_task *)d_tasks,
+                                                      (uint32_t)n_r, NULL)) ||
+        (rc = debig_hip_png_label_distance_cols_batch(c->rsz_weights.ptr,
+                                                      d_out, (const debig_png_label_distance_cols_task *)(d_tasks + n_r * sizeof *tr),
+                                                      (uint32_t)n_c, NULL)))
+        goto done;
+    rc = debig_hip_stream_sync(NULL);
+done:
+    free(blob);
+    return rc;
+}
+
 /* ---- the affine warp of the tensor and the label decode (decode_png.h) ------------------------------------------------------ */
 
 #define WARP_TASK_PIXELS 4096u /* output pixels of one warp task (a run of whole rows; one row when it is wider): 16 per lane */

@@ -204,7 +204,7 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * tasks -- debig_hip_apng_composite_batch, debig_hip_png_resize_batch / _resize_alpha / _resize_cubic / _resize_color,
  * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp,
  * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur, _label_stats and
- * _label_boundary --
+ * _label_boundary, _label_distance_rows / _label_distance_cols --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -989,6 +989,46 @@ typedef struct debig_png_label_boundary_task {
       ((((((((tile_w) + 2u * (radius)) << (dtype)) + 30u) & ~15u) >> (dtype)) + 15u) & ~15u)))
 int debig_hip_png_label_boundary_batch(const void *d_labels, void *d_out, const debig_png_label_boundary_task *d_tasks, uint32_t n_tasks,
                                        void *hip_stream);
+
+/* ---- exact squared Euclidean distance maps of a dense label tensor (csrc/png_label_distance_kernel.inc, behind
+ * debig_png_label_distance in decode_png.h, which has the rule), in two launches on one stream:
+ *   ROWS  reads the labels and writes the G PLANE d_g, one uint16 per element of the image (w x h, dense): bits 0 .. 14 the distance
+ *         along the row to the nearest site of the element in its row (0 .. 16383, or 0x7fff: none), bit 15 "differs from the
+ *         element above" (sites 0 only, never in row 0).  One TASK is a run of whole rows of one image for one workgroup of 256
+ *         lanes: rows x w <= DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS, or one row.
+ *   COLS  reads the g plane and writes the output plane d_out, 4 bytes per element (int32 under format 0, float32 under format 1).
+ *         One TASK is a strip of 1 .. DEBIG_PNG_LABEL_DISTANCE_COLS adjacent columns of one image for one wavefront, one lane per
+ *         column.  WHILE IT RUNS, A COLUMN'S OUTPUT ELEMENTS HOLD ITS ENVELOPE STACK; every element of the strip is written last
+ *         with its result.  It never reads the labels.
+ * Both are pure functions of their input, whatever the cut, the grid and the order of the tasks; both do work linear in the row /
+ * column length whatever the data.  d_g must not overlap d_labels or d_out.
+ * A rows task is skipped when dtype is above 3, sites above 1, w or h is 0 or above 16384, rows is 0 or the run leaves the image,
+ * rows x w exceeds the cap with rows above 1, or an offset or address is not a multiple of the element size (of 2 for the g plane);
+ * a cols task when format is above 1, cap above 32767, w or h is 0 or above 16384, cols is 0 or above the cap or the strip leaves
+ * the image, or an offset or address is not a multiple of 2 (g) / 4 (output). */
+#define DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS 16384u
+#define DEBIG_PNG_LABEL_DISTANCE_COLS 64u
+typedef struct debig_png_label_distance_rows_task {
+    uint64_t label_off;     /* the image's first element, in bytes rel. to d_labels                                            */
+    uint64_t g_off;         /* the image's first g element, in bytes rel. to d_g                                               */
+    int64_t value;          /* sites 1: the elements equal to it are the sites (a value the dtype cannot hold: there are none) */
+    uint32_t w, h;          /* the image                                                                                       */
+    uint32_t row0, rows;    /* the run of rows                                                                                 */
+    uint32_t dtype;         /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                         */
+    uint32_t sites;         /* decode_png.h DEBIG_PNG_DISTANCE_DIFFERS 0, _TO_VALUE 1                                          */
+} debig_png_label_distance_rows_task;
+typedef struct debig_png_label_distance_cols_task {
+    uint64_t g_off;         /* the image's first g element, in bytes rel. to d_g                                               */
+    uint64_t out_off;       /* the image's first output element, in bytes rel. to d_out                                        */
+    uint32_t w, h;          /* the image                                                                                       */
+    uint32_t x0, cols;      /* the strip                                                                                       */
+    uint32_t cap;           /* 0: none, else 1 .. 32767: the result is min(D2, cap^2)                                          */
+    uint32_t format;        /* decode_png.h DEBIG_PNG_DISTANCE_SQUARED 0 (int32), _ROOT 1 (float32)                            */
+} debig_png_label_distance_cols_task;
+int debig_hip_png_label_distance_rows_batch(const void *d_labels, void *d_g, const debig_png_label_distance_rows_task *d_tasks,
+                                            uint32_t n_tasks, void *hip_stream);
+int debig_hip_png_label_distance_cols_batch(const void *d_g, void *d_out, const debig_png_label_distance_cols_task *d_tasks, uint32_t n_tasks,
+                                            void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

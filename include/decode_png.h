@@ -919,8 +919,8 @@ int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t out_w, uint
  * or larger where dtype and radius allow), launches once (debig_hip_png_label_boundary_batch) and is synchronous on the
  * library's stream, like debig_png_label_stats; the caller makes sure that whoever wrote d_labels on another stream has finished.
  * Otherwise 0 or an error code of the device layer.  Not thread safe against the tensor decodes of the same process (it uses
- * their arenas).  Not provided: a "transparent" value that never forms a boundary, inner- or outer-only bands, distance maps,
- * radii above 16, in-place operation, host tensors. */
+ * their arenas).  Not provided: a "transparent" value that never forms a boundary, inner- or outer-only bands,
+ * radii above 16 (debig_png_label_distance below makes distance maps), in-place operation, host tensors. */
 #define DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS 16u
 #define DEBIG_PNG_BOUNDARY_SQUARE 0u
 #define DEBIG_PNG_BOUNDARY_DIAMOND 1u
@@ -932,6 +932,46 @@ int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t out_w, uint
 void debig_png_label_boundary_reach(uint32_t radius, uint32_t shape, uint8_t reach[17]);
 int debig_png_label_boundary(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
                              uint32_t radius, uint32_t shape, uint32_t mode, int64_t value, const uint32_t *status /* host, may be NULL */);
+
+/* ---- exact Euclidean distance maps of a label tensor: border weights, signed distances, truncated targets, wide trimaps ---------------
+ * What scipy.ndimage.distance_transform_edt does on the host, image by image.  Like a ring, a distance map cannot be carried
+ * through a warp, so it is made from the warped map: d_labels is a dense (n, out_h, out_w) tensor of DEBIG_PNG_L_* elements in
+ * device memory, as for debig_png_label_stats.  Elements are compared whole (3 and 2^32 + 3 differ, -1 and 255 differ).
+ * THE RULE.  The SITES of element (x, y):
+ *   - DEBIG_PNG_DISTANCE_DIFFERS:  every element of the image that differs from the element at (x, y).  On a binary mask: the
+ *     distance to the other class, both halves of a signed distance map at once; on a multi-class map: the inside distance of
+ *     every class at once;
+ *   - DEBIG_PNG_DISTANCE_TO_VALUE: every element equal to `value` (scipy's distance_transform_edt(labels != value); the elements
+ *     equal to `value` get 0).  uint8 and uint16 elements are 0 .. 255 / 0 .. 65535, int32 and int64 elements are signed; a `value`
+ *     that the dtype cannot hold is not an error: no element equals it.
+ * D2(x, y) = min over the sites (x', y') of (x - x')^2 + (y - y')^2, an exact integer of at most 2 * 16383^2.  Positions outside the
+ * image are never sites.  NONE: the element has no site (a flat image under DIFFERS, an image without `value` under TO_VALUE).
+ * cap is 0 (no cap) or 1 .. 32767: with a cap the result is min(D2, cap^2) and NONE gives cap^2; without one NONE gives the
+ * format's "infinite" value.
+ *   - DEBIG_PNG_DISTANCE_SQUARED: int32, the result itself; NONE without a cap is INT32_MAX;
+ *   - DEBIG_PNG_DISTANCE_ROOT:    float32, the float32 NEAREST to the real square root of the result (round to nearest, the
+ *     correctly rounded square root of the integer: (float)sqrt((double)d2), NOT sqrtf((float)d2), which rounds the argument first
+ *     and differs above 2^24); NONE without a cap is +infinity.  A square root of an integer below 2^30 is an integer or lies at
+ *     least 2^-36 away from every midpoint of two float32, so the double route cannot round twice to another float.
+ * Identities: under DIFFERS, D2 <= r^2 is debig_png_label_boundary(radius r, DISK, EDGE) for r = 1 .. 16; under TO_VALUE it is the
+ * square of distance_transform_edt(labels != value) wherever `value` occurs.
+ * d_out is a dense (n, out_h, out_w) tensor of 4-byte elements.  The result is a pure function of the input.  The slot in d_out of
+ * an image whose status[i] != 0 is not written (status NULL: no image is left out).  n == 0: returns 0 and touches nothing.
+ * DEBIG_PNG_BAD_ARG, before any device work, for d_labels or d_out NULL with n > 0, d_labels not aligned to its element size, d_out
+ * not aligned to 4, dtype above DEBIG_PNG_L_I64, sites above TO_VALUE, format above ROOT, cap above 32767, out_w or out_h 0 or above
+ * 16384, and d_out's byte range overlapping d_labels's.  The call makes a row-distance plane of 2 bytes per element in the context's
+ * arenas (debig_hip_png_label_distance_rows_batch), then the column pass (debig_hip_png_label_distance_cols_batch), both linear in
+ * the image whatever it holds, and is synchronous on the library's stream, like debig_png_label_stats; the caller makes sure that
+ * whoever wrote d_labels on another stream has finished.  Otherwise 0 or an error code of the device layer.  Not thread safe
+ * against the tensor decodes of the same process (it uses their arenas).  Not provided: signed output, a stack of maps per class,
+ * the index of the nearest site, anisotropic spacing, other metrics, in-place operation, host tensors. */
+#define DEBIG_PNG_DISTANCE_DIFFERS 0u
+#define DEBIG_PNG_DISTANCE_TO_VALUE 1u
+#define DEBIG_PNG_DISTANCE_SQUARED 0u
+#define DEBIG_PNG_DISTANCE_ROOT 1u
+#define DEBIG_PNG_LABEL_DISTANCE_MAX_CAP 32767u
+int debig_png_label_distance(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
+                             uint32_t sites, int64_t value, uint32_t cap, uint32_t format, const uint32_t *status /* host, may be NULL */);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

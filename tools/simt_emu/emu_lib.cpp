@@ -29,6 +29,7 @@
 #include "../../debigulator_amd/csrc/png_blur_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_stats_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_boundary_kernel.inc"
+#include "../../debigulator_amd/csrc/png_label_distance_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
@@ -587,5 +588,23 @@ extern "C" int emu_png_label_boundary_batch(const void *labels, void *out, const
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_label_boundary_kernel, grid, LBD_THREADS, (const uint8_t *)labels, (uint8_t *)out, tasks, n);
+    return 0;
+}
+
+/* distance maps of a dense label tensor (png_label_distance_kernel.inc), as debig_hip_png_label_distance_rows_batch and
+ * debig_hip_png_label_distance_cols_batch launch the two kernels (grid as above) */
+extern "C" int emu_png_label_distance_rows_batch(const void *labels, void *g, const debig_png_label_distance_rows_task *tasks, uint32_t n,
+                                                 uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_distance_rows_kernel, grid, LDR_THREADS, (const uint8_t *)labels, (uint8_t *)g, tasks, n);
+    return 0;
+}
+
+extern "C" int emu_png_label_distance_cols_batch(const void *g, void *out, const debig_png_label_distance_cols_task *tasks, uint32_t n,
+                                                 uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_distance_cols_kernel, grid, LDC_THREADS, (const uint8_t *)g, (uint8_t *)out, tasks, n);
     return 0;
 }
