@@ -13,14 +13,21 @@ array stands for the address it starts at), a ctypes array or None.
          (include/debig_hip.h) set to `grid`.  Every buffer is uploaded whole (for a view: the array it is a view of, so the
          sentinels in front of an output travel too) to an address with the host address's residue mod 64, and every buffer
          comes back: the outputs (KERNELS) are copied over the host arrays, the inputs and the bytes around every buffer must be
-         unchanged.  tests/test_gpu_png_stage_kernels.py runs the batteries this way."""
+         unchanged.  tests/test_gpu_png_stage_kernels.py runs the batteries this way.
+
+The four launchers of the general PNG de-filter (NO_GRID: png_spec_defilter, _fmt, _planar, _index) start one workgroup per task and
+take no grid: for them `grid` must be 0, the emulator twin gets none and DEBIG_STAGE_GRID is left as it is.  Their first buffer is
+the arena (INOUT): the kernel reads the streams and palettes in it and writes the tasks' scratch rings, which lie in it too, so it
+is uploaded and copied back like an output, and its runner (tests/test_emu_png_spec.py: launch_defilter) asserts which bytes of it
+may have changed.  tests/test_gpu_png_defilter_kernels.py runs their batteries on the GPU."""
 import ctypes as C
 import os
 
 import numpy as np
 
-IN, OUT, TASKS = "in", "out", "tasks"
-# kernel name -> its buffer arguments in the launchers' order (include/debig_hip.h); OUT: the kernel writes or accumulates into it
+IN, OUT, TASKS, INOUT = "in", "out", "tasks", "inout"
+# kernel name -> its buffer arguments in the launchers' order (include/debig_hip.h); OUT: the kernel writes or accumulates into it;
+# INOUT: it reads the buffer and writes a part of it that the caller knows (copied back like OUT, the caller checks the rest)
 KERNELS = {
     "apng_composite": (IN, OUT, TASKS),
     "png_resize": (IN, OUT, TASKS, IN),
@@ -36,7 +43,13 @@ KERNELS = {
     "png_tone_hist": (IN, OUT, TASKS),
     "png_tone_apply": (IN, OUT, TASKS, IN, IN),
     "png_blur": (IN, OUT, TASKS, IN),
+    "png_spec_defilter": (INOUT, OUT, TASKS, OUT),
+    "png_spec_defilter_fmt": (INOUT, OUT, TASKS, OUT),
+    "png_spec_defilter_planar": (INOUT, OUT, TASKS, OUT),
+    "png_spec_defilter_index": (INOUT, OUT, TASKS, OUT),
 }
+# the launchers without a task loop: one workgroup per task, no grid argument in the emulator twin, DEBIG_STAGE_GRID not read
+NO_GRID = {"png_spec_defilter", "png_spec_defilter_fmt", "png_spec_defilter_planar", "png_spec_defilter_index"}
 # the warp kernels under the other two maps: a persp kernel has the buffers of its warp twin, an elastic kernel its twin's and the fields
 for _w in ("png_warp", "png_warp_color", "png_label_warp", "png_color_label_warp"):
     KERNELS[_w.replace("warp", "persp")] = KERNELS[_w]
@@ -51,9 +64,11 @@ def launch(name, *args, emu=None):
     assert len(bufs) == len(KERNELS[name]), name
     if record is not None:
         record.append((name, bufs[KERNELS[name].index(TASKS)], n, grid))
+    if name in NO_GRID:
+        assert grid == 0, (name, "starts one workgroup per task")
     if backend == "emu":
         ptrs = [b.ctypes.data if isinstance(b, np.ndarray) else b for b in bufs]
-        return getattr(emu(), "emu_%s_batch" % name)(*ptrs, n, grid)
+        return getattr(emu(), "emu_%s_batch" % name)(*ptrs, n, *(() if name in NO_GRID else (grid,)))
     assert backend == "gpu", backend
     return _gpu_launch(name, bufs, n, grid)
 
@@ -94,7 +109,7 @@ def _gpu_launch(name, bufs, n, grid):
     old = os.environ.get("DEBIG_STAGE_GRID")
     if grid:
         os.environ["DEBIG_STAGE_GRID"] = str(grid)
-    else:
+    elif name not in NO_GRID:
         os.environ.pop("DEBIG_STAGE_GRID", None)
     try:
         rc = fn(*ptrs, n, torch.cuda.current_stream().cuda_stream)
@@ -109,7 +124,7 @@ def _gpu_launch(name, bufs, n, grid):
         back = t.cpu().numpy()
         end = shift + len(host)
         assert (back[:shift] == GUARD).all() and (back[end:] == GUARD).all(), (name, role, "bytes around the buffer were written")
-        if role == OUT:
+        if role in (OUT, INOUT):
             host[:] = back[shift:end]
         else:
             assert back[shift:end].tobytes() == bytes(stage[shift:end]), (name, role, "an input buffer was written")

@@ -1,7 +1,9 @@
 """The two kernels of debig_png_decode_batch_labels on the CPU lock-step emulator, against tests/png_label_ref.py:
   * debig_png_spec_defilter_index_kernel (csrc/png_spec_kernel.inc): colour type 0 at depths 1, 2, 4, 8, 16 and colour type 3
     at 1, 2, 4, 8, plain and Adam7, sizes from 1 x 1 (most Adam7 passes empty) to 3 x 130 (three 64-row bands), row filters
-    cycling y % 5; the bytes are labels(), every byte beyond the images keeps its sentinel; an index >= n_pal fails the task;
+    cycling y % 5, then 4, 5 and 6 bands (the four-row scratch ring wraps) and rows of 8 to 72 groups across three bands; the bytes
+    are labels(), every byte beyond the images keeps its sentinel and every byte of the arena outside the scratch rings its value; an
+    index >= n_pal fails the task; run_index launches through the seam, and tests/test_gpu_png_defilter_kernels.py runs it on the GPU;
   * debig_png_label_gather_kernel (csrc/png_label_kernel.inc): 1- and 2-byte sources into all four dtypes, output widths that
     are no multiple of any per-lane count, boxes at each corner, a 1-pixel-wide box, enlarging 40 x, with and without a LUT,
     a 4 KiB sentinel kept before and after the tensor; tasks that break a bound are skipped."""
@@ -86,7 +88,7 @@ def run_index(imgs):
     n = len(tasks)
     TT = (T.SpecTask * n)(*tasks)
     res = (T.SpecResult * n)()
-    assert _emu().emu_png_spec_defilter_index_batch(a.ctypes.data, out.ctypes.data, TT, res, n) == 0
+    T.launch_defilter("png_spec_defilter_index", a, out, TT, res, _emu)
     untouched = np.ones(len(out), dtype=bool)
     result = []
     for i, im in enumerate(imgs):
@@ -129,6 +131,20 @@ def test_index_defilter_every_filter_type_and_widths_1_to_70():
     imgs = [T._image(rng, 37, 66, ct, depth, 0, ft) for ct, depth in ((0, 2), (3, 8), (0, 16)) for ft in range(5)]
     imgs += [T._image(rng, w, 1 + w % 5, *LABEL_FORMATS[w % len(LABEL_FORMATS)], w % 2, None) for w in range(1, 71)]
     _check_index(imgs)
+
+
+@pytest.mark.parametrize("ct,depth", [f for f in T.UNIT_FORMATS if f in LABEL_FORMATS])
+@pytest.mark.parametrize("h", T.WRAP_HEIGHTS)
+def test_heights_past_the_ring_wrap(h, ct, depth):
+    """four, five and six bands (test_emu_png_spec.wrap_images) in the label formats of both filter units of this kernel, 1 and 2"""
+    assert T.R.bpp_f(ct, depth) == (2 if depth == 16 else 1)
+    _check_index(T.wrap_images(np.random.default_rng(h * 100 + ct * 10 + depth + 3), h, ct, depth))
+
+
+@pytest.mark.parametrize("ng", T.LONG_NGROUPS)
+def test_long_rows_across_bands(ng):
+    """filter unit 2: rows of 8 to 72 groups over three bands (test_emu_png_spec.long_image), Paeth throughout"""
+    _check_index([T.long_image(np.random.default_rng(ng + 3), 0, 16, ng)])
 
 
 def test_index_past_the_palette_and_other_colour_types_fail_the_task():

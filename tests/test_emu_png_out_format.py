@@ -1,8 +1,10 @@
 """The output-format twin of the general PNG de-filter (csrc/png_spec_kernel.inc: debig_png_spec_defilter_fmt_kernel) on
 the CPU lock-step emulator, plain and under ASan/UBSan, against the numpy converter of tests/png_out_format_ref.py:
 every filter unit x every filter type x every output format x interlace 0/1, widths 1..70, heights across the 64-row
-band edges, short palettes and tRNS keys; with out_fmt = 0 it must equal debig_png_spec_defilter_kernel byte for byte.
-Every byte between and after the images must stay untouched."""
+band edges and past the wrap of the scratch ring (4, 5 and 6 bands, every filter unit), rows of 8 to 72 groups of filter unit 6
+across three bands, short palettes and tRNS keys; with out_fmt = 0 it must equal debig_png_spec_defilter_kernel byte for byte.
+Every byte between and after the images must stay untouched, and every byte of the arena outside the scratch rings.  run_images
+launches through the seam tests/stage_launch.py: tests/test_gpu_png_defilter_kernels.py runs the same cases on the GPU."""
 import ctypes as C
 import os
 import sys
@@ -98,17 +100,15 @@ def run_images(imgs, fmts):
     n = len(tasks)
     TT = (SpecTask * n)(*tasks)
     res = (T.SpecResult * n)()
-    assert _emu().emu_png_spec_defilter_fmt_batch(a.ctypes.data, out.ctypes.data, TT, res, n) == 0
-    untouched = np.ones(len(out), dtype=bool)
+    T.launch_defilter("png_spec_defilter_fmt", a, out, TT, res, _emu)
+    T.assert_fill_outside(out, zip(offs, sizes), FILL)
     result = []
     for i, im in enumerate(imgs):
         h, w = im["samples"].shape[:2]
         lay, bits = res_fmts[i] & 15, 16 if res_fmts[i] & F.D16 else 8
-        untouched[offs[i]: offs[i] + sizes[i]] = False
         st = [(res[k].status, res[k].bad_row) for k in range(n) if owners[k] == i]
         px = out[offs[i]: offs[i] + sizes[i]].view("<u2" if bits == 16 else np.uint8).reshape(h, w, F.LAYOUT_CHANNELS[lay])
         result.append((st, px, res_fmts[i]))
-    assert (out[untouched] == FILL).all(), "bytes outside the images were written"
     return result
 
 
@@ -164,6 +164,21 @@ def test_heights_across_bands(h):
             T._image(rng, 19, h, 3, 8, 0, 3), T._image(rng, 27, h, 4, 16, 1, None)]
     for fmts in ([F.GRAY | F.D16] * 5, [F.RGB, F.GRAY_ALPHA, F.NATIVE | F.D_NATIVE, F.RGBA | F.D16, F.GRAY]):
         _check(imgs, fmts)
+
+
+@pytest.mark.parametrize("ct,depth", T.UNIT_FORMATS)
+@pytest.mark.parametrize("h", T.WRAP_HEIGHTS)
+def test_heights_past_the_ring_wrap(h, ct, depth):
+    """four, five and six bands (test_emu_png_spec.wrap_images), output formats in rotation"""
+    imgs = T.wrap_images(np.random.default_rng(h * 100 + ct * 10 + depth + 1), h, ct, depth)
+    k0 = h + T.UNIT_FORMATS.index((ct, depth))
+    _check(imgs, [ALL_FMTS[(k0 + k) % len(ALL_FMTS)] for k in range(len(imgs))])
+
+
+@pytest.mark.parametrize("ng", T.LONG_NGROUPS)
+def test_long_rows_across_bands(ng):
+    """filter unit 6: rows of 8 to 72 groups over three bands (test_emu_png_spec.long_image), Paeth throughout"""
+    _check([T.long_image(np.random.default_rng(ng + 1), 2, 16, ng)], [ALL_FMTS[ng % len(ALL_FMTS)]])
 
 
 def test_short_palette_and_keys():

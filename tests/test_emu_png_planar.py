@@ -3,7 +3,10 @@ on the CPU lock-step emulator, plain and under ASan/UBSan.  Expected pixels: the
 tests/png_out_format_ref.py, transposed to (channels, h, w).  Every filter unit x every filter type x every concrete
 output format x interlace 0/1, widths 1..70, heights across the 64-row band edges, short palettes and tRNS keys, odd
 w * h (the planes of 8-bit outputs then start at odd addresses); every byte between and after the images must stay
-untouched; the filter-byte and palette-index statuses are those of the format twin on the same tasks."""
+untouched, and every byte of the arena outside the scratch rings; the filter-byte and palette-index statuses are those of the
+format twin on the same tasks.  Also 4, 5 and 6 bands in every filter unit (the four-row scratch ring wraps) and rows of 8 to 72
+groups of 4-bit samples across three bands.  run_images launches through the seam tests/stage_launch.py:
+tests/test_gpu_png_defilter_kernels.py runs the same cases on the GPU."""
 import ctypes as C
 import os
 import sys
@@ -102,19 +105,16 @@ def run_images(imgs, fmts, planar=True):
     n = len(tasks)
     TT = (SpecTask * n)(*tasks)
     res = (T.SpecResult * n)()
-    fn = _emu().emu_png_spec_defilter_planar_batch if planar else _emu().emu_png_spec_defilter_fmt_batch
-    assert fn(a.ctypes.data, out.ctypes.data, TT, res, n) == 0
-    untouched = np.ones(len(out), dtype=bool)
+    T.launch_defilter("png_spec_defilter_planar" if planar else "png_spec_defilter_fmt", a, out, TT, res, _emu)
+    T.assert_fill_outside(out, zip(offs, sizes), FILL)  # (sizes: channels * h * w * sample bytes -- everything past the last plane too)
     result = []
     for i, im in enumerate(imgs):
         h, w = im["samples"].shape[:2]
         lay, bits = res_fmts[i] & 15, 16 if res_fmts[i] & F.D16 else 8
         ch = F.LAYOUT_CHANNELS[lay]
-        untouched[offs[i]: offs[i] + sizes[i]] = False
         st = [(res[k].status, res[k].bad_row) for k in range(n) if owners[k] == i]
         px = out[offs[i]: offs[i] + sizes[i]].view("<u2" if bits == 16 else np.uint8)
         result.append((st, px.reshape((ch, h, w) if planar else (h, w, ch)), res_fmts[i]))
-    assert (out[untouched] == FILL).all(), "bytes outside the images were written"
     return result
 
 
@@ -167,6 +167,21 @@ def test_heights_across_bands(h):
             T._image(rng, 19, h, 3, 8, 0, 3), T._image(rng, 27, h, 4, 16, 1, None)]
     for fmts in ([F.RGBA | F.D16] * 5, [F.RGB, F.GRAY_ALPHA, F.NATIVE | F.D_NATIVE, F.RGBA, F.GRAY_ALPHA | F.D16]):
         _check(imgs, fmts)
+
+
+@pytest.mark.parametrize("ct,depth", T.UNIT_FORMATS)
+@pytest.mark.parametrize("h", T.WRAP_HEIGHTS)
+def test_heights_past_the_ring_wrap(h, ct, depth):
+    """four, five and six bands (test_emu_png_spec.wrap_images), concrete output formats in rotation"""
+    imgs = T.wrap_images(np.random.default_rng(h * 100 + ct * 10 + depth + 2), h, ct, depth)
+    k0 = h + T.UNIT_FORMATS.index((ct, depth))
+    _check(imgs, [CONCRETE[(k0 + k) % len(CONCRETE)] for k in range(len(imgs))])
+
+
+@pytest.mark.parametrize("ng", T.LONG_NGROUPS)
+def test_long_rows_across_bands(ng):
+    """filter unit 1, two pixels per byte: rows of 8 to 72 groups over three bands (test_emu_png_spec.long_image), Paeth throughout"""
+    _check([T.long_image(np.random.default_rng(ng + 2), 0, 4, ng)], [CONCRETE[ng % len(CONCRETE)]])
 
 
 def test_short_palette_and_keys():

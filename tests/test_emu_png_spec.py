@@ -1,6 +1,9 @@
 """The general PNG de-filter kernel (csrc/png_spec_kernel.inc) on the CPU lock-step emulator, under ASan/UBSan, against
 the reference decoder of tests/png_spec_ref.py: every filter unit, every filter type, widths 1..130 (sub-byte row tails,
-empty Adam7 passes), heights across band edges."""
+empty Adam7 passes), heights across band edges and past the wrap of the four-row scratch ring (4, 5 and 6 bands), rows of 8 to 72
+groups across three bands, scanline bytes at every residue mod 4.  run_images launches through the seam tests/stage_launch.py, so
+tests/test_gpu_png_defilter_kernels.py runs the same cases on the GPU; on either back end the arena outside the scratch rings and
+the output arena outside the images must come back untouched."""
 import ctypes as C
 import os
 import sys
@@ -11,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import png_spec_ref as R  # noqa: E402
 from emu_binding import load_emu  # noqa: E402
+from stage_launch import launch  # noqa: E402
 
 
 class SpecTask(C.Structure):  # include/debig_hip.h: debig_png_spec_task
@@ -42,8 +46,31 @@ def _emu():
     return _LIB["L"]
 
 
-def run_images(imgs):
-    """imgs: [dict(samples, ct, depth, interlace, filters, key, pal (n, 3), trns)] -> [(status list, rgba)]"""
+def launch_defilter(name, a, out, tasks, res, emu):
+    """one launch of a general de-filter kernel through the launch seam (tests/stage_launch.py: the emulator, or the product library
+    on the GPU) on the arena a, the output arena out, the ctypes task and result arrays.  The kernel may write into the arena only
+    inside the tasks' scratch rings, [scratch_off, scratch_off + 4 * (a16(row bytes) + 16)) as the runners allocate them: every other
+    byte of it -- streams, palettes, padding -- must come back as it went in."""
+    before = a.copy()
+    assert a.ctypes.data % 4 == 0 and out.ctypes.data % 4 == 0  # (an offset's residue mod 4 is its address's: the kernel works in dwords)
+    assert launch(name, a, out, tasks, res, len(tasks), 0, emu=emu) == 0
+    fixed = np.ones(len(a), dtype=bool)
+    for t in tasks:
+        fixed[t.scratch_off: t.scratch_off + 4 * (_a16(R.row_bytes(t.width, t.color_type, t.depth)) + 16)] = False
+    assert np.array_equal(a[fixed], before[fixed]), ("the arena was written outside the scratch rings", np.flatnonzero((a != before) & fixed)[:8])
+
+
+def assert_fill_outside(out, spans, fill):
+    """every byte of the output arena outside the images' (offset, size) spans -- the 16-byte gaps, the tail -- keeps its fill"""
+    untouched = np.ones(len(out), dtype=bool)
+    for off, size in spans:
+        untouched[off: off + size] = False
+    assert (out[untouched] == fill).all(), ("bytes outside the images were written", np.flatnonzero(untouched & (out != fill))[:8])
+
+
+def run_images(imgs, shift=0, placed=None):
+    """imgs: [dict(samples, ct, depth, interlace, filters, key, pal (n, 3), trns)] -> [(status list, rgba)].  shift: every image's
+    scanline bytes start this many bytes behind a multiple of 16; placed: a list that receives every task's stream_off"""
     arena = bytearray(64)
     tasks, owners, rgba_offs = [], [], []
     rgba_total = 0
@@ -56,8 +83,9 @@ def run_images(imgs):
         if ct == 3:
             pal_off = len(arena)
             arena += R.full_palette(im["pal"], im.get("trns", b"")).tobytes()
+        arena += bytes(shift)
         base = len(arena)
-        arena += stream + bytes(_a16(len(stream)) - len(stream) + 32)
+        arena += stream + bytes(_a16(shift + len(stream)) - shift - len(stream) + 32)
         rgba_offs.append(rgba_total)
         pos = 0
         for x0, y0, dx, dy, wp, hp in R.passes(w, h, il):
@@ -88,7 +116,10 @@ def run_images(imgs):
     n = len(tasks)
     T = (SpecTask * n)(*tasks)
     res = (SpecResult * n)()
-    assert _emu().emu_png_spec_defilter_batch(a.ctypes.data, rgba.ctypes.data, T, res, n) == 0
+    launch_defilter("png_spec_defilter", a, rgba, T, res, _emu)
+    assert_fill_outside(rgba, [(rgba_offs[i], 4 * im["samples"].shape[0] * im["samples"].shape[1]) for i, im in enumerate(imgs)], 0xEE)
+    if placed is not None:
+        placed.extend(t.stream_off for t in tasks)
     out = []
     for i, im in enumerate(imgs):
         h, w = im["samples"].shape[:2]
@@ -132,8 +163,8 @@ FORMATS = [(0, 1), (0, 2), (0, 4), (0, 8), (0, 16), (2, 8), (2, 16), (3, 1), (3,
            (6, 8), (6, 16)]
 
 
-def _check(imgs):
-    for im, (st, px) in zip(imgs, run_images(imgs)):
+def _check(imgs, **kw):
+    for im, (st, px) in zip(imgs, run_images(imgs, **kw)):
         assert all(s == (0, 0xFFFFFFFF) for s in st), (im["ct"], im["depth"], im["samples"].shape, st)
         exp = expected(im)
         assert np.array_equal(px, exp), (im["ct"], im["depth"], im["samples"].shape, im.get("interlace"),
@@ -166,6 +197,79 @@ def test_heights_across_bands(h):
     imgs = [_image(rng, 45, h, 6, 16, 0, None), _image(rng, 70, h, 0, 1, 0, 4), _image(rng, 33, h, 2, 8, 1, None),
             _image(rng, 19, h, 3, 8, 0, 3)]
     _check(imgs)
+
+
+# ---- past the ring wrap, long rows, stream alignment: the shapes at which the hand-over between the wavefronts can go wrong ----------
+# (shared with the batteries of the other three store stages: tests/test_emu_png_out_format.py, _planar.py, _labels.py)
+
+GROUP_BYTES = {1: 8, 2: 8, 3: 12, 4: 16, 6: 12, 8: 16}  # filter unit -> bytes per group (png_spec_kernel.inc: PngSpecShape<BPP>::GB)
+# every filter unit the kernel is instantiated for: 1 (sub-byte and 8-bit), 2, 3, 4, 6, 8
+UNIT_FORMATS = [(0, 1), (0, 4), (3, 8), (0, 16), (4, 8), (2, 8), (6, 8), (2, 16), (6, 16)]
+WRAP_HEIGHTS = [256, 257, 321]  # 4, 5 and 6 bands of 64 rows: bands 4 and 5 take the ring rows of bands 0 and 1 (PNG_SPEC_NWD = 4)
+LONG_FORMATS = [(0, 4), (4, 8), (2, 8), (6, 8), (2, 16), (6, 16)]  # one format per filter unit
+LONG_NGROUPS = [8, 9, 63, 64, 65, 72]  # on both sides of PNG_SPEC_BLOCK = 8 and of the 63 steps that lane 63 runs behind lane 0
+
+
+def ngroups(w, ct, depth):
+    return -(-R.row_bytes(w, ct, depth) // GROUP_BYTES[R.bpp_f(ct, depth)])
+
+
+def _widest(ct, depth, rb):
+    """the widest row of at most rb bytes"""
+    return rb * 8 // (R.CHANNELS[ct] * depth)
+
+
+def wrap_images(rng, h, ct, depth):
+    """images of h rows whose rows are one group and three groups long, each also with a partial last group (sub-byte samples:
+    with a partial last byte too), under filter 4, 3 and 2 on every row and under the default mix, so that every band edge is crossed
+    by each filter that reads the row above; for sub-byte samples also an Adam7 image whose seventh pass has h + 1 rows"""
+    unit = R.bpp_f(ct, depth)
+    gb = GROUP_BYTES[unit]
+    sub = int(depth < 8)
+    full1, part1 = _widest(ct, depth, gb), _widest(ct, depth, gb - unit) - sub
+    full3, part3 = _widest(ct, depth, 3 * gb), _widest(ct, depth, 3 * gb - unit) - sub
+    assert [ngroups(w, ct, depth) for w in (full1, part1, full3, part3)] == [1, 1, 3, 3]
+    assert R.row_bytes(full1, ct, depth) == gb and R.row_bytes(full3, ct, depth) == 3 * gb
+    assert R.row_bytes(part1, ct, depth) % gb and R.row_bytes(part3, ct, depth) % gb and -(-h // 64) >= 4
+    imgs = [_image(rng, w, h, ct, depth, 0, ft)
+            for ft, ws in ((4, (full1, part3)), (3, (part1, full3)), (2, (full1, part3)), (None, (part1, full3))) for w in ws]
+    if sub:
+        imgs.append(_image(rng, 11, 2 * h + 3, ct, depth, 1, None))
+        assert R.passes(11, 2 * h + 3, 1)[6][5] == h + 1 > 256
+    return imgs
+
+
+def long_image(rng, ct, depth, ng):
+    """130 rows (three bands) of ng groups, the last one partial where ng is odd, Paeth on every row: one wrong "up" byte at a band
+    edge propagates to the end of the image"""
+    unit = R.bpp_f(ct, depth)
+    w = _widest(ct, depth, ng * GROUP_BYTES[unit] - (unit if ng % 2 else 0))
+    assert ngroups(w, ct, depth) == ng
+    return _image(rng, w, 130, ct, depth, 0, 4)
+
+
+@pytest.mark.parametrize("ct,depth", UNIT_FORMATS)
+@pytest.mark.parametrize("h", WRAP_HEIGHTS)
+def test_heights_past_the_ring_wrap(h, ct, depth):
+    """four, five and six bands: the fifth and sixth band's last rows go where the first and second band's were"""
+    _check(wrap_images(np.random.default_rng(h * 100 + ct * 10 + depth), h, ct, depth))
+
+
+@pytest.mark.parametrize("ng", LONG_NGROUPS)
+@pytest.mark.parametrize("ct,depth", LONG_FORMATS)
+def test_long_rows_across_bands(ct, depth, ng):
+    """rows longer than one load phase: the wavefront of the band below waits in mid-row for the groups it needs next"""
+    _check([long_image(np.random.default_rng(ng * 100 + ct * 10 + depth), ct, depth, ng)])
+
+
+@pytest.mark.parametrize("shift", [0, 1, 2, 3])
+def test_stream_alignment(shift):
+    """the same two-band images of the filter units 1, 3 and 6 with their scanline bytes at every residue mod 4"""
+    rng = np.random.default_rng(31)
+    imgs = [_image(rng, 21, 66, ct, depth, 0, ft) for ct, depth in ((0, 2), (2, 8), (2, 16)) for ft in (None, 4)]
+    placed = []
+    _check(imgs, shift=shift, placed=placed)
+    assert len(placed) == len(imgs) and all(p & 3 == shift for p in placed), placed
 
 
 def test_bad_filter_byte_and_palette_index():
