@@ -275,6 +275,15 @@ static bool no_handback()
     return e && *e && !(e[0] == '0' && e[1] == 0);
 }
 
+// DEBIG_DEFILTER_NO_REDO (include/debig_hip.h): the one-workgroup launch (only_redo) behind a several-workgroups de-filter
+// launch is left out, so an image that launch gave up stays good = 0, bad_row = PNG_ROW_REDO.  Read at every call, like
+// DEBIG_NO_HANDBACK.
+static bool defilter_no_redo()
+{
+    const char *e = getenv("DEBIG_DEFILTER_NO_REDO");
+    return e && *e && !(e[0] == '0' && e[1] == 0);
+}
+
 // workgroups of a tensor-stage launch (the APNG compositing, the resize / warp / label / tone / blur launchers below): one per
 // task up to 2^20, the kernels loop over the rest.  DEBIG_STAGE_GRID (include/debig_hip.h; tests: read at every call) lowers it.
 static uint32_t stage_grid(uint32_t n_tasks)
@@ -718,7 +727,9 @@ int debig_hip_png_defilter_batch(const void *d_streams_arena, void *d_rgba_arena
             // grid starts): a workgroup that waited in vain gave its image up as REDO after some tens of milliseconds,
             // and this launch -- one workgroup per image, nothing to wait for across workgroups -- decodes exactly
             // those images again.  Normally every workgroup finds nothing to do and leaves at once (a few us).
-            if (n <= 64u)
+            // (DEBIG_DEFILTER_NO_REDO: not launched -- what was given up stays REDO, everything else is the launch above's own work)
+            if (defilter_no_redo()) {
+            } else if (n <= 64u)
                 hipLaunchKernelGGL((debig_png_defilter_kernel<16, 6>), dim3(n), dim3(1024), 0, s, (const uint8_t *)d_streams_arena,
                                    (uint8_t *)d_rgba_arena, d_images, d_results, n, 1u, (uint32_t *)nullptr, 1u);
             else

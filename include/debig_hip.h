@@ -305,7 +305,14 @@ typedef struct debig_png_result {
  * does not hold them all at once), the bands of 64 rows handed from wavefront to wavefront through memory; images whose
  * workgroups turn out not to be resident together are decoded again by one workgroup inside the same call (never
  * failed).  That mode uses a per-device scratch of progress words shared by the callers of the device (calls are
- * ordered on it by events: such a call cannot be captured into a graph). */
+ * ordered on it by events: such a call cannot be captured into a graph).
+ * DEBIG_DEFILTER_NO_REDO (environment variable, read at every call like DEBIG_NO_HANDBACK; tests): set to anything but the
+ * empty string or "0", that second launch -- one workgroup per image over the images the several-workgroups launch gave
+ * up -- is left out.  An image given up then keeps what the first launch wrote: good = 0, bad_row = 0xfffffffd
+ * (PNG_ROW_REDO), pixels unspecified; every other image is the several-workgroups launch's own work, which is what the
+ * switch is for: without it nothing in the results says which launch produced the pixels.  Calls that take the
+ * one-workgroup kernels from the start (more than 128 images, or a device that does not hold two workgroups per image) do
+ * not read it.  debig_hip_png_decode_fused_batch has its own REDO launch and does not read it either. */
 int debig_hip_png_defilter_batch(const void *d_streams_arena, void *d_rgba_arena,
                                  const debig_png_image *d_images, debig_png_result *d_results,
                                  uint32_t n, void *hip_stream);

@@ -103,8 +103,9 @@ def test_defilter_several_workgroups_per_image(gpu_device, oracle, n):
     """Few images: the de-filter spreads one image over several workgroups (csrc/png_kernel.inc, MWG:
     8 x 4 wavefronts per image up to 32 images, 4 x 4 up to 64, 2 x 8 up to 128), bands handed from CU to
     CU through memory.  Odd widths (cache lines of the handed-over row straddle the groups), every
-    filter type, RGB and palette images, 200+ rows (several rounds of bands per slot) -- against the
-    oracle; one image with a filter byte > 4 fails alone (the failure flag is global)."""
+    filter type, RGB and palette images, up to 333 rows: at most 6 bands over 64, 32 or 16 slots, so NO slot
+    takes a second band here (the wrap of the band ring is tests/test_gpu_png_defilter_battery.py's) -- against
+    the oracle; one image with a filter byte > 4 fails alone (the failure flag is global)."""
     from debigulator_amd.png_device import DevicePngBatch
 
     rng = np.random.default_rng(n)

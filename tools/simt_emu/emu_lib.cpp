@@ -39,6 +39,13 @@ static bool emu_no_handback()
     return e && *e && !(e[0] == '0' && e[1] == 0);
 }
 
+/* DEBIG_DEFILTER_NO_REDO (include/debig_hip.h), as the shim reads it: no one-workgroup launch behind the several-workgroups de-filter */
+static bool emu_defilter_no_redo()
+{
+    const char *e = getenv("DEBIG_DEFILTER_NO_REDO");
+    return e && *e && !(e[0] == '0' && e[1] == 0);
+}
+
 /* the lengths huff_slow's canonical probe has tried since the last reset, over every kernel of this library */
 extern "C" unsigned long long emu_slow_probes(int reset)
 {
@@ -250,24 +257,35 @@ extern "C" int emu_png_defilter_batch_w(const void *streams_arena, void *rgba_ar
                results, n);
     return 0;
 }
-/* the several-workgroups-per-image mode as the shim launches it: G workgroups of 4 wavefronts per image, then the
- * one-workgroup pass over the images given up as REDO.  The emulator runs ONE workgroup at a time, i.e. the
- * workgroups of an image are never resident together: every cross-workgroup wait fails, which is exactly the
- * situation the REDO pass exists for.  *n_redo = images the first launch gave up. */
-extern "C" int emu_png_defilter_mwg(const void *streams_arena, void *rgba_arena, const debig_png_image *images,
-                                    debig_png_result *results, uint32_t n, uint32_t g, uint32_t *n_redo)
+/* the several-workgroups-per-image mode as the shim launches it: G workgroups of wpw = 4 or 8 wavefronts per image, then the
+ * one-workgroup pass over the images given up as REDO (left out under DEBIG_DEFILTER_NO_REDO, as in the shim).  The emulator
+ * runs ONE workgroup at a time, i.e. the workgroups of an image are never resident together: every cross-workgroup wait
+ * fails, which is exactly the situation the REDO pass exists for.  *n_redo = images the first launch gave up. */
+extern "C" int emu_png_defilter_mwg_w(const void *streams_arena, void *rgba_arena, const debig_png_image *images,
+                                      debig_png_result *results, uint32_t n, uint32_t g, uint32_t wpw, uint32_t *n_redo)
 {
+    if ((wpw != 4u && wpw != 8u) || g == 0 || g * wpw > PNG_GSYNC_STRIDE - 16u) return -1;
     uint32_t *gsync = (uint32_t *)calloc((size_t)n * PNG_GSYNC_STRIDE, sizeof(uint32_t));
-    EMU_LAUNCH((debig_png_defilter_kernel<4, 16, true, true>), n * g, 256, (const uint8_t *)streams_arena, (uint8_t *)rgba_arena, images,
-               results, n, g, gsync, 0u);
+    if (wpw == 8u)
+        EMU_LAUNCH((debig_png_defilter_kernel<8, 16, true, true>), n * g, 512, (const uint8_t *)streams_arena, (uint8_t *)rgba_arena, images,
+                   results, n, g, gsync, 0u);
+    else
+        EMU_LAUNCH((debig_png_defilter_kernel<4, 16, true, true>), n * g, 256, (const uint8_t *)streams_arena, (uint8_t *)rgba_arena, images,
+                   results, n, g, gsync, 0u);
     uint32_t redo = 0;
     for (uint32_t i = 0; i < n; i++) redo += results[i].good == 0 && results[i].bad_row == PNG_ROW_REDO;
     if (n_redo) *n_redo = redo;
-    EMU_LAUNCH((debig_png_defilter_kernel<16, 6>), n, 1024, (const uint8_t *)streams_arena, (uint8_t *)rgba_arena, images, results, n,
-               1u, (uint32_t *)nullptr, 1u);
+    if (!emu_defilter_no_redo())
+        EMU_LAUNCH((debig_png_defilter_kernel<16, 6>), n, 1024, (const uint8_t *)streams_arena, (uint8_t *)rgba_arena, images, results, n,
+                   1u, (uint32_t *)nullptr, 1u);
     EMU_LAUNCH(debig_png_p3_kernel, n, PNG_P3_THREADS, (const uint8_t *)streams_arena, (uint8_t *)rgba_arena, images, results, n);
     free(gsync);
     return 0;
+}
+extern "C" int emu_png_defilter_mwg(const void *streams_arena, void *rgba_arena, const debig_png_image *images,
+                                    debig_png_result *results, uint32_t n, uint32_t g, uint32_t *n_redo)
+{
+    return emu_png_defilter_mwg_w(streams_arena, rgba_arena, images, results, n, g, 4u, n_redo);
 }
 /* SURVEY.md 8(f) row 1, as debig_hip_png_decode_fused_batch launches it: plan, the fused kernel (scan | LZ77 | two de-filter
  * wavefronts per image), the one-kernel inflate for what the scan handed back, the one-workgroup de-filter for the images
