@@ -1331,6 +1331,73 @@ def png_label_distance(labels, to=None, cap=None, out="squared", status=None):
     return res
 
 
+_PNG_COMPONENTS_IDS = {"first": 0, "consecutive": 1}  # DEBIG_PNG_COMPONENTS_FIRST / _CONSECUTIVE
+
+
+def png_label_components(labels, connectivity=4, background=None, ids="consecutive", status=None):
+    """connected components of a dense (N, H, W) label tensor on the GPU (include/decode_png.h: debig_png_label_components, which
+    has the rule) -> (a NEW torch.int32 device tensor (N, H, W), a numpy int64 array (N,) of K, the components of every image):
+    what skimage.measure.label(x, background=..., connectivity=1|2) gives image by image on the host, and scipy.ndimage.label on a
+    binary mask -- instance ids from a class map, split "stuff" regions, specks to drop, a border weight per cell, per-instance boxes.
+    Two elements are neighbours iff they are adjacent (connectivity=4: by an edge; 8: by an edge or a corner) AND hold the same
+    value; a component is a class of the transitive closure.  Elements are compared whole (exact for packed colours and int64
+    ids).  background=None: every element belongs to a component; background=<int>: the elements equal to it belong to none (a
+    value the dtype cannot hold matches nothing).  ids="consecutive": the components are numbered 1 .. K in the raster order of
+    their first elements, scipy.ndimage.label's numbering, background 0; ids="first": every element gets y * W + x of its
+    component's first element in raster order, background -1 -- canonical, and one launch less.  labels: a contiguous tensor of
+    torch.uint8, uint16 (or int16, read as the uint16 bits: background is then 0 .. 65535), int32 or int64 on the current device --
+    the tensor of png_decode_batch_labels / png_decode_batch_color_labels under any of their maps, or one made otherwise.  A warp
+    tears objects apart and a crop cuts them, so the documented use is labels -> png_label_components -> png_label_stats(ids, K + 1):
+    decode (and warp) first, label the tensor that came back, and png_label_stats(ids, int(K.max()) + 1) then has every instance's
+    pixel count and tight box in record k = 1 .. K, with nothing in "other".  status: None, or one entry per image: an image whose
+    entry is not 0 is not looked at and comes back as zeros with K = 0.  Union-find in three (first) or five launches; its work
+    depends on the data (include/decode_png.h).  The call waits for the work queued on the device before it, and for its own."""
+    import torch
+
+    if connectivity not in (4, 8) or isinstance(connectivity, bool):
+        raise ValueError(f"connectivity must be 4 or 8, not {connectivity!r}")
+    if background is not None and (isinstance(background, bool) or not isinstance(background, (int, np.integer)) or
+                                   not -2 ** 63 <= int(background) < 2 ** 63):
+        raise ValueError(f"background must be None or an integer that fits 64 bits, not {background!r}")
+    if not isinstance(ids, str) or ids not in _PNG_COMPONENTS_IDS:
+        raise ValueError(f"ids must be one of {sorted(_PNG_COMPONENTS_IDS)}, not {ids!r}")
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be a (N, H, W) tensor")
+    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = 1
+    if labels.dtype not in codes:
+        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
+    if not labels.is_contiguous():
+        raise ValueError("labels must be contiguous")
+    if labels.device.type != "cuda":
+        raise ValueError("labels must be on the GPU")
+    n, H, W = (int(v) for v in labels.shape)
+    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
+    if status is not None and len(status) != n:
+        raise ValueError("status needs one entry per image")
+    res = torch.empty((n, H, W), dtype=torch.int32, device=labels.device)
+    if n == 0:
+        return res, np.zeros(0, np.int64)
+    L = _png_spec_lib()
+    _png_device(L, labels.device)
+    L.debig_png_label_components.restype = C.c_int
+    L.debig_png_label_components.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]
+    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
+    for i in ([] if status is None else [i for i in range(n) if st[i] != 0]):  # the images the library leaves alone, and only they
+        res[i].zero_()
+    counts = (C.c_uint32 * n)()
+    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
+    rc = L.debig_png_label_components(labels.data_ptr(), res.data_ptr(), n, W, H, codes[labels.dtype], int(connectivity),
+                                      0 if background is None else 1, 0 if background is None else int(background),
+                                      _PNG_COMPONENTS_IDS[ids], st, counts)
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"debig_png_label_components rejected its arguments ({rc})")
+    N.check(rc, "debig_png_label_components")
+    return res, np.array(list(counts), np.int64)
+
+
 class PngLabelDesc(C.Structure):  # include/decode_png.h: debig_png_label_desc
     _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("dtype", C.c_uint32), ("reserved", C.c_uint32),
                 ("lut", C.POINTER(C.c_int32))]

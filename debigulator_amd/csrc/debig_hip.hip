@@ -29,6 +29,7 @@
 #include "png_label_stats_kernel.inc"
 #include "png_label_boundary_kernel.inc"
 #include "png_label_distance_kernel.inc"
+#include "png_label_components_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -1014,6 +1015,47 @@ int debig_hip_png_label_distance_cols_batch(const void *d_g, void *d_out, const 
 {
     return launch_stage(debig_png_label_distance_cols_kernel, LDC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_g, (uint8_t *)d_out,
                         d_tasks);
+}
+
+// connected components of a dense label tensor (png_label_components_kernel.inc), one workgroup per run of rows in all five: the
+// runs of equal values into the parent plane ...
+int debig_hip_png_label_components_rows_batch(const void *d_labels, void *d_parent, const debig_png_label_components_task *d_tasks,
+                                              uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_components_rows_kernel, LCC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_labels,
+                        (uint8_t *)d_parent, d_tasks);
+}
+
+// ... the unions between adjacent rows ...
+int debig_hip_png_label_components_merge_batch(const void *d_labels, void *d_parent, const debig_png_label_components_task *d_tasks,
+                                               uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_components_merge_kernel, LCC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_labels,
+                        (uint8_t *)d_parent, d_tasks);
+}
+
+// ... the roots of every task ...
+int debig_hip_png_label_components_count_batch(const void *d_parent, void *d_counts, const debig_png_label_components_task *d_tasks,
+                                               uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_components_count_kernel, LCC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_parent,
+                        (uint32_t *)d_counts, d_tasks);
+}
+
+// ... their numbers 1 .. K in raster order ...
+int debig_hip_png_label_components_number_batch(const void *d_parent, const void *d_counts, void *d_out,
+                                                const debig_png_label_components_task *d_tasks, uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_components_number_kernel, LCC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_parent,
+                        (const uint32_t *)d_counts, (uint8_t *)d_out, d_tasks);
+}
+
+// ... and every element's id
+int debig_hip_png_label_components_finish_batch(const void *d_parent, void *d_out, const debig_png_label_components_task *d_tasks,
+                                                uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_label_components_finish_kernel, LCC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_parent,
+                        (uint8_t *)d_out, d_tasks);
 }
 
 // inflate -> de-filter in one kernel (png_fused_kernel.inc).  Per group of at most SPLIT_GROUP

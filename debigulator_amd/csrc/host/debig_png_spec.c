@@ -2128,6 +2128,86 @@ done:
     return rc;
 }
 
+/* ---- debig_png_label_components: connected components of a dense label tensor (decode_png.h) ------------------------------------- */
+
+_Static_assert(sizeof(debig_png_label_components_task) == 80 && offsetof(debig_png_label_components_task, w) == 32,
+               "four 64-bit fields, twelve uint32");
+
+DEBIG_API int debig_png_label_components(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
+                                         uint32_t connectivity, uint32_t use_background, int64_t background, uint32_t ids,
+                                         const uint32_t *status, uint32_t *counts)
+{
+    if (n == 0) return 0;
+    if (!d_labels || !d_out || dtype > DEBIG_PNG_L_I64 || (connectivity != 4u && connectivity != 8u) || ids > DEBIG_PNG_COMPONENTS_CONSECUTIVE ||
+        out_w == 0 || out_w > 16384u || out_h == 0 || out_h > 16384u)
+        return DEBIG_PNG_BAD_ARG;
+    const uint32_t es = 1u << dtype;
+    if (((uintptr_t)d_labels & (es - 1u)) || ((uintptr_t)d_out & 3u)) return DEBIG_PNG_BAD_ARG;
+    const uint64_t img = (uint64_t)out_w * out_h, in_bytes = (uint64_t)n * img * es, out_bytes = (uint64_t)n * img * 4u;
+    if ((uintptr_t)d_out < (uintptr_t)d_labels + in_bytes && (uintptr_t)d_labels < (uintptr_t)d_out + out_bytes) return DEBIG_PNG_BAD_ARG;
+    if (counts) memset(counts, 0, (size_t)n * sizeof *counts);
+    /* a task: a run of whole rows of at most DEBIG_PNG_LABEL_COMPONENTS_ELEMS elements, the same cut for all five launches */
+    const uint32_t run = out_w >= DEBIG_PNG_LABEL_COMPONENTS_ELEMS ? 1u : DEBIG_PNG_LABEL_COMPONENTS_ELEMS / out_w;
+    const uint64_t per = (out_h + run - 1u) / run;
+    uint64_t n_good = 0;
+    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
+    if (n_good * per >= 0x7fffffffu) return 2;
+    if (n_good == 0) return 0;
+    int rc = 2;
+    const uint64_t n_tasks = n_good * per;
+    debig_png_label_components_task *tasks = (debig_png_label_components_task *)calloc((size_t)n_tasks, sizeof *tasks), *t = tasks;
+    uint32_t *task_counts = (uint32_t *)malloc((size_t)n_tasks * sizeof *task_counts);
+    /* the parent planes of the images that are looked at, the tasks' counts behind them: space only */
+    dev_table tab[2] = {{NULL, n_good * img * 4u, 0}, {NULL, n_tasks * sizeof(uint32_t), 0}};
+    dev_tables_place(tab, 2);
+    if (!tasks || !task_counts) goto done;
+    uint64_t k = 0; /* the image's place among the good ones */
+    for (uint32_t i = 0; i < n; i++) {
+        if (status && status[i] != 0) continue;
+        for (uint32_t y0 = 0; y0 < out_h; y0 += run, t++) {
+            t->label_off = (uint64_t)i * img * es;
+            t->parent_off = k * img * 4u;
+            t->out_off = (uint64_t)i * img * 4u;
+            t->background = background;
+            t->w = out_w;
+            t->h = out_h;
+            t->row0 = y0;
+            t->rows = out_h - y0 < run ? out_h - y0 : run;
+            t->dtype = dtype;
+            t->connectivity = connectivity;
+            t->use_background = use_background != 0;
+            t->ids = ids;
+            t->count_first = (uint32_t)(k * per);
+            t->count_idx = (uint32_t)(t - tasks);
+        }
+        k++;
+    }
+    debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, tab, 2, &rc);
+    if (!c) goto done;
+    const debig_png_label_components_task *d_tasks = (const debig_png_label_components_task *)c->rsz_tasks.ptr;
+    void *d_parent = c->rsz_weights.ptr, *d_counts = (uint8_t *)c->rsz_weights.ptr + tab[1].off;
+    if ((rc = debig_hip_png_label_components_rows_batch(d_labels, d_parent, d_tasks, (uint32_t)n_tasks, NULL)) ||
+        (rc = debig_hip_png_label_components_merge_batch(d_labels, d_parent, d_tasks, (uint32_t)n_tasks, NULL)) ||
+        (rc = debig_hip_png_label_components_count_batch(d_parent, d_counts, d_tasks, (uint32_t)n_tasks, NULL)) ||
+        (ids == DEBIG_PNG_COMPONENTS_CONSECUTIVE &&
+         (rc = debig_hip_png_label_components_number_batch(d_parent, d_counts, d_out, d_tasks, (uint32_t)n_tasks, NULL))) ||
+        (rc = debig_hip_png_label_components_finish_batch(d_parent, d_out, d_tasks, (uint32_t)n_tasks, NULL)) ||
+        (rc = debig_hip_memcpy_d2h(task_counts, d_counts, tab[1].bytes, NULL)) || (rc = debig_hip_stream_sync(NULL)))
+        goto done;
+    if (counts) {
+        k = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            if (status && status[i] != 0) continue;
+            for (uint64_t j = 0; j < per; j++) counts[i] += task_counts[k * per + j];
+            k++;
+        }
+    }
+done:
+    free(tasks);
+    free(task_counts);
+    return rc;
+}
+
 /* ---- the affine warp of the tensor and the label decode (decode_png.h) ------------------------------------------------------ */
 
 #define WARP_TASK_PIXELS 4096u /* output pixels of one warp task (a run of whole rows; one row when it is wider): 16 per lane */

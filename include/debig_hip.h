@@ -204,7 +204,8 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * tasks -- debig_hip_apng_composite_batch, debig_hip_png_resize_batch / _resize_alpha / _resize_cubic / _resize_color,
  * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp,
  * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur, _label_stats and
- * _label_boundary, _label_distance_rows / _label_distance_cols --
+ * _label_boundary, _label_distance_rows / _label_distance_cols -- and the five launchers of the label components,
+ * _label_components_rows / _merge / _count / _number / _finish --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -1036,6 +1037,55 @@ int debig_hip_png_label_distance_rows_batch(const void *d_labels, void *d_g, con
                                             uint32_t n_tasks, void *hip_stream);
 int debig_hip_png_label_distance_cols_batch(const void *d_g, void *d_out, const debig_png_label_distance_cols_task *d_tasks, uint32_t n_tasks,
                                             void *hip_stream);
+
+/* ---- connected components of a dense label tensor (csrc/png_label_components_kernel.inc, behind debig_png_label_components in
+ * decode_png.h, which has the rule): union-find over the PARENT PLANE d_parent, one uint32 per element of the image (w x h, dense):
+ * the index y * w + x of an element of the same component that is not larger than the element's own (a ROOT holds its own), or
+ * 0xffffffff for a background element.  Five launches on one stream share one TASK, a run of whole rows of one image for one
+ * workgroup of 256 lanes: rows x w <= DEBIG_PNG_LABEL_COMPONENTS_ELEMS, or one row.
+ *   ROWS    reads the labels and writes every slot of its rows: the start of the element's horizontal run of equal values.
+ *   MERGE   reads the labels of its rows and of the row above its first one, and joins the trees of neighbours in rows y - 1 and y
+ *           for every row y > 0 of the task, WITH ATOMICS ON SLOTS ANYWHERE IN THE IMAGE'S PLANE.  It is the one launch whose
+ *           workgroups write one structure together; afterwards the roots are the components' smallest elements, whatever the order.
+ *           The plane after it is not a pure function of the input, what the next three make of it is.
+ *   COUNT   d_counts[count_idx] = the roots in the task's rows.  The plane is only read from here on.
+ *   NUMBER  (ids CONSECUTIVE only) every root of the task gets out = 1 + its rank in raster order among the image's roots: the sum
+ *           of d_counts[count_first .. count_idx) plus its rank in the task.  The task sums those counts itself.
+ *   FINISH  ids FIRST: out = the root above the element, background -1.  CONSECUTIVE: a non-root gets the out of its root,
+ *           background 0; roots are left as NUMBER wrote them.
+ * d_out is int32, 4 bytes per element.  The work of MERGE and FINISH depends on the data and on the race (the depth of the trees).
+ * Every value read from the plane is checked before it is an index: one that is not below w x h, or above the slot it came from,
+ * makes the slot a root.  No launch waits for another workgroup.  d_parent and d_counts must not overlap d_labels, d_out or each
+ * other.  A task is skipped by every launch when dtype is above 3, connectivity is neither 4 nor 8, use_background or ids is above 1,
+ * w or h is 0 or above 16384, rows is 0 or the run leaves the image, rows x w exceeds the cap with rows above 1, count_first is above
+ * count_idx or more than 16383 below it, or an offset or address is not a multiple of the element size (of 4 for the plane, the
+ * output and the counts). */
+#define DEBIG_PNG_LABEL_COMPONENTS_ELEMS 16384u
+typedef struct debig_png_label_components_task {
+    uint64_t label_off;     /* the image's first element, in bytes rel. to d_labels                                            */
+    uint64_t parent_off;    /* the image's first slot, in bytes rel. to d_parent                                               */
+    uint64_t out_off;       /* the image's first output element, in bytes rel. to d_out                                        */
+    int64_t background;     /* use_background 1: the elements equal to it belong to no component (a value the dtype cannot hold: none) */
+    uint32_t w, h;          /* the image                                                                                       */
+    uint32_t row0, rows;    /* the run of rows                                                                                 */
+    uint32_t dtype;         /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                         */
+    uint32_t connectivity;  /* 4: edge neighbours, 8: edge and corner neighbours                                               */
+    uint32_t use_background;/* 0, 1                                                                                            */
+    uint32_t ids;           /* decode_png.h DEBIG_PNG_COMPONENTS_FIRST 0, _CONSECUTIVE 1                                       */
+    uint32_t count_idx;     /* the task's word in d_counts                                                                     */
+    uint32_t count_first;   /* the word of the image's first task: the image's tasks have consecutive words, in row order      */
+    uint32_t reserved[2];
+} debig_png_label_components_task;
+int debig_hip_png_label_components_rows_batch(const void *d_labels, void *d_parent, const debig_png_label_components_task *d_tasks,
+                                              uint32_t n_tasks, void *hip_stream);
+int debig_hip_png_label_components_merge_batch(const void *d_labels, void *d_parent, const debig_png_label_components_task *d_tasks,
+                                               uint32_t n_tasks, void *hip_stream);
+int debig_hip_png_label_components_count_batch(const void *d_parent, void *d_counts, const debig_png_label_components_task *d_tasks,
+                                               uint32_t n_tasks, void *hip_stream);
+int debig_hip_png_label_components_number_batch(const void *d_parent, const void *d_counts, void *d_out,
+                                                const debig_png_label_components_task *d_tasks, uint32_t n_tasks, void *hip_stream);
+int debig_hip_png_label_components_finish_batch(const void *d_parent, void *d_out, const debig_png_label_components_task *d_tasks,
+                                                uint32_t n_tasks, void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

@@ -973,6 +973,40 @@ int debig_png_label_boundary(const void *d_labels, void *d_out, uint32_t n, uint
 int debig_png_label_distance(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
                              uint32_t sites, int64_t value, uint32_t cap, uint32_t format, const uint32_t *status /* host, may be NULL */);
 
+/* ---- connected components of a label tensor: instance ids from a class map, split regions, specks, per-cell weights -------------------
+ * What skimage.measure.label(x, background=..., connectivity=1|2) does on the host, and scipy.ndimage.label on a binary mask with
+ * background 0.  A warp tears an object in two and a crop cuts one into pieces, so components are found in the warped map:
+ * d_labels is a dense (n, out_h, out_w) tensor of DEBIG_PNG_L_* elements in device memory, as for debig_png_label_stats.
+ * THE RULE.  Elements are compared whole (3 and 2^32 + 3 differ, -1 and 255 differ).  connectivity 4: edge neighbours; 8: edge and
+ * corner neighbours.  Two elements of an image are NEIGHBOURS iff they are adjacent under the connectivity AND hold the same value;
+ * a COMPONENT is a class of the transitive closure.  use_background 1: the elements equal to `background` belong to no component
+ * (uint8 and uint16 elements are 0 .. 255 / 0 .. 65535, int32 and int64 elements are signed; a `background` that the dtype cannot
+ * hold is not an error: nothing equals it); use_background 0: every element belongs to a component.  The FIRST of a component is the
+ * smallest y * out_w + x over its elements.  d_out is a dense int32 (n, out_h, out_w) tensor:
+ *   - DEBIG_PNG_COMPONENTS_FIRST:       every element gets the FIRST of its component, background -1: a canonical id that needs no
+ *     numbering pass;
+ *   - DEBIG_PNG_COMPONENTS_CONSECUTIVE: the components are numbered 1 .. K in increasing order of their FIRST, background 0:
+ *     scipy.ndimage.label's numbering.
+ * counts (host, may be NULL): counts[i] = K of image i, under both modes.  The result is a pure function of the input, whatever the
+ * cut, the grid and the order of the tasks.  With components numbered 1 .. K, debig_png_label_stats(d_out, ..., num_ids K + 1) gives
+ * every instance's pixel count and tight box.
+ * The slot in d_out of an image whose status[i] != 0 is not written and its count is 0 (status NULL: no image is left out).
+ * n == 0: returns 0 and touches nothing.  DEBIG_PNG_BAD_ARG, before any device work, for d_labels or d_out NULL with n > 0, d_labels
+ * not aligned to its element size, d_out not aligned to 4, dtype above DEBIG_PNG_L_I64, connectivity other than 4 and 8, ids above
+ * CONSECUTIVE, out_w or out_h 0 or above 16384, and d_out's byte range overlapping d_labels's.  The call makes a parent plane of 4
+ * bytes per element and a count per task in the context's arenas and launches debig_hip_png_label_components_rows_batch, _merge,
+ * _count, under CONSECUTIVE _number, and _finish (union-find; its work is not linear for every input: the depth of the trees depends on
+ * the data and on the race between workgroups), reads the counts back and is synchronous on the library's stream, like
+ * debig_png_label_stats; the caller makes sure that whoever wrote d_labels on another stream has finished.  Otherwise 0 or an error
+ * code of the device layer.  Not thread safe against the tensor decodes of the same process (it uses their arenas).  Not provided:
+ * tolerance-based (fuzzy) connectivity, a minimum-area filter (compose with debig_png_label_stats), 3-D labelling, in-place
+ * operation, host tensors. */
+#define DEBIG_PNG_COMPONENTS_FIRST 0u
+#define DEBIG_PNG_COMPONENTS_CONSECUTIVE 1u
+int debig_png_label_components(const void *d_labels, void *d_out, uint32_t n, uint32_t out_w, uint32_t out_h, uint32_t dtype,
+                               uint32_t connectivity, uint32_t use_background, int64_t background, uint32_t ids,
+                               const uint32_t *status /* host, may be NULL */, uint32_t *counts /* host, may be NULL */);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

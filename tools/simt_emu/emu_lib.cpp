@@ -30,6 +30,7 @@
 #include "../../debigulator_amd/csrc/png_label_stats_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_boundary_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_distance_kernel.inc"
+#include "../../debigulator_amd/csrc/png_label_components_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
@@ -624,5 +625,49 @@ extern "C" int emu_png_label_distance_cols_batch(const void *g, void *out, const
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_label_distance_cols_kernel, grid, LDC_THREADS, (const uint8_t *)g, (uint8_t *)out, tasks, n);
+    return 0;
+}
+
+/* connected components of a dense label tensor (png_label_components_kernel.inc), as debig_hip_png_label_components_*_batch launch
+ * the five kernels (grid as above).  Workgroups run one after the other here: this shows the rule and the bounds, not the races */
+extern "C" int emu_png_label_components_rows_batch(const void *labels, void *parent, const debig_png_label_components_task *tasks, uint32_t n,
+                                                   uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_components_rows_kernel, grid, LCC_THREADS, (const uint8_t *)labels, (uint8_t *)parent, tasks, n);
+    return 0;
+}
+
+extern "C" int emu_png_label_components_merge_batch(const void *labels, void *parent, const debig_png_label_components_task *tasks, uint32_t n,
+                                                    uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_components_merge_kernel, grid, LCC_THREADS, (const uint8_t *)labels, (uint8_t *)parent, tasks, n);
+    return 0;
+}
+
+extern "C" int emu_png_label_components_count_batch(const void *parent, void *counts, const debig_png_label_components_task *tasks, uint32_t n,
+                                                    uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_components_count_kernel, grid, LCC_THREADS, (const uint8_t *)parent, (uint32_t *)counts, tasks, n);
+    return 0;
+}
+
+extern "C" int emu_png_label_components_number_batch(const void *parent, const void *counts, void *out,
+                                                     const debig_png_label_components_task *tasks, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n)
+        EMU_LAUNCH(debig_png_label_components_number_kernel, grid, LCC_THREADS, (const uint8_t *)parent, (const uint32_t *)counts,
+                   (uint8_t *)out, tasks, n);
+    return 0;
+}
+
+extern "C" int emu_png_label_components_finish_batch(const void *parent, void *out, const debig_png_label_components_task *tasks, uint32_t n,
+                                                     uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_label_components_finish_kernel, grid, LCC_THREADS, (const uint8_t *)parent, (uint8_t *)out, tasks, n);
     return 0;
 }

@@ -227,6 +227,9 @@ template <typename T> static inline T atomicAnd(T *p, T v) { T o = *p; *p = o & 
 template <typename T> static inline T atomicAdd(T *p, T v) { T o = *p; *p = o + v; return o; }
 template <typename T> static inline T atomicMin(T *p, T v) { T o = *p; if (v < o) *p = v; return o; }
 template <typename T> static inline T atomicMax(T *p, T v) { T o = *p; if (v > o) *p = v; return o; }
+/* an atomic load with a scope (png_label_components_kernel.inc): workgroups run one after the other here, so every load is one */
+#define __HIP_MEMORY_SCOPE_AGENT 4
+template <typename T> static inline T __hip_atomic_load(const T *p, int, int) { return *p; }
 
 struct uint4 { unsigned x, y, z, w; };
 struct uint2 { unsigned x, y; };
