@@ -1131,6 +1131,60 @@ def _png_stats_ids(num_ids):
     return int(num_ids)
 
 
+def _png_label_code(labels):
+    """the labels of the calls that post-process a dense label tensor -> the DEBIG_PNG_L_* code of their dtype, or ValueError"""
+    import torch
+
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be a (N, H, W) tensor")
+    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = 1
+    if labels.dtype not in codes:
+        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
+    return codes[labels.dtype]
+
+
+def _png_label_input(labels, status):
+    """what follows _png_label_code (a check of the call's own that needs the code stands between the two) -> (n, H, W, the
+    status as a ctypes array or None), or ValueError"""
+    if not labels.is_contiguous():
+        raise ValueError("labels must be contiguous")
+    if labels.device.type != "cuda":
+        raise ValueError("labels must be on the GPU")
+    n, H, W = (int(v) for v in labels.shape)
+    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
+    if status is not None and len(status) != n:
+        raise ValueError("status needs one entry per image")
+    return n, H, W, None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
+
+
+def _png_label_skipped(out, st, src=None):
+    """the images the library leaves alone (a status entry that is not 0), and only they: zeros, or the image of src"""
+    for i in ([] if st is None else [i for i in range(len(st)) if st[i] != 0]):
+        if src is None:
+            out[i].zero_()
+        else:
+            out[i].copy_(src[i])
+
+
+def _png_label_call(name, argtypes, labels, *args):
+    """one C call on a label tensor, which is its first argument -> None; ValueError where the library rejects its arguments"""
+    import torch
+
+    L = _png_spec_lib()
+    _png_device(L, labels.device)
+    fn = getattr(L, name)
+    fn.restype = C.c_int
+    fn.argtypes = argtypes
+    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
+    rc = fn(labels.data_ptr(), *args)
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"{name} rejected its arguments ({rc})")
+    N.check(rc, name)
+
+
 def png_label_stats(labels, num_ids, status=None):
     """per-id pixel counts and bounding boxes of a dense (N, H, W) label tensor on the GPU (include/decode_png.h:
     debig_png_label_stats, which has the rule) -> a numpy int64 array (N, num_ids + 1, 5) of (count, x0, y0, x1, y1): record
@@ -1141,40 +1195,16 @@ def png_label_stats(labels, num_ids, status=None):
     png_decode_batch_color_labels under any of their maps, or one made otherwise.  num_ids: 1 .. 1024.  status: None, or one
     entry per image: the records of an image whose entry is not 0 stay zero.  One kernel launch reads the tensor once; the call
     waits for the work queued on the device before it, and for its own."""
-    import torch
-
     num_ids = _png_stats_ids(num_ids)
     if num_ids is None:
         raise ValueError("num_ids must be an integer")
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
-        raise ValueError("labels must be a (N, H, W) tensor")
-    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
-    if hasattr(torch, "uint16"):
-        codes[torch.uint16] = 1
-    if labels.dtype not in codes:
-        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
-    if not labels.is_contiguous():
-        raise ValueError("labels must be contiguous")
-    if labels.device.type != "cuda":
-        raise ValueError("labels must be on the GPU")
-    n, H, W = (int(v) for v in labels.shape)
-    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
-        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
-    if status is not None and len(status) != n:
-        raise ValueError("status needs one entry per image")
+    code = _png_label_code(labels)
+    n, H, W, st = _png_label_input(labels, status)
     out = np.zeros((n, num_ids + 1, 5), np.uint32)
     if n == 0:
         return out.astype(np.int64)
-    L = _png_spec_lib()
-    _png_device(L, labels.device)
-    L.debig_png_label_stats.restype = C.c_int
-    L.debig_png_label_stats.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p]
-    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
-    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
-    rc = L.debig_png_label_stats(labels.data_ptr(), n, W, H, codes[labels.dtype], num_ids, st, out.ctypes.data)
-    if rc == PNG_BAD_ARG:
-        raise ValueError(f"debig_png_label_stats rejected its arguments ({rc})")
-    N.check(rc, "debig_png_label_stats")
+    _png_label_call("debig_png_label_stats", [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p],
+                    labels, n, W, H, code, num_ids, st, out.ctypes.data)
     return out.astype(np.int64)
 
 
@@ -1223,46 +1253,19 @@ def png_label_boundary(labels, radius=1, shape="square", mode="ring", value=255,
     radius, shape_code = _png_boundary_shape(radius, shape)
     if not isinstance(mode, str) or mode not in _PNG_BOUNDARY_MODES:
         raise ValueError(f"mode must be one of {sorted(_PNG_BOUNDARY_MODES)}, not {mode!r}")
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
-        raise ValueError("labels must be a (N, H, W) tensor")
-    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
-    if hasattr(torch, "uint16"):
-        codes[torch.uint16] = 1
-    if labels.dtype not in codes:
-        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
-    code = codes[labels.dtype]
+    code = _png_label_code(labels)
     if mode == "ring":
         lo, hi = [(0, 255), (0, 65535), (-2 ** 31, 2 ** 31 - 1), (-2 ** 63, 2 ** 63 - 1)][code]
         if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
             raise ValueError(f"value must be an integer in {lo} .. {hi} for {labels.dtype}, not {value!r}")
-    if not labels.is_contiguous():
-        raise ValueError("labels must be contiguous")
-    if labels.device.type != "cuda":
-        raise ValueError("labels must be on the GPU")
-    n, H, W = (int(v) for v in labels.shape)
-    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
-        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
-    if status is not None and len(status) != n:
-        raise ValueError("status needs one entry per image")
+    n, H, W, st = _png_label_input(labels, status)
     out = torch.empty((n, H, W), dtype=torch.uint8 if mode == "edge" else labels.dtype, device=labels.device)
     if n == 0:
         return out
-    L = _png_spec_lib()
-    _png_device(L, labels.device)
-    L.debig_png_label_boundary.restype = C.c_int
-    L.debig_png_label_boundary.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_int64, C.c_void_p]
-    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
-    for i in ([] if status is None else [i for i in range(n) if st[i] != 0]):  # the images the library leaves alone, and only they
-        if mode == "edge":
-            out[i].zero_()
-        else:
-            out[i].copy_(labels[i])
-    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
-    rc = L.debig_png_label_boundary(labels.data_ptr(), out.data_ptr(), n, W, H, code, radius, shape_code, _PNG_BOUNDARY_MODES[mode],
-                                    int(value) if mode == "ring" else 0, st)
-    if rc == PNG_BAD_ARG:
-        raise ValueError(f"debig_png_label_boundary rejected its arguments ({rc})")
-    N.check(rc, "debig_png_label_boundary")
+    _png_label_skipped(out, st, None if mode == "edge" else labels)
+    _png_label_call("debig_png_label_boundary", [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_int64, C.c_void_p],
+                    labels, out.data_ptr(), n, W, H, code, radius, shape_code, _PNG_BOUNDARY_MODES[mode],
+                    int(value) if mode == "ring" else 0, st)
     return out
 
 
@@ -1296,38 +1299,16 @@ def png_label_distance(labels, to=None, cap=None, out="squared", status=None):
         raise ValueError(f"cap must be None or an integer in 1 .. {PNG_LABEL_DISTANCE_MAX_CAP}, not {cap!r}")
     if not isinstance(out, str) or out not in _PNG_DISTANCE_FORMATS:
         raise ValueError(f"out must be one of {sorted(_PNG_DISTANCE_FORMATS)}, not {out!r}")
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
-        raise ValueError("labels must be a (N, H, W) tensor")
-    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
-    if hasattr(torch, "uint16"):
-        codes[torch.uint16] = 1
-    if labels.dtype not in codes:
-        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
-    if not labels.is_contiguous():
-        raise ValueError("labels must be contiguous")
-    if labels.device.type != "cuda":
-        raise ValueError("labels must be on the GPU")
-    n, H, W = (int(v) for v in labels.shape)
-    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
-        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
-    if status is not None and len(status) != n:
-        raise ValueError("status needs one entry per image")
+    code = _png_label_code(labels)
+    n, H, W, st = _png_label_input(labels, status)
     res = torch.empty((n, H, W), dtype=torch.int32 if out == "squared" else torch.float32, device=labels.device)
     if n == 0:
         return res
-    L = _png_spec_lib()
-    _png_device(L, labels.device)
-    L.debig_png_label_distance.restype = C.c_int
-    L.debig_png_label_distance.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_int64, C.c_uint32, C.c_uint32, C.c_void_p]
-    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
-    for i in ([] if status is None else [i for i in range(n) if st[i] != 0]):  # the images the library leaves alone, and only they
-        res[i].zero_()
-    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
-    rc = L.debig_png_label_distance(labels.data_ptr(), res.data_ptr(), n, W, H, codes[labels.dtype], 0 if to is None else 1,
-                                    0 if to is None else int(to), 0 if cap is None else int(cap), _PNG_DISTANCE_FORMATS[out], st)
-    if rc == PNG_BAD_ARG:
-        raise ValueError(f"debig_png_label_distance rejected its arguments ({rc})")
-    N.check(rc, "debig_png_label_distance")
+    _png_label_skipped(res, st)
+    _png_label_call("debig_png_label_distance",
+                    [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_int64, C.c_uint32, C.c_uint32, C.c_void_p],
+                    labels, res.data_ptr(), n, W, H, code, 0 if to is None else 1, 0 if to is None else int(to),
+                    0 if cap is None else int(cap), _PNG_DISTANCE_FORMATS[out], st)
     return res
 
 
@@ -1361,40 +1342,17 @@ def png_label_components(labels, connectivity=4, background=None, ids="consecuti
         raise ValueError(f"background must be None or an integer that fits 64 bits, not {background!r}")
     if not isinstance(ids, str) or ids not in _PNG_COMPONENTS_IDS:
         raise ValueError(f"ids must be one of {sorted(_PNG_COMPONENTS_IDS)}, not {ids!r}")
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
-        raise ValueError("labels must be a (N, H, W) tensor")
-    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
-    if hasattr(torch, "uint16"):
-        codes[torch.uint16] = 1
-    if labels.dtype not in codes:
-        raise ValueError(f"labels must be uint8, uint16 (or int16), int32 or int64, not {labels.dtype}")
-    if not labels.is_contiguous():
-        raise ValueError("labels must be contiguous")
-    if labels.device.type != "cuda":
-        raise ValueError("labels must be on the GPU")
-    n, H, W = (int(v) for v in labels.shape)
-    if n and not (1 <= H <= 16384 and 1 <= W <= 16384):
-        raise ValueError(f"labels must be (N, H, W) with 1 <= H, W <= 16384, not {tuple(labels.shape)}")
-    if status is not None and len(status) != n:
-        raise ValueError("status needs one entry per image")
+    code = _png_label_code(labels)
+    n, H, W, st = _png_label_input(labels, status)
     res = torch.empty((n, H, W), dtype=torch.int32, device=labels.device)
     if n == 0:
         return res, np.zeros(0, np.int64)
-    L = _png_spec_lib()
-    _png_device(L, labels.device)
-    L.debig_png_label_components.restype = C.c_int
-    L.debig_png_label_components.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]
-    st = None if status is None else (C.c_uint32 * n)(*[int(v) for v in status])
-    for i in ([] if status is None else [i for i in range(n) if st[i] != 0]):  # the images the library leaves alone, and only they
-        res[i].zero_()
+    _png_label_skipped(res, st)
     counts = (C.c_uint32 * n)()
-    torch.cuda.synchronize(labels.device)  # whoever wrote the tensor runs on torch's stream, the library on its own
-    rc = L.debig_png_label_components(labels.data_ptr(), res.data_ptr(), n, W, H, codes[labels.dtype], int(connectivity),
-                                      0 if background is None else 1, 0 if background is None else int(background),
-                                      _PNG_COMPONENTS_IDS[ids], st, counts)
-    if rc == PNG_BAD_ARG:
-        raise ValueError(f"debig_png_label_components rejected its arguments ({rc})")
-    N.check(rc, "debig_png_label_components")
+    _png_label_call("debig_png_label_components",
+                    [C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p],
+                    labels, res.data_ptr(), n, W, H, code, int(connectivity), 0 if background is None else 1,
+                    0 if background is None else int(background), _PNG_COMPONENTS_IDS[ids], st, counts)
     return res, np.array(list(counts), np.int64)
 
 

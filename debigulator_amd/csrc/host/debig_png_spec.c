@@ -982,6 +982,11 @@ static debig_ctx *dev_upload(const void *tasks, uint64_t n_tasks, size_t elem, c
     return c;
 }
 
+/* the row-run cut: a task is a run of whole rows of at most max_elems elements, or one row when a row is wider.  -> the rows of a
+ * full run; run_rows: those of the run that starts in row y0 of h */
+static uint32_t row_run(uint32_t w, uint32_t max_elems) { return w >= max_elems ? 1u : max_elems / w; }
+static uint32_t run_rows(uint32_t h, uint32_t y0, uint32_t run) { return h - y0 < run ? h - y0 : run; }
+
 /* ---- the per-image colour matrix of the tensor decodes (decode_png.h) --------------------------------------------------------- */
 
 _Static_assert(offsetof(debig_png_resize_color_task, reserved2) == RSZ_TASK_FIELDS && sizeof(debig_png_resize_color_task) == 120 &&
@@ -1669,14 +1674,14 @@ static int lbl_axes(lbl_job *J, const stage *S, const uint32_t *status, uint32_t
  * the fields named above filled in.  -> 0 or 2 */
 static int lbl_runs(lbl_job *J, const stage *S, uint32_t i, uint32_t px, uint64_t slot, void *proto)
 {
-    const uint32_t run = J->W >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / J->W;
+    const uint32_t run = row_run(J->W, LBL_TASK_ELEMS);
     const lbl_head h = {S->offs[i] + ((uint64_t)S->box[i].y * S->inf[i].width + S->box[i].x) * px, (uint64_t)i * slot,
                         J->tx->off + lbl_axis_get(&J->TX, S->box[i].w), J->ty->off + lbl_axis_get(&J->TY, S->box[i].h)};
     memcpy(proto, &h, sizeof h);
     for (uint32_t y0 = 0; y0 < J->H; y0 += run) {
         if (J->n_tasks >= 0x7fffffffu || !grow((void **)&J->tasks, &J->cap_tasks, (uint32_t)J->n_tasks, J->elem)) return 2;
         uint8_t *t = J->tasks + J->n_tasks++ * J->elem;
-        const uint32_t rows[2] = {y0, J->H - y0 < run ? J->H - y0 : run};
+        const uint32_t rows[2] = {y0, run_rows(J->H, y0, run)};
         memcpy(t, proto, J->elem);
         memcpy(t + J->row_at, rows, sizeof rows);
     }
@@ -1902,6 +1907,42 @@ done:
     return rc;
 }
 
+/* ---- what the calls that post-process a dense (n, h, w) label tensor share: stats, boundary, distance, components ---------------- */
+
+#define LABEL_POST_NO_OUT UINT32_MAX
+
+/* the tensor arguments of such a call: labels of a known dtype, aligned to their element, sides of 1 .. 16384; and, unless
+ * out_shift is LABEL_POST_NO_OUT, a device output of 1 << out_shift bytes per element, aligned to that and apart from the input.
+ * (out_shift is read behind the dtype test, so a caller may hand in the dtype itself.)  -> 1, or 0: DEBIG_PNG_BAD_ARG */
+static int label_post_args_ok(const void *d_labels, const void *d_out, uint32_t out_shift, uint32_t n, uint32_t w, uint32_t h, uint32_t dtype)
+{
+    if (!d_labels || dtype > DEBIG_PNG_L_I64 || w == 0 || w > 16384u || h == 0 || h > 16384u) return 0;
+    const uint64_t es = 1u << dtype, elems = (uint64_t)n * w * h;
+    if ((uintptr_t)d_labels & (es - 1u)) return 0;
+    if (out_shift == LABEL_POST_NO_OUT) return 1;
+    const uint64_t os = 1u << out_shift;
+    if (!d_out || ((uintptr_t)d_out & (os - 1u))) return 0;
+    return !((uintptr_t)d_out < (uintptr_t)d_labels + elems * es && (uintptr_t)d_labels < (uintptr_t)d_out + elems * os);
+}
+
+/* the GOOD images, those the call looks at (no status, or an entry of 0): *i moves on to the first one at or behind it -> 0: there
+ * is none.  for (i = 0, k = 0; label_post_good(status, n, &i); i++, k++) visits them all, k the image's place among them. */
+static int label_post_good(const uint32_t *status, uint32_t n, uint32_t *i)
+{
+    while (*i < n && status && status[*i] != 0) (*i)++;
+    return *i < n;
+}
+
+static uint64_t label_post_n_good(const uint32_t *status, uint32_t n)
+{
+    uint64_t n_good = 0;
+    for (uint32_t i = 0; label_post_good(status, n, &i); i++) n_good++;
+    return n_good;
+}
+
+/* per tasks for each of n_good images: does a launch take them?  (0: the call returns 2) */
+static int label_post_tasks_fit(uint64_t n_good, uint64_t per) { return n_good * per < 0x7fffffffu; }
+
 /* ---- debig_png_label_stats: per-id counts and bounding boxes of a dense label tensor (decode_png.h) -------------------------- */
 
 _Static_assert(sizeof(debig_png_label_stat) == 20 && sizeof(debig_png_label_box) == 20 && sizeof(debig_png_label_stats_task) == 40,
@@ -1922,14 +1963,13 @@ DEBIG_API int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t o
                                     const uint32_t *status, debig_png_label_box *out)
 {
     if (n == 0) return 0;
-    if (!d_labels || !out || dtype > DEBIG_PNG_L_I64 || n_ids == 0 || n_ids > DEBIG_PNG_LABEL_STATS_MAX_IDS || out_w == 0 ||
-        out_w > 16384u || out_h == 0 || out_h > 16384u || ((uintptr_t)d_labels & ((1u << dtype) - 1u)))
+    if (!out || n_ids == 0 || n_ids > DEBIG_PNG_LABEL_STATS_MAX_IDS ||
+        !label_post_args_ok(d_labels, NULL, LABEL_POST_NO_OUT, n, out_w, out_h, dtype))
         return DEBIG_PNG_BAD_ARG;
     const uint32_t es = 1u << dtype, recs = n_ids + 1u;
-    const uint32_t run = out_w >= LBL_TASK_ELEMS ? 1u : LBL_TASK_ELEMS / out_w, per = (out_h + run - 1u) / run;
-    uint64_t n_good = 0;
-    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
-    if (n_good * per >= 0x7fffffffu) return 2;
+    const uint32_t run = row_run(out_w, LBL_TASK_ELEMS), per = (out_h + run - 1u) / run;
+    const uint64_t n_good = label_post_n_good(status, n);
+    if (!label_post_tasks_fit(n_good, per)) return 2;
     memset(out, 0, (size_t)n * recs * sizeof *out);
     if (n_good == 0) return 0;
     int rc = 2;
@@ -1938,8 +1978,7 @@ DEBIG_API int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t o
     uint32_t *raw = (uint32_t *)malloc((size_t)tab[0].bytes);
     uint64_t n_tasks = 0;
     if (!tasks || !raw) goto done;
-    for (uint32_t i = 0; i < n; i++) {
-        if (status && status[i] != 0) continue;
+    for (uint32_t i = 0; label_post_good(status, n, &i); i++) {
         for (uint32_t y0 = 0; y0 < out_h; y0 += run) {
             debig_png_label_stats_task *t = &tasks[n_tasks++];
             t->label_off = ((uint64_t)i * out_h + y0) * out_w * es;
@@ -1947,7 +1986,7 @@ DEBIG_API int debig_png_label_stats(const void *d_labels, uint32_t n, uint32_t o
             t->out_w = out_w;
             t->out_h = out_h;
             t->row0 = y0;
-            t->rows = out_h - y0 < run ? out_h - y0 : run;
+            t->rows = run_rows(out_h, y0, run);
             t->n_ids = n_ids;
             t->dtype = dtype;
         }
@@ -1999,31 +2038,27 @@ DEBIG_API int debig_png_label_boundary(const void *d_labels, void *d_out, uint32
                                        uint32_t radius, uint32_t shape, uint32_t mode, int64_t value, const uint32_t *status)
 {
     if (n == 0) return 0;
-    if (!d_labels || !d_out || dtype > DEBIG_PNG_L_I64 || radius == 0 || radius > DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS ||
-        shape > DEBIG_PNG_BOUNDARY_DISK || mode > DEBIG_PNG_BOUNDARY_EDGE || out_w == 0 || out_w > 16384u || out_h == 0 || out_h > 16384u)
+    if (radius == 0 || radius > DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS || shape > DEBIG_PNG_BOUNDARY_DISK || mode > DEBIG_PNG_BOUNDARY_EDGE ||
+        !label_post_args_ok(d_labels, d_out, mode == DEBIG_PNG_BOUNDARY_RING ? dtype : 0u, n, out_w, out_h, dtype))
         return DEBIG_PNG_BAD_ARG;
-    const uint32_t es = 1u << dtype, os = mode == DEBIG_PNG_BOUNDARY_RING ? es : 1u;
-    if (((uintptr_t)d_labels & (es - 1u)) || ((uintptr_t)d_out & (os - 1u))) return DEBIG_PNG_BAD_ARG;
     if (mode == DEBIG_PNG_BOUNDARY_RING &&
         ((dtype == DEBIG_PNG_L_U8 && (value < 0 || value > 255)) || (dtype == DEBIG_PNG_L_U16 && (value < 0 || value > 65535)) ||
          (dtype == DEBIG_PNG_L_I32 && (value < INT32_MIN || value > INT32_MAX))))
         return DEBIG_PNG_BAD_ARG;
-    const uint64_t img = (uint64_t)out_w * out_h, in_bytes = (uint64_t)n * img * es, out_bytes = (uint64_t)n * img * os;
-    if ((uintptr_t)d_out < (uintptr_t)d_labels + in_bytes && (uintptr_t)d_labels < (uintptr_t)d_out + out_bytes) return DEBIG_PNG_BAD_ARG;
+    const uint32_t es = 1u << dtype, os = mode == DEBIG_PNG_BOUNDARY_RING ? es : 1u;
+    const uint64_t img = (uint64_t)out_w * out_h;
     uint32_t tw, th;
     boundary_tile(dtype, radius, &tw, &th);
     const uint64_t per = (uint64_t)((out_w + tw - 1u) / tw) * ((out_h + th - 1u) / th);
-    uint64_t n_good = 0;
-    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
-    if (n_good * per >= 0x7fffffffu) return 2;
+    const uint64_t n_good = label_post_n_good(status, n);
+    if (!label_post_tasks_fit(n_good, per)) return 2;
     if (n_good == 0) return 0;
     int rc = 2;
     debig_png_label_boundary_task *tasks = (debig_png_label_boundary_task *)calloc((size_t)(n_good * per), sizeof *tasks);
     dev_table tab[1] = {{NULL, 0, 0}}; /* no tables */
     uint64_t n_tasks = 0;
     if (!tasks) goto done;
-    for (uint32_t i = 0; i < n; i++) {
-        if (status && status[i] != 0) continue;
+    for (uint32_t i = 0; label_post_good(status, n, &i); i++) {
         for (uint32_t y0 = 0; y0 < out_h; y0 += th)
             for (uint32_t x0 = 0; x0 < out_w; x0 += tw) {
                 debig_png_label_boundary_task *t = &tasks[n_tasks++];
@@ -2064,19 +2099,16 @@ DEBIG_API int debig_png_label_distance(const void *d_labels, void *d_out, uint32
                                        uint32_t sites, int64_t value, uint32_t cap, uint32_t format, const uint32_t *status)
 {
     if (n == 0) return 0;
-    if (!d_labels || !d_out || dtype > DEBIG_PNG_L_I64 || sites > DEBIG_PNG_DISTANCE_TO_VALUE || format > DEBIG_PNG_DISTANCE_ROOT ||
-        cap > DEBIG_PNG_LABEL_DISTANCE_MAX_CAP || out_w == 0 || out_w > 16384u || out_h == 0 || out_h > 16384u)
+    if (sites > DEBIG_PNG_DISTANCE_TO_VALUE || format > DEBIG_PNG_DISTANCE_ROOT || cap > DEBIG_PNG_LABEL_DISTANCE_MAX_CAP ||
+        !label_post_args_ok(d_labels, d_out, 2u, n, out_w, out_h, dtype))
         return DEBIG_PNG_BAD_ARG;
     const uint32_t es = 1u << dtype;
-    if (((uintptr_t)d_labels & (es - 1u)) || ((uintptr_t)d_out & 3u)) return DEBIG_PNG_BAD_ARG;
-    const uint64_t img = (uint64_t)out_w * out_h, in_bytes = (uint64_t)n * img * es, out_bytes = (uint64_t)n * img * 4u;
-    if ((uintptr_t)d_out < (uintptr_t)d_labels + in_bytes && (uintptr_t)d_labels < (uintptr_t)d_out + out_bytes) return DEBIG_PNG_BAD_ARG;
+    const uint64_t img = (uint64_t)out_w * out_h;
     /* a rows task: a run of whole rows of at most DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS elements; a cols task: a strip of 64 columns */
-    const uint32_t run = out_w >= DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS ? 1u : DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS / out_w;
+    const uint32_t run = row_run(out_w, DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS);
     const uint64_t per_r = (out_h + run - 1u) / run, per_c = (out_w + DEBIG_PNG_LABEL_DISTANCE_COLS - 1u) / DEBIG_PNG_LABEL_DISTANCE_COLS;
-    uint64_t n_good = 0;
-    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
-    if (n_good * per_r >= 0x7fffffffu || n_good * per_c >= 0x7fffffffu) return 2;
+    const uint64_t n_good = label_post_n_good(status, n);
+    if (!label_post_tasks_fit(n_good, per_r) || !label_post_tasks_fit(n_good, per_c)) return 2;
     if (n_good == 0) return 0;
     int rc = 2;
     /* both task lists in one upload: the rows tasks, the cols tasks behind them (48 is a multiple of 8) */
@@ -2087,9 +2119,7 @@ DEBIG_API int debig_png_label_distance(const void *d_labels, void *d_out, uint32
     if (!blob) goto done;
     debig_png_label_distance_rows_task *tr = (debig_png_label_distance_rows_task *)blob;
     debig_png_label_distance_cols_task *tc = (debig_png_label_distance_cols_task *)(blob + n_r * sizeof *tr);
-    uint64_t k = 0; /* the image's place among the good ones */
-    for (uint32_t i = 0; i < n; i++) {
-        if (status && status[i] != 0) continue;
+    for (uint32_t i = 0, k = 0; label_post_good(status, n, &i); i++, k++) {
         for (uint32_t y0 = 0; y0 < out_h; y0 += run, tr++) {
             tr->label_off = (uint64_t)i * img * es;
             tr->g_off = k * img * 2u;
@@ -2097,7 +2127,7 @@ DEBIG_API int debig_png_label_distance(const void *d_labels, void *d_out, uint32
             tr->w = out_w;
             tr->h = out_h;
             tr->row0 = y0;
-            tr->rows = out_h - y0 < run ? out_h - y0 : run;
+            tr->rows = run_rows(out_h, y0, run);
             tr->dtype = dtype;
             tr->sites = sites;
         }
@@ -2111,7 +2141,6 @@ DEBIG_API int debig_png_label_distance(const void *d_labels, void *d_out, uint32
             tc->cap = cap;
             tc->format = format;
         }
-        k++;
     }
     debig_ctx *c = dev_upload(blob, bytes, 1, tab, 1, &rc);
     if (!c) goto done;
@@ -2138,20 +2167,17 @@ DEBIG_API int debig_png_label_components(const void *d_labels, void *d_out, uint
                                          const uint32_t *status, uint32_t *counts)
 {
     if (n == 0) return 0;
-    if (!d_labels || !d_out || dtype > DEBIG_PNG_L_I64 || (connectivity != 4u && connectivity != 8u) || ids > DEBIG_PNG_COMPONENTS_CONSECUTIVE ||
-        out_w == 0 || out_w > 16384u || out_h == 0 || out_h > 16384u)
+    if ((connectivity != 4u && connectivity != 8u) || ids > DEBIG_PNG_COMPONENTS_CONSECUTIVE ||
+        !label_post_args_ok(d_labels, d_out, 2u, n, out_w, out_h, dtype))
         return DEBIG_PNG_BAD_ARG;
     const uint32_t es = 1u << dtype;
-    if (((uintptr_t)d_labels & (es - 1u)) || ((uintptr_t)d_out & 3u)) return DEBIG_PNG_BAD_ARG;
-    const uint64_t img = (uint64_t)out_w * out_h, in_bytes = (uint64_t)n * img * es, out_bytes = (uint64_t)n * img * 4u;
-    if ((uintptr_t)d_out < (uintptr_t)d_labels + in_bytes && (uintptr_t)d_labels < (uintptr_t)d_out + out_bytes) return DEBIG_PNG_BAD_ARG;
+    const uint64_t img = (uint64_t)out_w * out_h;
     if (counts) memset(counts, 0, (size_t)n * sizeof *counts);
     /* a task: a run of whole rows of at most DEBIG_PNG_LABEL_COMPONENTS_ELEMS elements, the same cut for all five launches */
-    const uint32_t run = out_w >= DEBIG_PNG_LABEL_COMPONENTS_ELEMS ? 1u : DEBIG_PNG_LABEL_COMPONENTS_ELEMS / out_w;
+    const uint32_t run = row_run(out_w, DEBIG_PNG_LABEL_COMPONENTS_ELEMS);
     const uint64_t per = (out_h + run - 1u) / run;
-    uint64_t n_good = 0;
-    for (uint32_t i = 0; i < n; i++) n_good += !status || status[i] == 0;
-    if (n_good * per >= 0x7fffffffu) return 2;
+    const uint64_t n_good = label_post_n_good(status, n);
+    if (!label_post_tasks_fit(n_good, per)) return 2;
     if (n_good == 0) return 0;
     int rc = 2;
     const uint64_t n_tasks = n_good * per;
@@ -2161,9 +2187,7 @@ DEBIG_API int debig_png_label_components(const void *d_labels, void *d_out, uint
     dev_table tab[2] = {{NULL, n_good * img * 4u, 0}, {NULL, n_tasks * sizeof(uint32_t), 0}};
     dev_tables_place(tab, 2);
     if (!tasks || !task_counts) goto done;
-    uint64_t k = 0; /* the image's place among the good ones */
-    for (uint32_t i = 0; i < n; i++) {
-        if (status && status[i] != 0) continue;
+    for (uint32_t i = 0, k = 0; label_post_good(status, n, &i); i++, k++) {
         for (uint32_t y0 = 0; y0 < out_h; y0 += run, t++) {
             t->label_off = (uint64_t)i * img * es;
             t->parent_off = k * img * 4u;
@@ -2172,7 +2196,7 @@ DEBIG_API int debig_png_label_components(const void *d_labels, void *d_out, uint
             t->w = out_w;
             t->h = out_h;
             t->row0 = y0;
-            t->rows = out_h - y0 < run ? out_h - y0 : run;
+            t->rows = run_rows(out_h, y0, run);
             t->dtype = dtype;
             t->connectivity = connectivity;
             t->use_background = use_background != 0;
@@ -2180,7 +2204,6 @@ DEBIG_API int debig_png_label_components(const void *d_labels, void *d_out, uint
             t->count_first = (uint32_t)(k * per);
             t->count_idx = (uint32_t)(t - tasks);
         }
-        k++;
     }
     debig_ctx *c = dev_upload(tasks, n_tasks, sizeof *tasks, tab, 2, &rc);
     if (!c) goto done;
@@ -2194,14 +2217,9 @@ DEBIG_API int debig_png_label_components(const void *d_labels, void *d_out, uint
         (rc = debig_hip_png_label_components_finish_batch(d_parent, d_out, d_tasks, (uint32_t)n_tasks, NULL)) ||
         (rc = debig_hip_memcpy_d2h(task_counts, d_counts, tab[1].bytes, NULL)) || (rc = debig_hip_stream_sync(NULL)))
         goto done;
-    if (counts) {
-        k = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            if (status && status[i] != 0) continue;
+    if (counts)
+        for (uint32_t i = 0, k = 0; label_post_good(status, n, &i); i++, k++)
             for (uint64_t j = 0; j < per; j++) counts[i] += task_counts[k * per + j];
-            k++;
-        }
-    }
 done:
     free(tasks);
     free(task_counts);
@@ -2411,7 +2429,7 @@ static int map_task_runs(map_tasks *T, const warp_map *mp, const void *task, uin
         if (T->n >= 0x7fffffffu || !grow((void **)&T->v, &T->cap, (uint32_t)T->n, T->elem)) return 0;
         uint8_t *at = T->v + T->n++ * T->elem;
         *row0 = y0;
-        *rows = H - y0 < run ? H - y0 : run;
+        *rows = run_rows(H, y0, run);
         memcpy(at, task, T->base);
         if (mp->kind == MAP_PERSP) memcpy(at + T->base, mp->m + MAP_INTS * (size_t)i + 6, 3 * sizeof(int64_t));
         if (mp->kind == MAP_ELASTIC) {
@@ -2505,7 +2523,7 @@ static int tensor_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     const uint32_t W = desc->out_w, H = desc->out_h;
     const uint32_t es = desc->dtype == DEBIG_PNG_T_UINT ? sb : desc->dtype == DEBIG_PNG_T_F32 ? 4u : 2u;
     const uint64_t slot = (uint64_t)H * W * ch * es;
-    const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
+    const uint32_t run = row_run(W, WARP_TASK_PIXELS);
     const int ela = mp->kind == MAP_ELASTIC;
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
@@ -2761,7 +2779,7 @@ static int labels_warp_core(const uint8_t *const *inputs, const uint64_t *input_
     if (badarg) return badarg;
     if (label_warp_check(mp, wd, desc->dtype)) return DEBIG_PNG_BAD_ARG;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype;
-    const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
+    const uint32_t run = row_run(W, WARP_TASK_PIXELS);
 
     stage S = {NULL, NULL, NULL, NULL, NULL};
     map_tasks T = {NULL, 0, 0, sizeof(debig_png_label_warp_task), sizeof(debig_png_label_warp_task) + map_tail_bytes(mp)};
@@ -2861,7 +2879,7 @@ static int color_labels_warp_core(const uint8_t *const *inputs, const uint64_t *
     if ((rc = label_warp_check(mp, wd, desc->dtype))) goto done;
     const int map_mode = desc->mode == DEBIG_PNG_CL_MAP;
     const uint32_t W = desc->out_w, H = desc->out_h, es = 1u << desc->dtype, n_maps = map_mode ? desc->n_maps : 0;
-    const uint32_t run = W >= WARP_TASK_PIXELS ? 1u : WARP_TASK_PIXELS / W;
+    const uint32_t run = row_run(W, WARP_TASK_PIXELS);
     /* the maps' tables (first: map_off needs no base), the counters (16-byte aligned: a table is a multiple of 16 bytes) */
     dev_table tab[3] = {{M.tab, M.bytes, 0}, {NULL, (uint64_t)n * sizeof(uint32_t), 0}, {NULL, 0, 0}}; /* (the fields come last) */
     const uint32_t n_tab = mp->kind == MAP_ELASTIC ? 3u : 2u;

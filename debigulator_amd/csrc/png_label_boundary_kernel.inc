@@ -54,7 +54,7 @@ DEV_INLINE bool lbd_task_ok(const debig_png_label_boundary_task &t, const uint8_
     if (t.dtype > 3u || t.mode > 1u || t.radius == 0u || t.radius > DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS) return false;
     for (uint32_t d = 0; d <= DEBIG_PNG_LABEL_BOUNDARY_MAX_RADIUS; d++)
         if (d <= t.radius && t.reach[d] > t.radius) return false;
-    if (t.w == 0u || t.w > 16384u || t.h == 0u || t.h > 16384u) return false;
+    if (!stage_dim_ok(t.w, t.h)) return false;
     if (t.tile_w == 0u || t.tile_w > DEBIG_PNG_LABEL_BOUNDARY_MAX_TILE || t.tile_h == 0u || t.tile_h > DEBIG_PNG_LABEL_BOUNDARY_MAX_TILE)
         return false;
     if (t.x0 >= t.w || t.tile_w > t.w - t.x0 || t.y0 >= t.h || t.tile_h > t.h - t.y0) return false;
@@ -66,9 +66,7 @@ DEV_INLINE bool lbd_task_ok(const debig_png_label_boundary_task &t, const uint8_
         if (t.dtype == 2u && (t.value < -2147483647 - 1 || t.value > 2147483647)) return false;
     }
     const uint64_t es1 = (1u << t.dtype) - 1u, os1 = t.mode == 0u ? es1 : 0u;
-    if ((t.label_off & es1) || (t.out_off & os1)) return false;
-    // (and the addresses themselves, for a caller whose buffers are not aligned: the loads and stores below are typed)
-    return (((uintptr_t)labels + t.label_off) & es1) == 0u && (((uintptr_t)out + t.out_off) & os1) == 0u;
+    return stage_addr_ok(labels, t.label_off, es1) && stage_addr_ok(out, t.out_off, os1);
 }
 
 // the reach table in registers: entry 0 in the low byte of lo; next() drops the entry in front
@@ -91,51 +89,6 @@ DEV_UNROLL
         top = 0u;
     }
 };
-
-// one element of ES bytes at p as (low word, high word)
-template <uint32_t ES>
-DEV_INLINE uint2 lbd_load1(const uint8_t *p)
-{
-    uint2 q;
-    q.y = 0u;
-    if (ES == 1u) q.x = *p;
-    else if (ES == 2u) q.x = *reinterpret_cast<const uint16_t *>(p);
-    else if (ES == 4u) q.x = *reinterpret_cast<const uint32_t *>(p);
-    else q = *reinterpret_cast<const uint2 *>(p);
-    return q;
-}
-
-template <uint32_t ES>
-DEV_INLINE void lbd_store1(uint8_t *p, uint2 q)
-{
-    if (ES == 1u) *p = (uint8_t)q.x;
-    else if (ES == 2u) *reinterpret_cast<uint16_t *>(p) = (uint16_t)q.x;
-    else if (ES == 4u) *reinterpret_cast<uint32_t *>(p) = q.x;
-    else *reinterpret_cast<uint2 *>(p) = q;
-}
-
-// element j of the item in w[4] as (low word, high word)
-template <uint32_t ES>
-DEV_INLINE uint2 lbd_elem(const uint32_t (&w)[4], uint32_t j)
-{
-    uint2 q;
-    q.y = 0u;
-    if (ES == 1u) q.x = (w[j >> 2] >> (8u * (j & 3u))) & 255u;
-    else if (ES == 2u) q.x = (w[j >> 1] >> (16u * (j & 1u))) & 65535u;
-    else if (ES == 4u) q.x = w[j];
-    else { q.x = w[2u * j]; q.y = w[2u * j + 1u]; }
-    return q;
-}
-
-// element j of the item in w[4] := q
-template <uint32_t ES>
-DEV_INLINE void lbd_put(uint32_t (&w)[4], uint32_t j, uint2 q)
-{
-    if (ES == 1u) w[j >> 2] = (w[j >> 2] & ~(255u << (8u * (j & 3u)))) | (q.x << (8u * (j & 3u)));
-    else if (ES == 2u) w[j >> 1] = (w[j >> 1] & ~(65535u << (16u * (j & 1u)))) | (q.x << (16u * (j & 1u)));
-    else if (ES == 4u) w[j] = q.x;
-    else { w[2u * j] = q.x; w[2u * j + 1u] = q.y; }
-}
 
 // N bytes (16, 8, 4 or 2) at p, aligned to N, into the low bytes of w[4] / out of them
 template <uint32_t N>
@@ -184,9 +137,9 @@ DEV_INLINE uint32_t lbd_row_bits(const uint8_t *lds, const LbdGeo &g, uint32_t r
     lbd_load_bytes<EPI>(lds + g.dist0 + row * g.dpitch + ib / ES, dd);
 DEV_UNROLL
     for (uint32_t j = 0; j < EPI; j++) {
-        const uint2 a = lbd_elem<ES>(q, j), b = lbd_elem<ES>(c, j);
+        const uint2 a = lbl_item_get<ES>(q, j), b = lbl_item_get<ES>(c, j);
         const uint32_t d = (dd[j >> 2] >> (8u * (j & 3u))) & 255u;
-        bits |= (uint32_t)(a.x != b.x || a.y != b.y || d <= reach) << j;
+        bits |= (uint32_t)(!lbl_same(a, b) || d <= reach) << j;
     }
     return bits;
 }
@@ -209,8 +162,8 @@ DEV_INLINE void lbd_run(uint8_t *lds, const uint8_t *__restrict__ labels, uint8_
     {
         StageWalk at(tid, g.sw, LBD_THREADS);
         for (uint32_t i = tid; i < g.sw * g.sh; i += LBD_THREADS) {
-            const uint2 v = lbd_load1<ES>(in + ((uint64_t)(g.sy0 + at.r) * W + g.sx0 + at.x) * ES);
-            lbd_store1<ES>(lds + at.r * g.pitch + shift + at.x * ES, v);
+            const uint2 v = lbl_load<ES>(in + ((uint64_t)(g.sy0 + at.r) * W + g.sx0 + at.x) * ES);
+            lbl_store<ES>(lds + at.r * g.pitch + shift + at.x * ES, v);
             at.next();
         }
     }
@@ -223,17 +176,17 @@ DEV_INLINE void lbd_run(uint8_t *lds, const uint8_t *__restrict__ labels, uint8_
         for (uint32_t i = tid; i < t.tile_w * g.sh; i += LBD_THREADS) {
             const uint32_t c = c0 + at.x; /* the window holds columns c - r .. c + r as far as the image has them */
             const uint8_t *row = lds + at.r * g.pitch + shift;
-            const uint2 v = lbd_load1<ES>(row + c * ES);
+            const uint2 v = lbl_load<ES>(row + c * ES);
             uint32_t d = r + 1u;
             for (uint32_t k = r; k >= 1u; k--) { /* from far to near: the nearest one is written last */
                 bool differs = false;
                 if (c >= k) {
-                    const uint2 u = lbd_load1<ES>(row + (c - k) * ES);
-                    differs = u.x != v.x || u.y != v.y;
+                    const uint2 u = lbl_load<ES>(row + (c - k) * ES);
+                    differs = !lbl_same(u, v);
                 }
                 if (c + k < g.sw) {
-                    const uint2 u = lbd_load1<ES>(row + (c + k) * ES);
-                    differs = differs || u.x != v.x || u.y != v.y;
+                    const uint2 u = lbl_load<ES>(row + (c + k) * ES);
+                    differs = differs || !lbl_same(u, v);
                 }
                 if (differs) d = k;
             }
@@ -275,7 +228,7 @@ DEV_UNROLL
 DEV_UNROLL
             for (uint32_t j = 0; j < EPI; j++) {
                 if (EDGE) res[j >> 2] |= ((bits >> j) & 1u) << (8u * (j & 3u));
-                else lbd_put<ES>(res, j, (bits >> j) & 1u ? val : lbd_elem<ES>(c, j));
+                else lbl_item_put<ES>(res, j, (bits >> j) & 1u ? val : lbl_item_get<ES>(c, j));
             }
             uint8_t *dst = o + ((int64_t)((uint64_t)(t.y0 + at.r) * W) + x_first) * (int64_t)OS;
             constexpr uint32_t NB = EPI * OS; /* bytes of an item's results */
@@ -284,7 +237,7 @@ DEV_UNROLL
             } else {
 DEV_UNROLL
                 for (uint32_t j = 0; j < EPI; j++)
-                    if ((inside >> j) & 1u) lbd_store1<OS>(dst + (int64_t)j * OS, lbd_elem<OS>(res, j));
+                    if ((inside >> j) & 1u) lbl_store<OS>(dst + (int64_t)j * OS, lbl_item_get<OS>(res, j));
             }
             at.next();
         }

@@ -26,7 +26,7 @@
 // The work is NOT linear for every input: a find walks a tree whose depth depends on the data and on the race.
 // A task that breaks a bound is skipped (never indexed out of range).  No scratch, no inline assembly.
 // Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs inflate_kernel.inc and
-// png_label_boundary_kernel.inc (lbd_load1) in front of it.
+// png_stage_common.inc in front of it.
 
 #define LCC_THREADS 256u
 #define LCC_BG 0xffffffffu
@@ -34,16 +34,12 @@
 DEV_INLINE bool lcc_task_ok(const debig_png_label_components_task &t, const void *labels, const void *parent, const void *out, const void *counts)
 {
     if (t.dtype > 3u || (t.connectivity != 4u && t.connectivity != 8u) || t.use_background > 1u || t.ids > 1u) return false;
-    if (t.w == 0u || t.w > 16384u || t.h == 0u || t.h > 16384u) return false;
-    if (t.rows == 0u || t.row0 >= t.h || t.rows > t.h - t.row0) return false;
-    if (t.rows > DEBIG_PNG_LABEL_COMPONENTS_ELEMS / t.w && t.rows != 1u) return false;
+    if (!stage_dim_ok(t.w, t.h) || !stage_rows_ok(t.h, t.row0, t.rows)) return false;
+    if (!stage_budget_ok(t.rows, t.w, DEBIG_PNG_LABEL_COMPONENTS_ELEMS)) return false;
     if (t.count_first > t.count_idx || t.count_idx - t.count_first > 16383u) return false;
-    const uint64_t es1 = (1u << t.dtype) - 1u;
-    if ((t.label_off & es1) || (t.parent_off & 3u) || (t.out_off & 3u)) return false;
-    // (and the addresses themselves, for a caller whose buffers are not aligned: the loads and stores below are typed; a kernel
-    // hands in NULL for a buffer it does not have)
-    return (((uintptr_t)labels + t.label_off) & es1) == 0u && (((uintptr_t)parent + t.parent_off) & 3u) == 0u &&
-           (((uintptr_t)out + t.out_off) & 3u) == 0u && ((uintptr_t)counts & 3u) == 0u;
+    // (a kernel hands in NULL for a buffer it does not have: its offset is tested all the same)
+    return stage_addr_ok(labels, t.label_off, (1u << t.dtype) - 1u) && stage_addr_ok(parent, t.parent_off, 3u) &&
+           stage_addr_ok(out, t.out_off, 3u) && stage_addr_ok(counts, 0u, 3u);
 }
 
 // the slot's value as a link: an index below the slot's own and inside the image, or the slot itself (a root, a background
@@ -98,20 +94,14 @@ DEV_INLINE void lcc_union(uint32_t *parent, uint32_t a, uint32_t b, uint32_t n_p
     }
 }
 
-DEV_INLINE bool lcc_same(uint2 a, uint2 b) { return a.x == b.x && a.y == b.y; }
-
-// what the background is for elements of ES bytes: the value's words, and whether an element can equal it at all (uint8 and uint16
-// are zero-extended, int32 is sign-extended)
+// what the background is for elements of ES bytes: the value as an element, and whether an element is tested against it at all
 struct LccBg { uint2 want; bool on; };
 
 template <uint32_t ES>
 DEV_INLINE LccBg lcc_background(const debig_png_label_components_task &t)
 {
     LccBg b;
-    b.want.x = (uint32_t)(uint64_t)t.background;
-    b.want.y = ES == 8u ? (uint32_t)((uint64_t)t.background >> 32) : 0u;
-    const bool possible = ES == 1u ? (t.background >= 0 && t.background <= 255) : ES == 2u ? (t.background >= 0 && t.background <= 65535)
-                        : ES == 4u ? (t.background >= -2147483647 - 1 && t.background <= 2147483647) : true;
+    const bool possible = lbl_value<ES>(t.background, b.want);
     b.on = t.use_background != 0u && possible;
     return b;
 }
@@ -124,7 +114,7 @@ DEV_INLINE int32_t lcc_key(const uint8_t *in, uint32_t W, uint32_t i, uint32_t n
 {
     if (i >= n_el) return -1;
     if (i % W == 0u) return (int32_t)i;
-    return lcc_same(lbd_load1<ES>(in + (uint64_t)i * ES), lbd_load1<ES>(in + (uint64_t)(i - 1u) * ES)) ? -1 : (int32_t)i;
+    return lbl_same(lbl_load<ES>(in + (uint64_t)i * ES), lbl_load<ES>(in + (uint64_t)(i - 1u) * ES)) ? -1 : (int32_t)i;
 }
 
 // one task; lds: [0, 256) the segments' maxima, then what comes in from the left; [256, 260) the four wavefronts' totals
@@ -185,7 +175,7 @@ DEV_UNROLL
         const int32_t c = lds[seg];
         a = a > c ? a : c;
         if (i < n_el) {
-            const bool back = bg.on && lcc_same(lbd_load1<ES>(in + (uint64_t)i * ES), bg.want);
+            const bool back = bg.on && lbl_same(lbl_load<ES>(in + (uint64_t)i * ES), bg.want);
             pp[i] = back ? LCC_BG : p0 + (uint32_t)a;
         }
     }
@@ -221,12 +211,12 @@ DEV_INLINE void lcc_merge_run(const uint8_t *__restrict__ labels, uint8_t *paren
     // row 0 of the image has no row above it (the row above a task's first row belongs to the image, if not to the task)
     for (uint32_t p = (p0 ? p0 : W) + tid; p < p1; p += LCC_THREADS) {
         const uint32_t x = p % W;
-        const uint2 v = lbd_load1<ES>(in + (uint64_t)p * ES);
-        if (bg.on && lcc_same(v, bg.want)) continue;
+        const uint2 v = lbl_load<ES>(in + (uint64_t)p * ES);
+        if (bg.on && lbl_same(v, bg.want)) continue;
         const bool lft = x > 0u, rgt = x + 1u < W;
-        const bool up = lcc_same(v, lbd_load1<ES>(in + (uint64_t)(p - W) * ES));
-        const bool l = lft && lcc_same(v, lbd_load1<ES>(in + (uint64_t)(p - 1u) * ES));
-        const bool ul = lft && lcc_same(v, lbd_load1<ES>(in + (uint64_t)(p - W - 1u) * ES));
+        const bool up = lbl_same(v, lbl_load<ES>(in + (uint64_t)(p - W) * ES));
+        const bool l = lft && lbl_same(v, lbl_load<ES>(in + (uint64_t)(p - 1u) * ES));
+        const bool ul = lft && lbl_same(v, lbl_load<ES>(in + (uint64_t)(p - W - 1u) * ES));
         if (up) {
             // the first column of the overlap of the two runs: the pair to the left is not the same overlap
             if (!(l && ul)) lcc_union(pp, p, p - W, n_px);
@@ -234,7 +224,7 @@ DEV_INLINE void lcc_merge_run(const uint8_t *__restrict__ labels, uint8_t *paren
             // a diagonal adds something only where the vertical pair differs, and the element beside p, if it is of p's run, has
             // the same link as its own vertical pair
             if (ul && !l) lcc_union(pp, p, p - W - 1u, n_px);
-            if (rgt && lcc_same(v, lbd_load1<ES>(in + (uint64_t)(p - W + 1u) * ES)) && !lcc_same(v, lbd_load1<ES>(in + (uint64_t)(p + 1u) * ES)))
+            if (rgt && lbl_same(v, lbl_load<ES>(in + (uint64_t)(p - W + 1u) * ES)) && !lbl_same(v, lbl_load<ES>(in + (uint64_t)(p + 1u) * ES)))
                 lcc_union(pp, p, p - W + 1u, n_px);
         }
     }

@@ -37,7 +37,7 @@
 // A task that breaks a bound is skipped (never indexed out of range).  Nothing waits on another workgroup.  No scratch, no inline
 // assembly, plain vector loads and stores.
 // Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs inflate_kernel.inc and
-// png_label_boundary_kernel.inc (lbd_load1) in front of it.
+// png_stage_common.inc in front of it.
 
 #ifdef DEBIG_EMU
 #include <math.h> /* sqrt: the emulator build is plain C++ */
@@ -52,22 +52,17 @@
 DEV_INLINE bool ldr_task_ok(const debig_png_label_distance_rows_task &t, const uint8_t *labels, const uint8_t *g)
 {
     if (t.dtype > 3u || t.sites > 1u) return false;
-    if (t.w == 0u || t.w > 16384u || t.h == 0u || t.h > 16384u) return false;
-    if (t.rows == 0u || t.row0 >= t.h || t.rows > t.h - t.row0) return false;
-    if (t.rows > DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS / t.w && t.rows != 1u) return false;
-    const uint64_t es1 = (1u << t.dtype) - 1u;
-    if ((t.label_off & es1) || (t.g_off & 1u)) return false;
-    // (and the addresses themselves, for a caller whose buffers are not aligned: the loads and stores below are typed)
-    return (((uintptr_t)labels + t.label_off) & es1) == 0u && (((uintptr_t)g + t.g_off) & 1u) == 0u;
+    if (!stage_dim_ok(t.w, t.h) || !stage_rows_ok(t.h, t.row0, t.rows)) return false;
+    if (!stage_budget_ok(t.rows, t.w, DEBIG_PNG_LABEL_DISTANCE_ROWS_ELEMS)) return false;
+    return stage_addr_ok(labels, t.label_off, (1u << t.dtype) - 1u) && stage_addr_ok(g, t.g_off, 1u);
 }
 
 DEV_INLINE bool ldc_task_ok(const debig_png_label_distance_cols_task &t, const uint8_t *g, const uint8_t *out)
 {
     if (t.format > 1u || t.cap > 32767u) return false;
-    if (t.w == 0u || t.w > 16384u || t.h == 0u || t.h > 16384u) return false;
+    if (!stage_dim_ok(t.w, t.h)) return false;
     if (t.cols == 0u || t.cols > LDC_THREADS || t.x0 >= t.w || t.cols > t.w - t.x0) return false;
-    if ((t.g_off & 1u) || (t.out_off & 3u)) return false;
-    return (((uintptr_t)g + t.g_off) & 1u) == 0u && (((uintptr_t)out + t.out_off) & 3u) == 0u;
+    return stage_addr_ok(g, t.g_off, 1u) && stage_addr_ok(out, t.out_off, 3u);
 }
 
 // the two scan keys of element i of the flat range (none: -1 / LDR_NO_KEY) and its "differs from the element above" bit
@@ -79,23 +74,23 @@ DEV_INLINE LdrKeys ldr_keys(const uint8_t *in, const debig_png_label_distance_ro
     LdrKeys k = {-1, LDR_NO_KEY, 0u};
     if (i >= n_el) return k;
     const uint32_t W = t.w, r = i / W, x = i - r * W;
-    const uint2 v = lbd_load1<ES>(in + (uint64_t)i * ES);
+    const uint2 v = lbl_load<ES>(in + (uint64_t)i * ES);
     bool fl, fr;
     if (TO_VALUE) {
-        fl = fr = possible && v.x == want.x && v.y == want.y;
+        fl = fr = possible && lbl_same(v, want);
     } else {
         fl = fr = false;
         if (x > 0u) {
-            const uint2 u = lbd_load1<ES>(in + (uint64_t)(i - 1u) * ES);
-            fl = u.x != v.x || u.y != v.y;
+            const uint2 u = lbl_load<ES>(in + (uint64_t)(i - 1u) * ES);
+            fl = !lbl_same(u, v);
         }
         if (x + 1u < W) {
-            const uint2 u = lbd_load1<ES>(in + (uint64_t)(i + 1u) * ES);
-            fr = u.x != v.x || u.y != v.y;
+            const uint2 u = lbl_load<ES>(in + (uint64_t)(i + 1u) * ES);
+            fr = !lbl_same(u, v);
         }
         if (t.row0 + r > 0u) { /* (the row above a task's first row belongs to the image, if not to the task) */
-            const uint2 u = lbd_load1<ES>(in + ((int64_t)i - (int64_t)W) * (int64_t)ES);
-            k.above = (u.x != v.x || u.y != v.y) ? LDG_ABOVE : 0u;
+            const uint2 u = lbl_load<ES>(in + ((int64_t)i - (int64_t)W) * (int64_t)ES);
+            k.above = !lbl_same(u, v) ? LDG_ABOVE : 0u;
         }
     }
     k.left = fl ? (int32_t)(2u * i + 1u) : x == 0u ? (int32_t)(2u * i) : -1;
@@ -117,11 +112,7 @@ DEV_INLINE void ldr_run(int32_t *lds, const uint8_t *__restrict__ labels, uint8_
     uint16_t *gp = reinterpret_cast<uint16_t *>(g + t.g_off) + (uint64_t)t.row0 * W;
     const uint32_t lane = tid & 63u, wave = tid >> 6;
     uint2 want;
-    want.x = (uint32_t)(uint64_t)t.value;
-    want.y = ES == 8u ? (uint32_t)((uint64_t)t.value >> 32) : 0u;
-    // can an element of this dtype equal `value` at all?  (uint8 and uint16 are zero-extended, int32 is sign-extended)
-    const bool possible = ES == 1u ? (t.value >= 0 && t.value <= 255) : ES == 2u ? (t.value >= 0 && t.value <= 65535)
-                        : ES == 4u ? (t.value >= -2147483647 - 1 && t.value <= 2147483647) : true;
+    const bool possible = lbl_value<ES>(t.value, want); /* can an element of this dtype equal `value` at all? */
 
     // STEP 1: the segments' aggregates (a segment is uniform over its wavefront: the shuffles are convergent)
     lds[tid] = -1;

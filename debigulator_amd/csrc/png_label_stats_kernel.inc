@@ -20,7 +20,8 @@
 //     clears it.  Integer adds and maxima commute: the records are exact whatever the grid and the order.
 // A task that breaks a bound is skipped (never indexed out of range).  Nothing waits on another workgroup.  No scratch, no inline
 // assembly, plain vector loads.
-// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs inflate_kernel.inc in front of it.
+// Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs inflate_kernel.inc and png_stage_common.inc in
+// front of it.
 
 #define LST_THREADS 256u
 #define LST_STRIDE (DEBIG_PNG_LABEL_STATS_MAX_IDS + 1u) /* words between two fields of one id */
@@ -28,12 +29,9 @@
 DEV_INLINE bool lst_task_ok(const debig_png_label_stats_task &t, const uint8_t *labels, const uint8_t *stats)
 {
     if (t.dtype > 3u || t.n_ids == 0u || t.n_ids > DEBIG_PNG_LABEL_STATS_MAX_IDS) return false;
-    if (t.out_w == 0u || t.out_w > 16384u || t.out_h == 0u || t.out_h > 16384u) return false;
-    if (t.rows == 0u || t.row0 >= t.out_h || t.rows > t.out_h - t.row0) return false;
-    const uint64_t es1 = (1u << t.dtype) - 1u;
-    if ((t.stat_off & 3u) || (t.label_off & es1)) return false;
-    // (and the addresses themselves, for a caller whose buffers are not aligned: the loads below are typed)
-    return (((uintptr_t)stats + t.stat_off) & 3u) == 0u && (((uintptr_t)labels + t.label_off) & es1) == 0u;
+    // (a run of any length: this kernel has no element budget)
+    if (!stage_dim_ok(t.out_w, t.out_h) || !stage_rows_ok(t.out_h, t.row0, t.rows)) return false;
+    return stage_addr_ok(stats, t.stat_off, 3u) && stage_addr_ok(labels, t.label_off, (1u << t.dtype) - 1u);
 }
 
 // the open record of a lane: n elements of key id (n 0: none) in columns x_lo .. x_hi of rows y_lo .. y_hi
@@ -63,27 +61,6 @@ DEV_INLINE void lst_take(uint32_t *tab, LstOpen &o, uint32_t v, uint32_t x, uint
     o.y_hi = y;
 }
 
-// element i of the run as the value lst_take compares
-template <uint32_t ES>
-DEV_INLINE uint32_t lst_load1(const uint8_t *p, uint32_t i)
-{
-    if (ES == 1u) return p[i];
-    if (ES == 2u) return reinterpret_cast<const uint16_t *>(p)[i];
-    if (ES == 4u) return reinterpret_cast<const uint32_t *>(p)[i];
-    const uint2 q = reinterpret_cast<const uint2 *>(p)[i];
-    return q.y ? 0xffffffffu : q.x;
-}
-
-// element j of the item in w[4]
-template <uint32_t ES>
-DEV_INLINE uint32_t lst_elem(const uint32_t (&w)[4], uint32_t j)
-{
-    if (ES == 1u) return (w[j >> 2] >> (8u * (j & 3u))) & 255u;
-    if (ES == 2u) return (w[j >> 1] >> (16u * (j & 1u))) & 65535u;
-    if (ES == 4u) return w[j];
-    return w[2u * j + 1u] ? 0xffffffffu : w[2u * j];
-}
-
 // are the 16 / ES elements of the item equal?
 template <uint32_t ES>
 DEV_INLINE bool lst_flat(const uint32_t (&w)[4])
@@ -103,7 +80,7 @@ DEV_INLINE void lst_run(uint32_t *tab, const uint8_t *__restrict__ p, const debi
     if (head > n_el) head = n_el;
     const uint32_t items = (n_el - head) / EPI, tail0 = head + items * EPI;
     LstOpen o = {0xffffffffu, 0u, 0u, 0u, 0u, 0u};
-    if (tid < head) lst_take(tab, o, lst_load1<ES>(p, tid), tid % W, t.row0 + tid / W, 1u, t);
+    if (tid < head) lst_take(tab, o, lbl_key(lbl_load<ES>(p + (uint64_t)tid * ES)), tid % W, t.row0 + tid / W, 1u, t);
     if (tid < items) {
         const uint32_t e0 = head + tid * EPI;
         StageWalk at(e0, W, LST_THREADS * EPI);
@@ -111,12 +88,12 @@ DEV_INLINE void lst_run(uint32_t *tab, const uint8_t *__restrict__ p, const debi
             const uint4 q = *reinterpret_cast<const uint4 *>(p + (uint64_t)(head + u * EPI) * ES);
             const uint32_t w[4] = {q.x, q.y, q.z, q.w};
             if (at.x + EPI <= W && lst_flat<ES>(w)) {
-                lst_take(tab, o, lst_elem<ES>(w, 0u), at.x, t.row0 + at.r, EPI, t);
+                lst_take(tab, o, lbl_key(lbl_item_get<ES>(w, 0u)), at.x, t.row0 + at.r, EPI, t);
             } else {
                 uint32_t x = at.x, y = t.row0 + at.r;
 DEV_UNROLL
                 for (uint32_t j = 0; j < EPI; j++) {
-                    lst_take(tab, o, lst_elem<ES>(w, j), x, y, 1u, t);
+                    lst_take(tab, o, lbl_key(lbl_item_get<ES>(w, j)), x, y, 1u, t);
                     if (++x == W) { x = 0u; y++; }
                 }
             }
@@ -125,7 +102,7 @@ DEV_UNROLL
     }
     if (tid >= 16u && tid - 16u < n_el - tail0) { /* (other lanes than the head's; their items lie in front of the tail) */
         const uint32_t i = tail0 + tid - 16u;
-        lst_take(tab, o, lst_load1<ES>(p, i), i % W, t.row0 + i / W, 1u, t);
+        lst_take(tab, o, lbl_key(lbl_load<ES>(p + (uint64_t)i * ES)), i % W, t.row0 + i / W, 1u, t);
     }
     lst_close(tab, o, W, t.out_h);
 }

@@ -1,5 +1,8 @@
 // png_stage_common.inc -- what the tensor-stage kernels share across their files: the lane walk over the items of a row run or
-// tile, the ONE conversion of a 30-bit value to an output element, and the store of one label.
+// tile, the ONE conversion of a 30-bit value to an output element, the store of one label, and what the kernels that post-process
+// a dense label tensor (png_label_{stats, boundary, distance, components}_kernel.inc) share: the bound tests of a task (stage_*_ok)
+// and the access to an element of 1 / 2 / 4 / 8 bytes as (low word, high word) -- load, store, out of and into a 16-byte item, the
+// compare, the 32-bit key, and an int64 `value` as such an element.
 // (What only one family shares stays with the family's first kernel: the resize tile in png_resize_kernel.inc, the gather row
 // body in png_label_kernel.inc, the colour map in png_color_label_kernel.inc, the warp picks in png_warp_kernel.inc.)
 // Included by debig_hip.hip (hipcc) and by the CPU emulator build (tests); needs inflate_kernel.inc in front of it.
@@ -92,4 +95,79 @@ DEV_INLINE void lbl_store1(uint8_t *p, uint32_t v)
         q.x = v; q.y = (uint32_t)((int32_t)v >> 31);
         *reinterpret_cast<uint2 *>(p) = q;
     }
+}
+
+// ---- a dense label tensor as the post-processing kernels read it -------------------------------------------------------------------
+
+// the bound tests every task of these kernels repeats: the image's sides; rows row0 .. row0 + rows - 1 inside an image of h rows;
+// such a run within a budget of max_elems elements, or one row; an offset and the address base + off aligned (align_mask: the
+// alignment - 1; typed loads and stores follow, and a caller's buffer need not be aligned)
+DEV_INLINE bool stage_dim_ok(uint32_t w, uint32_t h) { return w != 0u && w <= 16384u && h != 0u && h <= 16384u; }
+DEV_INLINE bool stage_rows_ok(uint32_t h, uint32_t row0, uint32_t rows) { return rows != 0u && row0 < h && rows <= h - row0; }
+DEV_INLINE bool stage_budget_ok(uint32_t rows, uint32_t w, uint32_t max_elems) { return rows <= max_elems / w || rows == 1u; }
+DEV_INLINE bool stage_addr_ok(const void *base, uint64_t off, uint64_t align_mask)
+{
+    return (off & align_mask) == 0u && (((uintptr_t)base + off) & align_mask) == 0u;
+}
+
+// one element of ES bytes at p (aligned to ES) as (low word, high word)
+template <uint32_t ES>
+DEV_INLINE uint2 lbl_load(const uint8_t *p)
+{
+    uint2 q;
+    q.y = 0u;
+    if (ES == 1u) q.x = *p;
+    else if (ES == 2u) q.x = *reinterpret_cast<const uint16_t *>(p);
+    else if (ES == 4u) q.x = *reinterpret_cast<const uint32_t *>(p);
+    else q = *reinterpret_cast<const uint2 *>(p);
+    return q;
+}
+
+template <uint32_t ES>
+DEV_INLINE void lbl_store(uint8_t *p, uint2 q)
+{
+    if (ES == 1u) *p = (uint8_t)q.x;
+    else if (ES == 2u) *reinterpret_cast<uint16_t *>(p) = (uint16_t)q.x;
+    else if (ES == 4u) *reinterpret_cast<uint32_t *>(p) = q.x;
+    else *reinterpret_cast<uint2 *>(p) = q;
+}
+
+// element j of the 16-byte item in w[4] as (low word, high word)
+template <uint32_t ES>
+DEV_INLINE uint2 lbl_item_get(const uint32_t (&w)[4], uint32_t j)
+{
+    uint2 q;
+    q.y = 0u;
+    if (ES == 1u) q.x = (w[j >> 2] >> (8u * (j & 3u))) & 255u;
+    else if (ES == 2u) q.x = (w[j >> 1] >> (16u * (j & 1u))) & 65535u;
+    else if (ES == 4u) q.x = w[j];
+    else { q.x = w[2u * j]; q.y = w[2u * j + 1u]; }
+    return q;
+}
+
+// element j of the item in w[4] := q
+template <uint32_t ES>
+DEV_INLINE void lbl_item_put(uint32_t (&w)[4], uint32_t j, uint2 q)
+{
+    if (ES == 1u) w[j >> 2] = (w[j >> 2] & ~(255u << (8u * (j & 3u)))) | (q.x << (8u * (j & 3u)));
+    else if (ES == 2u) w[j >> 1] = (w[j >> 1] & ~(65535u << (16u * (j & 1u)))) | (q.x << (16u * (j & 1u)));
+    else if (ES == 4u) w[j] = q.x;
+    else { w[2u * j] = q.x; w[2u * j + 1u] = q.y; }
+}
+
+// are two elements the same?  (whole: exact for packed colours and int64 ids)
+DEV_INLINE bool lbl_same(uint2 a, uint2 b) { return a.x == b.x && a.y == b.y; }
+
+// an element as a 32-bit key: its value, or 0xffffffff for an int64 whose upper word is not zero
+DEV_INLINE uint32_t lbl_key(uint2 q) { return q.y ? 0xffffffffu : q.x; }
+
+// an int64 `value` as an element of ES bytes: its words -> want, and whether an element can equal it at all (uint8 and uint16 are
+// zero-extended, int32 is sign-extended)
+template <uint32_t ES>
+DEV_INLINE bool lbl_value(int64_t value, uint2 &want)
+{
+    want.x = (uint32_t)(uint64_t)value;
+    want.y = ES == 8u ? (uint32_t)((uint64_t)value >> 32) : 0u;
+    return ES == 1u ? (value >= 0 && value <= 255) : ES == 2u ? (value >= 0 && value <= 65535)
+         : ES == 4u ? (value >= -2147483647 - 1 && value <= 2147483647) : true;
 }
