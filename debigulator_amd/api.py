@@ -212,7 +212,7 @@ def gunzip_batch(datas, out_caps):
 
 PNG_STATUS = {0: "ok", 1: "signature", 2: "chunk", 3: "ihdr", 4: "crc", 5: "zlib", 6: "inflate", 7: "adler",
               8: "data_short", 9: "data_long", 10: "filter", 11: "palette", 12: "output", 13: "animation", 14: "box", 15: "label",
-              16: "warp", 17: "color", 18: "tone", 19: "blur"}
+              16: "warp", 17: "color", 18: "tone", 19: "blur", 20: "encode", 21: "range"}
 PNG_FORCE_GENERAL = 1  # include/decode_png.h: DEBIG_PNG_FORCE_GENERAL
 
 
@@ -1354,6 +1354,121 @@ def png_label_components(labels, connectivity=4, background=None, ids="consecuti
                     labels, res.data_ptr(), n, W, H, code, int(connectivity), 0 if background is None else 1,
                     0 if background is None else int(background), _PNG_COMPONENTS_IDS[ids], st, counts)
     return res, np.array(list(counts), np.int64)
+
+
+class PngEncodeDesc(C.Structure):  # include/decode_png.h: debig_png_encode_desc
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("dtype", C.c_uint32), ("depth", C.c_uint32),
+                ("layout", C.c_uint32), ("palette_entries", C.c_uint32), ("trns_entries", C.c_uint32), ("palette_off", C.c_uint64),
+                ("trns_off", C.c_uint64)]
+
+
+PNG_ENCODE_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}  # DEBIG_PNG_FILTER_NONE .. _ADAPTIVE
+PNG_ENCODE_STATUS = {0: "ok", 12: "output", 20: "encode", 21: "range"}  # what png_encode_batch hands out (names: PNG_STATUS)
+
+
+def _png_encode_side(what, given, n, width):
+    """palette= / trns= of png_encode_batch -> one uint8 array or None per image.  A list or tuple has one entry per image; anything
+    else is one array for the batch: (entries, 3) for a palette (width 3), (entries,) for tRNS (width 0)"""
+    def one(v):
+        if v is None:
+            return None
+        a = np.asarray(v.cpu() if hasattr(v, "cpu") else (np.frombuffer(v, np.uint8) if isinstance(v, (bytes, bytearray)) else v))
+        ok = a.dtype == np.uint8 and ((a.ndim == 2 and a.shape[1] == 3) if width else a.ndim == 1) and 1 <= a.shape[0] <= 256
+        if not ok:
+            raise ValueError(f"{what} must be uint8 of shape " + ("(entries, 3)" if width else "(entries,)") + " with 1 .. 256 entries")
+        return np.ascontiguousarray(a)
+    if isinstance(given, (list, tuple)):
+        if len(given) != n:
+            raise ValueError(f"a list of {what}s needs one entry per image")
+        return [one(v) for v in given]
+    return [one(given)] * n
+
+
+def png_encode_batch(images, layout="hwc", depth=None, palette=None, trns=None, filter="adaptive", level=1):
+    """tensors on the GPU -> PNG files (include/decode_png.h: debig_png_encode_batch, which has the file's rules)
+    -> [(status, bytes or None)], one per image; status 0, or 12 "output", 20 "encode" (the descriptor breaks a rule: more than 4
+    channels, a depth that does not fit the dtype, more than one channel with int32 / int64, a palette with channels != 1 or
+    depth != 8, more tRNS than palette entries), 21 "range" (an int32 / int64 element outside 0 .. 2^depth - 1, or an element
+    that is not below the palette's entries).  images: ONE tensor (N, H, W), (N, H, W, C) under layout="hwc" or (N, C, H, W) under
+    "chw", or a LIST of tensors of different shapes (H, W), (H, W, C) or (C, H, W); torch.uint8, uint16 (or int16, read as the
+    uint16 bits, which is how the label calls hand out uint16), int32 or int64, on the current device; a tensor that is not
+    contiguous is made so.  1 / 2 / 3 / 4 channels give grey, grey + alpha, RGB, RGBA; depth: None -- 8 for uint8, 16 for uint16,
+    for int32 / int64 8 with a palette and 16 without --, 8 or 16.  palette: (entries, 3) uint8, one for the batch or a list with
+    one (or None) per image: colour type 3, one channel at depth 8; trns: the palette's alpha bytes, likewise.  filter: "none",
+    "sub", "up", "average", "paeth" for every row, or "adaptive" (per row the minimum sum of absolute differences); level 0
+    (stored) or 1 (LZ77 + fixed Huffman, never longer than level 0).  The bytes are a pure function of the arguments.  Filtering,
+    DEFLATE, Adler-32 and CRC-32 run on the device; each file comes down once.  The call waits for the work queued on the device
+    before it, and for its own.  Not provided: 1 / 2 / 4-bit depths, Adam7, other ancillary chunks, APNG, host tensors."""
+    import torch
+
+    if not isinstance(filter, str) or filter not in PNG_ENCODE_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(PNG_ENCODE_FILTERS)}, not {filter!r}")
+    if isinstance(level, bool) or level not in (0, 1):
+        raise ValueError(f"level must be 0 or 1, not {level!r}")
+    lay = png_layout_code(layout)
+    if depth is not None and (isinstance(depth, bool) or depth not in (8, 16)):
+        raise ValueError(f"depth must be None, 8 or 16, not {depth!r}")
+    one = isinstance(images, torch.Tensor)
+    if one:
+        if images.dim() not in (3, 4):
+            raise ValueError("one tensor must be (N, H, W), (N, H, W, C) or (N, C, H, W)")
+        items = [images[i] for i in range(images.shape[0])]
+    elif isinstance(images, (list, tuple)):
+        items = list(images)
+    else:
+        raise ValueError("images must be a tensor or a list of tensors")
+    n = len(items)
+    pals, trn = _png_encode_side("palette", palette, n, 3), _png_encode_side("trns", trns, n, 0)
+    codes = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = 1
+    for t in items:
+        if not isinstance(t, torch.Tensor) or t.dim() not in (2, 3):
+            raise ValueError("an image must be a tensor (H, W), (H, W, C) or (C, H, W)")
+        if t.dtype not in codes:
+            raise ValueError(f"images must be uint8, uint16 (or int16), int32 or int64, not {t.dtype}")
+        if t.device.type != "cuda":
+            raise ValueError("images must be on the GPU")
+    if n == 0:
+        return []
+    L = _png_spec_lib()
+    _png_device(L, items[0].device)
+    items = [t if t.is_contiguous() else t.contiguous() for t in items]
+    descs = (PngEncodeDesc * n)()
+    side = bytearray()
+    for i, t in enumerate(items):
+        d = descs[i]
+        if t.dim() == 2:
+            (H, W), Cn = t.shape, 1
+        elif lay == 0:
+            H, W, Cn = t.shape
+        else:
+            Cn, H, W = t.shape
+        d.width, d.height, d.channels, d.dtype, d.layout = int(W), int(H), int(Cn), codes[t.dtype], lay
+        d.depth = depth if depth is not None else 8 if d.dtype == 0 else 16 if d.dtype == 1 or pals[i] is None else 8
+        if pals[i] is not None:
+            d.palette_entries, d.palette_off = pals[i].shape[0], len(side)
+            side += pals[i].tobytes()
+        if trn[i] is not None:
+            d.trns_entries, d.trns_off = trn[i].shape[0], len(side)
+            side += trn[i].tobytes()
+    L.debig_png_encode_bound.restype = C.c_uint64
+    L.debig_png_encode_bound.argtypes = [C.POINTER(PngEncodeDesc)]
+    L.debig_png_encode_batch.restype = C.c_int
+    L.debig_png_encode_batch.argtypes = [C.c_void_p] * 7 + [C.c_uint32] * 3
+    caps = [int(L.debig_png_encode_bound(C.byref(descs[i]))) for i in range(n)]
+    outs = [np.empty(max(c, 1), np.uint8) for c in caps]
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in items])
+    out_ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    out_caps = (C.c_uint64 * n)(*caps)
+    sizes, status = (C.c_uint64 * n)(), (C.c_uint32 * n)()
+    side_buf = (C.c_uint8 * max(len(side), 1)).from_buffer_copy(bytes(side) or b"\0")
+    torch.cuda.synchronize(items[0].device)  # whoever wrote the tensors runs on torch's stream, the library on its own
+    rc = L.debig_png_encode_batch(ptrs, descs, side_buf, out_ptrs, out_caps, sizes, status, n, PNG_ENCODE_FILTERS[filter], int(level))
+    if rc == PNG_BAD_ARG:
+        raise ValueError(f"debig_png_encode_batch rejected its arguments ({rc})")
+    N.check(rc, "debig_png_encode_batch")
+    return [(int(status[i]), outs[i][: sizes[i]].tobytes() if status[i] == 0 else None) for i in range(n)]
 
 
 class PngLabelDesc(C.Structure):  # include/decode_png.h: debig_png_label_desc

@@ -30,6 +30,7 @@
 #include "png_label_boundary_kernel.inc"
 #include "png_label_distance_kernel.inc"
 #include "png_label_components_kernel.inc"
+#include "png_encode_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -1056,6 +1057,22 @@ int debig_hip_png_label_components_finish_batch(const void *d_parent, void *d_ou
 {
     return launch_stage(debig_png_label_components_finish_kernel, LCC_THREADS, n_tasks, hip_stream, (const uint8_t *)d_parent,
                         (uint8_t *)d_out, d_tasks);
+}
+
+// PNG encode (png_encode_kernel.inc): the filtered scanlines of dense tensors, one workgroup per run of rows ...
+int debig_hip_png_encode_filter_batch(const void *d_images, void *d_streams, const debig_png_encode_filter_task *d_tasks, void *d_flags,
+                                      uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_encode_filter_kernel, PEF_THREADS, n_tasks, hip_stream, (const uint8_t *)d_images, (uint8_t *)d_streams,
+                        d_tasks, (uint32_t *)d_flags);
+}
+
+// ... and their DEFLATE blocks, one wavefront per chunk
+int debig_hip_png_encode_deflate_batch(const void *d_streams, void *d_slots, const debig_png_encode_deflate_task *d_tasks, void *d_counts,
+                                       uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_encode_deflate_kernel, PED_THREADS, n_tasks, hip_stream, (const uint8_t *)d_streams, (uint8_t *)d_slots,
+                        d_tasks, (uint32_t *)d_counts);
 }
 
 // inflate -> de-filter in one kernel (png_fused_kernel.inc).  Per group of at most SPLIT_GROUP

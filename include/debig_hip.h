@@ -205,7 +205,7 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * _label_gather, _color_label, _warp / _warp_color / _label_warp / _color_label_warp, _persp / _persp_color / _label_persp / _color_label_persp,
  * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur, _label_stats and
  * _label_boundary, _label_distance_rows / _label_distance_cols -- and the five launchers of the label components,
- * _label_components_rows / _merge / _count / _number / _finish --
+ * _label_components_rows / _merge / _count / _number / _finish -- and the two of the PNG encode, _png_encode_filter / _png_encode_deflate --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -1086,6 +1086,66 @@ int debig_hip_png_label_components_number_batch(const void *d_parent, const void
                                                 const debig_png_label_components_task *d_tasks, uint32_t n_tasks, void *hip_stream);
 int debig_hip_png_label_components_finish_batch(const void *d_parent, void *d_out, const debig_png_label_components_task *d_tasks,
                                                 uint32_t n_tasks, void *hip_stream);
+
+/* ---- PNG encode (csrc/png_encode_kernel.inc, behind debig_png_encode_batch in decode_png.h, which has the file's rules): two
+ * launches on one stream.
+ *   FILTER   a task is a run of rows of one image (rows x row_bytes <= DEBIG_PNG_ENCODE_FILTER_BYTES, or one row) for one workgroup
+ *            of 256 lanes: it reads the dense tensor (HWC or CHW, elements of 1 / 2 / 4 / 8 bytes) and writes 1 + row_bytes bytes
+ *            per row, the filter type and the filtered bytes, at stream_off + y * (1 + row_bytes); 16-bit samples big-endian.
+ *            filter 0 .. 4: that type for every row; 5 (ADAPTIVE): per row the type with the smallest sum of min(b, 256 - b) over
+ *            its filtered bytes, ties to the lowest type.  An element above 2^depth - 1 (int32 / int64: negative ones too), or not
+ *            below palette_entries when that is not 0, stores 1 into d_flags[flag_idx]; the caller clears the flags.
+ *   DEFLATE  a task is one chunk of an image's filtered stream, at most DEBIG_PNG_ENCODE_CHUNK bytes, for one wavefront.  It writes
+ *            complete DEFLATE blocks that hold exactly the chunk's bytes into its slot, from the slot's first byte, and their byte
+ *            count into d_counts[count_idx].  last 0: the output ends on a byte boundary with an empty stored block (00 00 FF FF)
+ *            and sets no BFINAL; last 1: the last block has BFINAL, the bits up to the byte boundary are 0.  level 0: one stored
+ *            block.  level 1: one fixed-Huffman block, greedy, matches of 3 .. 258 bytes at distances 1 .. 32768 that may start in
+ *            the 32768 stream bytes in front of the chunk (never in front of the stream, never reading at or behind the chunk's
+ *            end); if that is not smaller than the chunk stored, the chunk is written stored (flags & DEBIG_PNG_ENCODE_NO_STORED:
+ *            never; tests).  The bytes are a pure function of the task and the stream: the same for every grid, order and run.
+ *            NOT BUILT: dynamic Huffman blocks, lazy matching, levels above 1.
+ * A filter task is skipped when dtype is above 3, channels is outside 1 .. 4, depth is neither 8 nor 16 or does not go with the dtype
+ * (uint8: 8, uint16: 16), channels is above 1 with int32 / int64, layout is above 1, filter is above 5, palette_entries is above 256
+ * or set with channels != 1 or depth != 8, w or h is 0 or above 16384, the run leaves the image or exceeds the budget with rows
+ * above 1, or the image is not aligned to its element.  A deflate task is skipped when level or last is above 1, bpp is outside
+ * 1 .. 8, chunk_len is 0 or above the chunk size, the chunk leaves the stream, stream_len does not fit 32 bits, slot_cap is below
+ * DEBIG_PNG_ENCODE_SLOT(chunk_len), or the slot is not aligned to 4. */
+#define DEBIG_PNG_ENCODE_CHUNK 32768u
+#define DEBIG_PNG_ENCODE_FILTER_BYTES 65536u
+#define DEBIG_PNG_ENCODE_SLOT(len) ((((uint64_t)(len) + (uint64_t)(len) / 8u + 32u) + 15u) & ~(uint64_t)15u) /* worst case of a chunk */
+#define DEBIG_PNG_ENCODE_NO_STORED 1u
+typedef struct debig_png_encode_filter_task {
+    uint64_t image_off;       /* the image's first element, in bytes rel. to d_images                                           */
+    uint64_t stream_off;      /* the image's filtered stream, in bytes rel. to d_streams                                        */
+    uint32_t w, h;            /* the image                                                                                      */
+    uint32_t row0, rows;      /* the run of rows                                                                                */
+    uint32_t channels;        /* 1 .. 4                                                                                         */
+    uint32_t dtype;           /* decode_png.h DEBIG_PNG_L_*: uint8, uint16, int32, int64                                        */
+    uint32_t depth;           /* 8, 16                                                                                          */
+    uint32_t layout;          /* decode_png.h DEBIG_PNG_LAYOUT_HWC 0, _CHW 1                                                    */
+    uint32_t filter;          /* 0 .. 4, or 5: adaptive                                                                         */
+    uint32_t palette_entries; /* 0: none                                                                                        */
+    uint32_t flag_idx;        /* the image's word in d_flags                                                                    */
+    uint32_t reserved;
+} debig_png_encode_filter_task;
+typedef struct debig_png_encode_deflate_task {
+    uint64_t stream_off;      /* the image's filtered stream, in bytes rel. to d_streams                                        */
+    uint64_t stream_len;      /* its length                                                                                     */
+    uint64_t chunk_off;       /* the chunk's first byte, rel. to the stream                                                     */
+    uint64_t slot_off;        /* the task's output, in bytes rel. to d_slots (a multiple of 4)                                  */
+    uint32_t chunk_len;       /* 1 .. DEBIG_PNG_ENCODE_CHUNK                                                                    */
+    uint32_t slot_cap;        /* at least DEBIG_PNG_ENCODE_SLOT(chunk_len)                                                      */
+    uint32_t level;           /* 0, 1                                                                                           */
+    uint32_t bpp;             /* channels x depth / 8: a distance that is always tried                                          */
+    uint32_t last;            /* 1: the image's last chunk                                                                      */
+    uint32_t count_idx;       /* the task's word in d_counts                                                                    */
+    uint32_t flags;           /* DEBIG_PNG_ENCODE_NO_STORED                                                                     */
+    uint32_t reserved;
+} debig_png_encode_deflate_task;
+int debig_hip_png_encode_filter_batch(const void *d_images, void *d_streams, const debig_png_encode_filter_task *d_tasks, void *d_flags,
+                                      uint32_t n_tasks, void *hip_stream);
+int debig_hip_png_encode_deflate_batch(const void *d_streams, void *d_slots, const debig_png_encode_deflate_task *d_tasks, void *d_counts,
+                                       uint32_t n_tasks, void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

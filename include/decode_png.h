@@ -1007,6 +1007,60 @@ int debig_png_label_components(const void *d_labels, void *d_out, uint32_t n, ui
                                uint32_t connectivity, uint32_t use_background, int64_t background, uint32_t ids,
                                const uint32_t *status /* host, may be NULL */, uint32_t *counts /* host, may be NULL */);
 
+/* ---- PNG encode: dense tensors in device memory -> PNG files in host memory ---------------------------------------------------------
+ * The way back from the decodes: predictions, label maps, instance ids (debig_png_label_components) or augmented images that live
+ * on the GPU become PNG files without a copy of the pixels to the host.  d_images[i] is image i, a dense tensor of DEBIG_PNG_L_*
+ * elements in device memory, (height, width, channels) under DEBIG_PNG_LAYOUT_HWC or (channels, height, width) under _CHW.
+ * THE FILE is deterministic: the signature; IHDR with colour type 0 / 4 / 2 / 6 for 1 / 2 / 3 / 4 channels, or 3 with a palette,
+ * depth 8 or 16, no interlace; PLTE (palette_entries x 3 bytes at side + palette_off) and tRNS (trns_entries bytes at side +
+ * trns_off) when given; exactly ONE IDAT; IEND; no other chunk.  The IDAT payload is a zlib stream: the header 78 01, the DEFLATE
+ * blocks, the Adler-32 of the filtered scanlines.  16-bit samples are big-endian in the file.
+ * filter: DEBIG_PNG_FILTER_NONE .. _PAETH, that type for every row, or DEBIG_PNG_FILTER_ADAPTIVE: per row the type 0 .. 4 with the
+ * smallest S = the sum of min(b, 256 - b) over the row's filtered bytes b, ties to the lowest type.  Filters are those of the PNG
+ * specification with bpp = channels x depth / 8; the row above the first row and everything left of column 0 are zeros.
+ * level: 0, stored blocks; 1, LZ77 + the fixed Huffman code.  The filtered stream is cut into chunks of DEBIG_PNG_ENCODE_CHUNK bytes
+ * (debig_hip.h) that are compressed side by side, as pigz does: every chunk's blocks end on a byte boundary (an empty stored block
+ * behind every chunk but the last), a chunk's matches may reach into the 32 KiB in front of it, and a level-1 chunk that is not
+ * smaller than the same chunk stored is written stored, so a level-1 file is never longer than the level-0 file.  The bytes are a
+ * pure function of the input.  NOT BUILT: dynamic Huffman blocks, lazy matching, levels above 1.
+ * Statuses are per image; a failed image writes nothing to outs[i] and does not disturb the others; out_sizes[i] is the file's size,
+ * 0 for a failed image (E_OUTPUT: the size that was needed).
+ *   0                    the file was written
+ *   DEBIG_PNG_E_ENCODE   the descriptor breaks a rule: a side of 0 or above 16384; channels outside 1 .. 4; more than one channel
+ *                        with int32 / int64; a depth that does not fit the dtype (uint8: 8, uint16: 16, int32 / int64: 8 or 16); a
+ *                        layout above _CHW; a palette of more than 256 entries, or with channels != 1 or depth != 8; more tRNS than
+ *                        palette entries (without a palette: any); an image pointer that is NULL or not aligned to its element
+ *   DEBIG_PNG_E_RANGE    found on the device: an element outside 0 .. 2^depth - 1 (int32 / int64), or not below palette_entries
+ *   DEBIG_PNG_E_OUTPUT   out_caps[i] is below the file's size, or outs[i] is NULL.  debig_png_encode_bound always suffices.
+ * DEBIG_PNG_BAD_ARG before any device work, statuses unwritten: a NULL array with n > 0 (side may be NULL when no descriptor has a
+ * palette), a filter above 5, a level above 1.  n == 0: returns 0 and touches nothing.  Otherwise 0 or an error code of the device
+ * layer.  The call launches debig_hip_png_encode_filter_batch and debig_hip_png_encode_deflate_batch, reads the chunks' byte counts
+ * and the range flags back, lays the files out in a device arena (header chunks from the host, chunk outputs by debig_hip_gather),
+ * takes the Adler-32 and the IDAT CRC-32 from debig_hip_checksum_batch and downloads every good file once; the host never loops
+ * over pixel or stream bytes.  It is SYNCHRONOUS on the library's stream, like debig_png_label_stats; the caller makes sure that
+ * whoever wrote the tensors on another stream has finished.  NOT THREAD SAFE against the tensor decodes of the same process (it
+ * uses their arenas).  Not provided: 1 / 2 / 4-bit depths, Adam7, ancillary chunks other than tRNS, APNG, files left on the device,
+ * host tensors, an asynchronous variant. */
+#define DEBIG_PNG_E_ENCODE 20 /* the encode descriptor (rules above) */
+#define DEBIG_PNG_E_RANGE 21  /* an element that the file's depth or palette cannot hold */
+enum { DEBIG_PNG_FILTER_NONE = 0, DEBIG_PNG_FILTER_SUB = 1, DEBIG_PNG_FILTER_UP = 2, DEBIG_PNG_FILTER_AVERAGE = 3,
+       DEBIG_PNG_FILTER_PAETH = 4, DEBIG_PNG_FILTER_ADAPTIVE = 5 };
+typedef struct debig_png_encode_desc {
+    uint32_t width, height;   /* 1 .. 16384 each                                                       */
+    uint32_t channels;        /* 1 grey (or palette index), 2 grey + alpha, 3 RGB, 4 RGBA              */
+    uint32_t dtype;           /* DEBIG_PNG_L_U8 / _U16 / _I32 / _I64                                   */
+    uint32_t depth;           /* 8 or 16                                                               */
+    uint32_t layout;          /* DEBIG_PNG_LAYOUT_HWC or _CHW, dense                                   */
+    uint32_t palette_entries; /* 0, or 1 .. 256: colour type 3                                         */
+    uint32_t trns_entries;    /* 0 .. palette_entries                                                  */
+    uint64_t palette_off;     /* the palette, 3 bytes per entry, rel. to side                          */
+    uint64_t trns_off;        /* the tRNS bytes, rel. to side                                          */
+} debig_png_encode_desc;
+uint64_t debig_png_encode_bound(const debig_png_encode_desc *d); /* bytes that always suffice for the file; 0 for a bad descriptor */
+int debig_png_encode_batch(const void *const *d_images /* host array of device pointers */, const debig_png_encode_desc *descs,
+                           const uint8_t *side /* host: palettes, tRNS */, void *const *outs /* host */, const uint64_t *out_caps,
+                           uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level);
+
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its
  * output is that of debig_png_decode_batch byte for byte.  A file whose acTL is honoured fails with E_ANIM when

@@ -31,6 +31,7 @@
 #include "../../debigulator_amd/csrc/png_label_boundary_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_distance_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_components_kernel.inc"
+#include "../../debigulator_amd/csrc/png_encode_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
@@ -669,5 +670,23 @@ extern "C" int emu_png_label_components_finish_batch(const void *parent, void *o
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_label_components_finish_kernel, grid, LCC_THREADS, (const uint8_t *)parent, (uint8_t *)out, tasks, n);
+    return 0;
+}
+
+/* PNG encode (png_encode_kernel.inc), as debig_hip_png_encode_filter_batch and debig_hip_png_encode_deflate_batch launch the two
+ * kernels (grid as above) */
+extern "C" int emu_png_encode_filter_batch(const void *images, void *streams, const debig_png_encode_filter_task *tasks, void *flags,
+                                           uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_encode_filter_kernel, grid, PEF_THREADS, (const uint8_t *)images, (uint8_t *)streams, tasks, (uint32_t *)flags, n);
+    return 0;
+}
+
+extern "C" int emu_png_encode_deflate_batch(const void *streams, void *slots, const debig_png_encode_deflate_task *tasks, void *counts,
+                                            uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_encode_deflate_kernel, grid, PED_THREADS, (const uint8_t *)streams, (uint8_t *)slots, tasks, (uint32_t *)counts, n);
     return 0;
 }
