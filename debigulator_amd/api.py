@@ -1398,13 +1398,27 @@ def png_encode_batch(images, layout="hwc", depth=None, palette=None, trns=None, 
     "sub", "up", "average", "paeth" for every row, or "adaptive" (per row the minimum sum of absolute differences); level 0
     (stored) or 1 (LZ77 + fixed Huffman, never longer than level 0).  The bytes are a pure function of the arguments.  Filtering,
     DEFLATE, Adler-32 and CRC-32 run on the device; each file comes down once.  The call waits for the work queued on the device
-    before it, and for its own.  Not provided: 1 / 2 / 4-bit depths, Adam7, other ancillary chunks, APNG, host tensors."""
+    before it, and for its own.  Not provided: 1 / 2 / 4-bit depths, Adam7, other ancillary chunks, APNG, host tensors.  Level 2
+    (dynamic Huffman blocks) is png_encode_batch_dyn."""
+    return _png_encode(images, layout, depth, palette, trns, filter, level, (0, 1), "debig_png_encode_batch")
+
+
+def png_encode_batch_dyn(images, layout="hwc", depth=None, palette=None, trns=None, filter="adaptive", level=2):
+    """png_encode_batch with level 0, 1 or 2 (include/decode_png.h: debig_png_encode_batch_dyn): the same arguments, rules, statuses
+    and errors.  Levels 0 and 1 give png_encode_batch's bytes.  Level 2 keeps level 1's chunks and matches and writes every chunk
+    as one dynamic Huffman block where that is smaller than the fixed-code block and than the chunk stored, so a level-2 file is
+    never longer than the level-1 file; its zlib header is 78 5E.  The bytes are a pure function of the arguments."""
+    return _png_encode(images, layout, depth, palette, trns, filter, level, (0, 1, 2), "debig_png_encode_batch_dyn")
+
+
+def _png_encode(images, layout, depth, palette, trns, filter, level, levels, call):
+    """the body of png_encode_batch and png_encode_batch_dyn: `levels` are the call's, `call` is its C entry point"""
     import torch
 
     if not isinstance(filter, str) or filter not in PNG_ENCODE_FILTERS:
         raise ValueError(f"filter must be one of {sorted(PNG_ENCODE_FILTERS)}, not {filter!r}")
-    if isinstance(level, bool) or level not in (0, 1):
-        raise ValueError(f"level must be 0 or 1, not {level!r}")
+    if isinstance(level, bool) or level not in levels:
+        raise ValueError(f"level must be {', '.join(str(v) for v in levels[:-1])} or {levels[-1]}, not {level!r}")
     lay = png_layout_code(layout)
     if depth is not None and (isinstance(depth, bool) or depth not in (8, 16)):
         raise ValueError(f"depth must be None, 8 or 16, not {depth!r}")
@@ -1454,8 +1468,9 @@ def png_encode_batch(images, layout="hwc", depth=None, palette=None, trns=None, 
             side += trn[i].tobytes()
     L.debig_png_encode_bound.restype = C.c_uint64
     L.debig_png_encode_bound.argtypes = [C.POINTER(PngEncodeDesc)]
-    L.debig_png_encode_batch.restype = C.c_int
-    L.debig_png_encode_batch.argtypes = [C.c_void_p] * 7 + [C.c_uint32] * 3
+    fn = getattr(L, call)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 7 + [C.c_uint32] * 3
     caps = [int(L.debig_png_encode_bound(C.byref(descs[i]))) for i in range(n)]
     outs = [np.empty(max(c, 1), np.uint8) for c in caps]
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in items])
@@ -1464,10 +1479,10 @@ def png_encode_batch(images, layout="hwc", depth=None, palette=None, trns=None, 
     sizes, status = (C.c_uint64 * n)(), (C.c_uint32 * n)()
     side_buf = (C.c_uint8 * max(len(side), 1)).from_buffer_copy(bytes(side) or b"\0")
     torch.cuda.synchronize(items[0].device)  # whoever wrote the tensors runs on torch's stream, the library on its own
-    rc = L.debig_png_encode_batch(ptrs, descs, side_buf, out_ptrs, out_caps, sizes, status, n, PNG_ENCODE_FILTERS[filter], int(level))
+    rc = fn(ptrs, descs, side_buf, out_ptrs, out_caps, sizes, status, n, PNG_ENCODE_FILTERS[filter], int(level))
     if rc == PNG_BAD_ARG:
-        raise ValueError(f"debig_png_encode_batch rejected its arguments ({rc})")
-    N.check(rc, "debig_png_encode_batch")
+        raise ValueError(f"{call} rejected its arguments ({rc})")
+    N.check(rc, call)
     return [(int(status[i]), outs[i][: sizes[i]].tobytes() if status[i] == 0 else None) for i in range(n)]
 
 

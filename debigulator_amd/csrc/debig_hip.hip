@@ -31,6 +31,7 @@
 #include "png_label_distance_kernel.inc"
 #include "png_label_components_kernel.inc"
 #include "png_encode_kernel.inc"
+#include "png_encode_dynamic_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -1073,6 +1074,21 @@ int debig_hip_png_encode_deflate_batch(const void *d_streams, void *d_slots, con
 {
     return launch_stage(debig_png_encode_deflate_kernel, PED_THREADS, n_tasks, hip_stream, (const uint8_t *)d_streams, (uint8_t *)d_slots,
                         d_tasks, (uint32_t *)d_counts);
+}
+
+// ... or, level 2, their DEFLATE blocks with a dynamic code per chunk (png_encode_dynamic_kernel.inc), the tokens in rows of their own
+int debig_hip_png_encode_dynamic_batch(const void *d_streams, void *d_slots, void *d_tokens, const debig_png_encode_dynamic_task *d_tasks,
+                                       void *d_counts, uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_encode_dynamic_kernel, PED_THREADS, n_tasks, hip_stream, (const uint8_t *)d_streams, (uint8_t *)d_slots,
+                        (uint8_t *)d_tokens, d_tasks, (uint32_t *)d_counts);
+}
+
+// the code builder of level 2 alone: histograms -> code lengths
+int debig_hip_png_encode_codes_batch(const void *d_counts, void *d_lens, const debig_png_encode_codes_task *d_tasks, uint32_t n_tasks,
+                                     void *hip_stream)
+{
+    return launch_stage(debig_png_encode_codes_kernel, PED_THREADS, n_tasks, hip_stream, (const uint8_t *)d_counts, (uint8_t *)d_lens, d_tasks);
 }
 
 // inflate -> de-filter in one kernel (png_fused_kernel.inc).  Per group of at most SPLIT_GROUP

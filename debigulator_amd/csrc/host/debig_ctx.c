@@ -52,6 +52,7 @@ void debig_ctx_release_ptr(debig_ctx *c)
     buf_free(&c->rsz_src);
     buf_free(&c->rsz_tasks);
     buf_free(&c->rsz_weights);
+    buf_free(&c->enc_tokens);
     buf_free(&c->tone_px);
     buf_free(&c->tone_tasks);
     buf_free(&c->tone_hist);

@@ -1,9 +1,13 @@
-/* debig_png_encode_batch (include/decode_png.h, which has the rules): dense tensors in device memory -> PNG files in host memory.
+/* debig_png_encode_batch and debig_png_encode_batch_dyn (include/decode_png.h, which has the rules): dense tensors in device memory
+ * -> PNG files in host memory.  The two calls are their argument checks in front of ONE body; level 2 differs from it in the DEFLATE
+ * launch -- debig_hip_png_encode_dynamic_batch (csrc/png_encode_dynamic_kernel.inc) in rounds of DEBIG_PNG_ENCODE_ROUND_TASKS tasks
+ * that share one arena of worst-case token rows -- and in the zlib header's second byte.
  * The host checks the descriptors, uploads the two task lists, launches the filter and the deflate kernel
  * (csrc/png_encode_kernel.inc), reads the chunks' byte counts and the range flags back, lays every good file out in a device arena
  * -- what stands in front of and behind the DEFLATE bytes comes from the host, the chunk outputs are moved by debig_hip_gather --,
  * takes the Adler-32 of every filtered stream and the CRC-32 of every IDAT from debig_hip_checksum_batch, and downloads each file
  * once.  It never loops over pixel or stream bytes. */
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include "decode_png.h"
@@ -11,6 +15,11 @@
 
 _Static_assert(sizeof(debig_png_encode_filter_task) == 64 && sizeof(debig_png_encode_deflate_task) == 64, "two and four 64-bit fields, the rest uint32");
 _Static_assert(sizeof(debig_png_encode_desc) == 48, "eight uint32, two uint64");
+_Static_assert(sizeof(debig_png_encode_dynamic_task) == 80 && offsetof(debig_png_encode_dynamic_task, token_off) == 64 &&
+                   offsetof(debig_png_encode_dynamic_task, slot_off) == offsetof(debig_png_encode_deflate_task, slot_off) &&
+                   offsetof(debig_png_encode_dynamic_task, flags) == offsetof(debig_png_encode_deflate_task, flags),
+               "a dynamic task is a deflate task and its token row");
+#define TOKEN_ROW (4u * (uint64_t)DEBIG_PNG_ENCODE_CHUNK) /* worst case: every byte of a chunk a literal */
 
 static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
 
@@ -79,15 +88,29 @@ typedef struct enc_image {
     uint64_t head_off;                /* what the host writes, among the uploaded bytes                      */
 } enc_image;
 
-DEBIG_API int debig_png_encode_batch(const void *const *d_images, const debig_png_encode_desc *descs, const uint8_t *side, void *const *outs,
-                                     const uint64_t *out_caps, uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter,
-                                     uint32_t level)
+/* the slot of deflate task k in the task list (tasks of ts bytes each) */
+static uint64_t task_slot_off(const uint8_t *tasks, size_t ts, uint64_t k)
 {
-    if (n == 0) return 0;
-    if (!d_images || !descs || !outs || !out_caps || !out_sizes || !status || filter > DEBIG_PNG_FILTER_ADAPTIVE || level > 1u)
-        return DEBIG_PNG_BAD_ARG;
+    uint64_t v;
+    memcpy(&v, tasks + k * ts + offsetof(debig_png_encode_deflate_task, slot_off), sizeof v);
+    return v;
+}
+
+/* what both calls check before any device work */
+static int args_ok(const void *const *d_images, const debig_png_encode_desc *descs, const uint8_t *side, void *const *outs, const uint64_t *out_caps,
+                   uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level, uint32_t top_level)
+{
+    if (!d_images || !descs || !outs || !out_caps || !out_sizes || !status || filter > DEBIG_PNG_FILTER_ADAPTIVE || level > top_level) return 0;
     for (uint32_t i = 0; i < n; i++)
-        if (descs[i].palette_entries && !side) return DEBIG_PNG_BAD_ARG;
+        if (descs[i].palette_entries && !side) return 0;
+    return 1;
+}
+
+/* the body of both calls; level 0 .. 2 */
+static int encode_body(const void *const *d_images, const debig_png_encode_desc *descs, const uint8_t *side, void *const *outs,
+                       const uint64_t *out_caps, uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level)
+{
+    const size_t ts = level == 2u ? sizeof(debig_png_encode_dynamic_task) : sizeof(debig_png_encode_deflate_task);
     int rc = 2;
     enc_image *im = (enc_image *)calloc(n, sizeof *im);
     uint8_t *blob = NULL, *heads = NULL;
@@ -125,11 +148,12 @@ DEBIG_API int debig_png_encode_batch(const void *const *d_images, const debig_pn
     if (n_ft >= 0x7fffffffu || n_dt >= 0x7fffffffu) goto done;
     /* the arena: the streams, the flags, the counts, then the slots; the files follow once their sizes are known */
     const uint64_t flags_off = at, counts_off = flags_off + debig_align16(4u * (uint64_t)n_good), slots_off = counts_off + debig_align16(4u * n_dt);
-    blob = (uint8_t *)calloc((size_t)(n_ft + n_dt), 64);
+    const uint64_t blob_len = n_ft * 64u + n_dt * ts;
+    blob = (uint8_t *)calloc((size_t)blob_len, 1);
     words = (uint32_t *)malloc((size_t)(n_good + n_dt) * 4u + 16u);
     if (!blob || !words) goto done;
     debig_png_encode_filter_task *ft = (debig_png_encode_filter_task *)blob;
-    debig_png_encode_deflate_task *dt = (debig_png_encode_deflate_task *)(blob + n_ft * 64u);
+    uint8_t *dt = blob + n_ft * 64u; /* deflate tasks, or dynamic tasks at level 2: ts bytes each */
     at = slots_off;
     for (uint32_t k = 0; k < n_good; k++) {
         const enc_image *g = &im[k];
@@ -151,35 +175,52 @@ DEBIG_API int debig_png_encode_batch(const void *const *d_images, const debig_pn
             ft->palette_entries = d->palette_entries;
             ft->flag_idx = k;
         }
-        for (uint64_t j = 0; j < g->tasks; j++, dt++) {
-            dt->stream_off = g->stream_off;
-            dt->stream_len = g->stream_len;
-            dt->chunk_off = j * DEBIG_PNG_ENCODE_CHUNK;
-            dt->chunk_len = (uint32_t)(g->stream_len - dt->chunk_off < DEBIG_PNG_ENCODE_CHUNK ? g->stream_len - dt->chunk_off : DEBIG_PNG_ENCODE_CHUNK);
-            dt->slot_off = at;
-            dt->slot_cap = (uint32_t)DEBIG_PNG_ENCODE_SLOT(dt->chunk_len);
-            dt->level = level;
-            dt->bpp = d->channels * (d->depth / 8u);
-            dt->last = j + 1u == g->tasks;
-            dt->count_idx = (uint32_t)(g->first_task + j);
-            at += dt->slot_cap;
+        for (uint64_t j = 0; j < g->tasks; j++) {
+            debig_png_encode_dynamic_task y; /* its first 64 bytes are the deflate task */
+            memset(&y, 0, sizeof y);
+            y.stream_off = g->stream_off;
+            y.stream_len = g->stream_len;
+            y.chunk_off = j * DEBIG_PNG_ENCODE_CHUNK;
+            y.chunk_len = (uint32_t)(g->stream_len - y.chunk_off < DEBIG_PNG_ENCODE_CHUNK ? g->stream_len - y.chunk_off : DEBIG_PNG_ENCODE_CHUNK);
+            y.slot_off = at;
+            y.slot_cap = (uint32_t)DEBIG_PNG_ENCODE_SLOT(y.chunk_len);
+            y.level = level;
+            y.bpp = d->channels * (d->depth / 8u);
+            y.last = j + 1u == g->tasks;
+            y.count_idx = (uint32_t)(g->first_task + j);
+            y.token_off = ((g->first_task + j) % DEBIG_PNG_ENCODE_ROUND_TASKS) * TOKEN_ROW; /* the row of its place in its round */
+            y.token_cap = (uint32_t)TOKEN_ROW;
+            memcpy(dt + (g->first_task + j) * ts, &y, ts);
+            at += y.slot_cap;
         }
     }
     const uint64_t files_off = at;
-    dt = (debig_png_encode_deflate_task *)(blob + n_ft * 64u);
     /* ---- 2. .. 5. upload, the two launches, the counts and the flags ---- */
     debig_ctx *c = debig_ctx_get(0);
     if (!c) goto done;
-    if ((rc = debig_devbuf_reserve(&c->rsz_tasks, (n_ft + n_dt) * 64u)) || (rc = debig_devbuf_reserve(&c->rsz_weights, files_off)) ||
-        (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, blob, (n_ft + n_dt) * 64u, NULL)))
+    if ((rc = debig_devbuf_reserve(&c->rsz_tasks, blob_len)) || (rc = debig_devbuf_reserve(&c->rsz_weights, files_off)) ||
+        (rc = debig_hip_memcpy_h2d(c->rsz_tasks.ptr, blob, blob_len, NULL)))
         goto done;
     uint8_t *arena = (uint8_t *)c->rsz_weights.ptr;
+    const uint8_t *d_dt = (const uint8_t *)c->rsz_tasks.ptr + n_ft * 64u;
     if ((rc = debig_hip_memset(arena + flags_off, 0, slots_off - flags_off, NULL)) ||
         (rc = debig_hip_png_encode_filter_batch((const void *)base, arena, (const debig_png_encode_filter_task *)c->rsz_tasks.ptr,
-                                                arena + flags_off, (uint32_t)n_ft, NULL)) ||
-        (rc = debig_hip_png_encode_deflate_batch(arena, arena, (const debig_png_encode_deflate_task *)((uint8_t *)c->rsz_tasks.ptr + n_ft * 64u),
-                                                 arena + counts_off, (uint32_t)n_dt, NULL)) ||
-        (rc = debig_hip_memcpy_d2h(words, arena + flags_off, 4u * (uint64_t)n_good, NULL)) ||
+                                                arena + flags_off, (uint32_t)n_ft, NULL)))
+        goto done;
+    if (level == 2u) {
+        /* rounds on one stream run one behind the other: a round's token rows are free when the next one starts */
+        const uint64_t round = n_dt < DEBIG_PNG_ENCODE_ROUND_TASKS ? n_dt : DEBIG_PNG_ENCODE_ROUND_TASKS;
+        if ((rc = debig_devbuf_reserve(&c->enc_tokens, round * TOKEN_ROW))) goto done;
+        for (uint64_t r0 = 0; r0 < n_dt; r0 += round) {
+            const uint64_t m = n_dt - r0 < round ? n_dt - r0 : round;
+            if ((rc = debig_hip_png_encode_dynamic_batch(arena, arena, c->enc_tokens.ptr, (const debig_png_encode_dynamic_task *)(d_dt + r0 * ts),
+                                                         arena + counts_off, (uint32_t)m, NULL)))
+                goto done;
+        }
+    } else if ((rc = debig_hip_png_encode_deflate_batch(arena, arena, (const debig_png_encode_deflate_task *)d_dt, arena + counts_off, (uint32_t)n_dt,
+                                                        NULL)))
+        goto done;
+    if ((rc = debig_hip_memcpy_d2h(words, arena + flags_off, 4u * (uint64_t)n_good, NULL)) ||
         (rc = debig_hip_memcpy_d2h(words + n_good, arena + counts_off, 4u * n_dt, NULL)) || (rc = debig_hip_stream_sync(NULL)))
         goto done;
     /* ---- 6. the files: sizes, statuses, places; what the host writes and the copy list ---- */
@@ -249,7 +290,7 @@ DEBIG_API int debig_png_encode_batch(const void *const *d_images, const debig_pn
         be32(h + hl, (uint32_t)(2u + g->deflate_bytes + 4u));
         memcpy(h + hl + 4, "IDAT", 4);
         h[hl + 8] = 0x78;
-        h[hl + 9] = 0x01;
+        h[hl + 9] = level == 2u ? 0x5E : 0x01; /* FLEVEL 0, or 1 at level 2; FCHECK */
         hl += 10;
         /* the head, the chunk outputs, IEND (the Adler-32 and the IDAT's CRC-32 are patched in behind the checksum launches) */
         cp->src_off = (heads_off - files_off) + g->head_off;
@@ -258,7 +299,7 @@ DEBIG_API int debig_png_encode_batch(const void *const *d_images, const debig_pn
         cp++;
         uint64_t to = g->file_off + hl;
         for (uint64_t j = 0; j < g->tasks; j++, cp++) {
-            cp->src_off = dt[g->first_task + j].slot_off;
+            cp->src_off = task_slot_off(dt, ts, g->first_task + j);
             cp->dst_off = to;
             cp->len = words[n_good + g->first_task + j];
             to += cp->len;
@@ -343,4 +384,22 @@ done:
     free(copies);
     free(spans);
     return rc;
+}
+
+DEBIG_API int debig_png_encode_batch(const void *const *d_images, const debig_png_encode_desc *descs, const uint8_t *side, void *const *outs,
+                                     const uint64_t *out_caps, uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter,
+                                     uint32_t level)
+{
+    if (n == 0) return 0;
+    if (!args_ok(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level, 1u)) return DEBIG_PNG_BAD_ARG;
+    return encode_body(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level);
+}
+
+DEBIG_API int debig_png_encode_batch_dyn(const void *const *d_images, const debig_png_encode_desc *descs, const uint8_t *side, void *const *outs,
+                                         const uint64_t *out_caps, uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter,
+                                         uint32_t level)
+{
+    if (n == 0) return 0;
+    if (!args_ok(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level, 2u)) return DEBIG_PNG_BAD_ARG;
+    return encode_body(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level);
 }

@@ -179,18 +179,29 @@ DEV_INLINE uint64_t ped_literal(uint32_t v, uint32_t &n)
     return ped_rev(0x190u + (v - 144u), 9u);
 }
 
+// a match length 3 .. 258 -> its length symbol - 257 (0 .. 28) | its extra bits << 8 | their value << 16
+DEV_INLINE uint32_t ped_len_sym(uint32_t len)
+{
+    const uint32_t m = len - 3u;
+    if (len == 258u) return 28u;
+    if (m < 8u) return m;
+    const uint32_t eb = ped_log2(m) - 2u;
+    return (4u * eb + 4u + ((m >> eb) & 3u)) | (eb << 8) | ((m & ((1u << eb) - 1u)) << 16);
+}
+
+// a match distance 1 .. 32768 -> its distance symbol (0 .. 29) | its extra bits << 8 | their value << 16
+DEV_INLINE uint32_t ped_dist_sym(uint32_t dist)
+{
+    const uint32_t dm = dist - 1u;
+    if (dm < 4u) return dm;
+    const uint32_t eb = ped_log2(dm) - 1u;
+    return (2u * eb + 2u + ((dm >> eb) & 1u)) | (eb << 8) | ((dm & ((1u << eb) - 1u)) << 16);
+}
+
 // a match (len 3 .. 258, dist 1 .. 32768) in the fixed code -> its bits in stream order, n: how many (at most 31)
 DEV_INLINE uint64_t ped_match(uint32_t len, uint32_t dist, uint32_t &n)
 {
-    uint32_t idx, leb = 0u, lex = 0u;
-    const uint32_t m = len - 3u;
-    if (len == 258u) idx = 28u;
-    else if (m < 8u) idx = m;
-    else {
-        leb = ped_log2(m) - 2u;
-        idx = 4u * leb + 4u + ((m >> leb) & 3u);
-        lex = m & ((1u << leb) - 1u);
-    }
+    const uint32_t ls = ped_len_sym(len), idx = ls & 255u, ds = ped_dist_sym(dist);
     uint32_t ln;
     uint64_t bits;
     if (idx < 23u) { /* symbols 257 .. 279: 7 bits from 0000000 */
@@ -200,20 +211,12 @@ DEV_INLINE uint64_t ped_match(uint32_t len, uint32_t dist, uint32_t &n)
         ln = 8u;
         bits = ped_rev(0xC0u + (idx - 23u), 8u);
     }
-    bits |= (uint64_t)lex << ln;
-    ln += leb;
-    uint32_t dcode, deb = 0u, dex = 0u;
-    const uint32_t dm = dist - 1u;
-    if (dm < 4u) dcode = dm;
-    else {
-        deb = ped_log2(dm) - 1u;
-        dcode = 2u * deb + 2u + ((dm >> deb) & 1u);
-        dex = dm & ((1u << deb) - 1u);
-    }
-    bits |= (uint64_t)ped_rev(dcode, 5u) << ln;
+    bits |= (uint64_t)(ls >> 16) << ln;
+    ln += (ls >> 8) & 255u;
+    bits |= (uint64_t)ped_rev(ds & 255u, 5u) << ln;
     ln += 5u;
-    bits |= (uint64_t)dex << ln;
-    n = ln + deb;
+    bits |= (uint64_t)(ds >> 16) << ln;
+    n = ln + ((ds >> 8) & 255u);
     return bits;
 }
 
@@ -256,69 +259,107 @@ DEV_UNROLL
     return total;
 }
 
+// the matcher's table before a chunk's first step: empty, then the window in front of the chunk (three bytes from a position may
+// reach into the chunk: they are stream bytes)
+DEV_INLINE void ped_window(uint32_t *hash, const uint8_t *__restrict__ stream, uint32_t c0, uint64_t stream_len, uint32_t lane)
+{
+    for (uint32_t k = lane; k < (1u << PED_HASH_BITS); k += 64u) hash[k] = 0u;
+    __syncthreads();
+    for (uint32_t q = (c0 > PED_WINDOW ? c0 - PED_WINDOW : 0u) + lane; q < c0; q += 64u)
+        if ((uint64_t)q + 2u < stream_len) atomicMax(&hash[ped_hash(stream + q)], q + 1u);
+    __syncthreads();
+}
+
+// one step of the matcher: the 64 positions from `base` of the chunk at c0 -> the lanes whose position starts a token; best, dist:
+// this lane's match (best 0: a literal); covered: the first position that no token covers yet, carried from step to step
+DEV_INLINE unsigned long long ped_step(uint32_t *hash, uint32_t *lens, const uint8_t *__restrict__ stream, uint32_t c0, uint32_t len, uint32_t bpp,
+                                       uint32_t base, uint32_t lane, uint32_t &covered, uint32_t &best_out, uint32_t &dist_out)
+{
+    const uint32_t p = base + lane, gp = c0 + p;
+    const uint32_t maxl = p < len ? (len - p < PED_MAX_MATCH ? len - p : PED_MAX_MATCH) : 0u;
+    uint32_t h = 0u, cand = 0u;
+    if (maxl >= 3u) {
+        h = ped_hash(stream + gp);
+        cand = hash[h];
+    }
+    __syncthreads(); /* every lane has read before any inserts */
+    if (maxl >= 3u) atomicMax(&hash[h], gp + 1u);
+    uint32_t best = 0u, dist = 0u;
+    if (maxl >= 3u && p >= covered) {
+        if (gp >= 1u) {
+            best = ped_match_len(stream + gp - 1u, stream + gp, maxl);
+            dist = 1u;
+        }
+        if (bpp > 1u && gp >= bpp && best < maxl) {
+            const uint32_t l = ped_match_len(stream + gp - bpp, stream + gp, maxl);
+            if (l > best) {
+                best = l;
+                dist = bpp;
+            }
+        }
+        // the table's candidate: a position in front of this one, inside the stream and inside the window
+        if (cand != 0u && cand - 1u < gp && gp - (cand - 1u) <= PED_WINDOW && best < maxl) {
+            const uint32_t d = gp - (cand - 1u);
+            if (d != 1u && d != bpp) {
+                const uint32_t l = ped_match_len(stream + gp - d, stream + gp, maxl);
+                if (l > best) {
+                    best = l;
+                    dist = d;
+                }
+            }
+        }
+        if (best < 3u || (best == 3u && dist > PED_TOO_FAR)) best = 0u;
+    }
+    lens[lane] = best;
+    __syncthreads();
+    // the greedy walk, the same in every lane
+    uint32_t q = covered - base; /* covered >= base: a step covers at least its own 64 positions */
+    unsigned long long starts = 0ull;
+    while (q < 64u && base + q < len) {
+        starts |= 1ull << q;
+        const uint32_t l = lens[q];
+        q += l ? l : 1u;
+    }
+    covered = base + q;
+    best_out = best;
+    dist_out = dist;
+    return starts;
+}
+
+// what ends a block whose last symbol's bits end at obits (`eob` zero bits of it are still to come: the fixed code's end of block is
+// 0000000): not the last chunk: an empty stored block (000, padding, 00 00 FF FF); the last: zero padding -> the task's bytes
+DEV_INLINE uint32_t ped_trailer(uint32_t *out, uint32_t *ow, uint32_t obits, uint32_t carry, uint32_t eob, uint32_t last, uint32_t lane)
+{
+    const uint32_t end = obits + eob + (last ? 0u : 3u), end8 = (end + 7u) & ~7u, bytes = (end8 >> 3) + (last ? 0u : 4u);
+    const uint32_t w0 = obits >> 5, nw = ((bytes + 3u) >> 2) - w0; /* at most 3 */
+    if (lane < 4u) out[lane] = lane == 0u ? carry : 0u;
+    __syncthreads();
+    if (lane == 0u && !last) {
+        const uint32_t off = end8 - (w0 << 5);
+        const uint64_t v = (uint64_t)0xFFFF0000u << (off & 31u);
+        out[off >> 5] |= (uint32_t)v;
+        out[(off >> 5) + 1u] |= (uint32_t)(v >> 32);
+    }
+    __syncthreads();
+    if (lane < nw) ow[w0 + lane] = out[lane];
+    __syncthreads();
+    return bytes;
+}
+
 // the chunk as one fixed-Huffman block -> the bytes written
 DEV_INLINE uint32_t ped_fixed(PedLds &L, const uint8_t *__restrict__ stream, uint8_t *__restrict__ slot,
                               const debig_png_encode_deflate_task &t, uint32_t lane)
 {
     const uint32_t len = t.chunk_len, c0 = (uint32_t)t.chunk_off;
     uint32_t *ow = reinterpret_cast<uint32_t *>(slot);
-    for (uint32_t k = lane; k < (1u << PED_HASH_BITS); k += 64u) L.hash[k] = 0u;
-    __syncthreads();
-    // the window in front of the chunk (three bytes from a position may reach into the chunk: they are stream bytes)
-    for (uint32_t q = (c0 > PED_WINDOW ? c0 - PED_WINDOW : 0u) + lane; q < c0; q += 64u)
-        if ((uint64_t)q + 2u < t.stream_len) atomicMax(&L.hash[ped_hash(stream + q)], q + 1u);
-    __syncthreads();
+    ped_window(L.hash, stream, c0, t.stream_len, lane);
     uint32_t obits = 3u, carry = t.last | 2u, covered = 0u; /* BFINAL, BTYPE 01 */
     for (uint32_t base = 0u; base < len; base += 64u) {
-        const uint32_t p = base + lane, gp = c0 + p;
-        const uint32_t maxl = p < len ? (len - p < PED_MAX_MATCH ? len - p : PED_MAX_MATCH) : 0u;
-        uint32_t h = 0u, cand = 0u;
-        if (maxl >= 3u) {
-            h = ped_hash(stream + gp);
-            cand = L.hash[h];
-        }
-        __syncthreads(); /* every lane has read before any inserts */
-        if (maxl >= 3u) atomicMax(&L.hash[h], gp + 1u);
-        uint32_t best = 0u, dist = 0u;
-        if (maxl >= 3u && p >= covered) {
-            if (gp >= 1u) {
-                best = ped_match_len(stream + gp - 1u, stream + gp, maxl);
-                dist = 1u;
-            }
-            if (t.bpp > 1u && gp >= t.bpp && best < maxl) {
-                const uint32_t l = ped_match_len(stream + gp - t.bpp, stream + gp, maxl);
-                if (l > best) {
-                    best = l;
-                    dist = t.bpp;
-                }
-            }
-            // the table's candidate: a position in front of this one, inside the stream and inside the window
-            if (cand != 0u && cand - 1u < gp && gp - (cand - 1u) <= PED_WINDOW && best < maxl) {
-                const uint32_t d = gp - (cand - 1u);
-                if (d != 1u && d != t.bpp) {
-                    const uint32_t l = ped_match_len(stream + gp - d, stream + gp, maxl);
-                    if (l > best) {
-                        best = l;
-                        dist = d;
-                    }
-                }
-            }
-            if (best < 3u || (best == 3u && dist > PED_TOO_FAR)) best = 0u;
-        }
-        L.lens[lane] = best;
-        __syncthreads();
-        // the greedy walk, the same in every lane
-        uint32_t q = covered - base; /* covered >= base: a step covers at least its own 64 positions */
-        unsigned long long starts = 0ull;
-        while (q < 64u && base + q < len) {
-            starts |= 1ull << q;
-            const uint32_t l = L.lens[q];
-            q += l ? l : 1u;
-        }
-        covered = base + q;
+        uint32_t best, dist;
+        const unsigned long long starts = ped_step(L.hash, L.lens, stream, c0, len, t.bpp, base, lane, covered, best, dist);
         uint32_t nb = 0u;
         uint64_t bits = 0u;
-        if ((starts >> lane) & 1ull) bits = best ? ped_match(best, dist, nb) : ped_literal(stream[gp], nb);
+        if ((starts >> lane) & 1ull) bits = best ? ped_match(best, dist, nb) : ped_literal(stream[c0 + base + lane], nb);
         uint32_t at = nb; /* inclusive prefix sum of the bit counts */
 DEV_UNROLL
         for (uint32_t d = 1u; d < 64u; d <<= 1) {
@@ -342,21 +383,7 @@ DEV_UNROLL
         obits += step_bits;
         __syncthreads();
     }
-    // end of block (0000000); not the last chunk: an empty stored block (000, padding, 00 00 FF FF); the last: zero padding
-    const uint32_t end = obits + 7u + (t.last ? 0u : 3u), end8 = (end + 7u) & ~7u, bytes = (end8 >> 3) + (t.last ? 0u : 4u);
-    const uint32_t w0 = obits >> 5, nw = ((bytes + 3u) >> 2) - w0; /* at most 3 */
-    if (lane < 4u) L.out[lane] = lane == 0u ? carry : 0u;
-    __syncthreads();
-    if (lane == 0u && !t.last) {
-        const uint32_t off = end8 - (w0 << 5);
-        const uint64_t v = (uint64_t)0xFFFF0000u << (off & 31u);
-        L.out[off >> 5] |= (uint32_t)v;
-        L.out[(off >> 5) + 1u] |= (uint32_t)(v >> 32);
-    }
-    __syncthreads();
-    if (lane < nw) ow[w0 + lane] = L.out[lane];
-    __syncthreads();
-    return bytes;
+    return ped_trailer(L.out, ow, obits, carry, 7u, t.last, lane);
 }
 
 __global__ void __launch_bounds__(PED_THREADS)

@@ -206,6 +206,7 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur, _label_stats and
  * _label_boundary, _label_distance_rows / _label_distance_cols -- and the five launchers of the label components,
  * _label_components_rows / _merge / _count / _number / _finish -- and the two of the PNG encode, _png_encode_filter / _png_encode_deflate --
+ * and the two of its level 2, _png_encode_dynamic / _png_encode_codes --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -1146,6 +1147,65 @@ int debig_hip_png_encode_filter_batch(const void *d_images, void *d_streams, con
                                       uint32_t n_tasks, void *hip_stream);
 int debig_hip_png_encode_deflate_batch(const void *d_streams, void *d_slots, const debig_png_encode_deflate_task *d_tasks, void *d_counts,
                                        uint32_t n_tasks, void *hip_stream);
+
+/* ---- PNG encode, level 2 (csrc/png_encode_dynamic_kernel.inc, behind debig_png_encode_batch_dyn in decode_png.h): the DEFLATE task
+ * of above with one dynamic-Huffman block per chunk where that is smaller.
+ *   DYNAMIC  a task is a deflate task (level 2) plus a token row: token_cap bytes at d_tokens + token_off (a multiple of 4), at
+ *            least 4 x chunk_len, the task's own.  One wavefront runs level 1's matcher -- the SAME token sequence --, stores one
+ *            32-bit token per literal or match into the row and counts the literal/length and distance symbols; builds the two
+ *            codes and the code-length code by the rule below; knows the exact sizes of the chunk stored, in the fixed code and in
+ *            the dynamic code (header included) before it writes; and writes the dynamic block iff dynamic_bits < fixed_bits and
+ *            its bytes with the trailer are below the stored bytes (flags & DEBIG_PNG_ENCODE_NO_STORED waives the second
+ *            condition), else exactly the bytes of level 1 for that task and those flags.  flags & DEBIG_PNG_ENCODE_ONLY_DYNAMIC
+ *            (tests): the dynamic block whenever its bytes fit slot_cap, whatever the sizes say.  Slot, count, trailer, `last` and
+ *            the purity of the bytes are those of the deflate task; per chunk level 2 <= level 1 <= level 0.
+ *   The rule for an alphabet of n symbols with counts c[s] and limit L (15: literal/length, n 286, and distance, n 30; 7: the
+ *   code-length code, n 19): the used symbols are those with c > 0; with fewer than two of them every used symbol gets length 1 and
+ *   then the unused symbols of lowest index get length 1 until two symbols have it.  Else the used symbols are ordered by (count,
+ *   index) ascending and a Huffman tree is built with two queues (leaves in that order, internal nodes in creation order; each step
+ *   takes the two smallest weights, a leaf before an internal node of the same weight); num[l] counts the leaves of depth l, depths
+ *   above L at L; while the Kraft total sum(num[l] << (L - l)) exceeds 1 << L: num[L] -= 1, the largest l < L with num[l] > 0 gives
+ *   num[l] -= 1 and num[l + 1] += 2, total -= 1; the lengths are handed out along the order, the first num[L] symbols get L, the
+ *   next num[L - 1] get L - 1, and so on; the codes are canonical (RFC 1951 3.2.2).  The header: HLIT = max(257, 1 + the last used
+ *   literal/length symbol), HDIST = 1 + the last used distance symbol; the two length lists are one list, coded greedily from the
+ *   front over maximal runs of one value v (v = 0: symbol 18 for min(run, 138) while run >= 11, then symbol 17 for a rest of
+ *   3 .. 10, a rest of 1 .. 2 as zeros; v != 0: v once, symbol 16 for min(rest, 6) while rest >= 3, a rest of 1 .. 2 as v); HCLEN
+ *   drops the trailing zeros of the RFC's order, down to 4.
+ *   CODES    a task is (n counts of 32 bits at d_counts + counts_off, the limit) -> n length bytes at d_lens + lens_off, one
+ *            wavefront per task, by the SAME device function: how tests reach the builder with histograms no stream produces.
+ * A dynamic task is skipped when a deflate task with its fields would be (level: anything but 2), token_off is no multiple of 4 or
+ * token_cap is below 4 x chunk_len.  A codes task is skipped when n is 0 or above 286, limit is 0 or above 15 or 1 << limit is
+ * below n, counts_off is no multiple of 4, or a count is above DEBIG_PNG_ENCODE_CODES_MAX_COUNT (the weights are summed in 32 bits). */
+#define DEBIG_PNG_ENCODE_ONLY_DYNAMIC 2u
+#define DEBIG_PNG_ENCODE_ROUND_TASKS 2048u /* the host launches level 2 in rounds of so many tasks: 256 MiB of token rows */
+#define DEBIG_PNG_ENCODE_CODES_MAX_COUNT (1u << 22)
+typedef struct debig_png_encode_dynamic_task {
+    uint64_t stream_off;      /* the fields of debig_png_encode_deflate_task ...                                                */
+    uint64_t stream_len;
+    uint64_t chunk_off;
+    uint64_t slot_off;
+    uint32_t chunk_len;
+    uint32_t slot_cap;
+    uint32_t level;           /* 2                                                                                              */
+    uint32_t bpp;
+    uint32_t last;
+    uint32_t count_idx;
+    uint32_t flags;           /* DEBIG_PNG_ENCODE_NO_STORED, DEBIG_PNG_ENCODE_ONLY_DYNAMIC                                      */
+    uint32_t reserved;
+    uint64_t token_off;       /* ... and the task's token row, in bytes rel. to d_tokens (a multiple of 4)                      */
+    uint32_t token_cap;       /* its bytes, at least 4 x chunk_len                                                              */
+    uint32_t reserved2;
+} debig_png_encode_dynamic_task;
+typedef struct debig_png_encode_codes_task {
+    uint64_t counts_off;      /* n counts of 32 bits, in bytes rel. to d_counts (a multiple of 4)                               */
+    uint64_t lens_off;        /* n length bytes, rel. to d_lens                                                                 */
+    uint32_t n;               /* 1 .. 286                                                                                       */
+    uint32_t limit;           /* 1 .. 15, 1 << limit >= n                                                                       */
+} debig_png_encode_codes_task;
+int debig_hip_png_encode_dynamic_batch(const void *d_streams, void *d_slots, void *d_tokens, const debig_png_encode_dynamic_task *d_tasks,
+                                       void *d_counts, uint32_t n_tasks, void *hip_stream);
+int debig_hip_png_encode_codes_batch(const void *d_counts, void *d_lens, const debig_png_encode_codes_task *d_tasks, uint32_t n_tasks,
+                                     void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

@@ -1022,7 +1022,8 @@ int debig_png_label_components(const void *d_labels, void *d_out, uint32_t n, ui
  * (debig_hip.h) that are compressed side by side, as pigz does: every chunk's blocks end on a byte boundary (an empty stored block
  * behind every chunk but the last), a chunk's matches may reach into the 32 KiB in front of it, and a level-1 chunk that is not
  * smaller than the same chunk stored is written stored, so a level-1 file is never longer than the level-0 file.  The bytes are a
- * pure function of the input.  NOT BUILT: dynamic Huffman blocks, lazy matching, levels above 1.
+ * pure function of the input.  NOT BUILT: dynamic Huffman blocks, lazy matching, levels above 1.  (In THIS call: level 2, one dynamic
+ * Huffman block per chunk, is debig_png_encode_batch_dyn below; this call's surface and bytes are as they were.)
  * Statuses are per image; a failed image writes nothing to outs[i] and does not disturb the others; out_sizes[i] is the file's size,
  * 0 for a failed image (E_OUTPUT: the size that was needed).
  *   0                    the file was written
@@ -1060,6 +1061,20 @@ uint64_t debig_png_encode_bound(const debig_png_encode_desc *d); /* bytes that a
 int debig_png_encode_batch(const void *const *d_images /* host array of device pointers */, const debig_png_encode_desc *descs,
                            const uint8_t *side /* host: palettes, tRNS */, void *const *outs /* host */, const uint64_t *out_caps,
                            uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level);
+/* The same call with level 0, 1 or 2.  Levels 0 and 1 are debig_png_encode_batch byte for byte.  LEVEL 2: the chunks and the token
+ * sequence of level 1 (the same greedy matcher), but every chunk is written as ONE DYNAMIC HUFFMAN BLOCK where that is smaller: the
+ * device knows the exact sizes of the chunk stored, in the fixed code and in its own dynamic code (header included) before it
+ * writes, and writes the dynamic block iff dynamic_bits < fixed_bits and its bytes with the trailer are below the stored bytes, else
+ * exactly what level 1 writes.  So per chunk and per file level 2 <= level 1 <= level 0, and debig_png_encode_bound holds.  The code
+ * lengths are a length-limited Huffman code by a rule that debig_hip.h states word for word (debig_hip_png_encode_dynamic_batch),
+ * so the bytes are a pure function of the input here too.  The zlib header is 78 5E at level 2 and 78 01 below.  Everything else --
+ * descriptors, statuses, filter, container, checksums, the three synchronisations, thread safety -- is the call above; the level-2
+ * tasks run in rounds of DEBIG_PNG_ENCODE_ROUND_TASKS that share one device arena of token rows (at most 256 MiB), which changes
+ * no byte.  DEBIG_PNG_BAD_ARG before any device work for a level above 2.  NOT BUILT: lazy matching and hash chains, levels above
+ * 2, more than one block per chunk, optimal (package-merge) lengths. */
+int debig_png_encode_batch_dyn(const void *const *d_images /* host array of device pointers */, const debig_png_encode_desc *descs,
+                               const uint8_t *side /* host: palettes, tRNS */, void *const *outs /* host */, const uint64_t *out_caps,
+                               uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

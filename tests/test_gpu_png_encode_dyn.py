@@ -1,0 +1,255 @@
+"""Level 2 of the PNG encode on the MI355X (include/decode_png.h: debig_png_encode_batch_dyn; csrc/png_encode_dynamic_kernel.inc):
+  * test_battery runs the emulator battery tests/test_emu_png_encode_dyn.py as it is -- the same run_*() / check_*(), inputs, cuts and
+    grids, check_task() for every task, the byte for byte comparison with the restated dynamic block built from the LEVEL-1 KERNEL's
+    tokens (which run on the GPU here too), the codes battery against the restated rule, the recorded digests -- with the launch
+    seam tests/stage_launch.py switched to the product library.  Nothing is compared with the emulator, which is neither built nor
+    loaded.  LEFT OUT on purpose: the tasks that break a bound, for the reason tests/test_gpu_png_stage_kernels.py and
+    tests/test_gpu_png_encode.py give (wrong on purpose, integer predicates that do not depend on the machine, and a wrong predicate
+    on a shared GPU would be an out-of-range access).  The seam checks that the inputs and the bytes around every buffer are unchanged.
+  * the whole call api.png_encode_batch_dyn at level 2 for every colour type x depth x layout under filters none and adaptive: the
+    payload inflated by zlib.decompress is the restated filtered stream, the container and every CRC are right, the header is 78 5E,
+    the file is not longer than the level-1 file, which is within the bound, and the file gives the input bit for bit through
+    api.png_decode_batch(mode="native", depth="native"): the project's own inflate reads its own dynamic blocks;
+  * a label-like map with at least one BTYPE 2 chunk, levels 0 and 1 against the old call, 2049 images of 1 x 1 (the round seam), a
+    mixed batch in which every status occurs, and the digests of tests/golden/png_encode_dyn.json, recorded from the EMULATOR."""
+import ctypes as C
+import hashlib
+import inspect
+import json
+import os
+import struct
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import png_encode_dyn_ref as D  # noqa: E402
+import png_encode_ref as R  # noqa: E402
+import stage_launch as SL  # noqa: E402
+import test_emu_png_encode as E  # noqa: E402  (imports neither build nor load the emulator)
+import test_emu_png_encode_dyn as Y  # noqa: E402
+from test_gpu_png_encode import _param_sets, _structured, _tensor, parse  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+EXCLUDED = {"test_tasks_that_break_a_bound_dynamic": "hands the dynamic kernel tasks that break a bound on purpose",
+            "test_tasks_that_break_a_bound_codes": "hands the codes kernel tasks that break a bound on purpose"}
+# the cases of which at least one launch must start fewer workgroups than it has tasks
+FEWER = {"test_tasks_not_in_the_launch_keep_their_slots_and_rows", "test_the_choice_takes_every_branch",
+         "test_codes_random_histograms"}
+NEW = {Y.DYNAMIC, Y.CODES}
+
+
+def _battery_tests():
+    return {name: fn for name, fn in vars(Y).items() if name.startswith("test") and inspect.isfunction(fn) and fn.__module__ == Y.__name__}
+
+
+def _cases():
+    out = []
+    for name, fn in _battery_tests().items():
+        if name in EXCLUDED:
+            continue
+        for kw in _param_sets(fn):
+            assert set(kw) == set(inspect.signature(fn).parameters), (name, "an argument that no parametrize mark gives")
+            out.append(pytest.param(name, kw, id=name[5:] + "".join("-" + str(v) for v in kw.values())))
+    return out
+
+
+@pytest.fixture(autouse=True)
+def on_the_gpu(gpu_device, monkeypatch):
+    """every launch of this module's tests goes to the product library, and is recorded: [(kernel, tasks, n, grid)]"""
+    for k, roles in Y.KERNELS.items():
+        monkeypatch.setitem(SL.KERNELS, k, roles)
+    monkeypatch.setattr(SL, "backend", "gpu")
+    monkeypatch.setattr(SL, "record", [])
+    monkeypatch.delenv("DEBIG_STAGE_GRID", raising=False)
+    return SL.record
+
+
+def test_every_battery_case_runs_or_is_excluded():
+    tests = _battery_tests()
+    ran = {c.values[0] for c in _cases()}
+    assert ran | set(EXCLUDED) == set(tests) and not ran & set(EXCLUDED) and all(EXCLUDED.values())
+    assert all(name.startswith("test_tasks_that_break_a_bound_") for name in EXCLUDED)
+    assert FEWER <= ran and len(ran) >= 15
+
+
+@pytest.mark.parametrize("name,kw", _cases())
+def test_battery(name, kw, on_the_gpu):
+    _battery_tests()[name](**kw)
+    assert on_the_gpu and {r[0] for r in on_the_gpu} <= set(Y.KERNELS), (name, "a kernel whose launch did not reach the GPU")
+    assert any(n > 0 and k in NEW for k, _, n, _ in on_the_gpu), name
+    if name in FEWER:
+        assert any(0 < g < n and k in NEW for k, _, n, g in on_the_gpu), (name, "no launch with fewer workgroups than tasks")
+
+
+# ---- the whole call ----------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def api(gpu_device):
+    from debigulator_amd import api as A_
+
+    return A_
+
+
+def check_file(data, samples, depth, filt, palette=None, trns=None):
+    """one level-2 file against the restatement: container, zlib stream, filtered stream -> (the IDAT's body, its DEFLATE blocks)"""
+    samples = np.asarray(samples)
+    H, W, Cn = samples.shape
+    ch = parse(data)
+    assert ch[b"IHDR"] == struct.pack(">IIBBBBB", W, H, depth, 3 if palette is not None else R.COLOR_TYPE[Cn], 0, 0, 0) and ch[b"IEND"] == b""
+    if palette is not None:
+        assert ch[b"PLTE"] == np.asarray(palette, np.uint8).tobytes()
+    assert ch.get(b"tRNS") == (None if trns is None else bytes(bytearray(trns)))
+    z = ch[b"IDAT"]
+    stream = R.filtered_stream(samples, depth, filt)
+    assert z[:2] == b"\x78\x5e" and zlib.decompress(z) == stream
+    assert z[-4:] == struct.pack(">I", zlib.adler32(stream) & 0xFFFFFFFF)
+    assert R.container(W, H, Cn, depth, z, palette, trns) == data
+    return z
+
+
+def btypes(z):
+    """the types of the blocks that hold bytes, and of the empty stored blocks between the chunks"""
+    return [b["btype"] for b in D.blocks(z[2:-4]) if b["bytes"] or b["btype"]]
+
+
+@pytest.mark.parametrize("filt", ["none", "adaptive"])
+@pytest.mark.parametrize("layout", ["hwc", "chw"])
+def test_every_colour_type_depth_and_layout_at_level_2(api, gpu_device, layout, filt):
+    imgs, metas = [], []
+    for Cn in (1, 2, 3, 4):
+        for dtype, depth in (("uint8", 8), ("uint16", 16)):
+            for s in (E._rand(Cn + depth, 23 + Cn, 37 - Cn, Cn, depth), _structured(Cn, 30, 41 + Cn, Cn, depth)):
+                imgs.append(_tensor(gpu_device, s, dtype, layout))
+                metas.append((s, depth))
+    res = api.png_encode_batch_dyn(imgs, layout=layout, filter=filt)
+    one = api.png_encode_batch(imgs, layout=layout, filter=filt, level=1)
+    assert [st for st, _ in res] == [0] * len(imgs) == [st for st, _ in one]
+    dynamic = 0
+    for (st, data), (_, data1), (s, depth) in zip(res, one, metas):
+        z = check_file(data, s, depth, R.FILTERS[filt])
+        H, W, Cn = s.shape
+        assert len(data) <= len(data1) <= R.bound(W, H, Cn, depth)
+        dynamic += 2 in btypes(z)
+        st2, got, _, _, _ = R.samples_of(data)
+        assert st2 == 0 and np.array_equal(got, s)
+    assert dynamic >= 1, "level 2 never chose a dynamic block"
+    back = api.png_decode_batch([d for _, d in res], mode="native", depth="native")
+    for (st, px, inf), (s, depth) in zip(back, metas):
+        assert st == 0 and px.dtype == (np.uint16 if depth == 16 else np.uint8) and np.array_equal(px.astype(np.int64), s)
+
+
+def _label_map(seed, H, W, classes):
+    rng = np.random.default_rng(seed)
+    return np.repeat(np.repeat(rng.integers(0, classes, (H // 8 + 1, W // 16 + 1)), 8, axis=0), 16, axis=1)[:H, :W, None]
+
+
+def test_a_label_map_of_several_chunks_has_dynamic_blocks_and_round_trips(api, gpu_device):
+    rng = np.random.default_rng(5)
+    pal = rng.integers(0, 256, (21, 3), dtype=np.uint8)
+    lab = _label_map(1, 300, 400, 21)  # 120 300 bytes: four chunks
+    ids = _label_map(2, 200, 300, 3000)  # at depth 16: 120 200 bytes
+    for filt in ("none", "adaptive"):
+        (st, data), = api.png_encode_batch_dyn([_tensor(gpu_device, lab)], palette=pal, filter=filt)
+        (_, data1), = api.png_encode_batch([_tensor(gpu_device, lab)], palette=pal, filter=filt)
+        z = check_file(data, lab, 8, R.FILTERS[filt], palette=pal)
+        assert st == 0 and btypes(z).count(2) >= 1 and len(data) < len(data1)
+        stl, t, _ = api.png_decode_batch_labels([data], (300, 400), dtype="uint8")
+        assert list(stl) == [0] and np.array_equal(t.cpu().numpy()[0], lab[:, :, 0])
+        (st, data), = api.png_encode_batch_dyn([_tensor(gpu_device, ids, "int32")], depth=16, filter=filt)
+        (_, data1), = api.png_encode_batch([_tensor(gpu_device, ids, "int32")], depth=16, filter=filt)
+        z = check_file(data, ids, 16, R.FILTERS[filt])
+        assert st == 0 and btypes(z).count(2) >= 1 and len(data) < len(data1)
+        (st2, px, _), = api.png_decode_batch([data], mode="native", depth="native")
+        assert st2 == 0 and np.array_equal(px.astype(np.int64), ids)
+
+
+def test_levels_0_and_1_through_the_new_call_are_the_old_call(api, gpu_device, monkeypatch):
+    imgs = [_tensor(gpu_device, _structured(k, 150, 160, 3, 8)) for k in range(3)] + [_tensor(gpu_device, E._rand(7, 40, 50, 1, 16), "uint16")]
+    for level in (0, 1):
+        for filt in ("none", "adaptive"):
+            assert api.png_encode_batch_dyn(imgs, filter=filt, level=level) == api.png_encode_batch(imgs, filter=filt, level=level)
+    # ... and the grid changes no byte of level 2
+    plain = api.png_encode_batch_dyn(imgs)
+    monkeypatch.setenv("DEBIG_STAGE_GRID", "3")
+    three = api.png_encode_batch_dyn(imgs)
+    monkeypatch.delenv("DEBIG_STAGE_GRID")
+    assert plain == three and all(s == 0 for s, _ in plain)
+
+
+def test_2049_images_of_one_pixel_cross_the_round_seam(api, gpu_device):
+    import torch
+
+    assert D.ROUND_TASKS == 2048
+    vals = np.arange(2049) % 251
+    t = torch.from_numpy(vals.astype(np.uint8).reshape(2049, 1, 1)).to(gpu_device)
+    res = api.png_encode_batch_dyn(t, filter="none")
+    assert len(res) == 2049 and all(st == 0 for st, _ in res)
+    want = {int(v): R.container(1, 1, 1, 8, b"\x78\x5e" + _two_byte_payload(bytes([0, int(v)]))) for v in set(vals.tolist())}
+    for k in (0, 1, 2047, 2048):
+        check_file(res[k][1], np.array([[[vals[k]]]]), 8, 0)
+    assert all(data == want[int(v)] for (_, data), v in zip(res, vals))
+
+
+def _two_byte_payload(stream):
+    """the level-2 payload of a stream of two bytes: what level 1 writes (a fixed block), and the Adler-32"""
+    tokens = list(stream)
+    assert D.choice(tokens, len(stream), True) == "fixed"
+    bits, n = 3, 3  # BFINAL, BTYPE 01
+    for v in tokens + [256]:
+        code, k = (0x30 + v, 8) if v < 144 else (0x190 + v - 144, 9) if v < 256 else (0, 7)
+        bits |= int(format(code, "0%db" % k)[::-1], 2) << n
+        n += k
+    return bits.to_bytes((n + 7) // 8, "little") + (zlib.adler32(stream) & 0xFFFFFFFF).to_bytes(4, "big")
+
+
+def test_a_mixed_batch_in_which_every_status_occurs(api, gpu_device):
+    import torch
+
+    good = [_label_map(k, 60 + k, 90, 9) for k in range(3)]
+    bad_range = good[1].copy()
+    bad_range[7, 9, 0] = 256
+    t_good = [_tensor(gpu_device, g, "int32") for g in good]
+    t_five = torch.zeros((4, 6, 5), dtype=torch.uint8, device=gpu_device)  # five channels
+    alone = api.png_encode_batch_dyn(t_good, depth=8)
+    mixed = api.png_encode_batch_dyn([t_good[0], _tensor(gpu_device, bad_range, "int32"), t_good[1], t_five, t_good[2]], depth=8)
+    assert [s for s, _ in mixed] == [0, R.E_RANGE, 0, R.E_ENCODE, 0] and mixed[1][1] is None and mixed[3][1] is None
+    assert [mixed[0][1], mixed[2][1], mixed[4][1]] == [d for _, d in alone]
+    for (s_, d), g in zip(alone, good):
+        assert s_ == 0
+        check_file(d, g, 8, 5)
+    # E_OUTPUT through the C call: a cap one below the size, beside a file that fits exactly; level 3 is refused
+    from debigulator_amd import _native as N
+
+    L = N.lib()
+    size = len(alone[0][1])
+    descs = (api.PngEncodeDesc * 2)()
+    for d in descs:
+        d.width, d.height, d.channels, d.dtype, d.depth = 90, 60, 1, 2, 8
+    bufs = [np.full(size + 8, 0xAB, np.uint8) for _ in range(2)]
+    sizes, status = (C.c_uint64 * 2)(), (C.c_uint32 * 2)()
+    torch.cuda.synchronize()
+    L.debig_png_encode_batch_dyn.restype = C.c_int
+    L.debig_png_encode_batch_dyn.argtypes = [C.c_void_p] * 7 + [C.c_uint32] * 3
+    args = ((C.c_void_p * 2)(t_good[0].data_ptr(), t_good[0].data_ptr()), descs, None, (C.c_void_p * 2)(*[b.ctypes.data for b in bufs]),
+            (C.c_uint64 * 2)(size - 1, size), sizes, status, 2, 5)
+    assert L.debig_png_encode_batch_dyn(*args, 3) == R.BAD_ARG and (bufs[1] == 0xAB).all()
+    rc = L.debig_png_encode_batch_dyn(*args, 2)
+    assert rc == 0 and list(status) == [R.E_OUTPUT, 0] and list(sizes) == [size, size]
+    assert (bufs[0] == 0xAB).all() and bufs[1][:size].tobytes() == alone[0][1] and (bufs[1][size:] == 0xAB).all()
+    with pytest.raises(ValueError, match="level"):
+        api.png_encode_batch_dyn(t_good, level=3)
+
+
+def test_the_digests_recorded_from_the_emulator(api, gpu_device):
+    rec = json.load(open(Y.golden_path()))
+    cases = Y.golden_inputs()
+    assert sorted(rec) == sorted(c[0] for c in cases)
+    for name, im, filt, pal, trns in cases:
+        t = _tensor(gpu_device, im.s, im.dtype, im.layout)
+        (st, data), = api.png_encode_batch_dyn([t], layout=im.layout, depth=im.depth, palette=pal, trns=trns,
+                                               filter=[k for k, v in R.FILTERS.items() if v == filt][0])
+        assert st == 0 and hashlib.sha256(data).hexdigest() == rec[name], name

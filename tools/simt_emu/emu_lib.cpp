@@ -32,6 +32,7 @@
 #include "../../debigulator_amd/csrc/png_label_distance_kernel.inc"
 #include "../../debigulator_amd/csrc/png_label_components_kernel.inc"
 #include "../../debigulator_amd/csrc/png_encode_kernel.inc"
+#include "../../debigulator_amd/csrc/png_encode_dynamic_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
@@ -688,5 +689,24 @@ extern "C" int emu_png_encode_deflate_batch(const void *streams, void *slots, co
 {
     if (grid == 0 || grid > n) grid = n;
     if (n) EMU_LAUNCH(debig_png_encode_deflate_kernel, grid, PED_THREADS, (const uint8_t *)streams, (uint8_t *)slots, tasks, (uint32_t *)counts, n);
+    return 0;
+}
+
+/* level 2 of the PNG encode (png_encode_dynamic_kernel.inc), as debig_hip_png_encode_dynamic_batch and debig_hip_png_encode_codes_batch
+ * launch its two kernels (grid as above) */
+extern "C" int emu_png_encode_dynamic_batch(const void *streams, void *slots, void *tokens, const debig_png_encode_dynamic_task *tasks,
+                                            void *counts, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n)
+        EMU_LAUNCH(debig_png_encode_dynamic_kernel, grid, PED_THREADS, (const uint8_t *)streams, (uint8_t *)slots, (uint8_t *)tokens, tasks,
+                   (uint32_t *)counts, n);
+    return 0;
+}
+
+extern "C" int emu_png_encode_codes_batch(const void *counts, void *lens, const debig_png_encode_codes_task *tasks, uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n) EMU_LAUNCH(debig_png_encode_codes_kernel, grid, PED_THREADS, (const uint8_t *)counts, (uint8_t *)lens, tasks, n);
     return 0;
 }
