@@ -173,6 +173,7 @@ typedef struct gz_item { /* one member in flight */
     uint32_t file;
     uint64_t payload;    /* file offset of its DEFLATE data            */
     uint64_t known_end;  /* file offset just past its trailer, or 0    */
+    uint64_t claimed_end; /* the same as its "BC" subfield has it, usable or not; 0 without one */
     uint64_t out_rel;    /* where its output starts in the file's output */
 } gz_item;
 
@@ -255,8 +256,9 @@ DEBIG_API int debig_gunzip_batch(const uint8_t *const *inputs, const uint64_t *i
                     uint64_t hl = 0, bs = 0;
                     uint32_t st = gz_member_header(inputs[i] + pos, input_sizes[i] - pos, &hl, &bs);
                     if (st != DEBIG_GZ_OK) {
-                        /* behind queued members the next pass meets this header again, first */
-                        if (fill && !queued) { F[i].status = st; F[i].failed = 1; F[i].active = 0; }
+                        /* behind queued members the next pass meets this header again, first.  The verdict falls in the
+                         * counting round already: when no file of the batch has a member left there is no filling round */
+                        if (!queued) { F[i].status = st; F[i].failed = 1; F[i].active = 0; }
                         break;
                     }
                     /* a BGZF member: its end and (from ISIZE) its output size are known now */
@@ -265,6 +267,7 @@ DEBIG_API int debig_gunzip_batch(const uint8_t *const *inputs, const uint64_t *i
                         items[n_items].file = i;
                         items[n_items].payload = pos + hl;
                         items[n_items].known_end = bg ? pos + bs : 0;
+                        items[n_items].claimed_end = bs ? pos + bs : 0;
                         items[n_items].out_rel = used;
                     }
                     n_items++;
@@ -300,7 +303,8 @@ DEBIG_API int debig_gunzip_batch(const uint8_t *const *inputs, const uint64_t *i
             /* the trailer (and whatever follows) stays part of the input span: the end-of-input
              * rule of the reference's inflate (Q2) never sees the stream's last byte */
             desc[k].in_len = (it->known_end ? it->known_end : input_sizes[i]) - it->payload;
-            desc[k].out_off = F[i].dev_out + it->out_rel;
+            /* an overstated ISIZE in front of this member can put out_rel anywhere: no room, and no offset outside the file's region */
+            desc[k].out_off = F[i].dev_out + (it->out_rel <= out_caps[i] ? it->out_rel : 0);
             desc[k].out_cap = it->out_rel <= out_caps[i] ? out_caps[i] - it->out_rel : 0;
             desc[k].flags = DEBIG_STREAM_NO_REF_GATES;
         }
@@ -330,7 +334,9 @@ DEBIG_API int debig_gunzip_batch(const uint8_t *const *inputs, const uint64_t *i
             }
             const uint64_t end = it->payload + (res[k].in_end_bits + 7u) / 8u; /* the trailer starts here */
             if (end + 8 > input_sizes[i]) { f->status = DEBIG_GZ_E_TRUNCATED; f->failed = 1; continue; }
-            if (it->known_end && end + 8 != it->known_end) { /* the BC size disagrees with the stream */
+            /* the BC size disagrees with the stream -- also one that was of no use for the split (past the end of the file, or
+             * too small for header + trailer): a lying BSIZE is an error wherever it points */
+            if (it->claimed_end && end + 8 != it->claimed_end) {
                 f->status = DEBIG_GZ_E_INFLATE;
                 f->failed = 1;
                 continue;

@@ -54,7 +54,32 @@ int debig_decode_gz_batch_ex(const uint8_t *const *inputs, const uint32_t *input
  * Zero bytes after the last member are accepted (tape padding); anything else that is not
  * a gzip header ends the file with DEBIG_GZ_E_TRAILING.
  * status[i]: DEBIG_GZ_*; out_sizes[i]: bytes produced (also on error: what was decoded before
- * it); n_members[i]: members decoded (may be NULL).  Returns 0 or a device error code. */
+ * it); n_members[i]: members decoded (may be NULL).  Returns 0 or a device error code.
+ *
+ * The first member that fails ends its file; per member the checks come in this order, and the
+ * first that fails gives the status:
+ *   0. the header: E_HEADER / E_TRUNCATED.  What follows a member is first looked at as trailing
+ *      bytes: nothing, or zeros only, ends the file well; fewer than 10 bytes, or bytes that do
+ *      not start 1f 8b, are E_TRAILING (so 1..9 bytes of a header are E_TRAILING, 10 or more that
+ *      start 1f 8b must be a whole header: E_HEADER / E_TRUNCATED, the output so far is kept);
+ *   1. inflate: E_OUTPUT_FULL when the bytes do not fit behind the members so far, E_INFLATE for
+ *      a damaged stream; a stream cut short is E_INFLATE or E_TRUNCATED, whichever the inflate
+ *      meets first (its end-of-input rule may take the cut for the end);
+ *   2. the 8 trailer bytes lie inside the file, else E_TRUNCATED;
+ *   3. a "BC" subfield (SLEN 2) names exactly the member's size, else E_INFLATE -- also a BSIZE
+ *      that points past the end of the file or leaves no room for header + trailer, which is of
+ *      no use for the split (the member is then inflated like a plain one) but is still a lie;
+ *   4. the ISIZE fields of the BGZF members in front of this one (same launch) add up to where
+ *      the members before it really end, else E_ISIZE;
+ *   5. the CRC-32, else E_CRC;   6. ISIZE, else E_ISIZE.
+ * out_sizes[i] and n_members[i] count the members that passed 0..4: a member that fails only
+ * its CRC-32 or ISIZE is counted and its bytes are in the output, under the error status.
+ * BGZF members are inflated at once, each writing where the ISIZE fields in front of it say.
+ * Behind an UNDERSTATED ISIZE the next member therefore writes over the last bytes of the lying
+ * one while its CRC-32 is taken: the status is E_CRC or E_ISIZE, out_sizes counts the lying
+ * member, and only the bytes of the members in front of it are defined.  Behind an overstated
+ * one nothing is written outside the file's out_caps[i] bytes.
+ * A NULL inputs[i] or outs[i] gives E_HEADER, 0 bytes, 0 members. */
 enum {
     DEBIG_GZ_OK = 0,
     DEBIG_GZ_E_HEADER = 1,      /* not a gzip header / CM != 8 / reserved flag bits       */

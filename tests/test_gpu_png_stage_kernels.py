@@ -35,8 +35,9 @@ debig_hip_png_spec_defilter* launchers start one workgroup per task and have no 
 they are in the same seam without a grid (stage_launch.NO_GRID), and tests/test_gpu_png_defilter_kernels.py runs their batteries on
 the GPU -- tests/test_emu_png_spec.py, test_emu_png_out_format.py, test_emu_png_planar.py and those index cases, past the wrap of
 the scratch ring and with rows long enough for the mid-row wait.  The tuned 8-bit de-filter has its own battery, run in every
-launch mode by tests/test_gpu_png_defilter_battery.py.  The inflate and the checksum kernels have no task loop either: the
-whole-call GPU tests reach them."""
+launch mode by tests/test_gpu_png_defilter_battery.py.  The inflate and the checksum kernels have no task loop either; the
+checksum kernel has its own battery (tests/checksum_battery.py: every alignment, tile and modulus edge, spans of one value inside
+the other, a grid past 65 535), run on the GPU by tests/test_gpu_checksum.py."""
 import ctypes as C
 import importlib
 import inspect
