@@ -1411,8 +1411,18 @@ def png_encode_batch_dyn(images, layout="hwc", depth=None, palette=None, trns=No
     return _png_encode(images, layout, depth, palette, trns, filter, level, (0, 1, 2), "debig_png_encode_batch_dyn")
 
 
+def png_encode_batch_lz(images, layout="hwc", depth=None, palette=None, trns=None, filter="adaptive", level=3):
+    """png_encode_batch with level 0, 1, 2 or 3 (include/decode_png.h: debig_png_encode_batch_lz): the same arguments, rules, statuses
+    and errors.  Levels 0 .. 2 give png_encode_batch_dyn's bytes.  Level 3 keeps level 2's chunks and blocks and matches otherwise:
+    it also tries the byte above and its two neighbours, and a short match gives way to a longer one that starts one byte later.
+    That is made for label maps, instance ids and other flat tensors, above all under filter="none"; on photographs it changes
+    next to nothing, and a level-3 file is NOT guaranteed to be at most the level-2 file.  Its zlib header is 78 9C.  The bytes are
+    a pure function of the arguments."""
+    return _png_encode(images, layout, depth, palette, trns, filter, level, (0, 1, 2, 3), "debig_png_encode_batch_lz")
+
+
 def _png_encode(images, layout, depth, palette, trns, filter, level, levels, call):
-    """the body of png_encode_batch and png_encode_batch_dyn: `levels` are the call's, `call` is its C entry point"""
+    """the body of png_encode_batch, png_encode_batch_dyn and png_encode_batch_lz: `levels` are the call's, `call` is its C entry point"""
     import torch
 
     if not isinstance(filter, str) or filter not in PNG_ENCODE_FILTERS:

@@ -32,6 +32,7 @@
 #include "png_label_components_kernel.inc"
 #include "png_encode_kernel.inc"
 #include "png_encode_dynamic_kernel.inc"
+#include "png_encode_lz_kernel.inc"
 #include "checksum_kernel.inc"
 
 // BTYPE 1 tables, built once per device by a tiny kernel and then only copied into LDS.  Two
@@ -1081,6 +1082,14 @@ int debig_hip_png_encode_dynamic_batch(const void *d_streams, void *d_slots, voi
                                        void *d_counts, uint32_t n_tasks, void *hip_stream)
 {
     return launch_stage(debig_png_encode_dynamic_kernel, PED_THREADS, n_tasks, hip_stream, (const uint8_t *)d_streams, (uint8_t *)d_slots,
+                        (uint8_t *)d_tokens, d_tasks, (uint32_t *)d_counts);
+}
+
+// ... or, level 3, the same with the matcher of png_encode_lz_kernel.inc: row-above candidates and one-step lazy matching
+int debig_hip_png_encode_lz_batch(const void *d_streams, void *d_slots, void *d_tokens, const debig_png_encode_lz_task *d_tasks, void *d_counts,
+                                  uint32_t n_tasks, void *hip_stream)
+{
+    return launch_stage(debig_png_encode_lz_kernel, PED_THREADS, n_tasks, hip_stream, (const uint8_t *)d_streams, (uint8_t *)d_slots,
                         (uint8_t *)d_tokens, d_tasks, (uint32_t *)d_counts);
 }
 

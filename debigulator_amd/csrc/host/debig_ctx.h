@@ -25,7 +25,7 @@ typedef struct debig_ctx {
     debig_devbuf tone_px, tone_tasks, tone_hist; /* debig_png_decode_batch_tensor_tone: the 8-bit intermediates, the pixel-run tasks, the histograms */
     debig_devbuf blur_tasks; /* debig_png_decode_batch_tensor_blur: the tile tasks (its intermediates are in tone_px) */
     debig_devbuf ws; /* token workspace of the scan / LZ77 kernel pair (DEBIG_WAVES_SPLIT) */
-    debig_devbuf enc_tokens; /* debig_png_encode_batch_dyn: the token rows of one round of level-2 tasks */
+    debig_devbuf enc_tokens; /* debig_png_encode_batch_dyn / _lz: the token rows of one round of level-2 or level-3 tasks */
     debig_devbuf pin_in, pin_out; /* page-locked staging arenas (host memory) */
     debig_devbuf dense, dense_list; /* sparse downloads: the decoded ranges packed on the device first */
     void *ev[DEBIG_STAGE_CHUNKS]; /* download pipeline events */

@@ -1,7 +1,8 @@
-/* debig_png_encode_batch and debig_png_encode_batch_dyn (include/decode_png.h, which has the rules): dense tensors in device memory
- * -> PNG files in host memory.  The two calls are their argument checks in front of ONE body; level 2 differs from it in the DEFLATE
- * launch -- debig_hip_png_encode_dynamic_batch (csrc/png_encode_dynamic_kernel.inc) in rounds of DEBIG_PNG_ENCODE_ROUND_TASKS tasks
- * that share one arena of worst-case token rows -- and in the zlib header's second byte.
+/* debig_png_encode_batch, debig_png_encode_batch_dyn and debig_png_encode_batch_lz (include/decode_png.h, which has the rules): dense
+ * tensors in device memory -> PNG files in host memory.  The three calls are their argument checks in front of ONE body; levels 2 and 3
+ * differ from it in the DEFLATE launch -- debig_hip_png_encode_dynamic_batch (csrc/png_encode_dynamic_kernel.inc) or
+ * debig_hip_png_encode_lz_batch (csrc/png_encode_lz_kernel.inc) in rounds of DEBIG_PNG_ENCODE_ROUND_TASKS tasks that share one arena of
+ * worst-case token rows --, level 3 in the task's row_stride, and both in the zlib header's second byte.
  * The host checks the descriptors, uploads the two task lists, launches the filter and the deflate kernel
  * (csrc/png_encode_kernel.inc), reads the chunks' byte counts and the range flags back, lays every good file out in a device arena
  * -- what stands in front of and behind the DEFLATE bytes comes from the host, the chunk outputs are moved by debig_hip_gather --,
@@ -19,6 +20,10 @@ _Static_assert(sizeof(debig_png_encode_dynamic_task) == 80 && offsetof(debig_png
                    offsetof(debig_png_encode_dynamic_task, slot_off) == offsetof(debig_png_encode_deflate_task, slot_off) &&
                    offsetof(debig_png_encode_dynamic_task, flags) == offsetof(debig_png_encode_deflate_task, flags),
                "a dynamic task is a deflate task and its token row");
+_Static_assert(sizeof(debig_png_encode_lz_task) == 80 && offsetof(debig_png_encode_lz_task, token_off) == 64 &&
+                   offsetof(debig_png_encode_lz_task, row_stride) == offsetof(debig_png_encode_dynamic_task, reserved2) &&
+                   offsetof(debig_png_encode_lz_task, flags) == offsetof(debig_png_encode_dynamic_task, flags),
+               "an lz task is a dynamic task with row_stride in its last word");
 #define TOKEN_ROW (4u * (uint64_t)DEBIG_PNG_ENCODE_CHUNK) /* worst case: every byte of a chunk a literal */
 
 static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
@@ -106,11 +111,11 @@ static int args_ok(const void *const *d_images, const debig_png_encode_desc *des
     return 1;
 }
 
-/* the body of both calls; level 0 .. 2 */
+/* the body of the three calls; level 0 .. 3 */
 static int encode_body(const void *const *d_images, const debig_png_encode_desc *descs, const uint8_t *side, void *const *outs,
                        const uint64_t *out_caps, uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level)
 {
-    const size_t ts = level == 2u ? sizeof(debig_png_encode_dynamic_task) : sizeof(debig_png_encode_deflate_task);
+    const size_t ts = level >= 2u ? sizeof(debig_png_encode_dynamic_task) : sizeof(debig_png_encode_deflate_task);
     int rc = 2;
     enc_image *im = (enc_image *)calloc(n, sizeof *im);
     uint8_t *blob = NULL, *heads = NULL;
@@ -153,7 +158,7 @@ static int encode_body(const void *const *d_images, const debig_png_encode_desc 
     words = (uint32_t *)malloc((size_t)(n_good + n_dt) * 4u + 16u);
     if (!blob || !words) goto done;
     debig_png_encode_filter_task *ft = (debig_png_encode_filter_task *)blob;
-    uint8_t *dt = blob + n_ft * 64u; /* deflate tasks, or dynamic tasks at level 2: ts bytes each */
+    uint8_t *dt = blob + n_ft * 64u; /* deflate tasks, or dynamic / lz tasks at levels 2 / 3: ts bytes each */
     at = slots_off;
     for (uint32_t k = 0; k < n_good; k++) {
         const enc_image *g = &im[k];
@@ -176,7 +181,7 @@ static int encode_body(const void *const *d_images, const debig_png_encode_desc 
             ft->flag_idx = k;
         }
         for (uint64_t j = 0; j < g->tasks; j++) {
-            debig_png_encode_dynamic_task y; /* its first 64 bytes are the deflate task */
+            debig_png_encode_lz_task y; /* its first 64 bytes are the deflate task, all but row_stride the dynamic task */
             memset(&y, 0, sizeof y);
             y.stream_off = g->stream_off;
             y.stream_len = g->stream_len;
@@ -190,6 +195,8 @@ static int encode_body(const void *const *d_images, const debig_png_encode_desc 
             y.count_idx = (uint32_t)(g->first_task + j);
             y.token_off = ((g->first_task + j) % DEBIG_PNG_ENCODE_ROUND_TASKS) * TOKEN_ROW; /* the row of its place in its round */
             y.token_cap = (uint32_t)TOKEN_ROW;
+            /* the byte above, where the rule takes it as a distance (a row of one pixel has S - bpp = 1: the rule skips it) */
+            if (level == 3u && y.bpp < 1u + rb && 1u + rb + y.bpp <= 32768u) y.row_stride = 1u + rb;
             memcpy(dt + (g->first_task + j) * ts, &y, ts);
             at += y.slot_cap;
         }
@@ -207,15 +214,19 @@ static int encode_body(const void *const *d_images, const debig_png_encode_desc 
         (rc = debig_hip_png_encode_filter_batch((const void *)base, arena, (const debig_png_encode_filter_task *)c->rsz_tasks.ptr,
                                                 arena + flags_off, (uint32_t)n_ft, NULL)))
         goto done;
-    if (level == 2u) {
+    if (level >= 2u) {
         /* rounds on one stream run one behind the other: a round's token rows are free when the next one starts */
         const uint64_t round = n_dt < DEBIG_PNG_ENCODE_ROUND_TASKS ? n_dt : DEBIG_PNG_ENCODE_ROUND_TASKS;
         if ((rc = debig_devbuf_reserve(&c->enc_tokens, round * TOKEN_ROW))) goto done;
         for (uint64_t r0 = 0; r0 < n_dt; r0 += round) {
             const uint64_t m = n_dt - r0 < round ? n_dt - r0 : round;
-            if ((rc = debig_hip_png_encode_dynamic_batch(arena, arena, c->enc_tokens.ptr, (const debig_png_encode_dynamic_task *)(d_dt + r0 * ts),
-                                                         arena + counts_off, (uint32_t)m, NULL)))
-                goto done;
+            if (level == 3u)
+                rc = debig_hip_png_encode_lz_batch(arena, arena, c->enc_tokens.ptr, (const debig_png_encode_lz_task *)(d_dt + r0 * ts), arena + counts_off,
+                                                   (uint32_t)m, NULL);
+            else
+                rc = debig_hip_png_encode_dynamic_batch(arena, arena, c->enc_tokens.ptr, (const debig_png_encode_dynamic_task *)(d_dt + r0 * ts),
+                                                        arena + counts_off, (uint32_t)m, NULL);
+            if (rc) goto done;
         }
     } else if ((rc = debig_hip_png_encode_deflate_batch(arena, arena, (const debig_png_encode_deflate_task *)d_dt, arena + counts_off, (uint32_t)n_dt,
                                                         NULL)))
@@ -290,7 +301,7 @@ static int encode_body(const void *const *d_images, const debig_png_encode_desc 
         be32(h + hl, (uint32_t)(2u + g->deflate_bytes + 4u));
         memcpy(h + hl + 4, "IDAT", 4);
         h[hl + 8] = 0x78;
-        h[hl + 9] = level == 2u ? 0x5E : 0x01; /* FLEVEL 0, or 1 at level 2; FCHECK */
+        h[hl + 9] = level == 3u ? 0x9C : level == 2u ? 0x5E : 0x01; /* FLEVEL 0, 1 at level 2, 2 at level 3; FCHECK */
         hl += 10;
         /* the head, the chunk outputs, IEND (the Adler-32 and the IDAT's CRC-32 are patched in behind the checksum launches) */
         cp->src_off = (heads_off - files_off) + g->head_off;
@@ -401,5 +412,14 @@ DEBIG_API int debig_png_encode_batch_dyn(const void *const *d_images, const debi
 {
     if (n == 0) return 0;
     if (!args_ok(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level, 2u)) return DEBIG_PNG_BAD_ARG;
+    return encode_body(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level);
+}
+
+DEBIG_API int debig_png_encode_batch_lz(const void *const *d_images, const debig_png_encode_desc *descs, const uint8_t *side, void *const *outs,
+                                        const uint64_t *out_caps, uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter,
+                                        uint32_t level)
+{
+    if (n == 0) return 0;
+    if (!args_ok(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level, 3u)) return DEBIG_PNG_BAD_ARG;
     return encode_body(d_images, descs, side, outs, out_caps, out_sizes, status, n, filter, level);
 }

@@ -324,34 +324,50 @@ DEV_INLINE bool pdy_task_ok(const debig_png_encode_dynamic_task &t, const void *
     return stage_addr_ok(slots, t.slot_off, 3u) && stage_addr_ok(tokens, t.token_off, 3u) && stage_addr_ok(counts, 0u, 3u) && streams != nullptr;
 }
 
-// the task's block -> the bytes written
-DEV_INLINE uint32_t pdy_run(PdyLds &L, const uint8_t *__restrict__ stream, uint8_t *__restrict__ slot, uint32_t *row,
-                            const debig_png_encode_dynamic_task &t, uint32_t lane)
+// MATCH, the end of a step: a lane whose position starts a token (best 0: the literal at `at`) stores it behind the ntok tokens of the
+// steps before and counts its symbols
+DEV_INLINE void pdy_step_tokens(PdyLds &L, uint32_t *row, uint32_t token_cap, unsigned long long starts, uint32_t &ntok, uint32_t best,
+                                uint32_t dist, const uint8_t *__restrict__ at, uint32_t lane)
+{
+    if ((starts >> lane) & 1ull) {
+        const uint32_t idx = ntok + (uint32_t)__popcll(starts & ((1ull << lane) - 1ull));
+        uint32_t tok;
+        if (best) {
+            tok = 0x80000000u | ((best - 3u) << 16) | (dist - 1u);
+            atomicAdd(&L.cnt[257u + (ped_len_sym(best) & 255u)], 1u);
+            atomicAdd(&L.cnt[PDY_LL + (ped_dist_sym(dist) & 255u)], 1u);
+        } else {
+            tok = *at;
+            atomicAdd(&L.cnt[tok], 1u);
+        }
+        if (idx < token_cap / 4u) row[idx] = tok; /* (always: a chunk has at most chunk_len tokens) */
+    }
+    ntok += (uint32_t)__popcll(starts);
+}
+
+// MATCH of level 2 -> the tokens in the row
+DEV_INLINE uint32_t pdy_match(PdyLds &L, const uint8_t *__restrict__ stream, uint32_t *row, const debig_png_encode_dynamic_task &t, uint32_t lane)
 {
     const uint32_t len = t.chunk_len, c0 = (uint32_t)t.chunk_off;
-    uint32_t *ow = reinterpret_cast<uint32_t *>(slot);
-    // ---- MATCH ----
     for (uint32_t k = lane; k < PDY_SYMS; k += 64u) L.cnt[k] = 0u;
     ped_window(L.u.hash, stream, c0, t.stream_len, lane);
     uint32_t covered = 0u, ntok = 0u;
     for (uint32_t base = 0u; base < len; base += 64u) {
         uint32_t best, dist;
         const unsigned long long starts = ped_step(L.u.hash, L.lens, stream, c0, len, t.bpp, base, lane, covered, best, dist);
-        if ((starts >> lane) & 1ull) {
-            const uint32_t idx = ntok + (uint32_t)__popcll(starts & ((1ull << lane) - 1ull));
-            uint32_t tok;
-            if (best) {
-                tok = 0x80000000u | ((best - 3u) << 16) | (dist - 1u);
-                atomicAdd(&L.cnt[257u + (ped_len_sym(best) & 255u)], 1u);
-                atomicAdd(&L.cnt[PDY_LL + (ped_dist_sym(dist) & 255u)], 1u);
-            } else {
-                tok = stream[c0 + base + lane];
-                atomicAdd(&L.cnt[tok], 1u);
-            }
-            if (idx < t.token_cap / 4u) row[idx] = tok; /* (always: a chunk has at most chunk_len tokens) */
-        }
-        ntok += (uint32_t)__popcll(starts);
+        pdy_step_tokens(L, row, t.token_cap, starts, ntok, best, dist, stream + c0 + base + lane, lane);
     }
+    return ntok;
+}
+
+// BUILD, CHOICE and EMIT: the block of the ntok tokens that MATCH left in the row and in the histograms -> the bytes written.  T: the
+// dynamic task, or the level-3 task (png_encode_lz_kernel.inc), which has the same fields in the same places
+template <class T>
+DEV_INLINE uint32_t pdy_finish(PdyLds &L, const uint8_t *__restrict__ stream, uint8_t *__restrict__ slot, const uint32_t *row, const T &t,
+                               uint32_t ntok, uint32_t lane)
+{
+    const uint32_t len = t.chunk_len, c0 = (uint32_t)t.chunk_off;
+    uint32_t *ow = reinterpret_cast<uint32_t *>(slot);
     if (ntok > t.token_cap / 4u) ntok = t.token_cap / 4u;
     if (lane == 0u) L.cnt[256] = 1u; /* the end of block */
     __syncthreads();
@@ -442,7 +458,9 @@ debig_png_encode_dynamic_kernel(const uint8_t *__restrict__ streams, uint8_t *__
         const debig_png_encode_dynamic_task t = tasks[ti];
         // (uniform over the wavefront: every lane skips, or none)
         if (!pdy_task_ok(t, streams, slots, tokens, counts)) continue;
-        const uint32_t bytes = pdy_run(L, streams + t.stream_off, slots + t.slot_off, reinterpret_cast<uint32_t *>(tokens + t.token_off), t, lane);
+        uint32_t *row = reinterpret_cast<uint32_t *>(tokens + t.token_off);
+        const uint32_t ntok = pdy_match(L, streams + t.stream_off, row, t, lane);
+        const uint32_t bytes = pdy_finish(L, streams + t.stream_off, slots + t.slot_off, row, t, ntok, lane);
         if (lane == 0u) counts[t.count_idx] = bytes;
         __syncthreads();
     }

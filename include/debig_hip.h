@@ -206,7 +206,7 @@ int debig_hip_inflate_batch(const void *d_in, void *d_out, const debig_stream *d
  * _elastic / _elastic_color / _label_elastic / _color_label_elastic, _tone_hist / _tone_apply, _blur, _label_stats and
  * _label_boundary, _label_distance_rows / _label_distance_cols -- and the five launchers of the label components,
  * _label_components_rows / _merge / _count / _number / _finish -- and the two of the PNG encode, _png_encode_filter / _png_encode_deflate --
- * and the two of its level 2, _png_encode_dynamic / _png_encode_codes --
+ * and the two of its level 2, _png_encode_dynamic / _png_encode_codes, and the one of its level 3, _png_encode_lz --
  * start min(n_tasks, 2^20) workgroups.  Set to a number G > 0 they start min(G, n_tasks, 2^20), so that a workgroup takes
  * tasks blockIdx.x, blockIdx.x + G, ... one after the other: what a call of more than 2^20 tasks does, at a size a test
  * can afford.  Unset, empty or 0: the launch is unchanged.  Results do not depend on it. */
@@ -1206,6 +1206,51 @@ int debig_hip_png_encode_dynamic_batch(const void *d_streams, void *d_slots, voi
                                        void *d_counts, uint32_t n_tasks, void *hip_stream);
 int debig_hip_png_encode_codes_batch(const void *d_counts, void *d_lens, const debig_png_encode_codes_task *d_tasks, uint32_t n_tasks,
                                      void *hip_stream);
+
+/* ---- PNG encode, level 3 (csrc/png_encode_lz_kernel.inc, behind debig_png_encode_batch_lz in decode_png.h): the dynamic task of
+ * above with another matcher in front of the same back end -- the token row, the code rule, the three sizes, the choice with
+ * DEBIG_PNG_ENCODE_NO_STORED and DEBIG_PNG_ENCODE_ONLY_DYNAMIC, the emit, the trailer and the stored block are level 2's code, run on
+ * level 3's tokens.  Per chunk level 3 is never longer than stored, debig_png_encode_bound holds, and the bytes are a pure function
+ * of the task and the stream: the same for every grid, order and run.  Level 3 is NOT guaranteed to be at most level 2: the tokens
+ * differ, and neither matcher is run to check the other.  It is made for label maps, instance ids and other flat tensors; on
+ * photographs it changes next to nothing.
+ *   THE RULE.  Chunks, the window and the table are level 1's and are not touched: ped_hash, the 4096 entries, position + 1 inserted
+ *   by atomicMax, ped_window, and every lane of a step reading before any lane inserts.
+ *   A task carries row_stride S.  S is 0 for none.  Otherwise bpp < S and S + bpp <= 32768.  The host passes S = 1 + width x
+ *   channels x depth / 8 when that holds, else 0.  The kernel treats S as a plain distance and does not need it to be a real row.
+ *   For position p of the chunk, gp = c0 + p and maxl = min(258, len - p).  If maxl < 3 then L(p) = 0.  Otherwise the candidates are
+ *   tried in this order: 1. distance 1; 2. bpp, if bpp > 1; 3. S; 4. S - bpp; 5. S + bpp; 6. the table's candidate, if it is in
+ *   front of gp, within 32768, and not one of the distances before it.  A candidate needs gp >= d.  A distance equal to an earlier
+ *   one is skipped.  The longest match wins, and ties go to the earlier candidate.  Then, as at level 1, a best below 3, or of 3
+ *   farther than 4096 (PED_TOO_FAR), is 0.
+ *   The walk is greedy and wave-uniform with steps of 64, as at level 1.  It adds one deferral.  At an uncovered position q, the
+ *   token is a literal when all of these hold: 3 <= L(q) < 16; q % 64 != 63; q + 1 < len; L(q + 1) > L(q).  Otherwise the token is
+ *   the match, or a literal.  The check applies again at q + 1.  16 is zlib's max_lazy at its default level; the rule fixes it, it
+ *   is not measured.  The last position of a step never defers, because its neighbour's length is not known yet.
+ *   Tokens go to the token row in level 2's 32-bit format.
+ * An lz task is skipped when a dynamic task with its fields would be (level: anything but 3), or row_stride is neither 0 nor
+ * bpp < row_stride <= 32768 - bpp.
+ * NOT BUILT: hash chains, a second or wider table, candidates beyond S +- bpp, several blocks per chunk, levels above 3, optimal
+ * parsing. */
+typedef struct debig_png_encode_lz_task {
+    uint64_t stream_off;      /* the fields of debig_png_encode_dynamic_task ...                                                */
+    uint64_t stream_len;
+    uint64_t chunk_off;
+    uint64_t slot_off;
+    uint32_t chunk_len;
+    uint32_t slot_cap;
+    uint32_t level;           /* 3                                                                                              */
+    uint32_t bpp;
+    uint32_t last;
+    uint32_t count_idx;
+    uint32_t flags;           /* DEBIG_PNG_ENCODE_NO_STORED, DEBIG_PNG_ENCODE_ONLY_DYNAMIC                                      */
+    uint32_t reserved;
+    uint64_t token_off;
+    uint32_t token_cap;
+    uint32_t row_stride;      /* ... and S: 0, or the distance of the byte above, bpp < S <= 32768 - bpp                        */
+} debig_png_encode_lz_task;
+int debig_hip_png_encode_lz_batch(const void *d_streams, void *d_slots, void *d_tokens, const debig_png_encode_lz_task *d_tasks,
+                                  void *d_counts, uint32_t n_tasks, void *hip_stream);
 
 /* A byte span of a device arena. */
 typedef struct debig_span {

@@ -1075,6 +1075,21 @@ int debig_png_encode_batch(const void *const *d_images /* host array of device p
 int debig_png_encode_batch_dyn(const void *const *d_images /* host array of device pointers */, const debig_png_encode_desc *descs,
                                const uint8_t *side /* host: palettes, tRNS */, void *const *outs /* host */, const uint64_t *out_caps,
                                uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level);
+/* The same call with level 0, 1, 2 or 3.  Levels 0 .. 2 are debig_png_encode_batch_dyn byte for byte (the two calls above keep their
+ * surface, their bytes and their refusal of level 3).  LEVEL 3: level 2's chunks, token rows, rounds, dynamic-code rule and choice
+ * between the stored, the fixed and the dynamic block, behind ANOTHER MATCHER: beside the distances 1 and bpp and the table's
+ * candidate it tries the byte above and its two neighbours -- the distances S, S - bpp and S + bpp with S = 1 + width x channels x
+ * depth / 8, the length of a filtered row, where bpp < S and S + bpp <= 32768 --, and a match of 3 .. 15 bytes gives way to a longer
+ * one that starts one byte later (one-step lazy matching).  debig_hip.h states the rule word for word
+ * (debig_hip_png_encode_lz_batch), so the bytes are a pure function of the input.  Per chunk level 3 is never longer than stored,
+ * and debig_png_encode_bound holds.  Level 3 is NOT guaranteed to be at most level 2: the tokens differ and neither matcher is run to
+ * check the other.  It is made for label maps, instance ids, boundary rings and other flat tensors, above all under filter none; on
+ * photographs it changes next to nothing.  The zlib header is 78 9C at level 3.  DEBIG_PNG_BAD_ARG before any device work for a
+ * level above 3.  NOT BUILT: hash chains, a second or wider table, candidates beyond S +- bpp, levels above 3, more than one block
+ * per chunk, optimal parsing, optimal (package-merge) lengths. */
+int debig_png_encode_batch_lz(const void *const *d_images /* host array of device pointers */, const debig_png_encode_desc *descs,
+                              const uint8_t *side /* host: palettes, tRNS */, void *const *outs /* host */, const uint64_t *out_caps,
+                              uint64_t *out_sizes, uint32_t *status, uint32_t n, uint32_t filter, uint32_t level);
 
 /* ---- animated PNG (APNG: acTL / fcTL / fdAT, PNG specification Third Edition) -----------------------------------------
  * A file without acTL is a still image of one frame (its fcTL / fdAT chunks are skipped as unknown ancillary chunks); its

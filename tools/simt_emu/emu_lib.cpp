@@ -33,6 +33,7 @@
 #include "../../debigulator_amd/csrc/png_label_components_kernel.inc"
 #include "../../debigulator_amd/csrc/png_encode_kernel.inc"
 #include "../../debigulator_amd/csrc/png_encode_dynamic_kernel.inc"
+#include "../../debigulator_amd/csrc/png_encode_lz_kernel.inc"
 #include "../../debigulator_amd/csrc/checksum_kernel.inc"
 
 /* DEBIG_NO_HANDBACK (include/debig_hip.h), as the shim reads it: the routes that hand streams back leave them so */
@@ -700,6 +701,17 @@ extern "C" int emu_png_encode_dynamic_batch(const void *streams, void *slots, vo
     if (grid == 0 || grid > n) grid = n;
     if (n)
         EMU_LAUNCH(debig_png_encode_dynamic_kernel, grid, PED_THREADS, (const uint8_t *)streams, (uint8_t *)slots, (uint8_t *)tokens, tasks,
+                   (uint32_t *)counts, n);
+    return 0;
+}
+
+/* level 3 (png_encode_lz_kernel.inc), as debig_hip_png_encode_lz_batch launches its kernel (grid as above) */
+extern "C" int emu_png_encode_lz_batch(const void *streams, void *slots, void *tokens, const debig_png_encode_lz_task *tasks, void *counts,
+                                       uint32_t n, uint32_t grid)
+{
+    if (grid == 0 || grid > n) grid = n;
+    if (n)
+        EMU_LAUNCH(debig_png_encode_lz_kernel, grid, PED_THREADS, (const uint8_t *)streams, (uint8_t *)slots, (uint8_t *)tokens, tasks,
                    (uint32_t *)counts, n);
     return 0;
 }
